@@ -10,13 +10,17 @@ region.  N > 1: one process per GPU (torchrun), every rank owns its own 4096-env
 as the reference gives every rank its own numEnvs) and the flat gradient is all-reduced with RCCL on
 every optimizer step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-roofline] [--no-student]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-roofline] [--no-peak-probe] [--no-student] [--no-experiments]
+                            [--no-multi-configs]]
 
-The JSON line also carries ``roofline`` (dominant kernel: algorithmic flops / the kernel's own dispatch-timestamp
-duration, the same figure recomputed from the tracked rocprofv3 summary under profiles/, and ``levels``: the backward
-levels that share that symbol, each with its own GFLOP / us / fraction), ``cpu_baseline`` (the oracle on this host's
-cores: 1 warm-up update + the median of 5 full updates, CPU model printed) and ``student`` (BASELINE configs[2] and the
-single-rank share of configs[3], a few updates each, outside ``value``).
+A plain run sets up, warms up, times the K updates, writes what the last of them computed if --dump-outputs is given
+(dump_outputs), and prints the headline line.  With --full the JSON line also carries ``roofline`` (dominant kernel:
+algorithmic flops / the kernel's own dispatch-timestamp duration, the same figure recomputed from the tracked rocprofv3
+summary under profiles/, and ``levels``: the backward levels that share that symbol, each with its own GFLOP / us /
+fraction), ``cpu_baseline`` (the oracle on this host's cores: 1 warm-up update + the median of 5 full updates, CPU model
+printed), ``student`` (BASELINE configs[2] and the single-rank share of configs[3], a few updates each, outside
+``value``), ``experiments`` and, at N > 1, ``multi_gpu_configs``; the --no-* switches turn single sections of it off.
 """
 import argparse
 import csv
@@ -452,6 +456,37 @@ def free_port():
         return so.getsockname()[1]
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, eng):
+    """What the last timed update handed its caller, as <path>/<name>.npy: the per-optimizer-step statistics it returns
+    and the state it leaves behind -- parameters and Adam moments (state_dict order, no padding), the running mean / std
+    normalisers (float64), the GAE outputs and the mu / sigma written back into the arena.  About 13 MB at 4096 x 32.  If
+    the whole would exceed DUMP_BUDGET_BYTES, the per-sample (horizon x envs) arrays are cut down to one fixed, seeded
+    sample of (t, env) positions, the same for all of them."""
+    import numpy as np
+    import torch
+    out = {"stats": eng.stats, "params": eng.packed(), "adam_m": eng.packed(eng.adam_m), "adam_v": eng.packed(eng.adam_v),
+           "rms_obs": eng.rms_obs, "rms_priv": eng.rms_priv, "rms_value": eng.rms_value}
+    per_sample = {"returns_raw": eng.returns_raw, "advantages": eng.advantages, "values_n": eng.values_n,
+                  "returns_n": eng.returns_n, "mus": eng.mus_w, "sigmas": eng.sigmas_w}
+    fixed = sum(t.numel() * t.element_size() for t in out.values())
+    rows = eng.T * eng.N
+    row_bytes = sum(t.numel() * t.element_size() for t in per_sample.values()) // rows
+    keep = min(rows, max(0, (DUMP_BUDGET_BYTES - fixed) // row_bytes))
+    idx = None
+    if keep < rows:
+        idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values.to(eng.device)
+    for k, t in per_sample.items():
+        out[k] = t if idx is None else t.reshape(rows, -1).index_select(0, idx)
+    os.makedirs(path, exist_ok=True)
+    for k, t in out.items():
+        a = t.detach().cpu().numpy()
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` started as ONE process (the way the driver starts every bench): this parent -- which
     has imported nothing that touches the GPU and makes no GPU call -- starts the N ranks the way the reference's
@@ -482,7 +517,19 @@ def main():
     ap.add_argument("--no-experiments", action="store_true", help="skip the `experiments` section (the bf16 three-plane split probe)")
     ap.add_argument("--no-multi-configs", action="store_true",
                     help="N > 1: skip the sub-records of the multi-GPU configurations (configs[4] teacher, configs[3] student)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything outside the headline: measured peaks, the per-kernel roofline region, the CPU "
+                         "baseline, the student legs, the experiments and (N > 1) the multi-GPU sub-records; without it "
+                         "the run does only what `value` needs and the --no-* switches have nothing left to turn off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed update computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_peak_probe = args.no_student = True
+        args.no_experiments = args.no_multi_configs = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -610,6 +657,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng)     # before the roofline region runs further updates on the same state
     stats = eng.stats.cpu()
     finite = bool(torch.isfinite(stats).all() and torch.isfinite(eng.params).all())
     # data-parallel sanity, outside the timed region: every rank applied the same summed gradient to the same

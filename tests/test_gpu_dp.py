@@ -85,7 +85,7 @@ def test_bench_self_launches_its_ranks():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+                          "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     # TWO lines at N > 1 (round 6): the complete headline record FIRST, before the multi-GPU sub-records start (a hang in a
     # sub-record cannot cost the headline), then the same record extended by multi_gpu_configs

@@ -42,7 +42,7 @@ traffic() {    # traffic <fetch dir> <write dir> <dest json>
 # ---- teacher bench: kernel trace + stats (the same command the driver runs, minus the CPU / student legs)
 rm -rf $O/${TAG}_stats
 run bench_stats $O/${TAG}_bench_under_rocprof -- rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -- \
-    python3 $R/bench.py --no-cpu-baseline --no-student --no-experiments --no-peak-probe \
+    python3 $R/bench.py --full --no-cpu-baseline --no-student --no-experiments --no-peak-probe \
   && cp $O/${TAG}_bench_under_rocprof.out $O/${TAG}_bench_under_rocprof.json \
   && stats_csv $O/${TAG}_stats $O/${TAG}_bench_kernel_stats.csv \
   && python3 $R/tools/levels_from_trace.py "$(find $O/${TAG}_stats -name '*kernel_trace.csv' | head -1)" --skip-first-updates $WS_SKIP > $O/${TAG}_bench_levels.csv

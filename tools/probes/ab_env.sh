@@ -3,7 +3,7 @@
 # several VAR=value separated by commas); prints the update time and the per-kernel table of bench.py for each
 cd "$(dirname "$0")/../.."
 for setting in "$@"; do
-  env $(echo "$setting" | tr ',' ' ') python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-student 2>/dev/null | python -c "
+  env $(echo "$setting" | tr ',' ' ') python bench.py --steps ${STEPS:-10} --warmup 3 --full --no-cpu-baseline --no-student 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('== $setting : update ms', d['ms_per_step'], 'updates/s', d['value'], 'frac', d['whole_update_mfma_frac'])

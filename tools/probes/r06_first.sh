@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 python3 tools/probes/x3_probe.py > $O/r06_x3_probe.json 2> $O/r06_x3_probe.err; echo "x3 rc=$?"; tail -3 $O/r06_x3_probe.err
 for nf in 1 0 1 0; do
-  IGI_NORM_FUSE=$nf python3 bench.py --no-cpu-baseline --no-student --steps 20 --warmup 3 > $O/r06_bench_nf$nf.json 2> $O/r06_bench_nf$nf.err
+  IGI_NORM_FUSE=$nf python3 bench.py --full --no-cpu-baseline --no-student --steps 20 --warmup 3 > $O/r06_bench_nf$nf.json 2> $O/r06_bench_nf$nf.err
   python3 - <<PY
 import json
 try:

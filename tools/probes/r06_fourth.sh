@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 timeout 1200 python3 -m pytest tests/test_gpu_teacher.py -x -q -k "golden or bitwise or stepwise or phased or infer or edges" 2>&1 | tail -8
 for v in 1 0 1 0; do
-  IGI_FWD12=$v python3 bench.py --no-cpu-baseline --no-student --no-peak-probe --steps 20 --warmup 3 > $O/r06_bench_f12_$v.json 2> $O/r06_bench_f12_$v.err
+  IGI_FWD12=$v python3 bench.py --full --no-cpu-baseline --no-student --no-peak-probe --steps 20 --warmup 3 > $O/r06_bench_f12_$v.json 2> $O/r06_bench_f12_$v.err
   python3 - <<PY
 import json
 try:

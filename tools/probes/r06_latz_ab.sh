@@ -5,7 +5,7 @@ O=$R/gpurun_out
 cd $R
 # (parity: the full GPU suite runs both settings, tests/test_gpu_teacher.py)
 for v in 1 0 1 0 1 0 1 0 1 0; do
-  IGI_LATZ_FUSE=$v python3 bench.py --no-cpu-baseline --no-student --no-peak-probe --no-experiments --steps 20 --warmup 3 > $O/r06_bench_latz_$v.json 2> $O/r06_bench_latz_$v.err
+  IGI_LATZ_FUSE=$v python3 bench.py --full --no-cpu-baseline --no-student --no-peak-probe --no-experiments --steps 20 --warmup 3 > $O/r06_bench_latz_$v.json 2> $O/r06_bench_latz_$v.err
   python3 - <<PY
 import json
 try:

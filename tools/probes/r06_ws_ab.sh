@@ -5,7 +5,7 @@ O=$R/gpurun_out
 cd $R
 for t in 4 1 4 1; do echo "IGI_WS_TRIALS=$t"; IGI_WS_TRIALS=$t python3 tools/probes/env_level_modes.py 2>&1 | tail -1 | cut -c1-1400; done
 for v in 4 1 4 1 4 1 4 1 4 1; do
-  IGI_WS_TRIALS=$v python3 bench.py --no-cpu-baseline --no-student --no-peak-probe --no-experiments --steps 20 --warmup 3 > $O/r06_bench_ws_$v.json 2> $O/r06_bench_ws_$v.err
+  IGI_WS_TRIALS=$v python3 bench.py --full --no-cpu-baseline --no-student --no-peak-probe --no-experiments --steps 20 --warmup 3 > $O/r06_bench_ws_$v.json 2> $O/r06_bench_ws_$v.err
   python3 - <<PY
 import json
 try:

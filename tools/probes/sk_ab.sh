@@ -2,7 +2,7 @@
 # update time, per-level launch times and the slab sum, two rounds on one box.
 for rep in 1 2; do
 for v in ${SK_SET:-"0,0,0,0,0,0" "0,64,0,0,0,0" "0,32,0,0,0,0" "0,64,32,0,0,0" "0,64,0,64,0,0" "0,64,0,0,32,0" "0,64,0,0,0,128"}; do
-IGI_SK_OVERRIDE=$v python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-student 2>/dev/null | python -c "
+IGI_SK_OVERRIDE=$v python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-student 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 lv={l['level'][:6]:l['avg_us'] for l in d['roofline']['levels']}
