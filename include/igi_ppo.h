@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define IGI_ABI_VERSION 3
+#define IGI_ABI_VERSION 4
 #define IGI_MAX_LAYERS 4
 #define IGI_MAX_ACT 8
 
@@ -129,6 +129,10 @@ typedef struct igi_teacher_cfg {
   float e_clip, critic_coef, entropy_coef, bounds_loss_coef; /* frozen_ppo.py:543-564 */
   float grad_norm;                    /* clip_grad_norm_ max norm; <=0: no clipping (:608-609) */
   float rms_eps;                      /* running_mean_std.py:24 (1e-5) */
+  /* ground-truth contacts (task.env.compute_contact_gt; models_split.py:41-55, 81-88, 172-177); all zero = off.
+   * contact_points = num_points P, contact_emb = contact_mlp.units[-1] (<= 32), only_contact = train.ppo.only_contact
+   * (the trunk then sees [obs | contact embedding] and env_mlp is not trained; needs contact_emb == priv_units[-1]). */
+  int32_t contact_points, contact_emb, only_contact;
 } igi_teacher_cfg;
 
 /* Time-major rollout arena, exactly what play_steps stores (frozen_ppo.py:655-683;
@@ -145,6 +149,7 @@ typedef struct igi_rollout {
   const float* mus;
   const float* sigmas;
   const float* last_values;
+  const float* contacts;   /* (T,N,contact_points); required when the cfg enables contacts, else ignored */
 } igi_rollout;
 
 /* Trainer-owned persistent state. */
@@ -317,6 +322,31 @@ int igi_rollout_policy_step(const igi_teacher_cfg* cfg, const igi_teacher_state*
                             const double* rms_value, float* obses_t, float* priv_t, float* actions_t,
                             float* neglogp_t, float* values_t, float* mus_t, float* sigmas_t, float* actions_clamped,
                             float* values_out, igi_stream_t stream);
+
+/* The two calls above for a teacher with ground-truth contacts: contacts (rows, contact_points), raw (not normalised,
+ * models_split.py:174).  latent of igi_teacher_infer_contacts is (rows, priv_units[-1] + contact_emb), or
+ * (rows, contact_emb) with only_contact.  The calls without contacts refuse such a cfg.  contacts_t (may be NULL):
+ * slot t of the (T, N, contact_points) arena, written with the raw contacts like obses_t / priv_t. */
+int igi_teacher_infer_contacts(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* obs,
+                               const float* priv, const float* contacts, int64_t rows, int normalize, float* mu,
+                               float* value, float* latent, igi_stream_t stream);
+int igi_rollout_policy_step_contacts(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* obs,
+                                     const float* priv, const float* contacts, int64_t rows, int normalize,
+                                     const float* noise, const double* rms_value, float* obses_t, float* priv_t,
+                                     float* contacts_t, float* actions_t, float* neglogp_t, float* values_t, float* mus_t, float* sigmas_t,
+                                     float* actions_clamped, float* values_out, igi_stream_t stream);
+
+/* The contact encoder alone (ContactAE.forward_enc, models_split.py:44-51), the kernels of the teacher's contact mode.
+ * Row i of the batch is row i of contacts (rows, P).  params = [W1 (32,P) | b1 (32) | W2 (E,32) | b2 (E)] packed.
+ * forward: emb (rows, E), hidden (rows, 32) = relu(C W1^T + b1).  backward: from d(pre-tanh) dz (rows, E) and that
+ * hidden, grads (packed like params) = the sums over the rows; workspace of
+ * igi_contact_encoder_workspace_bytes(rows, P, E) bytes. */
+int igi_contact_encoder_forward(const float* contacts, int64_t rows, int P, int E, const float* params, float* emb,
+                                float* hidden, igi_stream_t stream);
+size_t igi_contact_encoder_workspace_bytes(int64_t rows, int P, int E);
+int igi_contact_encoder_backward(const float* contacts, int64_t rows, int P, int E, const float* params,
+                                 const float* hidden, const float* dz, float* grads, void* workspace,
+                                 size_t workspace_bytes, igi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Rollout-side bookkeeping of PPO.play_steps, two launches per environment step.

@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libigi_hip.so")
 IGI_MAX_LAYERS = 4
 IGI_MAX_ACT = 8
 IGI_STATS_PER_STEP = 8
-ABI_VERSION = 3
+ABI_VERSION = 4
 IGI_E_BADARG, IGI_E_WORKSPACE, IGI_E_UNSUPPORTED, IGI_E_CALLBACK, IGI_E_COMM = -1, -2, -3, -5, -6   # include/igi_ppo.h
 
 EPI_STORE, EPI_BIAS_TANH, EPI_TANHGRAD, EPI_BIAS = 0, 1, 2, 3
@@ -30,6 +30,7 @@ class TeacherCfg(C.Structure):
         ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double),
         ("e_clip", C.c_float), ("critic_coef", C.c_float), ("entropy_coef", C.c_float),
         ("bounds_loss_coef", C.c_float), ("grad_norm", C.c_float), ("rms_eps", C.c_float),
+        ("contact_points", C.c_int32), ("contact_emb", C.c_int32), ("only_contact", C.c_int32),
     ]
 
 
@@ -37,7 +38,7 @@ class Rollout(C.Structure):
     """struct igi_rollout"""
     _fields_ = [(k, C.c_void_p) for k in
                 ("obses", "priv_info", "rewards", "values", "neglogpacs", "dones", "actions", "mus",
-                 "sigmas", "last_values")]
+                 "sigmas", "last_values", "contacts")]
 
 
 class TeacherState(C.Structure):
@@ -133,6 +134,17 @@ _EXPORTS = {
                                     C.c_void_p]),
     "igi_rollout_policy_step": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(TeacherState), C.c_void_p, C.c_void_p,
                                           C.c_int64, C.c_int] + [C.c_void_p] * 11 + [C.c_void_p]),
+    "igi_teacher_infer_contacts": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(TeacherState), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "igi_rollout_policy_step_contacts": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(TeacherState), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 12
+                                         + [C.c_void_p]),
+    "igi_contact_encoder_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "igi_contact_encoder_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "igi_contact_encoder_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "igi_clip_adam_workspace_bytes": (C.c_size_t, []),
     "igi_clip_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_double,
                                 C.c_double, C.c_double, C.c_double, C.c_int64, C.c_float, C.c_void_p, C.c_size_t,

@@ -65,6 +65,9 @@ class ExtrinsicAdapt(object):
             'num_contact_points': self.ppo_config['num_points'],
             'shared_parameters': self.ppo_config.shared_parameters, 'full_config': full_config, 'vt_policy': False,
         }
+        if agent_config['gt_contacts_info']:
+            raise NotImplementedError("ExtrinsicAdapt with a contact teacher (compute_contact_gt) is not supported: the "
+                                      "student path has no contact encoder")
         self.agent = ActorCritic(agent_config)
         self.agent.to(self.device)
         self.agent.eval()

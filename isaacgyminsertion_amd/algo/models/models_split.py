@@ -36,6 +36,34 @@ class MLP(nn.Module):
         self.mlp = nn.Sequential(*layers)
 
 
+class ContactAE(nn.Module):
+    """Ground-truth contact autoencoder (models_split.py:41-55).  Its Linears keep torch's default initialisation;
+    ``forward_enc`` runs the HIP contact encoder (csrc/contact.h).  The decoder is a state_dict member the trainer never
+    evaluates (no reconstruction loss in the reference); ``forward_dec`` runs it on the native Linear op."""
+
+    def __init__(self, input_size, embedding_size=16):
+        nn.Module.__init__(self)
+        self.embedding_size = embedding_size
+        self.contact_enc_mlp = nn.Sequential(nn.Linear(input_size, 32), nn.ReLU(), nn.Linear(32, embedding_size),
+                                             nn.Tanh())
+        self.contact_dec_mlp = nn.Sequential(nn.Linear(embedding_size, 32), nn.ReLU(), nn.Linear(32, input_size))
+
+    def forward_enc(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("ContactAE runs on the HIP device only (no CPU fallback)")
+        l1, l2 = self.contact_enc_mlp[0], self.contact_enc_mlp[2]
+        packed = torch.cat([l1.weight.detach().reshape(-1), l1.bias.detach(), l2.weight.detach().reshape(-1),
+                            l2.bias.detach()]).to(x.device, torch.float32)
+        emb, _ = torch.ops.mi355ppo.contact_encoder_fwd(x.float().contiguous(), packed, self.embedding_size)
+        return emb
+
+    def forward_dec(self, x):
+        from ...hip_linear import linear
+        l1, l2 = self.contact_dec_mlp[0], self.contact_dec_mlp[2]
+        h = linear(x, l1.weight.detach(), l1.bias.detach(), 'relu')
+        return linear(h, l2.weight.detach(), l2.bias.detach())
+
+
 class ActorCriticSplit(nn.Module):
     def __init__(self, kwargs):
         nn.Module.__init__(self)
@@ -50,14 +78,27 @@ class ActorCriticSplit(nn.Module):
         self.priv_info_dim = kwargs['priv_info_dim']
         self.shared_parameters = kwargs.get('shared_parameters', False)
         self.vt_policy = kwargs.get('vt_policy', False)
-        if not self.priv_info or self.contact_info or self.shared_parameters or self.vt_policy:
-            # reference defaults: priv_info True, compute_contact_gt False, shared_parameters False,
-            # vt_policy hard-wired False (frozen_ppo.py:139) -- the only configuration on the hot path
-            raise NotImplementedError("only priv_info=True, no contacts, separate critic is on the hot path")
+        if not self.priv_info or self.shared_parameters or self.vt_policy:
+            # reference defaults: priv_info True, shared_parameters False, vt_policy hard-wired False
+            # (frozen_ppo.py:139) -- the configurations on the hot path (with or without ground-truth contacts)
+            raise NotImplementedError("only priv_info=True with a separate critic is on the hot path")
         self.obs_dim = mlp_input_shape
         self.actions_num = actions_num
         mlp_input_shape += self.priv_mlp_units[-1]
         self.env_mlp = MLP(units=self.priv_mlp_units, input_size=self.priv_info_dim)
+        self.num_contact_points, self.contact_emb = 0, 0
+        if self.contact_info:                         # models_split.py:78-84
+            self.contact_mlp_units = list(kwargs['contacts_mlp_units'])
+            self.num_contact_points = int(kwargs['num_contact_points'])
+            self.contact_emb = int(self.contact_mlp_units[-1])
+            if self.only_contact and self.contact_emb != self.priv_mlp_units[-1]:
+                raise NotImplementedError("only_contact needs contact_mlp.units[-1] == priv_mlp_units[-1] (the reference "
+                                          "sizes the trunk input as obs + priv latent and feeds it the contact embedding)")
+            self.contact_ae = ContactAE(input_size=self.num_contact_points, embedding_size=self.contact_emb)
+            if not self.only_contact:
+                mlp_input_shape += self.contact_emb
+        elif self.only_contact:
+            raise NotImplementedError("only_contact without compute_contact_gt is not a configuration of the reference")
         self.actor_mlp = MLP(units=self.units, input_size=mlp_input_shape)
         self.critic_mlp = MLP(units=self.units, input_size=mlp_input_shape)
         self.value = layer_init(torch.nn.Linear(self.units[-1], 1), std=1.0)
@@ -76,7 +117,7 @@ class ActorCriticSplit(nn.Module):
     def _layout(self):
         from ...teacher_native import make_cfg, param_layout
         cfg, _ = make_cfg(self.obs_dim, self.priv_info_dim, self.actions_num, self.units, self.priv_mlp_units,
-                          2, 1, 1)
+                          2, 1, 1, **self.contact_kwargs())
         return param_layout(cfg)
 
     def _pack(self, device, flat=None):
@@ -97,6 +138,13 @@ class ActorCriticSplit(nn.Module):
     def bind_flat(self, flat):
         """Adopt the trainer engine's parameter vector (values are copied into it)."""
         self._pack(flat.device, flat)
+
+    def contact_kwargs(self):
+        """The contact fields of the teacher cfg (make_cfg / TeacherEngine keyword arguments)."""
+        if not self.contact_info:
+            return {}
+        return dict(contact_points=self.num_contact_points, contact_emb=self.contact_emb,
+                    only_contact=bool(self.only_contact))
 
     @property
     def flat_params(self):
@@ -123,7 +171,7 @@ class ActorCriticSplit(nn.Module):
             from ...teacher_native import TeacherEngine
             eng = TeacherEngine(4096, 1, 1, units=self.units, priv_units=self.priv_mlp_units,
                                 obs_dim=self.obs_dim, priv_dim=self.priv_info_dim, act_dim=self.actions_num,
-                                device=device)
+                                device=device, **self.contact_kwargs())
             self.bind_flat_to(eng)
             self._engine = eng
         return self._engine
@@ -140,7 +188,11 @@ class ActorCriticSplit(nn.Module):
         if 'latent' in obs_dict and obs_dict['latent'] is not None:
             return self._actor_critic_from_latent(obs_dict)
         eng = self._infer_engine(obs.device)
-        mu, value, latent = eng.infer(obs, obs_dict['priv_info'], want_latent=True, normalize=False)
+        if self.contact_info:                         # models_split.py:172-177: contacts go in raw
+            mu, value, latent = eng.infer_contacts(obs, obs_dict['priv_info'], obs_dict['contacts'], want_latent=True,
+                                                   normalize=False)
+        else:
+            mu, value, latent = eng.infer(obs, obs_dict['priv_info'], want_latent=True, normalize=False)
         logstd = mu * 0 + self.sigma.detach()
         return mu, logstd, value, None, latent
 
@@ -164,8 +216,13 @@ class ActorCriticSplit(nn.Module):
         extrin_gt = None
         if 'priv_info' in obs_dict and obs_dict['priv_info'] is not None:
             with torch.no_grad():
-                _, _, extrin_gt = self._infer_engine(x.device).infer(obs_dict['obs'], obs_dict['priv_info'],
-                                                                      want_latent=True, normalize=False)
+                eng = self._infer_engine(x.device)
+                if self.contact_info:
+                    _, _, extrin_gt = eng.infer_contacts(obs_dict['obs'], obs_dict['priv_info'], obs_dict['contacts'],
+                                                         want_latent=True, normalize=False)
+                else:
+                    _, _, extrin_gt = eng.infer(obs_dict['obs'], obs_dict['priv_info'], want_latent=True,
+                                                normalize=False)
         logstd = mu * 0 + self.sigma.detach()
         return mu, logstd, value, obs_dict['latent'], extrin_gt
 

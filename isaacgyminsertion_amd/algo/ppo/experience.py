@@ -202,7 +202,7 @@ class _LazyEnvMajor:
 
 class ExperienceBuffer(Dataset):
     def __init__(self, num_envs, horizon_length, batch_size, minibatch_size, obs_dim, act_dim, priv_dim, pts_dim,
-                 vt_poilcy, device, engine=None):
+                 vt_poilcy, device, engine=None, contacts=False):
         if vt_poilcy:
             raise NotImplementedError("vt_policy is a dead branch in the reference (frozen_ppo.py:139)")
         self.device = torch.device(device)
@@ -212,12 +212,14 @@ class ExperienceBuffer(Dataset):
         self.data_dict = None
         self.obs_dim, self.act_dim, self.priv_dim, self.pts_dim = obs_dim, act_dim, priv_dim, pts_dim
         self.vt_policy = vt_poilcy
+        self.contacts = bool(contacts)   # compute_contact_gt: real (T, N, pts) storage, read by the update
         T, N, f32 = horizon_length, num_envs, dict(dtype=torch.float32, device=self.device)
         self.storage_dict = {
             'obses': torch.zeros((T, N, obs_dim), **f32),
             'priv_info': torch.zeros((T, N, priv_dim), **f32),
             # (T,N,pts) zeros in the reference even when unused; kept as a broadcast view (no HBM cost)
-            'contacts': torch.zeros((1, 1, pts_dim), **f32).expand(T, N, pts_dim),
+            'contacts': torch.zeros((T, N, pts_dim), **f32) if self.contacts else
+            torch.zeros((1, 1, pts_dim), **f32).expand(T, N, pts_dim),
             'rewards': torch.zeros((T, N, 1), **f32),
             'values': torch.zeros((T, N, 1), **f32),
             'neglogpacs': torch.zeros((T, N), **f32),
@@ -269,7 +271,7 @@ class ExperienceBuffer(Dataset):
         eng.sigmas_w[b % T, b // T] = sigma
 
     def update_data(self, name, index, val):
-        if name == 'contacts':
+        if name == 'contacts' and not self.contacts:
             return
         self.storage_dict[name][index, :] = val
 
@@ -285,7 +287,8 @@ class ExperienceBuffer(Dataset):
         eng.cfg.gamma, eng.cfg.tau = float(self.gamma), float(self.tau)
         eng.hp["normalize_value"] = value_mean_std is not None
         ro = dict(self.storage_dict)
-        ro.pop('contacts')
+        if not getattr(eng, "contact_points", 0):
+            ro.pop('contacts')
         ro.pop('returns')
         ro['last_values'] = self.last_values
         if not getattr(eng, "_workspace_tuned", False):

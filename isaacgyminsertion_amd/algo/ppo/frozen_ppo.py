@@ -172,7 +172,8 @@ class PPO(object):
 
         self.storage = ExperienceBuffer(self.num_actors, self.horizon_length, self.batch_size,
                                         self.minibatch_size, self.obs_shape[0], self.actions_num,
-                                        self.priv_info_dim, self.num_contacts_points, self.vt_policy, self.device)
+                                        self.priv_info_dim, self.num_contacts_points, self.vt_policy, self.device,
+                                        contacts=self.gt_contacts_info)
 
         # ---- native engine: owns the flat parameter / gradient / Adam vectors and the workspace;
         #      model parameters and normaliser buffers become views into it
@@ -182,7 +183,7 @@ class PPO(object):
             priv_dim=self.priv_info_dim, act_dim=self.actions_num, device=self.device, perm=self.storage.indices,
             gamma=self.gamma, tau=self.tau, lr=self.last_lr, e_clip=self.e_clip, critic_coef=self.critic_coef,
             entropy_coef=self.entropy_coef, bounds_loss_coef=self.bounds_loss_coef, grad_norm=self.grad_norm,
-            truncate_grads=self.truncate_grads, normalize_value=self.normalize_value)
+            truncate_grads=self.truncate_grads, normalize_value=self.normalize_value, **self.model.contact_kwargs())
         self.model.bind_flat_to(self.engine)
         self.model.attach_engine(self.engine)
         self.running_mean_std.bind(self.engine.rms_obs)
@@ -249,6 +250,13 @@ class PPO(object):
         actions, mu, sigma, clamped = (torch.empty((n, a), **f32) for _ in range(4))
         nlp, values, values_out = torch.empty(n, **f32), torch.empty((n, 1), **f32), torch.empty((n, 1), **f32)
         noise = torch.randn_like(mu)
+        if self.gt_contacts_info:   # frozen_ppo.py:357-358: the raw contacts go to the contact encoder
+            cts = obs_dict['contacts'].to(**f32).contiguous()
+            torch.ops.mi355ppo.rollout_policy_step_contacts(
+                eng.state_list(), *eng._cfg_args(), obs, priv, cts, True, noise,
+                self.value_mean_std._packed if self.normalize_value else None, None, None, None,
+                actions, nlp, values, mu, sigma, clamped, values_out)
+            return {'neglogpacs': nlp, 'values': values, 'actions': actions, 'mus': mu, 'sigmas': sigma}
         # ONE native call: normalise, env_mlp, trunk, heads, sample, neglogp, value de-normalisation
         torch.ops.mi355ppo.rollout_policy_step(eng.state_list(), *eng._cfg_args(), obs, priv, True, noise,
                                                self.value_mean_std._packed if self.normalize_value else None,
@@ -418,9 +426,16 @@ class PPO(object):
             priv = self.obs['priv_info'].to(**f32).contiguous()
             noise = torch.randn_like(clamped)       # the reference's draw: Normal sampling is mu + sigma * randn_like(mu)
             # policy forward + sampling + arena writes of this step: one native call (igi_rollout_policy_step)
-            policy_step(state, icfg, fcfg, obs, priv, True, noise, rms_v, sd['obses'][n], sd['priv_info'][n],
-                        sd['actions'][n], sd['neglogpacs'][n], sd['values'][n], sd['mus'][n], sd['sigmas'][n],
-                        clamped, values)
+            if self.gt_contacts_info:   # + the contact encoder and the contacts' arena slot (frozen_ppo.py:663-664)
+                cts = self.obs['contacts'].to(**f32).contiguous()
+                torch.ops.mi355ppo.rollout_policy_step_contacts(
+                    state, icfg, fcfg, obs, priv, cts, True, noise, rms_v, sd['obses'][n], sd['priv_info'][n],
+                    sd['contacts'][n], sd['actions'][n], sd['neglogpacs'][n], sd['values'][n], sd['mus'][n],
+                    sd['sigmas'][n], clamped, values)
+            else:
+                policy_step(state, icfg, fcfg, obs, priv, True, noise, rms_v, sd['obses'][n], sd['priv_info'][n],
+                            sd['actions'][n], sd['neglogpacs'][n], sd['values'][n], sd['mus'][n], sd['sigmas'][n],
+                            clamped, values)
             self.obs, rewards, self.dones, infos = self.env.step(clamped)
             assert isinstance(infos, dict), 'Info Should be a Dict'
             rewards = rewards.to(**f32).contiguous()
@@ -459,7 +474,10 @@ class PPO(object):
         steps, last = 0, int(getattr(self.env, 'max_episode_length', total_steps)) - 1
         while steps < min(total_steps, last):
             steps += 1
-            mu, _ = self.engine.infer(obs['obs'], obs['priv_info'], normalize=True)
+            if self.gt_contacts_info:
+                mu, _ = self.engine.infer_contacts(obs['obs'], obs['priv_info'], obs['contacts'], normalize=True)
+            else:
+                mu, _ = self.engine.infer(obs['obs'], obs['priv_info'], normalize=True)
             obs, r, done, info = self.env.step(torch.clamp(mu, -1.0, 1.0))
         if not hasattr(self.env, 'test_reset_buf'):
             return 0, 0

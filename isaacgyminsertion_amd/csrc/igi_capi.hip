@@ -235,6 +235,12 @@ int igi_teacher_param_offsets(const igi_teacher_cfg* cfg, int64_t* off, int64_t*
   };
   put(p.o_sigma, p.act);
   for (int l = 0; l < p.npl; ++l) { put(p.o_envW[l], (long long)p.pu[l] * igi::env_in(p, l)); put(p.o_envB[l], p.pu[l]); }
+  if (p.ct_P > 0) {   // contact_ae.contact_enc_mlp.{0,2}, contact_ae.contact_dec_mlp.{0,2}
+    put(p.o_ctW1, (long long)igi::CT_HID * p.ct_P); put(p.o_ctB1, igi::CT_HID);
+    put(p.o_ctW2, (long long)p.ct_E * igi::CT_HID); put(p.o_ctB2, p.ct_E);
+    put(p.o_cdW1, (long long)igi::CT_HID * p.ct_E); put(p.o_cdB1, igi::CT_HID);
+    put(p.o_cdW2, (long long)p.ct_P * igi::CT_HID); put(p.o_cdB2, p.ct_P);
+  }
   for (int net = 0; net < 2; ++net)
     for (int l = 0; l < p.nl; ++l) {
       put(p.o_acW[l] + net * p.ac_block, (long long)p.u[l] * igi::ac_in(p, l));
@@ -346,6 +352,72 @@ int igi_rollout_policy_step(const igi_teacher_cfg* cfg, const igi_teacher_state*
   return fail(igi::teacher_policy_step(cfg, st, obs, priv, rows, normalize, noise, rms_value, obses_t, priv_t,
                                        actions_t, neglogp_t, values_t, mus_t, sigmas_t, actions_clamped, values_out,
                                        S(stream)), "igi_rollout_policy_step");
+}
+
+int igi_teacher_infer_contacts(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* obs,
+                               const float* priv, const float* contacts, int64_t rows, int normalize, float* mu,
+                               float* value, float* latent, igi_stream_t stream) {
+  if (!contacts) return fail(IGI_E_BADARG, "igi_teacher_infer_contacts");
+  return fail(igi::teacher_infer(cfg, st, obs, priv, rows, normalize, mu, value, latent, S(stream), contacts),
+              "igi_teacher_infer_contacts");
+}
+
+int igi_rollout_policy_step_contacts(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* obs,
+                                     const float* priv, const float* contacts, int64_t rows, int normalize,
+                                     const float* noise, const double* rms_value, float* obses_t, float* priv_t,
+                                     float* contacts_t, float* actions_t, float* neglogp_t, float* values_t,
+                                     float* mus_t, float* sigmas_t, float* actions_clamped, float* values_out,
+                                     igi_stream_t stream) {
+  if (!contacts) return fail(IGI_E_BADARG, "igi_rollout_policy_step_contacts");
+  return fail(igi::teacher_policy_step(cfg, st, obs, priv, rows, normalize, noise, rms_value, obses_t, priv_t,
+                                       actions_t, neglogp_t, values_t, mus_t, sigmas_t, actions_clamped, values_out,
+                                       S(stream), contacts, contacts_t), "igi_rollout_policy_step_contacts");
+}
+
+static bool contact_shape_ok(int64_t rows, int P, int E) {
+  return rows >= 1 && rows <= (1LL << 30) && P >= 1 && E >= 1 && E <= igi::CT_MAX_EMB;
+}
+
+int igi_contact_encoder_forward(const float* contacts, int64_t rows, int P, int E, const float* params, float* emb,
+                                float* hidden, igi_stream_t stream) {
+  if (!contacts || !params || !emb || !hidden || !contact_shape_ok(rows, P, E))
+    return fail(IGI_E_BADARG, "igi_contact_encoder_forward");
+  igi::ContactArgs a;
+  a.C = contacts; a.rows = (int)rows; a.N = (int)rows; a.T = 1; a.P = P; a.E = E;
+  a.W1 = params; a.b1 = a.W1 + (long long)igi::CT_HID * P; a.W2 = a.b1 + igi::CT_HID; a.b2 = a.W2 + E * igi::CT_HID;
+  a.H = hidden; a.out = emb; a.ldo = E;
+  return fail((int)igi::contact_forward(a, S(stream)), "igi_contact_encoder_forward");
+}
+
+size_t igi_contact_encoder_workspace_bytes(int64_t rows, int P, int E) {
+  if (!contact_shape_ok(rows, P, E)) return 0;
+  return sizeof(float) * (size_t)igi::ct_bwd_blocks((int)rows) * (size_t)igi::ct_rec_floats(P, E);
+}
+
+int igi_contact_encoder_backward(const float* contacts, int64_t rows, int P, int E, const float* params,
+                                 const float* hidden, const float* dz, float* grads, void* workspace,
+                                 size_t workspace_bytes, igi_stream_t stream) {
+  if (!contacts || !params || !hidden || !dz || !grads || !workspace || !contact_shape_ok(rows, P, E))
+    return fail(IGI_E_BADARG, "igi_contact_encoder_backward");
+  if (workspace_bytes < igi_contact_encoder_workspace_bytes(rows, P, E))
+    return fail(IGI_E_WORKSPACE, "igi_contact_encoder_backward");
+  igi::ContactArgs a;
+  a.C = contacts; a.rows = (int)rows; a.N = (int)rows; a.T = 1; a.P = P; a.E = E;
+  a.W1 = params; a.b1 = a.W1 + (long long)igi::CT_HID * P; a.W2 = a.b1 + igi::CT_HID; a.b2 = a.W2 + E * igi::CT_HID;
+  a.H = const_cast<float*>(hidden); a.dZ = dz; a.ldz = E;
+  a.part = static_cast<float*>(workspace); a.rec = igi::ct_rec_floats(P, E);
+  hipStream_t s = S(stream);
+  int rc = (int)igi::contact_backward(a, s);
+  if (rc) return fail(rc, "igi_contact_encoder_backward");
+  // the partial records in index order (the teacher's k_slab_reduce), packed like params
+  igi::SegTable t;
+  t.n = 1;
+  igi::Segment& sg = t.s[0];
+  sg.dst = 0; sg.src = a.part; sg.stride = a.rec;
+  sg.count = (int)(igi::CT_HID * (long long)P + igi::CT_HID + E * igi::CT_HID + E);
+  sg.cols = sg.count; sg.src_ld = 0; sg.nparts = igi::ct_bwd_blocks((int)rows);
+  IGI_LAUNCH(igi::k_slab_reduce, dim3(64, 1), dim3(igi::RED_THREADS), 0, s, t, grads);
+  return fail((int)hipGetLastError(), "igi_contact_encoder_backward");
 }
 
 size_t igi_clip_adam_workspace_bytes(void) { return sizeof(double) * 2 * igi::SUMSQ_BLOCKS; }

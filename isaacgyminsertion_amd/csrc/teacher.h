@@ -24,6 +24,7 @@
 #include "fwd12.h"
 #include "gemm_f32.h"
 #include "rollout.h"
+#include "contact.h"
 
 namespace igi {
 
@@ -57,6 +58,11 @@ struct TeacherPlan {
   int N, T, E, mb, nmb;
   long long Bsz;
   int latent, xw, xld;  // xcat = [obs_n | latent | 0...], width xw, leading dim xld (multiple of 32)
+  // ground-truth contacts (cfg contact_points > 0): xcat = [obs_n | latent | contact embedding | 0...], or
+  // [obs_n | contact embedding | 0...] with only_contact (env_mlp is then neither run nor trained)
+  int ct_P, ct_E, ct_only, ct_col, ct_blocks;
+  long long o_ctW1, o_ctB1, o_ctW2, o_ctB2, o_cdW1, o_cdB1, o_cdW2, o_cdB2, ct_rec;
+  size_t w_ct_h, w_ct_part;
   int u0p;              // first trunk width rounded up to 4
   // parameter offsets (floats) in the flat vector
   long long o_sigma, o_envW[IGI_MAX_LAYERS], o_envB[IGI_MAX_LAYERS];
@@ -147,7 +153,13 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   if (p->mb < 2) return IGI_E_BADARG;
   p->nmb = (int)(p->Bsz / p->mb);
   p->latent = p->pu[p->npl - 1];
-  p->xw = p->obs + p->latent;
+  p->ct_P = c->contact_points; p->ct_E = c->contact_emb; p->ct_only = c->only_contact;
+  if (p->ct_P < 0 || p->ct_E < 0 || p->ct_only < 0 || p->ct_only > 1) return IGI_E_BADARG;
+  if (p->ct_P == 0 && (p->ct_E != 0 || p->ct_only)) return IGI_E_BADARG;
+  if (p->ct_P > 0 && (p->ct_E < 1 || p->ct_E > CT_MAX_EMB)) return IGI_E_BADARG;
+  if (p->ct_only && p->ct_E != p->latent) return IGI_E_UNSUPPORTED;   // the reference's trunk width is obs + latent
+  p->ct_col = p->obs + (p->ct_only ? 0 : p->latent);
+  p->xw = p->ct_col + p->ct_E;
   p->xld = (p->xw + 31) & ~31;  // zero-padded to the LDS-DMA kernel's k-tile
   p->u0p = ru4(p->u[0]);
 
@@ -158,6 +170,12 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   for (int l = 0; l < p->npl; ++l) {
     p->o_envW[l] = put((long long)p->pu[l] * env_in(*p, l));
     p->o_envB[l] = put(p->pu[l]);
+  }
+  if (p->ct_P > 0) {   // contact_ae: encoder then decoder, state_dict order (models_split.py:45-47)
+    p->o_ctW1 = put((long long)CT_HID * p->ct_P); p->o_ctB1 = put(CT_HID);
+    p->o_ctW2 = put((long long)p->ct_E * CT_HID); p->o_ctB2 = put(p->ct_E);
+    p->o_cdW1 = put((long long)CT_HID * p->ct_E); p->o_cdB1 = put(CT_HID);
+    p->o_cdW2 = put((long long)p->ct_P * CT_HID); p->o_cdB2 = put(p->ct_P);
   }
   long long ac0 = o;
   for (int l = 0; l < p->nl; ++l) {
@@ -192,7 +210,7 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   {
     const int K2 = 2 * ru4(p->u[0]);
     // LDS: transposed weight slice 8 x (K2p+4) + 32 x 260 staging tile (also hosts the 4 x (8*H2+8) final reduction)
-    p->lat_fused = (p->latent == 8 && p->npl >= 2 && p->pu[p->npl - 2] <= 256 && K2 <= 2048) ? 1 : 0;
+    p->lat_fused = (p->latent == 8 && p->ct_P == 0 && p->npl >= 2 && p->pu[p->npl - 2] <= 256 && K2 <= 2048) ? 1 : 0;
     p->lat_rpw = 0;
     p->lat_blocks = (int)((mb + 31) / 32);
     p->w_lat_part = p->lat_fused ? take(sizeof(float) * (size_t)p->lat_blocks * (8 * p->pu[p->npl - 2] + 8)) : 0;
@@ -205,6 +223,12 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   p->w_xcat = take(sizeof(float) * mb * p->xld);
   p->w_dxcat = take(sizeof(float) * mb * p->xld);
   p->w_w1p = take(sizeof(float) * 2 * p->u0p * p->xld);
+  if (p->ct_P > 0) {
+    p->ct_blocks = ct_bwd_blocks(p->mb);
+    p->ct_rec = ct_rec_floats(p->ct_P, p->ct_E);
+    p->w_ct_h = take(sizeof(float) * mb * CT_HID);
+    p->w_ct_part = take(sizeof(float) * (size_t)p->ct_blocks * p->ct_rec);
+  }
   for (int l = 0; l < p->npl; ++l) {
     // rows rounded up to the fused env_mlp kernel's 64-row blocks: it stores whole blocks (env_mlp.h)
     p->w_e[l] = (l < p->npl - 1) ? take(sizeof(float) * ((mb + 63) / 64 * 64) * ru4(p->pu[l])) : 0;
@@ -274,7 +298,7 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
     p->sk_env[l] = pick(sk, sk_over[l], p->mb);
     // layer l's weight gradient and the data gradient into layer l - 1 as one row-block kernel (the last layer's
     // backward is k_latent_bwd's when lat_fused): decided from the shapes alone, like every other plan entry
-    if (l >= 1 && l < p->npl - p->lat_fused && rb_level_shape_ok(p->mb, p->pu[l], p->pu[l - 1], 1)) {
+    if (l >= 1 && l < p->npl - p->lat_fused - (p->ct_P > 0) && rb_level_shape_ok(p->mb, p->pu[l], p->pu[l - 1], 1)) {
       p->rb_env[l] = rb_level_ranges(p->mb, p->pu[l - 1], 1);
       p->sk_env[l] = p->rb_env[l];
     }
@@ -2394,9 +2418,12 @@ __global__ __launch_bounds__(256) void k_latent_bwd(const float* __restrict__ dz
 
 // forward through env_mlp -> xcat -> actor/critic trunk for `rows` rows already staged
 // (normalised) in priv_g / xcat.
+// (the contact-encoder arguments of this call, filled by contact_args: required in contact mode)
 static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int rows, bool pad_w1, hipStream_t s,
-                         int nl_run = -1) {   // nl_run: trunk layers to run (the training step leaves the last one to k_trunk_loss)
+                         int nl_run = -1,   // nl_run: trunk layers to run (the training step leaves the last one to k_trunk_loss)
+                         const ContactArgs* ct = nullptr) {
   if (nl_run < 0) nl_run = p.nl;
+  if (p.ct_P > 0 && !ct) return IGI_E_BADARG;
   const float* P = st->params;
   float* priv_g = wsp<float>(st, p.w_priv);
   float* xcat = wsp<float>(st, p.w_xcat);
@@ -2414,11 +2441,11 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
   if (fuse_head < 0) { const char* e = getenv("IGI_FUSE_HEAD"); fuse_head = e ? atoi(e) : 1; }
   static int env_fused = -1;
   if (env_fused < 0) { const char* e = getenv("IGI_ENV_FUSED"); env_fused = e ? atoi(e) : 1; }
-  bool env_done = false;
+  bool env_done = p.ct_only != 0;   // only_contact: the privileged embedding is not used (models_split.py:176-177)
   int first_trunk_layer = 0;
   // round 6: env_mlp AND the first trunk layer of both nets as one persistent launch (fwd12.h); IGI_FWD12=0 keeps
   // k_env_fwd + the layer's own launch below
-  if (fwd12_enabled() && env_fused && p.npl == 3 && nl_run >= 1 && rows >= 2048 && !bf16_mode() &&
+  if (fwd12_enabled() && env_fused && p.npl == 3 && p.ct_P == 0 && nl_run >= 1 && rows >= 2048 && !bf16_mode() &&
       fwd12_supported(p.priv, p.pu[0], p.pu[1], p.pu[2], p.obs, p.xld, p.u[0]) && p.u0p == p.u[0]) {
     Fwd12Args f;
     f.priv = priv_g; f.ldp = ldin; f.xcat = xcat; f.ldx = p.xld; f.M = rows; f.obs = p.obs;
@@ -2463,6 +2490,10 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
     }
     IGI_HIP_TRY(gemm(g, true, true, s));
     in = g.C; ldin = g.ldc;
+  }
+  if (p.ct_P > 0) {   // contact embedding -> xcat[:, ct_col:ct_col + ct_E]
+    const hipError_t e = contact_forward(*ct, s);
+    if (e != hipSuccess) return (int)e;
   }
   // actor + critic, batched (critic parameters sit ac_block floats after the actor's)
   in = xcat; ldin = p.xld;
@@ -2568,6 +2599,22 @@ static bool latent_rowdot(const TeacherPlan& p, const igi_teacher_state* st) {
 // norm_parts (phase -1 only): non-null turns the norm fusion on -- k_slab_reduce also leaves the gradient's sum-of-squares
 // partials (their count comes back in *norm_parts) and writes this step's statistics row; the caller then runs
 // teacher_apply(..., norm_mode 2), which does not launch k_sumsq_stats
+// the contact encoder of a minibatch (perm != nullptr: rows start.. of the permutation over the (T, N, P) arena) or of
+// `rows` plain rows (perm == nullptr, T = 1)
+static ContactArgs contact_args(const TeacherPlan& p, const igi_teacher_state* st, const float* contacts,
+                                const int64_t* perm, long long start, int rows) {
+  ContactArgs a;
+  const float* P = st->params;
+  a.C = contacts; a.perm = perm; a.start = start; a.rows = rows;
+  a.N = perm ? p.N : rows; a.T = perm ? p.T : 1; a.P = p.ct_P; a.E = p.ct_E;
+  a.W1 = P + p.o_ctW1; a.b1 = P + p.o_ctB1; a.W2 = P + p.o_ctW2; a.b2 = P + p.o_ctB2;
+  a.H = wsp<float>(st, p.w_ct_h);
+  a.out = wsp<float>(st, p.w_xcat) + p.ct_col; a.ldo = p.xld;
+  a.dZ = wsp<float>(st, p.w_dxcat) + p.ct_col; a.ldz = p.xld;
+  a.part = wsp<float>(st, p.w_ct_part); a.rec = p.ct_rec;
+  return a;
+}
+
 static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
                            const igi_teacher_state* st, int mb_index, int step_slot, hipStream_t s,
                            int phase = -1, bool skip_gather = false, int* norm_parts = nullptr) {
@@ -2577,10 +2624,11 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   if ((rc = check_state(p, st))) return rc;
   if (!ro || !ro->obses || !ro->priv_info || !ro->actions || !ro->neglogpacs || !st->grads ||
       !st->perm || !st->rms_obs || !st->rms_priv || !st->stats || !st->advantages ||
-      mb_index < 0 || mb_index >= p.nmb || step_slot < 0)
+      mb_index < 0 || mb_index >= p.nmb || step_slot < 0 || (p.ct_P > 0 && !ro->contacts))
     return IGI_E_BADARG;
   const float* P = st->params;
   const int mb = p.mb;
+  const ContactArgs cta = p.ct_P > 0 ? contact_args(p, st, ro->contacts, st->perm, (long long)mb_index * p.mb, p.mb) : ContactArgs();
   const long long mbs = mb;
   float* priv_g = wsp<float>(st, p.w_priv);
   float* xcat = wsp<float>(st, p.w_xcat);
@@ -2601,7 +2649,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
     IGI_LAUNCH(k_gather_normalize, dim3(p.gs_blocks + pad_blocks), dim3(GS_THREADS), 0, s, ga);
   }
   // ---- forward trunk (models_split.py:166-232)
-  if (do0 && (rc = trunk_forward(p, st, mb, false, s, p.loss_fused ? p.nl - 1 : p.nl))) return rc;
+  if (do0 && (rc = trunk_forward(p, st, mb, false, s, p.loss_fused ? p.nl - 1 : p.nl, p.ct_P > 0 ? &cta : nullptr))) return rc;
 
   // ---- heads + loss + head backward.  d(pre-activation) of the FIRST trunk layer is kept
   // interleaved [row][net][u0p] so that the dgrad into xcat is one contraction over both nets.
@@ -2771,7 +2819,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
 #undef IGI_LATP
         } else if (maxj <= 2) IGI_LATB(2); else IGI_LATB(4);
 #undef IGI_LATB
-      } else if (p.latent == 8 && K2 % 256 == 0 && K2 <= 1024) {
+      } else if (p.latent == 8 && p.ct_P == 0 && K2 % 256 == 0 && K2 <= 1024) {
         ProfScope ps(PC_OTHER, s, 2.0 * mbs * K2 * 8, 4.0 * mbs * K2);
         const int rpw = 8;
         const int nb = (mb + 4 * rpw - 1) / (4 * rpw);
@@ -2790,10 +2838,14 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
         g.epilogue = EPI_TANHGRAD;
         IGI_HIP_TRY(gemm(g, true, false, s));
       }
+      if (p.ct_P > 0) {   // contact encoder backward from d(pre-tanh) of its columns of dxcat
+        const hipError_t e = contact_backward(cta, s);
+        if (e != hipSuccess) return (int)e;
+      }
     }
   }
   // ---- backward through env_mlp (its last layer is already done when k_latent_bwd ran)
-  for (int l = p.npl - 1 - p.lat_fused; l >= 0 && do1; --l) {
+  for (int l = p.npl - 1 - p.lat_fused; l >= 0 && do1 && !p.ct_only; --l) {
     const int out = p.pu[l], in = env_in(p, l);
     const bool last = (l == p.npl - 1);
     const float* dz = last ? dxcat + p.obs : wsp<float>(st, p.w_de[l]);
@@ -2874,7 +2926,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
     add(p.o_valB, hs + p.act * H + p.act + H, hc, 1, 1, 0, p.loss_blocks);
   }
   if (do1) add(p.o_sigma, hs + p.act * H + p.act + H + 1, hc, 1, p.act, 0, p.loss_blocks);
-  for (int l = 0; l < p.npl - p.lat_fused && do1; ++l) {
+  for (int l = 0; l < p.npl - p.lat_fused && do1 && !p.ct_only; ++l) {
     const int out = p.pu[l], in = env_in(p, l);
     add(p.o_envW[l], slab + p.s_envW[l], (long long)out * in, 1, out * in, 0, p.sk_env[l]);
     add(p.o_envB[l], slab + p.s_envB[l], out, 1, out, 0, p.sk_env[l]);
@@ -2885,6 +2937,15 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
     const int nrec = (p.latz && latent_rowdot(p, st)) ? p.rb_env[1] : p.lat_blocks;   // LATZ: one record per row range
     add(p.o_envW[p.npl - 1], part, pc, 1, 8 * H2, 0, nrec);
     add(p.o_envB[p.npl - 1], part + 8 * H2, pc, 1, 8, 0, nrec);
+  }
+  if (p.ct_P > 0 && do1) {   // encoder partial records [dW1 | db1 | dW2 | db2]; the decoder's slots are never written
+    if (t.n + 4 > MAX_SEG) return IGI_E_UNSUPPORTED;
+    const float* part = wsp<float>(st, p.w_ct_part);
+    const long long w1 = (long long)CT_HID * p.ct_P;
+    add(p.o_ctW1, part, p.ct_rec, 1, (int)w1, 0, p.ct_blocks);
+    add(p.o_ctB1, part + w1, p.ct_rec, 1, CT_HID, 0, p.ct_blocks);
+    add(p.o_ctW2, part + w1 + CT_HID, p.ct_rec, 1, p.ct_E * CT_HID, 0, p.ct_blocks);
+    add(p.o_ctB2, part + w1 + CT_HID + p.ct_E * CT_HID, p.ct_rec, 1, p.ct_E, 0, p.ct_blocks);
   }
   for (int l = 0; l < p.nl; ++l) {
     if (!(l > 0 ? do0 : do1)) continue;
@@ -3045,12 +3106,14 @@ static int teacher_update_dp(const igi_teacher_cfg* c, const igi_rollout* ro, co
 
 static int teacher_infer(const igi_teacher_cfg* c, const igi_teacher_state* st, const float* obs,
                          const float* priv, int64_t rows, int normalize, float* mu, float* value,
-                         float* latent, hipStream_t s) {
+                         float* latent, hipStream_t s, const float* contacts = nullptr) {
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
   if ((rc = check_state(p, st))) return rc;
   if (!obs || !priv || rows < 0 || (normalize && (!st->rms_obs || !st->rms_priv))) return IGI_E_BADARG;
+  if (p.ct_P > 0 && !contacts) return IGI_E_BADARG;
+  const int lat_w = p.xw - p.obs;   // latent_gt: [priv latent | contact embedding] (models_split.py:172-177)
   float* priv_g = wsp<float>(st, p.w_priv);
   float* xcat = wsp<float>(st, p.w_xcat);
   float* ncoef = wsp<float>(st, p.w_norm_coef);
@@ -3071,10 +3134,11 @@ static int teacher_infer(const igi_teacher_cfg* c, const igi_teacher_state* st, 
     if (normalize)
       IGI_LAUNCH(k_normalize, dim3(nb), dim3(256), 0, s, xcat, p.xld, p.xw, priv_g, pld, nr, p.obs,
                          p.priv, ncoef);
-    if ((rc = trunk_forward(p, st, nr, true, s))) return rc;
+    const ContactArgs cta = p.ct_P > 0 ? contact_args(p, st, contacts + r0 * p.ct_P, nullptr, 0, nr) : ContactArgs();
+    if ((rc = trunk_forward(p, st, nr, true, s, -1, p.ct_P > 0 ? &cta : nullptr))) return rc;
     if (latent)
-      IGI_HIP_TRY(hipMemcpy2DAsync(latent + r0 * p.latent, sizeof(float) * p.latent, xcat + p.obs,
-                                   sizeof(float) * p.xld, sizeof(float) * p.latent, nr,
+      IGI_HIP_TRY(hipMemcpy2DAsync(latent + r0 * lat_w, sizeof(float) * lat_w, xcat + p.obs,
+                                   sizeof(float) * p.xld, sizeof(float) * lat_w, nr,
                                    hipMemcpyDeviceToDevice, s));
     if (mu || value) {
       const float* P = st->params;
@@ -3232,7 +3296,8 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
                                const float* priv, int64_t rows, int normalize, const float* noise,
                                const double* rms_value, float* obses_t, float* priv_t, float* actions_t, float* nlp_t,
                                float* values_t, float* mus_t, float* sigmas_t, float* actions_clamped,
-                               float* values_out, hipStream_t s) {
+                               float* values_out, hipStream_t s, const float* contacts = nullptr,
+                               float* contacts_t = nullptr) {   // contacts_t: slot t of the (T, N, P) arena, may be NULL
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
@@ -3241,6 +3306,7 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
       !actions_clamped || !values_out || (normalize && (!st->rms_obs || !st->rms_priv)))
     return IGI_E_BADARG;
   if (p.act > 64) return IGI_E_UNSUPPORTED;
+  if (p.ct_P > 0 && !contacts) return IGI_E_BADARG;
   const float* P = st->params;
   const int H = p.u[p.nl - 1];
   const int ldh = ru4(H);
@@ -3264,7 +3330,7 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
       ProfScope ps(PC_OTHER, s, 0.0, 8.0 * tot);
       IGI_LAUNCH(k_policy_stage, dim3(nb + pad_blocks), dim3(256), 0, s, a);
     }
-    if (policy_fwd_enabled() && !bf16_mode() && policy_fwd_shape_ok(p.obs, p.priv, p.act, p.npl, p.pu, p.nl, p.u) && p.xld == 32) {
+    if (p.ct_P == 0 && policy_fwd_enabled() && !bf16_mode() && policy_fwd_shape_ok(p.obs, p.priv, p.act, p.npl, p.pu, p.nl, p.u) && p.xld == 32) {
       // env_mlp, both trunks, the heads, the sample and the arena writes of these rows as ONE persistent launch (policy_fwd.h)
       PolicyFwdArgs f;
       f.priv = a.priv_g; f.ldp = a.pld; f.xcat = a.xcat; f.ldx = p.xld; f.rows = nr; f.obs = p.obs; f.act = p.act;
@@ -3281,7 +3347,11 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
       if (e == hipSuccess) continue;
       if (e != hipErrorInvalidValue) return (int)e;      // (alignment of the caller's buffers: the per-layer launches below)
     }
-    if ((rc = trunk_forward(p, st, nr, false, s))) return rc;
+    const ContactArgs cta = p.ct_P > 0 ? contact_args(p, st, contacts + r0 * p.ct_P, nullptr, 0, nr) : ContactArgs();
+    if ((rc = trunk_forward(p, st, nr, false, s, -1, p.ct_P > 0 ? &cta : nullptr))) return rc;
+    if (p.ct_P > 0 && contacts_t)   // the arena write of this step's contacts (frozen_ppo.py:663-664), raw
+      IGI_HIP_TRY(hipMemcpyAsync(contacts_t + r0 * p.ct_P, contacts + r0 * p.ct_P, sizeof(float) * nr * p.ct_P,
+                                 hipMemcpyDeviceToDevice, s));
     ActStoreArgs t;
     t.logstd = P + p.o_sigma; t.noise = noise + r0 * p.act; t.rms_value = rms_value; t.eps = c->rms_eps;
     t.actions_t = actions_t + r0 * p.act; t.nlp_t = nlp_t + r0; t.values_t = values_t + r0;

@@ -52,14 +52,18 @@ float* fpo(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(
 // ---- teacher marshalling: (int[] icfg, float[] fcfg) <-> struct igi_teacher_cfg, tensor lists <-> the structs
 igi_teacher_cfg unpack_cfg(at::IntArrayRef ic, at::ArrayRef<double> fc) {
   constexpr int M = IGI_MAX_LAYERS;
-  TORCH_CHECK((int)ic.size() == 8 + 2 * M && fc.size() == 12, "teacher cfg: expected ", 8 + 2 * M, " ints and 12 floats, got ",
-              ic.size(), " and ", fc.size());
+  TORCH_CHECK(((int)ic.size() == 8 + 2 * M || (int)ic.size() == 11 + 2 * M) && fc.size() == 12, "teacher cfg: expected ",
+              8 + 2 * M, " (or ", 11 + 2 * M, " with contacts) ints and 12 floats, got ", ic.size(), " and ", fc.size());
   igi_teacher_cfg c;
   std::memset(&c, 0, sizeof(c));
   c.obs_dim = (int32_t)ic[0]; c.priv_dim = (int32_t)ic[1]; c.act_dim = (int32_t)ic[2]; c.n_priv_layers = (int32_t)ic[3];
   for (int i = 0; i < M; ++i) { c.priv_units[i] = (int32_t)ic[4 + i]; c.units[i] = (int32_t)ic[5 + M + i]; }
   c.n_layers = (int32_t)ic[4 + M];
   c.num_envs = (int32_t)ic[5 + 2 * M]; c.horizon = (int32_t)ic[6 + 2 * M]; c.mini_epochs = (int32_t)ic[7 + 2 * M];
+  if ((int)ic.size() == 11 + 2 * M) {   // contact mode (ops.py pack_cfg)
+    c.contact_points = (int32_t)ic[8 + 2 * M]; c.contact_emb = (int32_t)ic[9 + 2 * M]; c.only_contact = (int32_t)ic[10 + 2 * M];
+    TORCH_CHECK(c.contact_points >= 1, "teacher cfg: the contact fields need contact_points >= 1");
+  }
   c.gamma = fc[0]; c.tau = fc[1]; c.lr = fc[2]; c.beta1 = fc[3]; c.beta2 = fc[4]; c.adam_eps = fc[5];
   c.e_clip = (float)fc[6]; c.critic_coef = (float)fc[7]; c.entropy_coef = (float)fc[8]; c.bounds_loss_coef = (float)fc[9];
   c.grad_norm = (float)fc[10]; c.rms_eps = (float)fc[11];
@@ -102,7 +106,8 @@ igi_teacher_state state_struct(at::TensorList st, const igi_teacher_cfg& c) {
 igi_rollout rollout_struct(at::TensorList ro, const igi_teacher_cfg& c, const at::Device& dev) {
   static const char* names[10] = {"obses", "priv_info", "rewards", "values", "neglogpacs", "dones", "actions", "mus",
                                   "sigmas", "last_values"};
-  TORCH_CHECK(ro.size() == 10, "rollout: expected 10 tensors (struct igi_rollout field order), got ", ro.size());
+  const size_t want_n = c.contact_points > 0 ? 11 : 10;   // + contacts (T, N, P) in contact mode
+  TORCH_CHECK(ro.size() == want_n, "rollout: expected ", want_n, " tensors (struct igi_rollout field order), got ", ro.size());
   const int64_t T = c.horizon, N = c.num_envs, A = c.act_dim;
   const int64_t want[10] = {T * N * c.obs_dim, T * N * c.priv_dim, T * N, T * N, T * N, T * N, T * N * A, T * N * A, T * N * A, N};
   for (int i = 0; i < 10; ++i) {
@@ -114,6 +119,13 @@ igi_rollout rollout_struct(at::TensorList ro, const igi_teacher_cfg& c, const at
   igi_rollout r;
   r.obses = fp(ro[0]); r.priv_info = fp(ro[1]); r.rewards = fp(ro[2]); r.values = fp(ro[3]); r.neglogpacs = fp(ro[4]);
   r.dones = ro[5].data_ptr<uint8_t>(); r.actions = fp(ro[6]); r.mus = fp(ro[7]); r.sigmas = fp(ro[8]); r.last_values = fp(ro[9]);
+  r.contacts = nullptr;
+  if (want_n == 11) {
+    check(ro[10], "rollout.contacts", at::kFloat);
+    TORCH_CHECK(ro[10].device() == dev, "rollout.contacts: all arguments must share one device");
+    TORCH_CHECK(ro[10].numel() == T * N * c.contact_points, "rollout.contacts: expected ", T * N * c.contact_points, " elements");
+    r.contacts = fp(ro[10]);
+  }
   return r;
 }
 

@@ -9,7 +9,8 @@ from ..utils.config import AttrDict, to_attr
 
 class SyntheticInsertionEnv:
     def __init__(self, num_envs=4096, obs_dim=15, priv_dim=64, act_dim=6, device="cuda:0", seed=1234,
-                 done_p=0.01, reward_scale=0.1, max_episode_length=512, tactile_hw=None, pcl_points=0, img_hw=None):
+                 done_p=0.01, reward_scale=0.1, max_episode_length=512, tactile_hw=None, pcl_points=0, img_hw=None,
+                 contact_points=0, contact_p=0.1):
         self.num_envs, self.obs_dim, self.priv_dim, self.act_dim = num_envs, obs_dim, priv_dim, act_dim
         self.device = torch.device(device)
         self.gen = torch.Generator(device=self.device).manual_seed(seed)
@@ -36,6 +37,8 @@ class SyntheticInsertionEnv:
         # external camera (factory_task_insertion.py: image_buf / seg_buf queues): depth (N, hist=1, H*W) in [0, 1]
         # and the segmentation ids of the same pixels (0 background, 1 robot, 2 plug, 3 socket)
         self.img_hw = img_hw
+        # ground-truth contacts (task.env.compute_contact_gt, num_points): 0/1 labels per point, drawn with contact_p
+        self.contact_points, self.contact_p = contact_points, contact_p
         self.img_queue = torch.zeros(num_envs, 1, img_hw[0] * img_hw[1], device=self.device) if img_hw else None
         self.seg_queue = torch.zeros(num_envs, 1, img_hw[0] * img_hw[1], device=self.device) if img_hw else None
 
@@ -49,6 +52,8 @@ class SyntheticInsertionEnv:
         if self.img_hw:
             o["img"] = torch.rand(self.img_queue.shape, generator=self.gen, device=d)
             o["seg"] = torch.randint(0, 4, self.seg_queue.shape, generator=self.gen, device=d).float()
+        if self.contact_points:
+            o["contacts"] = (torch.rand(n, self.contact_points, generator=self.gen, device=d) < self.contact_p).float()
         if self.pcl_points:
             c = 0.3 * torch.randn(n, 1, 1, 3, generator=self.gen, device=d)
             p = c + 0.05 * torch.randn(n, 1, self.pcl_points, 3, generator=self.gen, device=d)

@@ -131,6 +131,8 @@ def pack_cfg(cfg):
     """struct igi_teacher_cfg -> (int[], float[]) op arguments."""
     icfg = [cfg.obs_dim, cfg.priv_dim, cfg.act_dim, cfg.n_priv_layers] + [int(x) for x in cfg.priv_units] + \
            [cfg.n_layers] + [int(x) for x in cfg.units] + [cfg.num_envs, cfg.horizon, cfg.mini_epochs]
+    if cfg.contact_points > 0:   # contact mode: three trailing ints (a contact-free cfg packs exactly as before)
+        icfg += [cfg.contact_points, cfg.contact_emb, cfg.only_contact]
     fcfg = [cfg.gamma, cfg.tau, cfg.lr, cfg.beta1, cfg.beta2, cfg.adam_eps, cfg.e_clip, cfg.critic_coef,
             cfg.entropy_coef, cfg.bounds_loss_coef, cfg.grad_norm, cfg.rms_eps]
     return [int(x) for x in icfg], [float(x) for x in fcfg]
@@ -138,8 +140,9 @@ def pack_cfg(cfg):
 
 def _unpack_cfg(icfg, fcfg):
     M = _lib.IGI_MAX_LAYERS
-    if len(icfg) != 8 + 2 * M or len(fcfg) != 12:
-        raise RuntimeError(f"teacher cfg: expected {8 + 2 * M} ints and 12 floats, got {len(icfg)} and {len(fcfg)}")
+    if len(icfg) not in (8 + 2 * M, 11 + 2 * M) or len(fcfg) != 12:
+        raise RuntimeError(f"teacher cfg: expected {8 + 2 * M} (or {11 + 2 * M} with contacts) ints and 12 floats, "
+                           f"got {len(icfg)} and {len(fcfg)}")
     c = _lib.TeacherCfg()
     c.obs_dim, c.priv_dim, c.act_dim, c.n_priv_layers = icfg[0:4]
     for i in range(M):
@@ -147,6 +150,10 @@ def _unpack_cfg(icfg, fcfg):
         c.units[i] = icfg[5 + M + i]
     c.n_layers = icfg[4 + M]
     c.num_envs, c.horizon, c.mini_epochs = icfg[5 + 2 * M:8 + 2 * M]
+    if len(icfg) == 11 + 2 * M:
+        c.contact_points, c.contact_emb, c.only_contact = icfg[8 + 2 * M:11 + 2 * M]
+        if c.contact_points < 1:
+            raise RuntimeError("teacher cfg: the contact fields need contact_points >= 1")
     (c.gamma, c.tau, c.lr, c.beta1, c.beta2, c.adam_eps, c.e_clip, c.critic_coef, c.entropy_coef,
      c.bounds_loss_coef, c.grad_norm, c.rms_eps) = fcfg
     if min(c.obs_dim, c.priv_dim, c.act_dim, c.num_envs, c.horizon, c.mini_epochs) < 1 or \
@@ -201,8 +208,10 @@ def _state_struct(state, cfg, need=()):
 
 
 def _rollout_struct(rollout, cfg, dev):
-    if len(rollout) != len(ROLLOUT_FIELDS):
-        raise RuntimeError(f"rollout: expected {len(ROLLOUT_FIELDS)} tensors ({', '.join(ROLLOUT_FIELDS)}), got {len(rollout)}")
+    want = len(ROLLOUT_FIELDS) + (1 if cfg.contact_points > 0 else 0)
+    if len(rollout) != want:
+        raise RuntimeError(f"rollout: expected {want} tensors ({', '.join(ROLLOUT_FIELDS)}"
+                           f"{', contacts' if want > len(ROLLOUT_FIELDS) else ''}), got {len(rollout)}")
     T, N, A = cfg.horizon, cfg.num_envs, cfg.act_dim
     shapes = dict(obses=(T, N, cfg.obs_dim), priv_info=(T, N, cfg.priv_dim), rewards=(T, N, 1), values=(T, N, 1),
                   neglogpacs=(T, N), dones=(T, N), actions=(T, N, A), mus=(T, N, A), sigmas=(T, N, A),
@@ -212,6 +221,9 @@ def _rollout_struct(rollout, cfg, dev):
         _check(t, f"rollout.{name}", dtype=torch.uint8 if name == "dones" else torch.float32, shape=shapes[name],
                device=dev)
         setattr(r, name, t.data_ptr())
+    if cfg.contact_points > 0:
+        _check(rollout[-1], "rollout.contacts", shape=(T, N, cfg.contact_points), device=dev)
+        r.contacts = rollout[-1].data_ptr()
     return r
 
 
@@ -367,6 +379,141 @@ def _(state, icfg, fcfg, obs, priv, normalize, want_latent):
     act, lat = icfg[2], icfg[4 + icfg[3] - 1]
     rows = obs.shape[0]
     return (obs.new_empty(rows, act), obs.new_empty(rows, 1), obs.new_empty(rows if want_latent else 0, lat))
+
+
+def _latent_gt_width(icfg):
+    M = _lib.IGI_MAX_LAYERS
+    lat = icfg[4 + icfg[3] - 1]
+    if len(icfg) == 11 + 2 * M:
+        return icfg[9 + 2 * M] + (0 if icfg[10 + 2 * M] else lat)
+    return lat
+
+
+@_op("actor_critic_infer_contacts(Tensor(a!)[] state, int[] icfg, float[] fcfg, Tensor obs, Tensor priv, Tensor contacts, bool normalize, bool want_latent) -> (Tensor, Tensor, Tensor)")
+def actor_critic_infer_contacts(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequence[float], obs: Tensor,
+                                priv: Tensor, contacts: Tensor, normalize: bool,
+                                want_latent: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """actor_critic_infer for a teacher with ground-truth contacts (models_split.py:172-177): contacts (rows, P) raw;
+    latent = latent_gt (rows, priv latent + contact embedding), or (rows, embedding) with only_contact
+    -> igi_teacher_infer_contacts."""
+    cfg, st, dev = _teacher_args(state, icfg, fcfg)
+    if cfg.contact_points < 1:
+        raise RuntimeError("actor_critic_infer_contacts: the cfg has no contacts (use actor_critic_infer)")
+    _check(obs, "obs", shape=(None, cfg.obs_dim), device=dev)
+    rows = obs.shape[0]
+    _check(priv, "priv", shape=(rows, cfg.priv_dim), device=dev)
+    _check(contacts, "contacts", shape=(rows, cfg.contact_points), device=dev)
+    mu = torch.empty(rows, cfg.act_dim, dtype=torch.float32, device=dev)
+    val = torch.empty(rows, 1, dtype=torch.float32, device=dev)
+    lat = torch.empty(rows if want_latent else 0, _latent_gt_width(icfg), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _rc(_lib.lib().igi_teacher_infer_contacts(C.byref(cfg), C.byref(st), _p(obs), _p(priv), _p(contacts), rows,
+                                                  1 if normalize else 0, _p(mu), _p(val),
+                                                  _p(lat) if want_latent else None, _stream(obs)),
+            "igi_teacher_infer_contacts")
+    return mu, val, lat
+
+
+@_fake("actor_critic_infer_contacts")
+def _(state, icfg, fcfg, obs, priv, contacts, normalize, want_latent):
+    rows = obs.shape[0]
+    return (obs.new_empty(rows, icfg[2]), obs.new_empty(rows, 1),
+            obs.new_empty(rows if want_latent else 0, _latent_gt_width(icfg)))
+
+
+@_op("rollout_policy_step_contacts(Tensor(a!)[] state, int[] icfg, float[] fcfg, Tensor obs, Tensor priv, Tensor contacts, bool normalize, Tensor noise, Tensor? rms_value, Tensor(b!)? obses_t, Tensor(c!)? priv_t, Tensor(k!)? contacts_t, Tensor(d!) actions_t, Tensor(e!) neglogp_t, Tensor(f!) values_t, Tensor(g!) mus_t, Tensor(h!) sigmas_t, Tensor(i!) actions_clamped, Tensor(j!) values_out) -> ()")
+def rollout_policy_step_contacts(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequence[float], obs: Tensor,
+                                 priv: Tensor, contacts: Tensor, normalize: bool, noise: Tensor,
+                                 rms_value: Optional[Tensor], obses_t: Optional[Tensor], priv_t: Optional[Tensor],
+                                 contacts_t: Optional[Tensor], actions_t: Tensor, neglogp_t: Tensor, values_t: Tensor, mus_t: Tensor,
+                                 sigmas_t: Tensor, actions_clamped: Tensor, values_out: Tensor) -> None:
+    """rollout_policy_step for a teacher with ground-truth contacts (rows, P); contacts_t: the arena slot the raw
+    contacts are written to (frozen_ppo.py:663-664) -> igi_rollout_policy_step_contacts."""
+    cfg, st, dev = _teacher_args(state, icfg, fcfg)
+    if cfg.contact_points < 1:
+        raise RuntimeError("rollout_policy_step_contacts: the cfg has no contacts (use rollout_policy_step)")
+    n = _check(obs, "obs", shape=(None, cfg.obs_dim), device=dev).shape[0]
+    _check(priv, "priv", shape=(n, cfg.priv_dim), device=dev)
+    _check(contacts, "contacts", shape=(n, cfg.contact_points), device=dev)
+    a = cfg.act_dim
+    _check(noise, "noise", shape=(n, a), device=dev)
+    if rms_value is not None:
+        _check(rms_value, "rms_value", dtype=torch.float64, shape=(3,), device=dev)
+    if obses_t is not None:
+        _check(obses_t, "obses_t", shape=(n, cfg.obs_dim), device=dev)
+    if priv_t is not None:
+        _check(priv_t, "priv_t", shape=(n, cfg.priv_dim), device=dev)
+    for nm, t in (("actions_t", actions_t), ("mus_t", mus_t), ("sigmas_t", sigmas_t), ("actions_clamped", actions_clamped)):
+        _check(t, nm, shape=(n, a), device=dev)
+    for nm, t in (("neglogp_t", neglogp_t), ("values_t", values_t), ("values_out", values_out)):
+        _check(t, nm, device=dev)
+        if t.numel() != n:
+            raise RuntimeError(f"{nm}: expected {n} elements, got shape {tuple(t.shape)}")
+    if contacts_t is not None:
+        _check(contacts_t, "contacts_t", shape=(n, cfg.contact_points), device=dev)
+    with torch.cuda.device(dev):
+        _rc(_lib.lib().igi_rollout_policy_step_contacts(
+            C.byref(cfg), C.byref(st), _p(obs), _p(priv), _p(contacts), n, 1 if normalize else 0, _p(noise),
+            _p(rms_value), _p(obses_t), _p(priv_t), _p(contacts_t), _p(actions_t), _p(neglogp_t), _p(values_t), _p(mus_t),
+            _p(sigmas_t), _p(actions_clamped), _p(values_out), _stream(obs)), "igi_rollout_policy_step_contacts")
+
+
+@_fake("rollout_policy_step_contacts")
+def _(state, icfg, fcfg, obs, priv, contacts, normalize, noise, rms_value, obses_t, priv_t, contacts_t, actions_t, neglogp_t,
+      values_t, mus_t, sigmas_t, actions_clamped, values_out):
+    return None      # writes only into its mutable arguments
+
+
+CONTACT_HIDDEN = 32   # ContactAE.contact_enc_mlp hidden width (models_split.py:46)
+
+
+def _contact_dims(contacts, params, emb):
+    rows, P = _check(contacts, "contacts", dim=2).shape
+    if rows < 1 or not (1 <= emb <= 32):
+        raise RuntimeError(f"contact encoder: need rows >= 1 and 1 <= emb <= 32, got {rows} rows, emb {emb}")
+    _check(params, "params", shape=(CONTACT_HIDDEN * P + CONTACT_HIDDEN + emb * CONTACT_HIDDEN + emb,),
+           device=contacts.device)
+    return rows, P
+
+
+@_op("contact_encoder_fwd(Tensor contacts, Tensor params, int emb) -> (Tensor, Tensor)")
+def contact_encoder_fwd(contacts: Tensor, params: Tensor, emb: int) -> Tuple[Tensor, Tensor]:
+    """ContactAE.forward_enc (models_split.py:44-51): (tanh(relu(C W1^T + b1) W2^T + b2) (rows, emb), the ReLU output
+    (rows, 32)); params = [W1 (32,P) | b1 | W2 (emb,32) | b2] packed -> igi_contact_encoder_forward."""
+    rows, P = _contact_dims(contacts, params, emb)
+    out = torch.empty(rows, emb, dtype=torch.float32, device=contacts.device)
+    hid = torch.empty(rows, CONTACT_HIDDEN, dtype=torch.float32, device=contacts.device)
+    with torch.cuda.device(contacts.device):
+        _rc(_lib.lib().igi_contact_encoder_forward(_p(contacts), rows, P, emb, _p(params), _p(out), _p(hid),
+                                                   _stream(contacts)), "igi_contact_encoder_forward")
+    return out, hid
+
+
+@_fake("contact_encoder_fwd")
+def _(contacts, params, emb):
+    return contacts.new_empty(contacts.shape[0], emb), contacts.new_empty(contacts.shape[0], CONTACT_HIDDEN)
+
+
+@_op("contact_encoder_bwd(Tensor contacts, Tensor params, Tensor hidden, Tensor dz) -> Tensor")
+def contact_encoder_bwd(contacts: Tensor, params: Tensor, hidden: Tensor, dz: Tensor) -> Tensor:
+    """Gradient of the packed encoder parameters from d(pre-tanh) dz (rows, emb) and the forward's hidden (rows, 32),
+    summed over the rows in a fixed order -> igi_contact_encoder_backward."""
+    emb = _check(dz, "dz", dim=2).shape[1]
+    rows, P = _contact_dims(contacts, params, emb)
+    _check(dz, "dz", shape=(rows, emb), device=contacts.device)
+    _check(hidden, "hidden", shape=(rows, CONTACT_HIDDEN), device=contacts.device)
+    L = _lib.lib()
+    ws = torch.empty(int(L.igi_contact_encoder_workspace_bytes(rows, P, emb)), dtype=torch.uint8, device=contacts.device)
+    grads = torch.empty_like(params)
+    with torch.cuda.device(contacts.device):
+        _rc(L.igi_contact_encoder_backward(_p(contacts), rows, P, emb, _p(params), _p(hidden), _p(dz), _p(grads),
+                                           _p(ws), ws.numel(), _stream(contacts)), "igi_contact_encoder_backward")
+    return grads
+
+
+@_fake("contact_encoder_bwd")
+def _(contacts, params, hidden, dz):
+    return torch.empty_like(params)
 
 
 # ---------------------------------------------------------------------------------------------------------------

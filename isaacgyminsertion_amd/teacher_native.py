@@ -24,11 +24,21 @@ ROLLOUT_KEYS = ("obses", "priv_info", "rewards", "values", "neglogpacs", "dones"
                 "sigmas", "last_values")
 
 
-def teacher_param_names(n_priv_layers, n_layers):
-    """ActorCriticSplit.state_dict() key order (models_split.py:73-106)."""
+CONTACT_HIDDEN = 32   # ContactAE hidden width (models_split.py:46-47)
+CONTACT_NAMES = ("contact_ae.contact_enc_mlp.0.weight", "contact_ae.contact_enc_mlp.0.bias",
+                 "contact_ae.contact_enc_mlp.2.weight", "contact_ae.contact_enc_mlp.2.bias",
+                 "contact_ae.contact_dec_mlp.0.weight", "contact_ae.contact_dec_mlp.0.bias",
+                 "contact_ae.contact_dec_mlp.2.weight", "contact_ae.contact_dec_mlp.2.bias")
+
+
+def teacher_param_names(n_priv_layers, n_layers, contacts=False):
+    """ActorCriticSplit.state_dict() key order (models_split.py:73-106); contact_ae between env_mlp
+    and actor_mlp when the teacher has ground-truth contacts (models_split.py:81-84)."""
     names = ["sigma"]
     for i in range(n_priv_layers):
         names += [f"env_mlp.mlp.{2 * i}.weight", f"env_mlp.mlp.{2 * i}.bias"]
+    if contacts:
+        names += list(CONTACT_NAMES)
     for net in ("actor_mlp", "critic_mlp"):
         for i in range(n_layers):
             names += [f"{net}.mlp.{2 * i}.weight", f"{net}.mlp.{2 * i}.bias"]
@@ -36,7 +46,8 @@ def teacher_param_names(n_priv_layers, n_layers):
     return names
 
 
-def teacher_param_shapes(obs_dim, priv_dim, act_dim, units, priv_units):
+def teacher_param_shapes(obs_dim, priv_dim, act_dim, units, priv_units, contact_points=0, contact_emb=0,
+                         only_contact=False):
     shapes = OrderedDict()
     shapes["sigma"] = (act_dim,)
     d = priv_dim
@@ -44,8 +55,15 @@ def teacher_param_shapes(obs_dim, priv_dim, act_dim, units, priv_units):
         shapes[f"env_mlp.mlp.{2 * i}.weight"] = (u, d)
         shapes[f"env_mlp.mlp.{2 * i}.bias"] = (u,)
         d = u
+    trunk_in = obs_dim + priv_units[-1]
+    if contact_points:
+        H, P, E = CONTACT_HIDDEN, contact_points, contact_emb
+        for k, shp in zip(CONTACT_NAMES, ((H, P), (H,), (E, H), (E,), (H, E), (H,), (P, H), (P,))):
+            shapes[k] = shp
+        if not only_contact:
+            trunk_in += E
     for net in ("actor_mlp", "critic_mlp"):
-        d = obs_dim + priv_units[-1]
+        d = trunk_in
         for i, u in enumerate(units):
             shapes[f"{net}.mlp.{2 * i}.weight"] = (u, d)
             shapes[f"{net}.mlp.{2 * i}.bias"] = (u,)
@@ -57,9 +75,20 @@ def teacher_param_shapes(obs_dim, priv_dim, act_dim, units, priv_units):
     return shapes
 
 
-def make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon, mini_epochs, **hp):
+def make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon, mini_epochs, contact_points=0,
+             contact_emb=0, only_contact=False, **hp):
+    """contact_points > 0: the teacher with ground-truth contacts (task.env.compute_contact_gt; num_points P,
+    contact_mlp.units[-1] = contact_emb, train.ppo.only_contact)."""
     h = dict(DEFAULT_HP)
     h.update(hp)
+    if contact_points:
+        if not 1 <= contact_emb <= 32:
+            raise ValueError(f"contact embedding width {contact_emb}: 1 .. 32 supported")
+        if only_contact and contact_emb != priv_units[-1]:
+            raise NotImplementedError("only_contact needs contact_mlp.units[-1] == priv_mlp_units[-1] "
+                                      "(the reference sizes the trunk input as obs + priv latent)")
+    elif contact_emb or only_contact:
+        raise ValueError("contact_emb / only_contact need contact_points > 0")
     if len(units) > _lib.IGI_MAX_LAYERS or len(priv_units) > _lib.IGI_MAX_LAYERS:
         raise ValueError(f"at most {_lib.IGI_MAX_LAYERS} layers per MLP are supported")
     c = _lib.TeacherCfg()
@@ -76,6 +105,7 @@ def make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon, m
     c.entropy_coef, c.bounds_loss_coef = float(h["entropy_coef"]), float(h["bounds_loss_coef"])
     c.grad_norm = float(h["grad_norm"]) if h["truncate_grads"] else 0.0
     c.rms_eps = float(h["rms_eps"])
+    c.contact_points, c.contact_emb, c.only_contact = int(contact_points), int(contact_emb), int(bool(only_contact))
     return c, h
 
 
@@ -94,20 +124,24 @@ def param_layout(cfg):
 
 class TeacherEngine:
     def __init__(self, num_envs, horizon, mini_epochs, units=(512, 256, 128), priv_units=(256, 128, 8),
-                 obs_dim=15, priv_dim=64, act_dim=6, device="cuda:0", perm=None, **hp):
+                 obs_dim=15, priv_dim=64, act_dim=6, device="cuda:0", perm=None, contact_points=0, contact_emb=0,
+                 only_contact=False, **hp):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("TeacherEngine needs a HIP device (there is no CPU path)")
         self.L = _lib.lib()
         self.cfg, self.hp = make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon,
-                                     mini_epochs, **hp)
+                                     mini_epochs, contact_points=contact_points, contact_emb=contact_emb,
+                                     only_contact=only_contact, **hp)
+        self.contact_points, self.contact_emb, self.only_contact = int(contact_points), int(contact_emb), bool(only_contact)
         self.N, self.T, self.E = num_envs, horizon, mini_epochs
         self.B = num_envs * horizon
         self.mb = self.B // mini_epochs
         self.n_mb = self.B // self.mb
         self.obs_dim, self.priv_dim, self.act_dim = obs_dim, priv_dim, act_dim
         self.units, self.priv_units = list(units), list(priv_units)
-        self.shapes = teacher_param_shapes(obs_dim, priv_dim, act_dim, self.units, self.priv_units)
+        self.shapes = teacher_param_shapes(obs_dim, priv_dim, act_dim, self.units, self.priv_units, contact_points,
+                                           contact_emb, only_contact)
         self.P, self.layout = param_layout(self.cfg)
         assert len(self.layout) == len(self.shapes)
         dev = self.device
@@ -174,9 +208,10 @@ class TeacherEngine:
         return ops.pack_cfg(self.cfg)
 
     def set_rollout(self, ro):
-        """ro: dict of time-major device tensors (ROLLOUT_KEYS); kept referenced, not copied."""
+        """ro: dict of time-major device tensors (ROLLOUT_KEYS, + "contacts" (T, N, P) for a contact teacher); kept
+        referenced, not copied."""
         keep = []
-        for k in ROLLOUT_KEYS:
+        for k in ROLLOUT_KEYS + (("contacts",) if self.contact_points else ()):
             t = ro[k]
             want = torch.uint8 if k == "dones" else torch.float32
             if t.device != self.device or t.dtype != want or not t.is_contiguous():
@@ -333,6 +368,16 @@ class TeacherEngine:
         priv = priv.to(self.device, torch.float32).contiguous()
         mu, val, lat = torch.ops.mi355ppo.actor_critic_infer(self.state_list(), *self._cfg_args(), obs, priv,
                                                               bool(normalize), bool(want_latent))
+        return (mu, val, lat) if want_latent else (mu, val)
+
+    def infer_contacts(self, obs, priv, contacts, want_latent=False, normalize=True):
+        """``infer`` for a contact teacher: contacts (rows, P) raw; the latent is latent_gt = [priv latent | contact
+        embedding] (models_split.py:172-177)."""
+        obs = obs.to(self.device, torch.float32).contiguous()
+        priv = priv.to(self.device, torch.float32).contiguous()
+        contacts = contacts.to(self.device, torch.float32).contiguous()
+        mu, val, lat = torch.ops.mi355ppo.actor_critic_infer_contacts(self.state_list(), *self._cfg_args(), obs, priv,
+                                                                       contacts, bool(normalize), bool(want_latent))
         return (mu, val, lat) if want_latent else (mu, val)
 
     # ---- reference-shaped accessors ------------------------------------------------------------

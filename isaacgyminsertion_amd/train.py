@@ -64,7 +64,8 @@ def make_synthetic_env(cfg):
         act_dim=env.numActions, device=cfg.rl_device, seed=1234 + int(cfg.seed),
         max_episode_length=cfg.task.rl.max_episode_length,
         tactile_hw=(off.tactile_width, off.tactile_height) if ppo.tactile_info else None, pcl_points=pts,
-        img_hw=(off.img_width, off.img_height) if (ppo.img_info or ppo.seg_info) else None)
+        img_hw=(off.img_width, off.img_height) if (ppo.img_info or ppo.seg_info) else None,
+        contact_points=int(ppo.num_points) if ppo.compute_contact_gt else 0)
 
 
 def run(cfg, env_factory=None):
