@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define IGI_ABI_VERSION 4
+#define IGI_ABI_VERSION 5
 #define IGI_MAX_LAYERS 4
 #define IGI_MAX_ACT 8
 
@@ -224,18 +224,10 @@ int igi_teacher_fwd_bwd_phase(const igi_teacher_cfg* cfg, const igi_rollout* ro,
 int igi_teacher_grad_buckets(const igi_teacher_cfg* cfg, int64_t* offsets, int64_t* lengths);
 
 /* Whole single-GPU update: mini_epochs x n_minibatch (fwd_bwd + apply), enqueued back to back
- * with no host synchronisation (frozen_ppo.py:508-640).  adam_t0 = steps taken before. */
+ * with no host synchronisation (frozen_ppo.py:508-640).  adam_t0 = steps taken before.  Bit-identical to the
+ * igi_teacher_fwd_bwd / igi_teacher_apply loop and to the data-parallel updates on one rank. */
 int igi_teacher_update(const igi_teacher_cfg* cfg, const igi_rollout* ro,
                        const igi_teacher_state* st, int64_t adam_t0, igi_stream_t stream);
-/* Norm fusion of igi_teacher_update (default OFF -- measured slower, profiles/r06_norm_fuse_ab.log; IGI_NORM_FUSE=1 in the
- * environment starts it on): from the second
- * optimizer step of an update on, the gradient norm of clip_grad_norm_ (frozen_ppo.py:608) is summed from per-block partials
- * the gradient assembly leaves behind and the logged parameter norm (frozen_ppo.py:605-606) from partials of the previous
- * step's Adam pass -- one launch less per step.  Same values up to the order of the fp64 additions; with 0 every step runs
- * the separate norm kernel, and igi_teacher_update is then bit-identical to the igi_teacher_fwd_bwd / _apply loop and to
- * the data-parallel updates on one rank (which always run it: the norm there is taken AFTER the all-reduce).  Returns the
- * previous setting. */
-int igi_teacher_set_norm_fusion(int on);
 /* Latent-gradient fusion of the teacher backward (default ON; IGI_LATZ_FUSE=0 in the environment starts it off;
  * profiles/r06_latz_ab.log): the backward of env_mlp's last (8-wide) layer -- d(latent) from the first trunk layer's row dots,
  * its rank-8 weight / bias gradient and dZ of the 128-wide layer below (autograd of models_split.py:185-232 as called from

@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libigi_hip.so")
 IGI_MAX_LAYERS = 4
 IGI_MAX_ACT = 8
 IGI_STATS_PER_STEP = 8
-ABI_VERSION = 4
+ABI_VERSION = 5
 IGI_E_BADARG, IGI_E_WORKSPACE, IGI_E_UNSUPPORTED, IGI_E_CALLBACK, IGI_E_COMM = -1, -2, -3, -5, -6   # include/igi_ppo.h
 
 EPI_STORE, EPI_BIAS_TANH, EPI_TANHGRAD, EPI_BIAS = 0, 1, 2, 3
@@ -78,7 +78,6 @@ _EXPORTS = {
     "igi_build_info": (C.c_char_p, []),
     "igi_gemm_set_bf16_inputs": (C.c_int, [C.c_int]),
     "igi_gemm_set_bf16x3": (C.c_int, [C.c_int]),
-    "igi_teacher_set_norm_fusion": (C.c_int, [C.c_int]),
     "igi_teacher_set_latz_fuse": (C.c_int, [C.c_int]),
     "igi_prof_enable": (C.c_int, [C.c_int]),
     "igi_prof_read": (C.c_int, [C.POINTER(ProfEntry), C.c_int]),

@@ -51,13 +51,6 @@ constexpr int F12_Q = 8 * PF_IMG;                       // region Q: env layer 2
 constexpr int F12_LDS_FLOATS = PF_P + F12_Q + F12_RING + 2 * F12_PRIV + 2 * PF_IMG + PF_IMG + 8 * 128 + 32 * 8;
 static_assert(F12_LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 
-// IGI_FWD12=0: k_env_fwd + the first trunk layer's own launch (A/B)
-static inline bool fwd12_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("IGI_FWD12"); on = e ? atoi(e) != 0 : 1; }
-  return on != 0;
-}
-
 // The data engine's copy of NIMG [32][32] operand images (k-contiguous, swizzled) to global rows: thread st (0 .. 255) moves
 // 16-byte pieces st, st + 256, ... (NIMG store instructions per thread); eight consecutive threads cover one 128-byte row
 // segment.  Rows >= rows_ok are skipped (only the last row block of a ragged batch has any).

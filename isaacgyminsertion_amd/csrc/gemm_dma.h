@@ -1126,7 +1126,7 @@ struct GemmMulti {
   GemmArgs g[DMA_MULTI_MAX];
   int tile_end[DMA_MULTI_MAX];
   int n_tiles[DMA_MULTI_MAX], m_tiles[DMA_MULTI_MAX];
-  int chain = 1;             // data-gradient tiles per workgroup (consecutive row tiles of one column tile), IGI_DGRAD_CHAIN
+  int chain = 1;             // data-gradient tiles per workgroup (consecutive row tiles of one column tile)
   int kind[DMA_MULTI_MAX];   // weight gradients (reduction-major operands, plain store): 0 = 128 x 128 tiles, 1 = 128 x 64,
                              // 3 = 256 x 32 (<= 32 input columns: the zero-padded first trunk layer, no padded MFMA columns);
                              // 2 = data gradient dZ.W times tanh' (A k-contiguous, B reduction-major), 128 x 128 tiles
@@ -1207,15 +1207,6 @@ __global__ __launch_bounds__(DMA_THREADS, 4) void gemm_dma_wgrad_multi_kernel(co
       }
     }
   }
-}
-
-// Tile width: 256 keeps each A row-tile read once, but only if that still yields one workgroup
-// per CU; narrow outputs (padded first layer, latent) take the 64-wide tile.
-static inline int dma_pick_bn(int M, int N, int zcount) {
-  if (N <= 64) return 64;
-  const long long mt = (M + DMA_BM - 1) / DMA_BM;
-  if ((N % 256 == 0 || N > 256) && mt * ((N + 255) / 256) * zcount >= 256) return 256;
-  return 128;
 }
 
 // split-k factor for a weight-gradient product (reduction over the minibatch): one workgroup per CU,
@@ -1458,13 +1449,11 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   if (!dma_eligible(g, akc, bkc)) return g.gather ? hipErrorInvalidValue : launch_gemm(g, akc, bkc, s);
   const double fl = 2.0 * g.M * g.N * (double)g.K * g.nbatch * g.flop_credit;
   const double by = 4.0 * g.nbatch * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N * g.splitk);
-  // Default policy (measured on the teacher update, 4096 x 32): 128-wide tiles with a 2-stage ring
-  // = 64-72 KB of LDS, so TWO workgroups share a CU and one computes while the other is in its DMA
-  // prologue / store epilogue; the 256-wide, 3-stage variant (one workgroup per CU) was 4 % slower
-  // end to end.  IGI_DMA_MODE=0 selects the latter for experiments.
-  static int mode = -1;
-  if (mode < 0) { const char* e = getenv("IGI_DMA_MODE"); mode = e ? atoi(e) : 1; }
-  int bn = dma_pick_bn(g.M, g.N, g.nbatch * g.splitk);
+  // Tile width (measured on the teacher update, 4096 x 32): 128-wide tiles with a 2-stage ring = 64-72 KB of LDS, so TWO
+  // workgroups share a CU and one computes while the other is in its DMA prologue / store epilogue (a 256-wide, 3-stage
+  // tile, one workgroup per CU, was 4 % slower end to end); narrow outputs (padded first layer, latent) take the 64-wide,
+  // 3-stage tile.
+  int bn = g.N <= 64 ? 64 : 128;
   // im2col forward / dgrad with <= 64 output channels (every tactile convolution): a 256 x 64 tile gives
   // each wave the same 64 x 32 sub-tile (two independent accumulator chains, 32 MFMAs per barrier) as the
   // 128 x 128 configuration; 2 stages x 40 KB so two workgroups still share a CU.
@@ -1497,24 +1486,15 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
     ProfScope ps(conv_pw_ok(g) ? PC_CONV_PW64 : PC_CONV_WG_TALL64, s, fl, by);
     return launch_dma_cfg<64, 2, 256>(g, akc, bkc, s);
   }
-  bool two_stage = (mode == 1 && bn >= 128);
-  if (two_stage) bn = 128;
   // a 128-wide grid that covers at most half the CUs (the 256 -> 128 env_mlp layer: 128 workgroups)
   // runs on 64-wide tiles instead: twice the workgroups, +1.2 % on the update.
-  static int fill = -1;
-  if (fill < 0) { const char* e = getenv("IGI_BN64_FILL"); fill = e ? atoi(e) : 128; }
-  if (two_stage && (long long)((g.M + DMA_BM - 1) / DMA_BM) * ((g.N + 127) / 128) * g.nbatch * g.splitk <= fill) {
-    two_stage = false;
-    bn = 64;
-  }
+  if (bn == 128 && (long long)((g.M + DMA_BM - 1) / DMA_BM) * ((g.N + 127) / 128) * g.nbatch * g.splitk <= 128) bn = 64;
   // one-k-tile products (the first trunk layer: K = 32, 67 MB of tanh outputs): the launch is epilogue + store, and the
-  // 128-wide tile's 73 KB of epilogue staging allows two workgroups per CU; 64-wide tiles stage 37 KB (IGI_K1_BN64, A/B)
-  static int k1bn64 = -1;
-  if (k1bn64 < 0) { const char* e = getenv("IGI_K1_BN64"); k1bn64 = e ? atoi(e) : 1; }   // 20.6 -> 19.4 us for the first trunk layer
-  if (k1bn64 && two_stage && !g.gather && g.K <= DMA_BK) { two_stage = false; bn = 64; }
+  // 128-wide tile's 73 KB of epilogue staging allows two workgroups per CU; 64-wide tiles stage 37 KB: 20.6 -> 19.4 us
+  if (bn == 128 && !g.gather && g.K <= DMA_BK) bn = 64;
   const int lay = akc ? (bkc ? 0 : 1) : (bkc ? 3 : 2);
-  ProfScope ps((bn == 256 ? PC_DMA_256_TT : (bn == 128 ? PC_DMA_128_TT : PC_DMA_64_TT)) + lay, s, fl, by);
-  if (two_stage && x3_mode() && !bf16_mode() && !g.gather && akc && bkc && g.K >= 256) {
+  ProfScope ps((bn == 128 ? PC_DMA_128_TT : PC_DMA_64_TT) + lay, s, fl, by);
+  if (bn == 128 && x3_mode() && !bf16_mode() && !g.gather && akc && bkc && g.K >= 256) {
     // experiment: exact three-plane bf16 split (same tiles, loaders and epilogues; only the inner loop differs)
     const int n_tiles = (g.N + 127) / 128, m_tiles = (g.M + DMA_BM - 1) / DMA_BM;
     GemmArgs gg = g;
@@ -1535,7 +1515,7 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
     else IGI_LAUNCH((gemm_dma_x3_kernel<6>), grid, dim3(DMA_THREADS), shm, s, gg, n_tiles, m_tiles);
     return hipGetLastError();
   }
-  if (two_stage && bf16_mode() && !g.gather && akc) {
+  if (bn == 128 && bf16_mode() && !g.gather && akc) {
     // opt-in bf16-input mode: same tiles, same loaders, same epilogues
     const int n_tiles = (g.N + 127) / 128, m_tiles = (g.M + DMA_BM - 1) / DMA_BM;
     GemmArgs gg = g;
@@ -1566,9 +1546,7 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
     }
     return hipGetLastError();
   }
-  if (two_stage) return launch_dma_cfg<128, 2>(g, akc, bkc, s);
-  if (bn == 256) return launch_dma_cfg<256>(g, akc, bkc, s);
-  if (bn == 128) return launch_dma_cfg<128>(g, akc, bkc, s);
+  if (bn == 128) return launch_dma_cfg<128, 2>(g, akc, bkc, s);
   return launch_dma_cfg<64>(g, akc, bkc, s);
 }
 
@@ -1595,17 +1573,12 @@ static inline bool gemm_multi_dgrad_ok(GemmArgs& g) {
 static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, const GemmArgs* dgrad = nullptr) {
   GemmMulti mt_;
   double fl = 0, by = 0;
-  static int dgrad_first = -1;
-  if (dgrad_first < 0) { const char* e = getenv("IGI_MULTI_DGRAD_FIRST"); dgrad_first = e ? atoi(e) : 0; }
   if (dgrad) {
     GemmArgs g = *dgrad;
     if (g.splitk < 1) g.splitk = 1;
     const long long mtl = (g.M + DMA_BM - 1) / DMA_BM, ntl = (g.N + 127) / 128;
     if (!gemm_multi_dgrad_ok(g)) return hipErrorNotSupported;
     dma_set_divs(g, (int)ntl, (int)mtl);
-    static int chain = -1;
-    if (chain < 0) { const char* e = getenv("IGI_DGRAD_CHAIN"); chain = e ? atoi(e) : 1; if (chain < 1) chain = 1; }
-    mt_.chain = (chain > 1 && mtl % chain == 0 && count > 0) ? chain : 1;
     bool loww = false;
     if (g.lw_out) {   // the planner asked for the layer below's weight gradient from these tiles: its conditions, or nothing
       // (lw_xw <= 31: lane 31 of the padded input row feeds the ONE of the bias gradient -- a 32-wide real input has no
@@ -1637,12 +1610,10 @@ static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, con
       if (e != hipSuccess) return e;
       continue;
     }
-    static int narrow = -1;
-    // 256 x 32 tiles for a <= 32-wide input (the zero-padded first trunk layer): slower while that product shared the
-    // env level's grid with two heavier ones (round 3), faster once the level runs as the row-block kernel and the
-    // product is left with the first env layer's in the step's last launch (24.0 vs 29.7 us, round 5)
-    if (narrow < 0) { const char* e = getenv("IGI_WGRAD_N32"); narrow = e ? atoi(e) : (rb_level_enabled() ? 1 : 0); }
-    const bool n32 = narrow && g.N <= 32 && (g.M % 256) == 0;   // 256 x 32 tiles: no padded columns for a <= 32-wide input
+    // 256 x 32 tiles for a <= 32-wide input (the zero-padded first trunk layer): no padded columns.  Slower while that
+    // product shared the env level's grid with two heavier ones (round 3), faster once the level runs as the row-block
+    // kernel and the product is left with the first env layer's in the step's last launch (24.0 vs 29.7 us, round 5)
+    const bool n32 = g.N <= 32 && (g.M % 256) == 0;
     const int bn = n32 ? 32 : ((g.N <= 64) ? 64 : 128);
     const int bm = n32 ? 256 : DMA_BM;
     const int nt = (g.N + bn - 1) / bn, mt = (g.M + bm - 1) / bm;
@@ -1657,7 +1628,7 @@ static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, con
     by += 4.0 * g.nbatch * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N * g.splitk);
   }
   if (mt_.n == 0) return hipSuccess;
-  if (dgrad && mt_.n > 1 && !dgrad_first) {
+  if (dgrad && mt_.n > 1) {
     // longest first: a weight-gradient workgroup runs two to four times as many k-tiles as a data-gradient one, and
     // there is one of them per CU -- started first they share their CU with a stream of short data-gradient tiles and
     // finish with them; started last they ran alone at the end (fused trunk-2 level 150 -> 142 us with its 256
@@ -1686,11 +1657,10 @@ static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, con
   return hipGetLastError();
 }
 
+// fp32 inputs: one gemm_wgrad_multi grid; bf16-input mode: the grouped kernels below
 static hipError_t gemm_wgrad_group(GemmArgs* list, int count, hipStream_t s) {
-  static int multi = -1;
-  if (multi < 0) { const char* e = getenv("IGI_WGRAD_MULTI"); multi = e ? atoi(e) : 1; }
-  if (multi && !bf16_mode()) return gemm_wgrad_multi(list, count, s);
-  GemmGroup grp[2];   // [0]: 128-wide two-stage tiles, [1]: 64-wide three-stage tiles
+  if (!bf16_mode()) return gemm_wgrad_multi(list, count, s);
+  GemmGroup grp[2];   // [0]: 128-wide two-stage tiles (bf16 inputs), [1]: 64-wide three-stage tiles
   double fl[2] = {0, 0}, by[2] = {0, 0};
   for (int i = 0; i < count; ++i) {
     GemmArgs& g = list[i];
@@ -1723,24 +1693,13 @@ static hipError_t gemm_wgrad_group(GemmArgs* list, int count, hipStream_t s) {
                                ? sizeof(float) * DMA_WAVES * 64 * (32 + 4) : sizeof(float) * 2 * (DMA_BM + 128) * DMA_BK;
     static bool attr = false;
     if (!attr) {
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_group_kernel<128, false, false, 2>,
+      hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_group_kernel<128, false, false, 2, true>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
       if (e != hipSuccess) return e;
       attr = true;
     }
     ProfScope ps(PC_GROUP_128_FF, s, fl[0], by[0]);
-    if (bf16_mode()) {
-      static bool attr2 = false;
-      if (!attr2) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_group_kernel<128, false, false, 2, true>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return e;
-        attr2 = true;
-      }
-      IGI_LAUNCH((gemm_dma_group_kernel<128, false, false, 2, true>), dim3(grp[0].tile_end[grp[0].n - 1]),
-                         dim3(DMA_THREADS), shm, s, grp[0]);
-    } else
-    IGI_LAUNCH((gemm_dma_group_kernel<128, false, false, 2>), dim3(grp[0].tile_end[grp[0].n - 1]),
+    IGI_LAUNCH((gemm_dma_group_kernel<128, false, false, 2, true>), dim3(grp[0].tile_end[grp[0].n - 1]),
                        dim3(DMA_THREADS), shm, s, grp[0]);
   }
   if (grp[1].n > 0) {
@@ -1760,15 +1719,10 @@ static hipError_t gemm_wgrad_group(GemmArgs* list, int count, hipStream_t s) {
 }
 
 // One level of a backward chain: the data gradient `dgrad` (k-contiguous dZ times reduction-major W, tanh' epilogue)
-// together with the weight-gradient products that are ready at this point, in one grid when the shapes allow it.
-static inline bool gemm_level_enabled() {
-  static int fuse = -1, multi = -1;
-  if (fuse < 0) { const char* e = getenv("IGI_LEVEL_FUSE"); fuse = e ? atoi(e) : 1; }
-  if (multi < 0) { const char* e = getenv("IGI_WGRAD_MULTI"); multi = e ? atoi(e) : 1; }
-  return fuse && multi && !bf16_mode();
-}
+// together with the weight-gradient products that are ready at this point, in one grid when the shapes allow it (not in
+// bf16-input mode).
 static hipError_t gemm_level(const GemmArgs& dgrad, GemmArgs* wgrads, int count, hipStream_t s) {
-  if (gemm_level_enabled() && count > 0) {
+  if (!bf16_mode() && count > 0) {
     hipError_t e = gemm_wgrad_multi(wgrads, count, s, &dgrad);
     if (e != hipErrorNotSupported) return e;
   }

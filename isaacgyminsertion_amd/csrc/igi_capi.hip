@@ -119,12 +119,6 @@ int igi_level_backward_below(const float* dz, const float* weight, const float* 
   return fail((int)e, "igi_level_backward_below");
 }
 
-int igi_teacher_set_norm_fusion(int on) {
-  const int prev = igi::norm_fusion_ref();
-  igi::norm_fusion_ref() = on != 0;
-  return prev;
-}
-
 int igi_teacher_set_latz_fuse(int on) {
   const int prev = igi::latz_fuse_ref();
   igi::latz_fuse_ref() = on != 0;

@@ -80,7 +80,6 @@ struct RbLevelArgs {
   float* dBp = nullptr; long long sBpart = 0, sBnet = 0;                 // partials [ranges][nets][128]
   int rows = 0, IN = 0, nets = 1;
   int nslices = 0, ranges = 0, nblocks = 0;     // IN / 64; row ranges per net (= partial count); rows / 64
-  int variant = 0;                              // A/B switches of tools/probes/rb_level_probe.hip (IGI_RB_VARIANT)
   // LOWX (nets == 1): the weight / bias gradient of the layer BELOW from the finished data-gradient tiles -- lx_X = that
   // layer's input rows [rows][64]; lx_W partials [ranges][IN][lx_ldw], lx_B partials [ranges][IN] -- and dX is NOT written
   const float* lx_X = nullptr; int lx_ld = 0;
@@ -106,28 +105,20 @@ static inline int rb_level_ranges(int rows, int IN, int nets) {
   return r < 1 ? 1 : r;
 }
 
-// IGI_RB_LEVEL=0: the tile kernels for every level (A/B)
-static inline bool rb_level_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("IGI_RB_LEVEL"); on = e ? atoi(e) : 1; }
-  return on != 0;
-}
-
 // Shapes this kernel is built for (the caller runs the tile kernels otherwise).
 static inline bool rb_level_shape_ok(long long rows, int KO, int IN, int nets) {
-  const bool on = rb_level_enabled();
-  return on && KO == RB_KO && IN >= RB_S && (IN % RB_S) == 0 && IN <= 1024 && rows >= 4 * RB_BR && (rows % RB_BR) == 0 &&
+  return KO == RB_KO && IN >= RB_S && (IN % RB_S) == 0 && IN <= 1024 && rows >= 4 * RB_BR && (rows % RB_BR) == 0 &&
          rows < (1 << 24) && nets >= 1 && nets <= 2 && !bf16_mode();
 }
 
 // NETS: one instantiation per level (trunk: actor + critic, env_mlp: one net), so that a kernel trace tells them apart.
-// MODE 0: data gradient parked in LDS and stored 16 bytes per lane; 1: 4-byte stores from the accumulators (probe);
+// MODE 0: data gradient parked in LDS and stored 16 bytes per lane;
 // 2: the data gradient is not stored -- element by element it is the A operand of a second product, the weight gradient of
 // the layer below, dW_below[c][j] += dX[row][c] * X_below[row][j] (j < 64: two more accumulator tiles per wave) -- the
 // accumulator layout IS the operand layout (lane = column, register = row pair), so nothing goes through LDS.
 template <int MODE, int NETS>
 __global__ __launch_bounds__(RB_THREADS) void k_rb_level(const RbLevelArgs a) {
-  constexpr bool DIRECT = MODE == 1, LOWX = MODE == 2 || MODE == 3, LATZ = MODE == 3;
+  constexpr bool LOWX = MODE == 2 || MODE == 3, LATZ = MODE == 3;
   extern __shared__ __attribute__((aligned(1024))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, h = lane >> 5;
@@ -256,8 +247,7 @@ __global__ __launch_bounds__(RB_THREADS) void k_rb_level(const RbLevelArgs a) {
     asm volatile("" ::: "memory");
     float* park = smem + 2 * RB_STAGE + w4 * (32 * RB_EPLD);
     const int prow = lane >> 3, pc4 = lane & 7;
-    unsigned lo = DIRECT ? 4u * ((unsigned)(4 * h) * (unsigned)a.lddx + (unsigned)l31)
-                         : 4u * ((unsigned)prow * (unsigned)a.lddx + 4u * (unsigned)pc4);
+    unsigned lo = 4u * ((unsigned)prow * (unsigned)a.lddx + 4u * (unsigned)pc4);
     // The epilogue of block b - 1 (tanh' from the X values read while that block was resident, then the stores) is
     // issued BETWEEN the MFMA groups of block b: its vector instructions cost their issue slots wherever they stand
     // (exact-fp32 MFMAs and VALU do not overlap on a SIMD), but its LDS round trips and the store issue are no phase of
@@ -290,10 +280,6 @@ __global__ __launch_bounds__(RB_THREADS) void k_rb_level(const RbLevelArgs a) {
         lxb += v;
         lxacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v, pb0[r], lxacc[0], 0, 0, 0);
         lxacc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(v, pb1[r], lxacc[1], 0, 0, 0);
-      } else if (DIRECT) {
-        char* ob = reinterpret_cast<char*>(dX + ((long long)bp * RB_BR + 32 * rt) * a.lddx + 32 * ct);
-        asm volatile("" : "+v"(lo));
-        *reinterpret_cast<float*>(ob + (size_t)((r & 3) + 8 * (r >> 2)) * a.lddx * 4 + lo) = v;
       } else {
         park[((r & 3) + 8 * (r >> 2) + 4 * h) * RB_EPLD + l31] = v;
       }
@@ -329,7 +315,7 @@ __global__ __launch_bounds__(RB_THREADS) void k_rb_level(const RbLevelArgs a) {
       const int zrow = (32 * rt + l31) * RB_KO, zsw = (32 * rt + l31) & 15;
       auto zoffs = [&](int c) { return LOWX ? zrow + 4 * ((2 * c + h) ^ zsw) : zq[c]; };
       fa[0] = *reinterpret_cast<const f32x4*>(zs + zoffs(0));
-      const bool epi = b > 0 && !(a.variant & 8);
+      const bool epi = b > 0;
       if (LOWX && epi) { lx_load(b - 1, 0); lx_load(b - 1, 1); }
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
@@ -343,7 +329,6 @@ __global__ __launch_bounds__(RB_THREADS) void k_rb_level(const RbLevelArgs a) {
           acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c & 1][j], wf[4 * c + j], acc, 0, 0, 0);
         if (epi) {
           if (LOWX) { if (c + 2 < 16) lx_load(b - 1, c + 2); epi_elem(b - 1, c); }
-          else if (DIRECT) epi_elem(b - 1, c);
           else if (c < 8) { epi_elem(b - 1, 2 * c); epi_elem(b - 1, 2 * c + 1); }
           else if (c >= 9 && c < 13) epi_store(b - 1, c - 9);    // the read was requested in front of this group's MFMAs
         }
@@ -382,17 +367,16 @@ __global__ __launch_bounds__(RB_THREADS) void k_rb_level(const RbLevelArgs a) {
         rec[8 * 128 + tid] = sdb;
       }
     }
-    if (!(a.variant & 8)) {          // the last block's epilogue, beside the weight-gradient waves' final stores
-      if (LOWX) { lx_load(nb - 1, 0); lx_load(nb - 1, 1); }
+    // the last block's epilogue, beside the weight-gradient waves' final stores
+    if (LOWX) { lx_load(nb - 1, 0); lx_load(nb - 1, 1); }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (LOWX && r + 2 < 16) lx_load(nb - 1, r + 2);
-        epi_elem(nb - 1, r);
-      }
-      if (MODE == 0) {
+    for (int r = 0; r < 16; ++r) {
+      if (LOWX && r + 2 < 16) lx_load(nb - 1, r + 2);
+      epi_elem(nb - 1, r);
+    }
+    if (MODE == 0) {
 #pragma unroll
-        for (int it = 0; it < 4; ++it) { epi_read(it); epi_store(nb - 1, it); }
-      }
+      for (int it = 0; it < 4; ++it) { epi_read(it); epi_store(nb - 1, it); }
     }
     if (LOWX) {
       // the two row halves (rt = 0, 1) of a column half meet: rt = 1 parks [32 c][64 j] + its bias sums, rt = 0 adds and
@@ -586,26 +570,24 @@ __global__ __launch_bounds__(RB_THREADS) void k_rb_level(const RbLevelArgs a) {
   }
   // ---- the workgroup's weight-gradient partial: accumulators -> LDS (stage 0 is idle) -> 16-byte stores
   __syncthreads();
-  if (!((a.variant & 4) && accw[0][0] != 12345.f)) {
-    float* wp = smem + ot * (32 * RB_WPLD);
+  float* wp = smem + ot * (32 * RB_WPLD);
 #pragma unroll
-    for (int n = 0; n < 2; ++n)
+  for (int n = 0; n < 2; ++n)
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        wp[((r & 3) + 8 * (r >> 2) + 4 * h) * RB_WPLD + 32 * n + l31] = accw[n][r];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    float* out = a.dWp + range * a.sWpart + net * a.sWnet + (long long)(32 * ot) * a.ldwp + c0;
-    const int prow = lane >> 4, pc4 = lane & 15;
+    for (int r = 0; r < 16; ++r)
+      wp[((r & 3) + 8 * (r >> 2) + 4 * h) * RB_WPLD + 32 * n + l31] = accw[n][r];
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  float* out = a.dWp + range * a.sWpart + net * a.sWnet + (long long)(32 * ot) * a.ldwp + c0;
+  const int prow = lane >> 4, pc4 = lane & 15;
 #pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(wp + (4 * it + prow) * RB_WPLD + 4 * pc4);
-      *reinterpret_cast<f32x4*>(out + (long long)(4 * it + prow) * a.ldwp + 4 * pc4) = v;
-    }
-    if (do_bias) {
-      // lane (l31, h) summed rows 4 h + j (mod 8) of column 32 ot + l31: add the two halves in fixed order
-      const float other = __shfl_xor(bsum, 32, 64);
-      if (h == 0) a.dBp[range * a.sBpart + net * a.sBnet + 32 * ot + l31] = bsum + other;
-    }
+  for (int it = 0; it < 8; ++it) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(wp + (4 * it + prow) * RB_WPLD + 4 * pc4);
+    *reinterpret_cast<f32x4*>(out + (long long)(4 * it + prow) * a.ldwp + 4 * pc4) = v;
+  }
+  if (do_bias) {
+    // lane (l31, h) summed rows 4 h + j (mod 8) of column 32 ot + l31: add the two halves in fixed order
+    const float other = __shfl_xor(bsum, 32, 64);
+    if (h == 0) a.dBp[range * a.sBpart + net * a.sBnet + 32 * ot + l31] = bsum + other;
   }
   if (LOWX) __syncthreads();          // (the data-gradient waves' exchange of their second product)
 }
@@ -620,9 +602,6 @@ static hipError_t rb_level_backward(RbLevelArgs a, hipStream_t s, int prof_class
     return hipErrorNotSupported;
   a.nslices = a.IN / RB_S;
   a.nblocks = a.rows / RB_BR;
-  static int variant = -1;
-  if (variant < 0) { const char* e = getenv("IGI_RB_VARIANT"); variant = e ? atoi(e) : 0; }
-  a.variant = variant;
   if (a.ranges < 1 || a.ranges > a.nblocks) return hipErrorInvalidValue;
   const bool lowx = a.lx_W != nullptr;
   if (lowx && (a.nets != 1 || !a.lx_X || !a.lx_B || a.lx_ld < 64 || a.lx_ldw < 64)) return hipErrorInvalidValue;
@@ -632,8 +611,7 @@ static hipError_t rb_level_backward(RbLevelArgs a, hipStream_t s, int prof_class
     return hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
-    const void* ks[5] = {(const void*)k_rb_level<0, 1>, (const void*)k_rb_level<0, 2>, (const void*)k_rb_level<1, 1>,
-                         (const void*)k_rb_level<1, 2>, (const void*)k_rb_level<2, 1>};
+    const void* ks[3] = {(const void*)k_rb_level<0, 1>, (const void*)k_rb_level<0, 2>, (const void*)k_rb_level<2, 1>};
     for (const void* k : ks) {
       hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * RB_LDS_FLOATS));
       if (e != hipSuccess) return e;
@@ -651,13 +629,8 @@ static hipError_t rb_level_backward(RbLevelArgs a, hipStream_t s, int prof_class
   const size_t shm = sizeof(float) * RB_LDS_FLOATS;
   if (latz) IGI_LAUNCH((k_rb_level<3, 1>), grid, dim3(RB_THREADS), sizeof(float) * RB_LDS_FLOATS_LATZ, s, a);
   else if (lowx) IGI_LAUNCH((k_rb_level<2, 1>), grid, dim3(RB_THREADS), shm, s, a);
-  else if (a.variant & 32) {
-    if (a.nets == 1) IGI_LAUNCH((k_rb_level<1, 1>), grid, dim3(RB_THREADS), shm, s, a);
-    else IGI_LAUNCH((k_rb_level<1, 2>), grid, dim3(RB_THREADS), shm, s, a);
-  } else {
-    if (a.nets == 1) IGI_LAUNCH((k_rb_level<0, 1>), grid, dim3(RB_THREADS), shm, s, a);
-    else IGI_LAUNCH((k_rb_level<0, 2>), grid, dim3(RB_THREADS), shm, s, a);
-  }
+  else if (a.nets == 1) IGI_LAUNCH((k_rb_level<0, 1>), grid, dim3(RB_THREADS), shm, s, a);
+  else IGI_LAUNCH((k_rb_level<0, 2>), grid, dim3(RB_THREADS), shm, s, a);
   return hipGetLastError();
 }
 

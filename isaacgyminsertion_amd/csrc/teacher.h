@@ -40,12 +40,10 @@ static inline long long ru64(long long x) { return (x + 63) & ~63LL; }  // 256-b
 constexpr int PREP_THREADS = 256;
 constexpr int GS_THREADS = 256;
 constexpr int LOSS_THREADS = 256;
-constexpr int LOSS_BLOCKS_MAX = 1024;
 constexpr int LOSS_BLOCKS_DEFAULT = 512;  // measured: 256 -> 55 us, 512 -> 35 us, 1024 -> 37 us per launch
 constexpr int RED_THREADS = 256;
 constexpr int SUMSQ_BLOCKS = 512;
 constexpr int MAX_SEG = 32;
-constexpr int SLAB_GX_MAX = 2048;   // blocks per segment of k_slab_reduce (IGI_SLAB_GX is clamped to it)
 constexpr int ADAM_BLOCKS_MAX = 1024;
 
 // ---------------------------------------------------------------------------------------------
@@ -74,7 +72,7 @@ struct TeacherPlan {
   int lat_tiles;
   int lat_fused, lat_blocks, lat_rpw;  // fused latent / last-env-layer backward (k_latent_bwd)  // per-minibatch batch moments; per-step normaliser trajectory
   size_t w_e[IGI_MAX_LAYERS], w_de[IGI_MAX_LAYERS], w_h[IGI_MAX_LAYERS], w_dh[IGI_MAX_LAYERS];
-  size_t w_loss_part, w_head_slab, w_slab, w_sumsq, w_gpart, w_ppart, w_scal, w_total;
+  size_t w_loss_part, w_head_slab, w_slab, w_sumsq, w_scal, w_total;
   int gae_blocks, gs_rows, gs_blocks, loss_blocks, loss_rpw;
   int loss_fused;  // heads + loss + head backward ride in the last trunk layer's forward (k_trunk_loss); loss_blocks = its m-tiles
   // backward levels that run as ONE persistent row-block kernel (rowblock.h) instead of data-gradient + weight-gradient
@@ -104,9 +102,7 @@ static int choose_splitk(int M, int N, int K, int nbatch) {
     // workgroups of 32 k-tiles, first in the grid, halve its slab and run 7 us shorter)
     const int bn = N <= 64 ? 64 : 128;
     // (<= 32 input columns and whole 256-row tiles: gemm_wgrad_multi runs 256 x 32 tiles, kind 3)
-    static int narrow = -1;
-    if (narrow < 0) { const char* e = getenv("IGI_WGRAD_N32"); narrow = e ? atoi(e) : (rb_level_enabled() ? 1 : 0); }   // see gemm_wgrad_multi
-    const int bm = (narrow && N <= 32 && M % 256 == 0) ? 256 : DMA_BM;
+    const int bm = (N <= 32 && M % 256 == 0) ? 256 : DMA_BM;
     const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn) * nbatch;
     int sk = (int)(256 / tiles > 1 ? 256 / tiles : 1);
     const int maxsk = K / 128 > 1 ? K / 128 : 1;
@@ -241,27 +237,20 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   // loss kernel: one wave per row, loss_rpw rows per wave
   long long waves_needed = mb;
   int blocks = (int)((waves_needed + 4 * 4 - 1) / (4 * 4));
-  int max_blocks = LOSS_BLOCKS_DEFAULT;
-  if (const char* e = getenv("IGI_LOSS_BLOCKS")) {  // tuning knob (power of two, <= 1024)
-    const int v = atoi(e);
-    if (v >= 1 && v <= LOSS_BLOCKS_MAX) max_blocks = v;
-  }
-  if (blocks > max_blocks) blocks = max_blocks;
+  if (blocks > LOSS_BLOCKS_DEFAULT) blocks = LOSS_BLOCKS_DEFAULT;
   if (blocks < 1) blocks = 1;
   p->loss_blocks = blocks;
   p->loss_rpw = (int)((mb + (long long)blocks * 4 - 1) / ((long long)blocks * 4));
   {
     // the fused last-layer forward + loss (k_trunk_loss): decided from the shapes alone, so that the workspace carve-up,
     // the slab sums and the statistics kernel agree on the number of partial records (one per 64-row m-tile)
-    static int fused = -1;
-    if (fused < 0) { const char* e = getenv("IGI_LOSS_FUSED"); fused = e ? atoi(e) : 1; }
     // (the launch site re-checks dma_eligible and the 16-byte alignment of bias / dh: every offset and stride that enters
     // those checks is tested HERE, so that a shape which passes keeps passing at the launch and one which does not keeps
     // the two-launch path -- only a misaligned base pointer of the caller remains an error there)
     const int ll = p->nl - 1;
     const bool aligned = (p->o_acW[ll] & 3) == 0 && (p->o_acB[ll] & 3) == 0 && (p->ac_block & 3) == 0 &&
                          (ru4(p->u[ll]) & 3) == 0 && (ru4(p->u[ll - (ll > 0)]) & 3) == 0 && ((long long)p->mb * ru4(p->u[ll]) & 3) == 0;
-    p->loss_fused = (fused && p->nl >= 2 && H_last_is_128(p) && p->act <= 7 && (p->u[p->nl - 2] % DMA_BK) == 0 &&
+    p->loss_fused = (p->nl >= 2 && H_last_is_128(p) && p->act <= 7 && (p->u[p->nl - 2] % DMA_BK) == 0 &&
                      p->Bsz < (1LL << 31) && !bf16_mode() && aligned) ? 1 : 0;
     if (p->loss_fused) p->loss_blocks = (int)((mb + 63) / 64);   // TrunkLossHook::TILE_M
   }
@@ -273,29 +262,14 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   // workgroup slots exactly once: 84 -> ~40 MB of slabs) was measured and is SLOWER: 141 us + 14 us reduce against
   // 131.5 + 18.5 (`tools/scratch`-style sweep over slot targets 256..2048): uneven k-chunks lose the
   // per-problem XCD grouping and long workgroups run below the k-loop's steady rate.
-  // IGI_SK_OVERRIDE="e0,e1,e2,a0,a1,a2" (0 = keep): split factors of the env / trunk weight gradients, for A/B runs
-  int sk_over[2 * IGI_MAX_LAYERS] = {0};
-  if (const char* e = getenv("IGI_SK_OVERRIDE")) {
-    int i = 0;
-    for (const char* q = e; *q && i < 2 * IGI_MAX_LAYERS; ++i) {
-      sk_over[i] = atoi(q);
-      while (*q && *q != ',') ++q;
-      if (*q == ',') ++q;
-    }
-  }
-  auto pick = [&](int dflt, int over, int K) {
-    if (over <= 0) return dflt;
-    const int maxsk = K / 128 > 1 ? K / 128 : 1;
-    return over > maxsk ? maxsk : over;
-  };
   long long s = 0;
   for (int l = 0; l < p->npl; ++l) {
     int sk = choose_splitk(p->pu[l], env_in(*p, l), p->mb, 1);
     // the first env layer's weight gradient is a launch of its own and has to fill the chip; the later ones share the
     // env-level launch with two other products: half the split (8 k-tiles per workgroup instead of 4, half the slab) --
-    // env level 44.3 -> 42.4 us, slab sum 17.2 -> 15.4 us, A/B of tools/probes/sk_ab.sh (every other factor: slower)
+    // env level 44.3 -> 42.4 us, slab sum 17.2 -> 15.4 us (every other factor: slower)
     if (l > 0 && sk > 1) sk /= 2;
-    p->sk_env[l] = pick(sk, sk_over[l], p->mb);
+    p->sk_env[l] = sk;
     // layer l's weight gradient and the data gradient into layer l - 1 as one row-block kernel (the last layer's
     // backward is k_latent_bwd's when lat_fused): decided from the shapes alone, like every other plan entry
     if (l >= 1 && l < p->npl - p->lat_fused - (p->ct_P > 0) && rb_level_shape_ok(p->mb, p->pu[l], p->pu[l - 1], 1)) {
@@ -306,20 +280,16 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
     p->s_envB[l] = s; s += (long long)p->sk_env[l] * p->pu[l];
     s = (s + 3) & ~3LL;
   }
-  {
-    static int lx_on = -1;
-    if (lx_on < 0) { const char* e = getenv("IGI_LOWX_FUSE"); lx_on = e ? atoi(e) : 1; }
-    if (lx_on && p->npl >= 2 && p->rb_env[1] && p->priv == 64) {
-      // env layer 0's weight gradient from the data-gradient tiles of the level above: rb_env[1] partial records; the slab
-      // offsets of the layers behind it move accordingly (recomputed below)
-      p->lx_env = 1;
-      p->sk_env[0] = p->rb_env[1];
-      s = 0;
-      for (int l = 0; l < p->npl; ++l) {
-        p->s_envW[l] = s; s += (long long)p->sk_env[l] * p->pu[l] * env_in(*p, l);
-        p->s_envB[l] = s; s += (long long)p->sk_env[l] * p->pu[l];
-        s = (s + 3) & ~3LL;
-      }
+  if (p->npl >= 2 && p->rb_env[1] && p->priv == 64) {
+    // env layer 0's weight gradient from the data-gradient tiles of the level above: rb_env[1] partial records; the slab
+    // offsets of the layers behind it move accordingly (recomputed below)
+    p->lx_env = 1;
+    p->sk_env[0] = p->rb_env[1];
+    s = 0;
+    for (int l = 0; l < p->npl; ++l) {
+      p->s_envW[l] = s; s += (long long)p->sk_env[l] * p->pu[l] * env_in(*p, l);
+      p->s_envB[l] = s; s += (long long)p->sk_env[l] * p->pu[l];
+      s = (s + 3) & ~3LL;
     }
   }
   {
@@ -331,22 +301,20 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   }
   for (int l = 0; l < p->nl; ++l) {
     const int inw = (l == 0) ? p->xld : ac_in(*p, l);  // layer 0 multiplies the padded xcat
-    p->sk_ac[l] = pick(choose_splitk(p->u[l], inw, p->mb, 2), sk_over[p->npl + l], p->mb);
+    p->sk_ac[l] = choose_splitk(p->u[l], inw, p->mb, 2);
     // (l >= 2: the data gradient into trunk layer 0 keeps its interleaved layout and the latent row dots)
     if (l >= 2 && rb_level_shape_ok(p->mb, p->u[l], p->u[l - 1], 2)) {
       p->rb_ac[l] = rb_level_ranges(p->mb, p->u[l - 1], 2);
       p->sk_ac[l] = p->rb_ac[l];
     }
     if (l == 0) {
-      static int lw_on = -1;
-      if (lw_on < 0) { const char* e = getenv("IGI_LOWW_FUSE"); lw_on = e ? atoi(e) : 1; }
       const int mt128 = p->mb / DMA_BM;
       const int chain = (mt128 % 4 == 0) ? 4 : ((mt128 % 2 == 0) ? 2 : 1);
       // shapes only (the launch re-checks pointers): row dots from those tiles, 32-wide padded input with a FREE last
       // column (xw <= 31: column 31 carries the ONE of the bias gradient; obs + latent == 32 takes the separate
       // weight-gradient launch), whole 128-row / 128-column tiles, the level-fused grid
-      if (lw_on && p->nl >= 2 && p->lat_fused && p->xld == 32 && p->xw < 32 && (p->mb % DMA_BM) == 0 && (p->u[0] % 128) == 0 &&
-          gemm_level_enabled() && p->mb >= 4) {
+      if (p->nl >= 2 && p->lat_fused && p->xld == 32 && p->xw < 32 && (p->mb % DMA_BM) == 0 && (p->u[0] % 128) == 0 &&
+          !bf16_mode() && p->mb >= 4) {
         p->lw_chain = chain;
         p->lw_parts = mt128 / chain;
         p->sk_ac[0] = p->lw_parts;
@@ -360,8 +328,6 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   p->slab_floats = s;
   p->w_slab = take(sizeof(float) * (size_t)s);
   p->w_sumsq = take(sizeof(double) * 2 * SUMSQ_BLOCKS);
-  p->w_gpart = take(sizeof(double) * (size_t)SLAB_GX_MAX * MAX_SEG);   // k_slab_reduce's per-block gradient sums of squares (norm fusion)
-  p->w_ppart = take(sizeof(double) * 2 * ADAM_BLOCKS_MAX);             // the Adam blocks' parameter sums of squares, two alternating sets
   p->w_scal = take(sizeof(float) * 8);
   p->w_total = w;
   return 0;
@@ -1392,7 +1358,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_packed(const LossArgs a) 
 //       E  the waves' bias / sigma / loss partials in wave order -> the same record (mb / 64 records per minibatch)
 //     The hidden layer itself is not stored (nothing reads it: the data gradient below needs tanh' of the layer BELOW).
 //     Same formulas, expression by expression, as k_loss; the head sums run in the MFMA's k order.  H == 128, act <= 7;
-//     other shapes keep the two launches (IGI_LOSS_FUSED=0 forces them).  Same box, A/B: 21.6 + 15.4 -> 30.6 us per step.
+//     other shapes (and bf16-input mode) keep the two launches.  Same box, A/B: 21.6 + 15.4 -> 30.6 us per step.
 // ---------------------------------------------------------------------------------------------
 struct TrunkLossHook {
   const LossArgs& a;
@@ -1733,12 +1699,6 @@ struct SegTable {
   int n;
   int wide = 0;   // 1: dense 16-byte-aligned segments with >= 64 partials take the 16-byte part-group path (the student's
                   // per-workgroup gradient records: 170 - 512 partials of 16 - 80 K floats)
-  // Norm fusion (the teacher's one-call update on one GPU, steps >= 1; frozen_ppo.py:605-608): every block also leaves the
-  // sum of squares (fp64) of the gradient elements IT wrote in norm_part[blockIdx.y * gridDim.x + blockIdx.x], and the
-  // extra grid row y == n turns the loss partials into the step's statistics row -- k_sumsq_stats then has nothing left
-  // to do and is not launched (the Adam blocks add the partials in index order: clip_adam_body, NormSrc).
-  double* norm_part = nullptr;
-  const double* loss_part = nullptr; int loss_blocks = 0, mb = 0; float* stats_row = nullptr;
 };
 
 // strided fixed-order sums of the loss partial records -> the statistics row (means over the minibatch); one block
@@ -1772,32 +1732,9 @@ constexpr int SLAB_GX = 256;
 // (e = tid % (256/G), grp = tid / (256/G)) sums parts grp, grp+G, ... with 4 independent
 // accumulators; groups are combined through LDS in fixed order.  G grows with the number of
 // partials so long part lists (per-block head partials) are not a serial chain.
-// NORM: the norm-fusion variant (its own kernel, k_slab_reduce_norm: the block reduction costs two registers over the 64 that
-// keep eight waves per SIMD, and every other caller runs the plain one)
-template <bool NORM>
-__device__ __forceinline__ void slab_reduce_body(const SegTable& t, float* __restrict__ grads) {
+__global__ __launch_bounds__(RED_THREADS) void k_slab_reduce(const SegTable t, float* __restrict__ grads) {
   __shared__ float sh[RED_THREADS];
-  if (NORM && (int)blockIdx.y == t.n) {      // the statistics row of this step
-    if (blockIdx.x == 0 && t.stats_row) stats_row_block(t.loss_part, t.loss_blocks, t.mb, t.stats_row);
-    return;
-  }
   const Segment sg = t.s[blockIdx.y];
-  const bool norm = NORM && t.norm_part != nullptr;
-  double nsq = 0.0;                  // sum of squares of the elements this thread wrote
-  // fixed-order block sum of nsq -> this block's slot (every path below ends here)
-  __shared__ double nred[RED_THREADS / 64];
-  auto leave_norm = [&]() {
-    if (!norm) return;
-    nsq = wave_sum(nsq);
-    if ((threadIdx.x & 63) == 0) nred[threadIdx.x >> 6] = nsq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double v = nred[0];
-#pragma unroll
-      for (int w = 1; w < RED_THREADS / 64; ++w) v += nred[w];
-      t.norm_part[(long long)blockIdx.y * gridDim.x + blockIdx.x] = v;
-    }
-  };
   // 16-byte path (dense, aligned segments with few partials = the big split-K slabs): four elements per
   // thread and part, four parts in flight -> 16x the bytes in flight of the scalar path below
   if (sg.src_ld == 0 && sg.nparts < 64 && (sg.count & 3) == 0 && (sg.stride & 3) == 0 && (sg.dst & 3) == 0 &&
@@ -1823,9 +1760,7 @@ __device__ __forceinline__ void slab_reduce_body(const SegTable& t, float* __res
       o.x = (s0.x + s1.x) + (s2.x + s3.x); o.y = (s0.y + s1.y) + (s2.y + s3.y);
       o.z = (s0.z + s1.z) + (s2.z + s3.z); o.w = (s0.w + s1.w) + (s2.w + s3.w);
       *reinterpret_cast<float4*>(grads + sg.dst + 4 * (long long)e) = o;
-      if (norm) nsq += ((double)o.x * (double)o.x + (double)o.y * (double)o.y) + ((double)o.z * (double)o.z + (double)o.w * (double)o.w);
     }
-    leave_norm();
     return;
   }
   if (t.wide && sg.src_ld == 0 && sg.nparts >= 64 && (sg.count & 3) == 0 && (sg.stride & 3) == 0 && (sg.dst & 3) == 0 &&
@@ -1868,11 +1803,9 @@ __device__ __forceinline__ void slab_reduce_body(const SegTable& t, float* __res
           v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
         }
         *reinterpret_cast<float4*>(grads + sg.dst + 4 * (long long)e) = v;
-        if (norm) nsq += ((double)v.x * (double)v.x + (double)v.y * (double)v.y) + ((double)v.z * (double)v.z + (double)v.w * (double)v.w);
       }
       __syncthreads();
     }
-    leave_norm();
     return;
   }
   const int G = sg.nparts >= 256 ? 32 : (sg.nparts >= 64 ? 8 : 1);
@@ -1902,18 +1835,8 @@ __device__ __forceinline__ void slab_reduce_body(const SegTable& t, float* __res
       }
       __syncthreads();
     }
-    if (grp == 0 && e < sg.count) {
-      grads[sg.dst + e] = v;
-      if (norm) nsq += (double)v * (double)v;
-    }
+    if (grp == 0 && e < sg.count) grads[sg.dst + e] = v;
   }
-  leave_norm();
-}
-__global__ __launch_bounds__(RED_THREADS) void k_slab_reduce(const SegTable t, float* __restrict__ grads) {
-  slab_reduce_body<false>(t, grads);
-}
-__global__ __launch_bounds__(RED_THREADS) void k_slab_reduce_norm(const SegTable t, float* __restrict__ grads) {
-  slab_reduce_body<true>(t, grads);
 }
 
 // sum of squares of (grad*scale) and of the parameters, per block, in fp64; the extra last block
@@ -1957,41 +1880,15 @@ struct W1Mirror {
   long long o_w, ac_block; int u0, u0p, xw, xld, obs, K2p;
 };
 
-// Where the two norms of a step come from when k_sumsq_stats is not launched (the one-call update on one GPU, steps >= 1):
-// the gradient's sum of squares from k_slab_reduce's per-block partials (SegTable::norm_part), the parameters' from the
-// partials the PREVIOUS step's Adam blocks left of the parameters they had just written (pp_out of that pass = pp_in of
-// this one; two buffers alternate, a block reads all of pp_in while others already write pp_out).
-struct NormSrc {
-  const double* gpart = nullptr; int n_g = 0;
-  const double* pp_in = nullptr; int n_p = 0;
-  double* pp_out = nullptr;        // one fp64 per Adam block: sum of squares of the UPDATED parameters it wrote (may be set alone)
-};
-
 __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const float* __restrict__ grads,
                                                float* __restrict__ m, float* __restrict__ v, long long P,
                                                const double* __restrict__ part, float scale, float max_norm, float w1,
                                                float beta2, float w2, float step_size, float bc2_sqrt, float eps,
                                                float* __restrict__ stats_row, float decay, float l2, int bid,
-                                               int nblocks, const W1Mirror* mir, const NormSrc* ns = nullptr) {
+                                               int nblocks, const W1Mirror* mir) {
   __shared__ float s_coef;
   __shared__ double s_part[2][64];
-  const bool fused_norm = ns && ns->gpart;
-  if (fused_norm) {
-    // every thread adds its strided share of the partials in index order (eight loads in flight), the waves meet through
-    // the fixed butterfly of wave_sum, wave sums in wave order: the same value in every block, launch after launch
-    double sg = 0, sp = 0;
-    for (int b0 = threadIdx.x; b0 < ns->n_g; b0 += 256 * 8) {
-      double q[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { const int b = b0 + 256 * u; q[u] = b < ns->n_g ? ns->gpart[b] : 0.0; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) sg += q[u];
-    }
-    for (int b = threadIdx.x; b < ns->n_p; b += 256) sp += ns->pp_in[b];
-    sg = wave_sum(sg);
-    sp = wave_sum(sp);
-    if ((threadIdx.x & 63) == 0) { s_part[0][threadIdx.x >> 6] = sg; s_part[1][threadIdx.x >> 6] = sp; }
-  } else if (threadIdx.x < 64) {
+  if (threadIdx.x < 64) {
     // 128 partial pairs: lane b of the first wave adds pairs b and b + 64, lane 0 finishes in lane order
     // (every block repeats this, so a serial chain of 256 loads sat in front of each block's real work)
     double sg = 0, sp = 0;
@@ -2003,9 +1900,8 @@ __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const
   __syncthreads();
   if (threadIdx.x == 0) {
     double sg = 0, sp = 0;
-    const int nsum = fused_norm ? 4 : 64;
 #pragma unroll 4
-    for (int b = 0; b < nsum; ++b) { sg += s_part[0][b]; sp += s_part[1][b]; }
+    for (int b = 0; b < 64; ++b) { sg += s_part[0][b]; sp += s_part[1][b]; }
     const float total = (float)sqrt(sg);
     float coef = 1.0f;
     if (max_norm > 0.f) coef = fminf(max_norm / (total + 1e-6f), 1.0f);
@@ -2018,7 +1914,6 @@ __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const
   }
   __syncthreads();
   const float coef = s_coef;
-  double psq = 0.0;                  // sum of squares of the parameters this thread has written (for the NEXT step's log)
   // one element: exactly torch's single-tensor Adam arithmetic (each line one rounding, -ffp-contract=off)
   auto one = [&](long long i, float gi, float& pi, float& mi, float& vi) {
     float g = (gi * scale) * coef;
@@ -2028,7 +1923,6 @@ __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     // AdamW: param.mul_(1 - lr * weight_decay) first (decay == 1 for plain Adam: exact no-op)
     pi = pi * decay + (-step_size) * (mi / denom);  // param.addcdiv_(exp_avg, denom, -step_size)
-    psq += (double)pi * (double)pi;
     if (mir) {  // W1p[net][o][c] and the transposed latent columns follow the parameter they copy
       long long rel = i - mir->o_w;
       int net = 0;
@@ -2068,13 +1962,6 @@ __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const
       v[i] = vi;
     }
   }
-  if (ns && ns->pp_out) {   // this block's share of |params|^2 after the step, for the next step's statistics row
-    psq = wave_sum(psq);
-    __syncthreads();        // (s_part was read by thread 0 above)
-    if ((threadIdx.x & 63) == 0) s_part[0][threadIdx.x >> 6] = psq;
-    __syncthreads();
-    if (threadIdx.x == 0) ns->pp_out[bid] = (s_part[0][0] + s_part[0][1]) + (s_part[0][2] + s_part[0][3]);
-  }
 }
 
 __global__ __launch_bounds__(256) void k_clip_adam(float* __restrict__ params,
@@ -2084,9 +1971,9 @@ __global__ __launch_bounds__(256) void k_clip_adam(float* __restrict__ params,
                                                    float scale, float max_norm, float w1, float beta2,
                                                    float w2, float step_size, float bc2_sqrt, float eps,
                                                    float* __restrict__ stats_row, float decay = 1.0f,
-                                                   float l2 = 0.0f, const NormSrc ns = NormSrc()) {
+                                                   float l2 = 0.0f) {
   clip_adam_body(params, grads, m, v, P, part, scale, max_norm, w1, beta2, w2, step_size, bc2_sqrt, eps, stats_row,
-                 decay, l2, (int)blockIdx.x, (int)gridDim.x, nullptr, &ns);
+                 decay, l2, (int)blockIdx.x, (int)gridDim.x, nullptr);
 }
 
 // Tail of optimizer step s fused with the head of step s+1: blocks [0, adam_blocks) run clip + Adam (and keep the
@@ -2099,7 +1986,7 @@ struct AdamArgs {
   float scale, max_norm, w1, beta2, w2, step_size, bc2_sqrt, eps; float* stats_row;
 };
 __global__ __launch_bounds__(256) void k_adam_gather(const AdamArgs a, const W1Mirror mir, const GatherArgs g,
-                                                     int adam_blocks, const NormSrc ns) {
+                                                     int adam_blocks) {
   // the gather blocks come first in the grid (the longer dependent chain: index -> row -> store), so that both kinds
   // are resident from the start
   const int gblocks = (int)gridDim.x - adam_blocks;
@@ -2107,7 +1994,7 @@ __global__ __launch_bounds__(256) void k_adam_gather(const AdamArgs a, const W1M
     gather_normalize_body(g, (int)blockIdx.x, gblocks);
   else
     clip_adam_body(a.params, a.grads, a.m, a.v, a.P, a.part, a.scale, a.max_norm, a.w1, a.beta2, a.w2, a.step_size,
-                   a.bc2_sqrt, a.eps, a.stats_row, 1.0f, 0.0f, (int)blockIdx.x - gblocks, adam_blocks, &mir, &ns);
+                   a.bc2_sqrt, a.eps, a.stats_row, 1.0f, 0.0f, (int)blockIdx.x - gblocks, adam_blocks, &mir);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2437,15 +2324,13 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
   // env_mlp: tanh after every layer, the last one lands in xcat[:, obs:]
   const float* in = priv_g;
   int ldin = ru4(p.priv);
-  static int fuse_head = -1;
-  if (fuse_head < 0) { const char* e = getenv("IGI_FUSE_HEAD"); fuse_head = e ? atoi(e) : 1; }
   static int env_fused = -1;
   if (env_fused < 0) { const char* e = getenv("IGI_ENV_FUSED"); env_fused = e ? atoi(e) : 1; }
   bool env_done = p.ct_only != 0;   // only_contact: the privileged embedding is not used (models_split.py:176-177)
   int first_trunk_layer = 0;
-  // round 6: env_mlp AND the first trunk layer of both nets as one persistent launch (fwd12.h); IGI_FWD12=0 keeps
-  // k_env_fwd + the layer's own launch below
-  if (fwd12_enabled() && env_fused && p.npl == 3 && p.ct_P == 0 && nl_run >= 1 && rows >= 2048 && !bf16_mode() &&
+  // round 6: env_mlp AND the first trunk layer of both nets as one persistent launch (fwd12.h); other shapes keep
+  // k_env_fwd (or the per-layer launches) + the layer's own launch below
+  if (env_fused && p.npl == 3 && p.ct_P == 0 && nl_run >= 1 && rows >= 2048 && !bf16_mode() &&
       fwd12_supported(p.priv, p.pu[0], p.pu[1], p.pu[2], p.obs, p.xld, p.u[0]) && p.u0p == p.u[0]) {
     Fwd12Args f;
     f.priv = priv_g; f.ldp = ldin; f.xcat = xcat; f.ldx = p.xld; f.M = rows; f.obs = p.obs;
@@ -2481,7 +2366,7 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
     if (l == p.npl - 1) { g.C = xcat + p.obs; g.ldc = p.xld; }
     else { g.C = wsp<float>(st, p.w_e[l]); g.ldc = ru4(p.pu[l]); }
     g.epilogue = EPI_BIAS_TANH;
-    if (fuse_head && l == p.npl - 2 && p.pu[l + 1] <= 8) {
+    if (l == p.npl - 2 && p.pu[l + 1] <= 8) {
       // the <= 8-wide latent layer rides in this layer's epilogue (one launch less per step)
       GemmArgs gh = g;
       gh.head_W = P + p.o_envW[l + 1]; gh.head_b = P + p.o_envB[l + 1];
@@ -2588,17 +2473,11 @@ static GemmArgs trunk_dgrad_args(const TeacherPlan& p, const igi_teacher_state* 
 // addresses alone, with the very predicate the launcher applies (gemm_multi_dgrad_ok), so that both halves of a phased
 // step agree and the launch can never decline row dots the plan counted on (it falls back to k_latent_bwd<., false>).
 static bool latent_rowdot(const TeacherPlan& p, const igi_teacher_state* st) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("IGI_LAT_ROWDOT"); on = e ? atoi(e) : 1; }
-  if (!(on && p.lat_fused && p.nl >= 2 && gemm_level_enabled() && p.mb >= 4)) return false;
+  if (!(p.lat_fused && p.nl >= 2 && !bf16_mode() && p.mb >= 4)) return false;
   GemmArgs g = trunk_dgrad_args(p, st, 1, true);
   return gemm_multi_dgrad_ok(g);
 }
 
-// skip_gather: the previous step's fused tail (k_adam_gather) already gathered + normalised this minibatch
-// norm_parts (phase -1 only): non-null turns the norm fusion on -- k_slab_reduce also leaves the gradient's sum-of-squares
-// partials (their count comes back in *norm_parts) and writes this step's statistics row; the caller then runs
-// teacher_apply(..., norm_mode 2), which does not launch k_sumsq_stats
 // the contact encoder of a minibatch (perm != nullptr: rows start.. of the permutation over the (T, N, P) arena) or of
 // `rows` plain rows (perm == nullptr, T = 1)
 static ContactArgs contact_args(const TeacherPlan& p, const igi_teacher_state* st, const float* contacts,
@@ -2615,9 +2494,10 @@ static ContactArgs contact_args(const TeacherPlan& p, const igi_teacher_state* s
   return a;
 }
 
+// skip_gather: the previous step's fused tail (k_adam_gather) already gathered + normalised this minibatch
 static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
                            const igi_teacher_state* st, int mb_index, int step_slot, hipStream_t s,
-                           int phase = -1, bool skip_gather = false, int* norm_parts = nullptr) {
+                           int phase = -1, bool skip_gather = false) {
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
@@ -2704,9 +2584,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
                  4.0 * (double)mbs * (4.0 * ldh + 4 * p.act + 6));
     const size_t shm = sizeof(float) * 4 * p.head_count;
     const int maxj = (H + 63) / 64;
-    static int packed = -1;
-    if (packed < 0) { const char* e = getenv("IGI_LOSS_PACKED"); packed = e ? atoi(e) : 1; }
-    if (packed && p.act <= 7) {   // scalar section once per four rows
+    if (p.act <= 7) {   // scalar section once per four rows
       if (maxj <= 1) IGI_LAUNCH(k_loss_packed<1>, dim3(p.loss_blocks), dim3(LOSS_THREADS), shm, s, a);
       else if (maxj == 2) IGI_LAUNCH(k_loss_packed<2>, dim3(p.loss_blocks), dim3(LOSS_THREADS), shm, s, a);
       else IGI_LAUNCH(k_loss_packed<4>, dim3(p.loss_blocks), dim3(LOSS_THREADS), shm, s, a);
@@ -2960,47 +2838,30 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   }
   {
     ProfScope ps(PC_SLAB_REDUCE, s, 0.0, 4.0 * ((double)p.slab_floats + (double)hc * p.loss_blocks + p.P));
-    static int gx = -1;
-    // blocks per segment: 64 / 128 / 256 / 512 / 1024 / 2048 -> 29.5 / 19.2 / 15.4 / 14.3 / 15.0 / 17.9 us (IGI_SLAB_GX)
+    // blocks per segment: 64 / 128 / 256 / 512 / 1024 / 2048 -> 29.5 / 19.2 / 15.4 / 14.3 / 15.0 / 17.9 us
     // (with the row-block levels' fewer, larger partial sets: 256 -> 13.0 us, 384 -> 13.9, 512 -> 14.2)
-    if (gx < 0) { const char* e = getenv("IGI_SLAB_GX"); gx = e ? atoi(e) : (rb_level_enabled() ? SLAB_GX : 2 * SLAB_GX); if (gx < 1) gx = 1; if (gx > SLAB_GX_MAX) gx = SLAB_GX_MAX; }
-    int gy = t.n;
-    if (norm_parts) {
-      if (phase != -1 || !st->stats) return IGI_E_BADARG;
-      t.norm_part = wsp<double>(st, p.w_gpart);
-      t.loss_part = wsp<double>(st, p.w_loss_part); t.loss_blocks = p.loss_blocks; t.mb = p.mb;
-      t.stats_row = st->stats + (long long)step_slot * IGI_STATS_PER_STEP;
-      *norm_parts = gx * t.n;
-      gy = t.n + 1;     // + the statistics row
-    }
-    if (norm_parts) IGI_LAUNCH(k_slab_reduce_norm, dim3(gx, gy), dim3(RED_THREADS), 0, s, t, st->grads);
-    else IGI_LAUNCH(k_slab_reduce, dim3(gx, gy), dim3(RED_THREADS), 0, s, t, st->grads);
+    IGI_LAUNCH(k_slab_reduce, dim3(SLAB_GX, t.n), dim3(RED_THREADS), 0, s, t, st->grads);
   }
   return (int)hipGetLastError();
 }
 
 // next_ro != NULL: fuse the gather + normalise of optimizer step (next_mb, next_slot) into this step's Adam launch
-// norm_mode 0: k_sumsq_stats computes both norms and the statistics row (any caller, any grad_scale);
-//           1: the same, and the Adam blocks leave the updated parameters' sum-of-squares partials for the next step;
-//           2: no k_sumsq_stats -- the gradient norm comes from the norm_parts partials of this step's k_slab_reduce, the
-//              parameter norm from the previous step's Adam partials (that step ran mode 1 or 2), the statistics row was
-//              written by k_slab_reduce; the Adam blocks leave their partials again.  grad_scale must be 1.
+// (k_sumsq_stats computes both norms and the statistics row first)
 static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, int step_slot,
                          int64_t adam_t, float grad_scale, hipStream_t s, const igi_rollout* next_ro = nullptr,
-                         int next_mb = 0, int next_slot = 0, int norm_mode = 0, int norm_parts = 0) {
+                         int next_mb = 0, int next_slot = 0) {
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
   if ((rc = check_state(p, st))) return rc;
   if (!st->grads || !st->adam_m || !st->adam_v || adam_t < 1) return IGI_E_BADARG;
-  if (norm_mode < 0 || norm_mode > 2 || (norm_mode == 2 && (grad_scale != 1.0f || norm_parts < 1 || !st->stats))) return IGI_E_BADARG;
   double* part = wsp<double>(st, p.w_sumsq);
   float* row = st->stats ? st->stats + (long long)step_slot * IGI_STATS_PER_STEP : nullptr;
-  if (norm_mode != 2) {
-  ProfScope ps(PC_SUMSQ, s, 0.0, 8.0 * (double)p.P);
-  IGI_LAUNCH(k_sumsq_stats, dim3(SUMSQ_BLOCKS + (row ? 1 : 0)), dim3(256), 0, s, st->grads,
-                     st->params, p.P, grad_scale, part, wsp<double>(st, p.w_loss_part), p.loss_blocks,
-                     p.mb, row);
+  {
+    ProfScope ps(PC_SUMSQ, s, 0.0, 8.0 * (double)p.P);
+    IGI_LAUNCH(k_sumsq_stats, dim3(SUMSQ_BLOCKS + (row ? 1 : 0)), dim3(256), 0, s, st->grads,
+                       st->params, p.P, grad_scale, part, wsp<double>(st, p.w_loss_part), p.loss_blocks,
+                       p.mb, row);
   }
   // torch.optim.Adam (_single_tensor_adam): python-double scalars, cast to fp32 at the tensor op
   const double b1 = c->beta1, b2 = c->beta2;
@@ -3012,12 +2873,6 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
   int nb = (int)((p.P / 4 + 255) / 256);   // four elements per thread and trip
   if (nb > ADAM_BLOCKS_MAX) nb = ADAM_BLOCKS_MAX;
   if (nb < 1) nb = 1;
-  NormSrc ns;
-  if (norm_mode >= 1) ns.pp_out = wsp<double>(st, p.w_ppart) + (size_t)(step_slot & 1) * ADAM_BLOCKS_MAX;
-  if (norm_mode == 2) {
-    ns.gpart = wsp<double>(st, p.w_gpart); ns.n_g = norm_parts;
-    ns.pp_in = wsp<double>(st, p.w_ppart) + (size_t)((step_slot + 1) & 1) * ADAM_BLOCKS_MAX; ns.n_p = nb;
-  }
   if (next_ro) {
     if (!next_ro->obses || !next_ro->priv_info || !st->perm || !st->rms_obs || !st->rms_priv) return IGI_E_BADARG;
     const int D = p.obs + p.priv;
@@ -3030,25 +2885,14 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
     W1Mirror mir;
     mir.w1p = ga.w1p; mir.wlat = ga.wlat; mir.o_w = ga.o_w; mir.ac_block = ga.ac_block; mir.u0 = ga.u0;
     mir.u0p = ga.u0p; mir.xw = p.xw; mir.xld = p.xld; mir.obs = p.obs; mir.K2p = ga.K2p;
-    IGI_LAUNCH(k_adam_gather, dim3(nb + p.gs_blocks), dim3(256), 0, s, aa, mir, ga, nb, ns);
+    IGI_LAUNCH(k_adam_gather, dim3(nb + p.gs_blocks), dim3(256), 0, s, aa, mir, ga, nb);
     return (int)hipGetLastError();
   }
   ProfScope ps(PC_ADAM, s, 0.0, 28.0 * (double)p.P);  // 16 B read + 12 B written per parameter
   IGI_LAUNCH(k_clip_adam, dim3(nb), dim3(256), 0, s, st->params, st->grads, st->adam_m,
                      st->adam_v, p.P, part, grad_scale, c->grad_norm, w1, (float)b2, w2, step_size,
-                     bc2_sqrt, (float)c->adam_eps, row, 1.0f, 0.0f, ns);
+                     bc2_sqrt, (float)c->adam_eps, row, 1.0f, 0.0f);
   return (int)hipGetLastError();
-}
-
-// igi_teacher_set_norm_fusion / IGI_NORM_FUSE (initial value).  Default OFF: measured slower (profiles/r06_norm_fuse_ab.log,
-// A/B on one box, two rounds: 25.74 / 25.74 ms per update off, 26.05 / 25.90 on) -- the 4.2 us kernel it removes comes back
-// as +1.4 us in k_slab_reduce (a block reduction in each of its ~6,700 blocks), +1.0 us in the Adam blocks (every block
-// re-adds the partials) and ~1 % lower clocks in the matrix kernels around it (the chip is power-limited: a short
-// bandwidth-bound kernel between two MFMA-dense ones is not dead time for the clocks).
-static inline int& norm_fusion_ref() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("IGI_NORM_FUSE"); on = e ? (atoi(e) != 0) : 0; }
-  return on;
 }
 
 static int teacher_update(const igi_teacher_cfg* c, const igi_rollout* ro,
@@ -3056,23 +2900,15 @@ static int teacher_update(const igi_teacher_cfg* c, const igi_rollout* ro,
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
-  static int fuse_tail = -1;
-  if (fuse_tail < 0) { const char* e = getenv("IGI_FUSE_TAIL"); fuse_tail = e ? atoi(e) : 1; }
-  // igi_teacher_set_norm_fusion(0) / IGI_NORM_FUSE=0: k_sumsq_stats on every step (A/B; default off, see norm_fusion_ref).  With it on, from the second step of the update on, the two norms
-  // and the statistics row come from k_slab_reduce's and the previous Adam pass's partials (one launch less per step);
-  // the FIRST step keeps k_sumsq_stats -- the parameters may have been replaced since the last update's partials were left
-  const bool nf = norm_fusion_ref() && st->stats;
   const int total = p.E * p.nmb;
   int slot = 0;
   for (int e = 0; e < p.E; ++e) {
     for (int i = 0; i < p.nmb; ++i, ++slot) {
       // from the second step on the minibatch was gathered by the previous step's fused tail
-      int nparts = 0;
-      const bool fused = nf && slot > 0;
-      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, -1, fuse_tail && slot > 0, fused ? &nparts : nullptr))) return rc;
-      const bool more = fuse_tail && slot + 1 < total;
+      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, -1, slot > 0))) return rc;
+      const bool more = slot + 1 < total;
       if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, 1.0f, s, more ? ro : nullptr, (slot + 1) % p.nmb,
-                              slot + 1, nf ? (fused ? 2 : 1) : 0, nparts)))
+                              slot + 1)))
         return rc;
     }
   }

@@ -101,7 +101,7 @@ def test_average_scalar_meter():
 # scratch each may use (0 unless a row says otherwise, with the reason).  First matching row wins.
 _RESOURCE_TABLE = [
     # (regex on the demangled name, max VGPR + AGPR, max scratch bytes / lane, why)
-    (r"gemm_dma_kernel<256,", 256, 0, "the 256-wide 3-stage variants: one workgroup per CU by design"),
+    (r"gemm_dma_kernel<256,", -1, 0, "the 256-wide 3-stage tile is retired: gemm() launches 128- and 64-wide tiles"),
     (r"gemm_dma", 128, 0, "two workgroups of 8 waves per CU"),
     (r"k_trunk_loss", 128, 0, "the GEMM body + the loss epilogue: two workgroups per CU"),
     (r"k_rb_level<", 256, 0, "persistent row-block levels: one 512-thread workgroup per CU"),
@@ -115,7 +115,7 @@ _RESOURCE_TABLE = [
     (r"k_pointnet_fwd", 256, 0, "two 256-thread workgroups per CU"),
     (r"k_pointnet_bwd", 128, 0, "1024-thread workgroups"),
     (r"k_softargmax_|k_ssa_", 64, 0, "bandwidth kernels: eight waves per SIMD"),
-    (r"k_slab_reduce_norm", 72, 0, "the norm-fusion variant (off by default): seven waves per SIMD"),
+    (r"k_slab_reduce_norm", -1, 0, "the norm-fusion variant is retired"),
     (r"k_slab_reduce|k_sumsq_stats|k_clip_adam|k_adam_gather|k_gather_normalize|k_gather_rows|k_cat_cols", 64, 0,
      "bandwidth kernels: eight waves per SIMD"),
     (r"k_latent_bwd<\d, true>", 128, 0, "the row-dot path of the teacher step"),

@@ -35,7 +35,7 @@ SHAPES = {
                        gf(MB, 256, 64) + gf(MB, 128, 256) + gf(MB, 8, 128) + gf(MB, 512, 23, 2)),
     ("gemm_dma_kernel<128,true,true", 1024): ("trunk layer 1 forward, 23(32)->512 x2", gf(MB, 512, 23, 2)),
     ("gemm_dma_kernel<128,true,true", 512): ("trunk layer 2 forward, 512->256 x2", gf(MB, 256, 512, 2)),
-    ("gemm_dma_kernel<128,true,true", 256): ("trunk layer 3 forward, 256->128 x2 (IGI_LOSS_FUSED=0)", gf(MB, 128, 256, 2)),
+    ("gemm_dma_kernel<128,true,true", 256): ("trunk layer 3 forward, 256->128 x2 (shapes without k_trunk_loss)", gf(MB, 128, 256, 2)),
     # round 4: the last trunk layer's forward with the heads, the PPO loss and the head backward in its 64-row tiles
     ("k_trunk_loss", 512): ("trunk layer 3 forward 256->128 x2 + heads + PPO loss + head backward",
                             gf(MB, 128, 256, 2) + 3 * gf(MB, 7, 128)),

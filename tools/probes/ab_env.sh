@@ -1,5 +1,5 @@
 #!/bin/bash
-# same-box A/B of environment switches: ab_env.sh "IGI_LOSS_FUSED=0" "IGI_LOSS_FUSED=1" ...  (each argument: one setting,
+# same-box A/B of environment switches: ab_env.sh "IGI_LATZ_FUSE=0" "IGI_LATZ_FUSE=1" ...  (each argument: one setting,
 # several VAR=value separated by commas); prints the update time and the per-kernel table of bench.py for each
 cd "$(dirname "$0")/../.."
 for setting in "$@"; do

@@ -21,4 +21,4 @@ for i in range(int(os.environ.get("N_ALLOC", "12"))):
     torch.cuda.synchronize()
     cl = _lib.prof_read(); _lib.prof_enable(False)
     out.append([round(1e3 * c["total_ms"] / max(c["launches"], 1), 1) for c in cl if c["name"].startswith("k_rb_level#env2")][0])
-print(os.environ.get("IGI_RB_VARIANT", "0"), out)
+print(out)
