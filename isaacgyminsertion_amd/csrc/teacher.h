@@ -43,7 +43,13 @@ constexpr int LOSS_THREADS = 256;
 constexpr int LOSS_BLOCKS_DEFAULT = 512;  // measured: 256 -> 55 us, 512 -> 35 us, 1024 -> 37 us per launch
 constexpr int RED_THREADS = 256;
 constexpr int SUMSQ_BLOCKS = 512;
-constexpr int MAX_SEG = 32;
+// Segments of the flat-gradient assembly (teacher_fwd_bwd), worst case of what make_plan accepts, for L layers per MLP:
+// 4 heads (mu W, b; value W, b) + 1 sigma + 2 per env_mlp layer (W, b; the fused latent level's two records stand in for the
+// last layer's) + 4 contact encoder (W1, b1, W2, b2) + 4 per trunk layer (W, b of actor and critic) = 9 + 6 L; L = 4: 33.
+constexpr int teacher_max_segments(int max_layers) { return 4 + 1 + 2 * max_layers + 4 + 4 * max_layers; }
+constexpr int MAX_SEG = 33;
+static_assert(MAX_SEG >= teacher_max_segments(IGI_MAX_LAYERS),
+              "SegTable cannot hold the gradient segments of the largest network make_plan accepts: raise MAX_SEG");
 constexpr int ADAM_BLOCKS_MAX = 1024;
 
 // ---------------------------------------------------------------------------------------------
@@ -2789,8 +2795,10 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   // ---- assemble the flat gradient
   SegTable t;
   t.n = 0;
+  bool seg_overflow = false;   // a table that is full refuses the step: nothing is ever written past s[MAX_SEG - 1]
   auto add = [&](long long dst, const float* src, long long stride, int rows, int cols, int src_ld,
                  int nparts) {
+    if (t.n >= MAX_SEG) { seg_overflow = true; return; }
     Segment& sg = t.s[t.n++];
     sg.dst = dst; sg.src = src; sg.stride = stride; sg.count = rows * cols; sg.cols = cols;
     sg.src_ld = src_ld; sg.nparts = nparts;
@@ -2817,7 +2825,6 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
     add(p.o_envB[p.npl - 1], part + 8 * H2, pc, 1, 8, 0, nrec);
   }
   if (p.ct_P > 0 && do1) {   // encoder partial records [dW1 | db1 | dW2 | db2]; the decoder's slots are never written
-    if (t.n + 4 > MAX_SEG) return IGI_E_UNSUPPORTED;
     const float* part = wsp<float>(st, p.w_ct_part);
     const long long w1 = (long long)CT_HID * p.ct_P;
     add(p.o_ctW1, part, p.ct_rec, 1, (int)w1, 0, p.ct_blocks);
@@ -2836,6 +2843,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
           p.sk_ac[l]);
     }
   }
+  if (seg_overflow) return IGI_E_UNSUPPORTED;
   {
     ProfScope ps(PC_SLAB_REDUCE, s, 0.0, 4.0 * ((double)p.slab_floats + (double)hc * p.loss_blocks + p.P));
     // blocks per segment: 64 / 128 / 256 / 512 / 1024 / 2048 -> 29.5 / 19.2 / 15.4 / 14.3 / 15.0 / 17.9 us

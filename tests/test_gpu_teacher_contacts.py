@@ -16,12 +16,9 @@ def _enc64(C, W1, b1, W2, b2):
     return torch.tanh(h @ W2.T + b2), h
 
 
-@pytest.mark.parametrize("P", [1, 37, 400, 1000])
-@pytest.mark.parametrize("rows", [1, 77, 300, 4113])
-def test_contact_encoder_matches_float64(P, rows):
+def _encoder_vs_float64(P, rows, E):
     import isaacgyminsertion_amd.ops  # noqa: F401  (registers torch.ops.mi355ppo)
-    E = 8
-    g = torch.Generator().manual_seed(P * 7919 + rows)
+    g = torch.Generator().manual_seed(P * 7919 + rows + (0 if E == 8 else 104729 * E))
     C = (torch.rand(rows, P, generator=g) < 0.2).float()
     W1 = torch.randn(HID, P, generator=g) / np.sqrt(P)
     b1 = 0.1 * torch.randn(HID, generator=g)
@@ -46,6 +43,23 @@ def test_contact_encoder_matches_float64(P, rows):
     # deterministic
     again = torch.ops.mi355ppo.contact_encoder_bwd(C.cuda(), packed, hid, dz.cuda())
     assert torch.equal(again, grads)
+
+
+# P: 4 / 36 take the float4 loader (P % 4 == 0) with a last chunk shorter than a lane half's 16 columns, 33 the scalar one
+# with a one-column tail
+@pytest.mark.parametrize("P", [1, 4, 33, 36, 37, 400, 1000])
+@pytest.mark.parametrize("rows", [1, 77, 300, 4113])
+def test_contact_encoder_matches_float64(P, rows):
+    _encoder_vs_float64(P, rows, 8)
+
+
+# the embedding axis (E = 8 is the test above): one column, one past a float4 / a quarter tile, the last and the full 32-row
+# MFMA tile -- the e < E guards of both kernels.  Same bounds.
+@pytest.mark.parametrize("E", [1, 9, 31, 32])
+@pytest.mark.parametrize("P", [4, 37, 400])
+@pytest.mark.parametrize("rows", [1, 77, 300])
+def test_contact_encoder_embedding_widths_match_float64(rows, P, E):
+    _encoder_vs_float64(P, rows, E)
 
 
 # ---- the whole teacher step -------------------------------------------------------------------------------------
