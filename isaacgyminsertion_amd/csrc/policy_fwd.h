@@ -1,7 +1,8 @@
 // The rollout-side policy step as ONE persistent kernel per 32 environments (frozen_ppo.py:343-366 `model_act` +
 // :655-665 of `play_steps`; models_split.py:120-164 `act` = env_mlp -> [obs | latent] -> actor / critic trunks -> heads
 // -> Normal sample), for the reference's network shape (priv 64 -> 256 -> 128 -> 8, [obs 15 | latent 8] -> 512 -> 256 -> 128,
-// <= 7 actions).  Other shapes keep the layer-by-layer launches (teacher.h, teacher_policy_step).
+// <= 7 actions), with or without ground-truth contacts (below).  Other shapes keep the layer-by-layer launches (teacher.h,
+// teacher_policy_step).
 //
 // Why: at 4096 environments the layer-by-layer step is seven dependent launches of 64 - 256 workgroups, 80 us for 3.4
 // GFLOP (25 us of matrix pipe) -- every launch pays its fill, first DMA round trip, epilogue and drain with nothing to
@@ -23,7 +24,25 @@
 //    layer and the heads are VALU dot products in another summation order (fp32 rounding apart);
 //  * the heads, the Normal sample from the caller's noise, neglogp, the value de-normalisation and the seven arena writes
 //    (k_heads_act_store's arithmetic) close the kernel: 2 launches per policy step (k_policy_stage + this).
+//
+// Contact mode (template parameter CT; the teacher with ground-truth contacts, models_split.py:166-183): xcat =
+// [obs | latent 8 | embedding E] (PF_CONTACTS) or [obs | embedding 8] (PF_ONLY_CONTACT, no env_mlp), at most 32 columns.
+// The encoder of contact.h runs for the block's 32 rows before env_mlp, both products on exact-fp32 MFMA:
+//  * H = relu(C . W1^T + b1), C = [32][P], P a run-time value: the P / 32 k-chunks are dealt to the eight waves (wave w takes
+//    chunks w, w + 8, ...; 13 chunks at P = 400), straight from global memory into the MFMA operands (float4 loads when every
+//    row is 16-byte aligned, VEC; scalar loads with a column guard otherwise); the eight partial 32 x 32 tiles meet in LDS
+//    and are added in WAVE ORDER (((p0 + p1) + p2) + ... + p7) by all 512 threads -- a fixed order, no atomics, so the step is
+//    bit-reproducible; k_contact_fwd adds the same chunks one after the other, so the two agree at fp32 rounding only;
+//  * emb = tanh(H . W2^T + b2) on one wave with H as the B operand in its accumulator layout: wave 7, while waves 0 - 3
+//    compute the 128-wide env layer (waves 4 - 7 own no tile of it); wave 0 with only_contact;
+//  * LDS: nothing is added.  The partials (32 KB) and the embedding (4 KB) sit in images 4 - 11 and 15 of region Q, which
+//    hold nothing between the input images (0, 1) / env layer 2's output (0 - 3) and the first trunk layer's output;
+//  * the actor workgroups store the contact values they loaded to the step's slot of the (T, N, P) arena (the raw contacts,
+//    bit for bit: frozen_ppo.py:663-664) -- no copy is launched;
+//  * the xcat image is written whole: columns >= xw as zeros.
+// The instantiation without contacts is the kernel as it was (same registers, same bits).
 #pragma once
+#include "contact.h"
 #include "dma_util.h"
 #include "gemm_f32.h"
 
@@ -41,7 +60,14 @@ struct PolicyFwdArgs {
   // sampling + arena (the arguments of k_heads_act_store)
   const float* noise; const double* rms_value; float eps;
   float *actions_t, *nlp_t, *values_t, *mus_t, *sigmas_t, *actions_clamped, *values_out;
+  // contact mode (PF_CONTACTS / PF_ONLY_CONTACT): the step's raw contacts [rows][ctP], their arena slot (may be NULL), the
+  // encoder of contact.h (W1 [32][ctP], b1 [32], W2 [ctE][32], b2 [ctE]) and the live width of xcat
+  const float* ct = nullptr; float* ct_t = nullptr; int ctP = 0, ctE = 0, xw = 0;
+  const float *cW1 = nullptr, *cb1 = nullptr, *cW2 = nullptr, *cb2 = nullptr;
 };
+
+// what sits behind the observation in xcat: [latent 8] | [latent 8 | embedding ctE] | [embedding 8]
+constexpr int PF_NO_CONTACTS = 0, PF_CONTACTS = 1, PF_ONLY_CONTACT = 2;
 
 constexpr int PF_ROWS = 32;
 constexpr int PF_THREADS = 512;
@@ -53,12 +79,17 @@ constexpr int PF_NS = 3;                        // ring depth per wave
 constexpr int PF_RING = 8 * PF_NS * PF_CH;
 constexpr int PF_SMALL = 8 * 128 /* W3 */ + 8 * 128 /* head rows: mu 0.., value 7 */ + 2 * 32 * 8 /* partial dots */ + 32 * 8 /* latent | mu */;
 constexpr int PF_LDS_FLOATS = PF_P + PF_Q + PF_RING + PF_SMALL;
+// contact phase: images of Q that neither the privileged input (0, 1) nor env layer 2's output (0 .. 3) touches
+constexpr int PF_CT_PART = 4 * PF_IMG;          // Q + this: [8 waves][16 registers][64 lanes] partial tiles (8 images); H in slot 0
+constexpr int PF_CT_EMB = 15 * PF_IMG;          // Q + this: [32 rows][32] embedding, until xcat is built
+static_assert(PF_CT_PART >= 4 * PF_IMG && PF_CT_PART + 8 * PF_IMG <= PF_CT_EMB && PF_CT_EMB + PF_IMG <= PF_Q, "contact phase in Q");
 static_assert(PF_LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 constexpr float PF_LOG_SQRT_2PI = 0.918938533204672741780329736406f;
 
-static inline bool policy_fwd_shape_ok(int obs, int priv, int act, int npl, const int* pu, int nl, const int* u) {
+// xw: the live width of xcat = obs + 8 (+ embedding), or obs + embedding with only_contact
+static inline bool policy_fwd_shape_ok(int obs, int priv, int act, int npl, const int* pu, int nl, const int* u, int xw) {
   return priv == 64 && npl == 3 && pu[0] == 256 && pu[1] == 128 && pu[2] == 8 && nl == 3 && u[0] == 512 && u[1] == 256 &&
-         u[2] == 128 && obs >= 1 && obs + 8 <= 32 && act >= 1 && act <= 7;
+         u[2] == 128 && obs >= 1 && xw > obs && xw <= 32 && act >= 1 && act <= 7;
 }
 
 // IGI_POLICY_FUSED=0: the layer-by-layer policy step (A/B)
@@ -213,6 +244,87 @@ __device__ __forceinline__ void pf_dot8(const float* __restrict__ img, const flo
   part[(half * 32 + row) * 8 + out] = s;
 }
 
+// ---- contact phase (contact.h's encoder for the block's 32 rows) ----------------------------------------------------
+// First product, transposed as in k_contact_fwd (Z1^T = W1 . C^T: the row on the lane, the 32 hidden units in the
+// registers), with the k-chunks of 32 contact points dealt to the eight waves: wave w multiplies chunks w, w + 8, ... and
+// leaves its partial tile at part[w][register][lane] (waves without a chunk leave zeros).  Rows >= rows and columns >= P
+// contribute zeros.  store: this workgroup also writes what it loaded to the arena slot, bit for bit.
+template <bool VEC>
+__device__ __forceinline__ void pf_contact_partial(const PolicyFwdArgs& a, const PfWave& w, int m0, bool store, float* __restrict__ part) {
+  const int P = a.ctP, nch = (P + 31) >> 5;
+  const int grow = m0 + w.l31;
+  const bool valid = grow < a.rows;
+  const float* crow = a.ct + (long long)(valid ? grow : 0) * P;
+  const float* wrow = a.cW1 + (long long)w.l31 * P;          // hidden unit l31
+  float* trow = a.ct_t + (long long)(valid ? grow : 0) * P;
+  store = store && valid && a.ct_t != nullptr;
+  f32x16 acc;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+  for (int c = w.wave; c < nch; c += 8) {
+    const int k0 = 32 * c + 16 * w.h;                         // lane half h: columns k0 .. k0 + 15 of its row of C and of W1
+    float cv[16], wv[16];
+    if (VEC && k0 + 16 <= P) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 c4 = valid ? *reinterpret_cast<const float4*>(crow + k0 + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 w4 = *reinterpret_cast<const float4*>(wrow + k0 + 4 * q);
+        if (store) *reinterpret_cast<float4*>(trow + k0 + 4 * q) = c4;
+        cv[4 * q] = c4.x; cv[4 * q + 1] = c4.y; cv[4 * q + 2] = c4.z; cv[4 * q + 3] = c4.w;
+        wv[4 * q] = w4.x; wv[4 * q + 1] = w4.y; wv[4 * q + 2] = w4.z; wv[4 * q + 3] = w4.w;
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int k = k0 + u;
+        cv[u] = (valid && k < P) ? crow[k] : 0.f;
+        wv[u] = (k < P) ? wrow[k] : 0.f;
+        if (store && k < P) trow[k] = cv[u];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[u], cv[u], acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int g = 0; g < 16; ++g) part[(w.wave * 16 + g) * 64 + w.lane] = acc[g];
+}
+
+// the eight partial tiles summed in wave order, + b1 (b1v: this thread's two elements), ReLU: H in slot 0 of `part`,
+// in the accumulator layout [register][lane]
+__device__ __forceinline__ void pf_contact_hidden(float* __restrict__ part, const float (&b1v)[2], int tid) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int e = tid + PF_THREADS * i;
+    float s = part[e];
+#pragma unroll
+    for (int v = 1; v < 8; ++v) s += part[v * 1024 + e];
+    const float z1 = s + b1v[i];
+    part[e] = z1 > 0.f ? z1 : 0.f;
+  }
+}
+
+// second product on ONE wave, E^T = W2 . H^T with H as the B operand in its accumulator layout (k_contact_fwd), bias,
+// tanh: emb[row][e]
+__device__ __forceinline__ void pf_contact_emb(const PolicyFwdArgs& a, const float* __restrict__ hid, float* __restrict__ emb, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  float wv[16];
+#pragma unroll
+  for (int g = 0; g < 16; ++g) wv[g] = r < a.ctE ? a.cW2[r * CT_HID + ct_acc_row(g, h)] : 0.f;
+  f32x16 acc;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[g], hid[g * 64 + lane], acc, 0, 0, 0);
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int e = ct_acc_row(g, h);
+    if (e < a.ctE) emb[r * 32 + e] = tanhf(acc[g] + a.cb2[e]);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the layers' counted waits see weight requests and nothing else
+}
+
+// CT: PF_NO_CONTACTS | PF_CONTACTS | PF_ONLY_CONTACT;  VEC: contact rows and W1 rows load (and store) as float4
+template <int CT, bool VEC>
 __global__ __launch_bounds__(PF_THREADS) void k_policy_fwd(const PolicyFwdArgs a) {
   extern __shared__ __attribute__((aligned(1024))) float smem[];
   float* P = smem;
@@ -255,36 +367,64 @@ __global__ __launch_bounds__(PF_THREADS) void k_policy_fwd(const PolicyFwdArgs a
     const int r = e >> 7, k = e & 127;
     hwv[i] = r < a.act ? a.Wmu[r * 128 + k] : (r == 7 ? a.Wv[k] : 0.f);
   }
-  {  // the input block: two [32][32] images, four 1 KB pieces each, one per wave
+  if constexpr (CT != PF_ONLY_CONTACT) {  // the input block: two [32][32] images, four 1 KB pieces each, one per wave
     const int k = wave >> 2, i = wave & 3;
     const int m = 8 * i + (lane >> 3);
     const int row = min(m0 + m, a.rows - 1);
     dma16(a.priv + (long long)row * a.ldp + k * 32 + 4 * ((lane & 7) ^ ((m >> 1) & 7)), Q + k * PF_IMG + 256 * i);
   }
+  float* cpart = Q + PF_CT_PART;
+  float* cemb = Q + PF_CT_EMB;
+  float cb1v[2] = {0.f, 0.f};
+  if constexpr (CT != PF_NO_CONTACTS) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int e = tid + PF_THREADS * i;                             // element [register e >> 6][lane e & 63] of a tile
+      cb1v[i] = a.cb1[ct_acc_row(e >> 6, (e >> 5) & 1)];
+    }
+    pf_contact_partial<VEC>(a, w, m0, z == 0, cpart);
+  }
 #pragma unroll
   for (int i = 0; i < 2; ++i) { w3s[tid + PF_THREADS * i] = w3v[i]; hws[tid + PF_THREADS * i] = hwv[i]; }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-
-  // ---- env_mlp: 64 -> 256 (Q -> P), 256 -> 128 (P -> Q), 128 -> 8 (Q -> lat)
-  pf_layer<64, 256, 1>(w, Q, a.eW1, 64, be1, P);
-  __syncthreads();
-  pf_layer<256, 128, 1>(w, P, a.eW2, 256, be2, Q);
-  __syncthreads();
-  pf_dot8(Q, w3s, part, tid);
-  __syncthreads();
-  if (tid < 256) {
-    const int row = tid & 31, out = tid >> 5;
-    lat[row * 8 + out] = fast_tanh((part[row * 8 + out] + part[(32 + row) * 8 + out]) + a.eb3[out]);
+  if constexpr (CT != PF_NO_CONTACTS) pf_contact_hidden(cpart, cb1v, tid);
+  if constexpr (CT == PF_ONLY_CONTACT) {
+    // the privileged embedding is not used (models_split.py:176-178): no env_mlp, the embedding on wave 0
+    __syncthreads();
+    if (wave == 0) pf_contact_emb(a, cpart, cemb, lane);
+  } else {
+    // ---- env_mlp: 64 -> 256 (Q -> P), 256 -> 128 (P -> Q), 128 -> 8 (Q -> lat)
+    pf_layer<64, 256, 1>(w, Q, a.eW1, 64, be1, P);
+    __syncthreads();
+    // (waves 4 .. 7 own no tile of the 128-wide layer: the last of them forms the contact embedding meanwhile)
+    if constexpr (CT == PF_CONTACTS) { if (wave == 7) pf_contact_emb(a, cpart, cemb, lane); }
+    pf_layer<256, 128, 1>(w, P, a.eW2, 256, be2, Q);
+    __syncthreads();
+    pf_dot8(Q, w3s, part, tid);
+    __syncthreads();
+    if (tid < 256) {
+      const int row = tid & 31, out = tid >> 5;
+      lat[row * 8 + out] = fast_tanh((part[row * 8 + out] + part[(32 + row) * 8 + out]) + a.eb3[out]);
+    }
   }
   __syncthreads();
-  // ---- xcat = [obs_n | latent | 0] as ONE image in P
+  // ---- xcat = [obs_n | latent | 0], [obs_n | latent | emb | 0] or [obs_n | emb | 0] as ONE image in P
   {
     const int sw = (xrow >> 1) & 7;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int c = xc + q;
-      const float v = (c >= a.obs && c < a.obs + 8) ? lat[xrow * 8 + (c - a.obs)] : (q ? xv.y : xv.x);
+      float v;
+      if constexpr (CT == PF_NO_CONTACTS) {
+        v = (c >= a.obs && c < a.obs + 8) ? lat[xrow * 8 + (c - a.obs)] : (q ? xv.y : xv.x);
+      } else {
+        // columns >= xw are written as zeros whatever the staged row holds behind them
+        const int ec = a.obs + (CT == PF_CONTACTS ? 8 : 0);            // first embedding column
+        if (c < a.obs) v = q ? xv.y : xv.x;
+        else if (CT == PF_CONTACTS && c < ec) v = lat[xrow * 8 + (c - a.obs)];
+        else v = c < a.xw ? cemb[xrow * 32 + (c - ec)] : 0.f;
+      }
       P[xrow * 32 + (((c >> 2) ^ sw) << 2) + (c & 3)] = v;
     }
   }
@@ -332,21 +472,38 @@ __global__ __launch_bounds__(PF_THREADS) void k_policy_fwd(const PolicyFwdArgs a
   }
 }
 
-static hipError_t policy_forward(const PolicyFwdArgs& a, hipStream_t s) {
-  if (a.rows < 1 || !aligned16(a.priv) || !aligned16(a.xcat) || (a.ldp & 3) || a.ldp < 64 || a.ldx != 32 || !aligned16(a.eW1) ||
-      !aligned16(a.eW2) || !aligned16(a.w1p) || !aligned16(a.tW2) || !aligned16(a.tW3) || (a.ac_block & 3))
-    return hipErrorInvalidValue;
+template <int CT, bool VEC>
+static hipError_t policy_launch(const PolicyFwdArgs& a, int blocks, hipStream_t s) {
+  void (*kern)(const PolicyFwdArgs) = k_policy_fwd<CT, VEC>;
   static bool attr = false;
   if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_policy_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * PF_LDS_FLOATS));
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * PF_LDS_FLOATS));
     if (e != hipSuccess) return e;
     attr = true;
   }
-  const int blocks = (a.rows + PF_ROWS - 1) / PF_ROWS;
-  const double macs = 64.0 * 256 + 256.0 * 128 + 128.0 * 8 + 2.0 * ((a.obs + 8) * 512.0 + 512.0 * 256 + 256.0 * 128) + 128.0 * (a.act + 1);
-  ProfScope ps(PC_POLICY_FWD, s, 2.0 * macs * a.rows, 4.0 * a.rows * (64.0 + 32 + 4 * a.act + 3) + 4.0 * 404501);
-  IGI_LAUNCH(k_policy_fwd, dim3(2 * blocks), dim3(PF_THREADS), sizeof(float) * PF_LDS_FLOATS, s, a);
+  IGI_LAUNCH(kern, dim3(2 * blocks), dim3(PF_THREADS), sizeof(float) * PF_LDS_FLOATS, s, a);
   return hipGetLastError();
+}
+
+// mode: PF_NO_CONTACTS | PF_CONTACTS | PF_ONLY_CONTACT
+static hipError_t policy_forward(const PolicyFwdArgs& a, hipStream_t s, int mode = PF_NO_CONTACTS) {
+  if (a.rows < 1 || !aligned16(a.priv) || !aligned16(a.xcat) || (a.ldp & 3) || a.ldp < 64 || a.ldx != 32 || !aligned16(a.eW1) ||
+      !aligned16(a.eW2) || !aligned16(a.w1p) || !aligned16(a.tW2) || !aligned16(a.tW3) || (a.ac_block & 3))
+    return hipErrorInvalidValue;
+  const int blocks = (a.rows + PF_ROWS - 1) / PF_ROWS;
+  const int lat = mode == PF_ONLY_CONTACT ? 0 : 8, emb = mode == PF_NO_CONTACTS ? 0 : a.ctE;
+  if (mode != PF_NO_CONTACTS && (!a.ct || a.ctP < 1 || emb < 1 || a.xw != a.obs + lat + emb || a.xw > 32 || !a.cW1 || !a.cb1 || !a.cW2 || !a.cb2))
+    return hipErrorInvalidValue;
+  const double env_macs = mode == PF_ONLY_CONTACT ? 0.0 : 64.0 * 256 + 256.0 * 128 + 128.0 * 8;
+  const double ct_macs = mode == PF_NO_CONTACTS ? 0.0 : 2.0 * CT_HID * ((double)a.ctP + emb);   // both nets' workgroups encode
+  const double macs = env_macs + ct_macs + 2.0 * ((a.obs + lat + emb) * 512.0 + 512.0 * 256 + 256.0 * 128) + 128.0 * (a.act + 1);
+  const double ct_bytes = mode == PF_NO_CONTACTS ? 0.0 : 4.0 * a.rows * a.ctP * (a.ct_t ? 2.0 : 1.0) + 4.0 * CT_HID * ((double)a.ctP + emb);
+  ProfScope ps(PC_POLICY_FWD, s, 2.0 * macs * a.rows, 4.0 * a.rows * (64.0 + 32 + 4 * a.act + 3) + 4.0 * 404501 + ct_bytes);
+  if (mode == PF_NO_CONTACTS) return policy_launch<PF_NO_CONTACTS, false>(a, blocks, s);
+  // float4 loads and stores of the contact rows: every row 16-byte aligned, in the input, the arena slot and W1
+  const bool vec = (a.ctP & 3) == 0 && aligned16(a.ct) && aligned16(a.cW1) && (!a.ct_t || aligned16(a.ct_t));
+  if (mode == PF_CONTACTS) return vec ? policy_launch<PF_CONTACTS, true>(a, blocks, s) : policy_launch<PF_CONTACTS, false>(a, blocks, s);
+  return vec ? policy_launch<PF_ONLY_CONTACT, true>(a, blocks, s) : policy_launch<PF_ONLY_CONTACT, false>(a, blocks, s);
 }
 
 }  // namespace igi

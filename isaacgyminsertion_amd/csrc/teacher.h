@@ -3008,8 +3008,10 @@ static int teacher_infer(const igi_teacher_cfg* c, const igi_teacher_state* st, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Rollout-side policy step (frozen_ppo.py:343-366 + 655-665): ONE host call and 7-8 launches per environment step
-// instead of igi_teacher_infer (10 launches) + a torch randn + igi_rollout_act_store:
+// Rollout-side policy step (frozen_ppo.py:343-366 + 655-665): ONE host call per environment step instead of
+// igi_teacher_infer (10 launches) + a torch randn + igi_rollout_act_store.  With the reference's layer sizes and xcat
+// no wider than 32 columns -- with or without contacts -- it is k_policy_stage + the persistent kernel of policy_fwd.h;
+// every other shape takes 7-10 launches:
 //   k_policy_stage   : raw obs / priv -> arena slot t (raw copies), normalised xcat / priv_g with the CURRENT running
 //                      statistics (eval mode), zero padding, refresh of the padded first-layer weight
 //   trunk_forward    : env_mlp + actor / critic trunk (the launches of the training forward)
@@ -3174,9 +3176,15 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
       ProfScope ps(PC_OTHER, s, 0.0, 8.0 * tot);
       IGI_LAUNCH(k_policy_stage, dim3(nb + pad_blocks), dim3(256), 0, s, a);
     }
-    if (p.ct_P == 0 && policy_fwd_enabled() && !bf16_mode() && policy_fwd_shape_ok(p.obs, p.priv, p.act, p.npl, p.pu, p.nl, p.u) && p.xld == 32) {
-      // env_mlp, both trunks, the heads, the sample and the arena writes of these rows as ONE persistent launch (policy_fwd.h)
+    if (policy_fwd_enabled() && !bf16_mode() && policy_fwd_shape_ok(p.obs, p.priv, p.act, p.npl, p.pu, p.nl, p.u, p.xw) && p.xld == 32) {
+      // env_mlp, the contact encoder, both trunks, the heads, the sample and the arena writes (the step's raw contacts
+      // among them) of these rows as ONE persistent launch (policy_fwd.h)
       PolicyFwdArgs f;
+      if (p.ct_P > 0) {
+        f.ct = contacts + r0 * p.ct_P; f.ct_t = contacts_t ? contacts_t + r0 * p.ct_P : nullptr; f.ctP = p.ct_P; f.ctE = p.ct_E;
+        f.cW1 = P + p.o_ctW1; f.cb1 = P + p.o_ctB1; f.cW2 = P + p.o_ctW2; f.cb2 = P + p.o_ctB2;
+      }
+      f.xw = p.xw;
       f.priv = a.priv_g; f.ldp = a.pld; f.xcat = a.xcat; f.ldx = p.xld; f.rows = nr; f.obs = p.obs; f.act = p.act;
       f.eW1 = P + p.o_envW[0]; f.eb1 = P + p.o_envB[0]; f.eW2 = P + p.o_envW[1]; f.eb2 = P + p.o_envB[1];
       f.eW3 = P + p.o_envW[2]; f.eb3 = P + p.o_envB[2];
@@ -3187,7 +3195,7 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
       f.actions_t = actions_t + r0 * p.act; f.nlp_t = nlp_t + r0; f.values_t = values_t + r0;
       f.mus_t = mus_t + r0 * p.act; f.sigmas_t = sigmas_t + r0 * p.act;
       f.actions_clamped = actions_clamped + r0 * p.act; f.values_out = values_out + r0;
-      const hipError_t e = policy_forward(f, s);
+      const hipError_t e = policy_forward(f, s, p.ct_P == 0 ? PF_NO_CONTACTS : p.ct_only ? PF_ONLY_CONTACT : PF_CONTACTS);
       if (e == hipSuccess) continue;
       if (e != hipErrorInvalidValue) return (int)e;      // (alignment of the caller's buffers: the per-layer launches below)
     }

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Rollout-side throughput: PPO.play_steps with the synthetic environment (policy inference +
 sampling + buffer writes + GAE / prepare at the end) and the bare inference call, 4096 envs x 32 steps.
-    python tools/bench_rollout.py [--envs 4096] [--horizon 32]"""
+    python tools/bench_rollout.py [--envs 4096] [--horizon 32] [--contact-points P [--only-contact]]
+--contact-points P > 0: the contact teacher (task.env.compute_contact_gt, num_points P, contact_mlp.units [8])."""
 import argparse, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,9 +14,20 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--horizon", type=int, default=32)
 ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--contact-points", type=int, default=0)
+ap.add_argument("--only-contact", action="store_true")
 a = ap.parse_args()
-cfg = default_config(num_envs=a.envs, horizon_length=a.horizon, rl_device="cuda:0")
-env = SyntheticInsertionEnv(a.envs, device="cuda:0")
+if a.only_contact and not a.contact_points:
+    ap.error("--only-contact needs --contact-points")
+if a.contact_points:
+    cfg = default_config(num_envs=a.envs, horizon_length=a.horizon, rl_device="cuda:0", compute_contact_gt=True,
+                         num_points=a.contact_points, only_contact=a.only_contact)
+    cfg.task.env.compute_contact_gt = True
+    cfg.train.network.contact_mlp.units = [8]
+    env = SyntheticInsertionEnv(a.envs, device="cuda:0", contact_points=a.contact_points)
+else:
+    cfg = default_config(num_envs=a.envs, horizon_length=a.horizon, rl_device="cuda:0")
+    env = SyntheticInsertionEnv(a.envs, device="cuda:0")
 agent = PPO(env, None, cfg)
 agent.obs = env.reset()
 agent.set_eval()
@@ -36,6 +48,9 @@ for _ in range(200):
     agent.model_act(obs)
 torch.cuda.synchronize()
 di = (time.perf_counter() - t0) / 200
-print(json.dumps({"workload": f"PPO.play_steps, {a.envs} envs x {a.horizon} steps, synthetic environment",
-                  "ms_per_rollout": round(dt * 1e3, 3), "env_steps_per_s": round(a.envs * a.horizon / dt),
-                  "model_act_us": round(di * 1e6, 1), "policy_inferences_per_s": round(a.envs / di)}))
+rec = {"workload": f"PPO.play_steps, {a.envs} envs x {a.horizon} steps, synthetic environment",
+       "ms_per_rollout": round(dt * 1e3, 3), "env_steps_per_s": round(a.envs * a.horizon / dt),
+       "model_act_us": round(di * 1e6, 1), "policy_inferences_per_s": round(a.envs / di)}
+if a.contact_points:
+    rec.update(contact_points=a.contact_points, contact_emb=8, only_contact=a.only_contact)
+print(json.dumps(rec))
