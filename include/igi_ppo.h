@@ -87,6 +87,18 @@ int igi_mfma_peak_probe(int shape, int blocks, int iters, uint64_t* clocks_dev, 
  * off by default (also settable with IGI_GEMM_BF16=1), parity tests and the headline benchmark run with it off.
  * Returns the previous setting. */
 int igi_gemm_set_bf16_inputs(int on);
+/* The same opt-in mode for the three convolutions of the tactile encoder (igi_tactile_forward / igi_tactile_backward:
+ * forward, data gradient and weight gradient of every layer, on every tile the encoder launches).  Each product term
+ * is float(bf16(a)) * float(bf16(w)) -- exact in fp32 -- accumulated in fp32: the operands are rounded (nearest even)
+ * where they are fed to v_mfma_f32_32x32x16_bf16; activations, pre-activation gradients, repacked weights and split-K
+ * slabs stay fp32 in memory, and the loaders, the epilogues (bias + ReLU, ReLU', bias-gradient sums, soft-argmax
+ * partials), the soft-argmax kernels, the 128 -> latent Linear and the fixed-order slab reduction are unchanged: two
+ * runs are bit-identical.  Off by default; IGI_CONV_BF16=1 in the environment starts it on.  Independent of
+ * igi_gemm_set_bf16_inputs: that switch never applies to a convolution, this one to nothing else (PointNet, the depth
+ * backbone, the token encoder, every Linear and the teacher stay fp32).  igi_tactile_backward uses the setting in force
+ * when IT is called: a forward / backward pair must run under ONE setting (the Python op's autograd formula records the
+ * forward's setting and re-establishes it around the backward).  on < 0 only queries.  Returns the previous setting. */
+int igi_conv_set_bf16_inputs(int on);
 /* EXPERIMENT, off by default (IGI_GEMM_X3 = 6 | 9 in the environment starts it on): fp32 products on the bf16 matrix pipe by
  * an exact three-plane split of every operand element (x = hi + mid + lo in bf16: each plane product is exact in fp32, the
  * MFMA accumulates in fp32) for the large k-contiguous forward products (K >= 256).  products = 9: all nine cross products,
@@ -519,7 +531,8 @@ int igi_token_backward(const igi_token_cfg* cfg, const float* dy, const float* p
  * (batch, latent_dim).  params / grads are flat fp32 in the module's state_dict order:
  * cnn.0.weight (32,3,8,8) cnn.0.bias cnn.2.weight (64,32,4,4) cnn.2.bias cnn.4.weight (64,64,3,3)
  * cnn.4.bias cnn.7.weight (latent,128) cnn.7.bias.  batch must be a multiple of 32.
- * igi_tactile_backward must follow igi_tactile_forward on the same workspace (saved activations);
+ * igi_tactile_backward must follow igi_tactile_forward on the same workspace (saved activations)
+ * and under the same igi_conv_set_bf16_inputs setting;
  * it overwrites `grads` with d(loss)/d(params) given dy = d(loss)/d(y).
  * ---------------------------------------------------------------------------------------- */
 typedef struct igi_tactile_cfg {

@@ -22,9 +22,12 @@ import random
 from datetime import datetime
 from glob import glob
 
+import contextlib
+
 import numpy as np
 import torch
 
+from .... import ops
 from ....optim import FlatAdam
 from .data import DataNormalizer, ResidentLoader, TactileDataset
 from .tact import MultiModalModel
@@ -76,6 +79,11 @@ class Runner:
         self.scheduler = None
         self.tact = None
         self.sequence_length = self.cfg.model.transformer.sequence_length
+        # offline_train.model.conv_bf16_inputs (not a reference key): the tactile CNN's convolutions with bf16-rounded
+        # operands and fp32 accumulation, applied around every forward of this Runner's model (the backward follows the
+        # forward's setting by itself: ops.tactile_cnn_fwd).  None = key absent: the process switch is left alone.
+        self.conv_bf16_inputs = bool(self.cfg.model.get('conv_bf16_inputs', False)) \
+            if 'conv_bf16_inputs' in self.cfg.model else None
         gpu = self.cfg.gpu_ids[0] if 'gpu_ids' in self.cfg else 0
         self.device = cfg.get('rl_device', f'cuda:{gpu}') if hasattr(cfg, 'get') else f'cuda:{gpu}'
         self._init_transforms()
@@ -129,6 +137,11 @@ class Runner:
         self.model.to(self.device)
         return self.model
 
+    def _conv_mode(self):
+        if self.conv_bf16_inputs is None:
+            return contextlib.nullcontext()
+        return ops.conv_bf16_inputs(self.conv_bf16_inputs)
+
     def predict(self, obs_dict, requires_grad=False, display=False):
         """runner.py:374-381"""
         if not requires_grad:
@@ -158,7 +171,8 @@ class Runner:
             student_obs = student_obs.to(self.device)
         if self.cfg.model.use_pcl:
             pcl = pcl.to(self.device)
-        out = self.model(obs_tactile=tactile, obs_img=img, obs_seg=seg, lin_input=student_obs, obs_pcl=pcl)
+        with self._conv_mode():
+            out = self.model(obs_tactile=tactile, obs_img=img, obs_seg=seg, lin_input=student_obs, obs_pcl=pcl)
         return out, None
 
     # ------------------------------------------------------------------------------------------
@@ -171,7 +185,8 @@ class Runner:
         img = img.to(dev) if self.cfg.model.use_img else None
         seg = seg.to(dev) if self.cfg.model.use_seg else None
         stud_obs, latent, action = stud_obs.to(dev), latent.to(dev), action.to(dev)
-        out = self.model(tactile, img, seg, stud_obs, add_lin_input=None)
+        with self._conv_mode():
+            out = self.model(tactile, img, seg, stud_obs, add_lin_input=None)
         if self.only_bc:
             if clamp:
                 out = torch.clamp(out, -1, 1)                     # validation only (runner.py:326)

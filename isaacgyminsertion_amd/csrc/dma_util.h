@@ -1,5 +1,5 @@
 // Small pieces shared by the LDS-DMA kernels (gemm_dma.h, env_mlp.h, rowblock.h): the LDS-DMA instruction, scalar
-// pointers, the process-wide bf16-input switch.  Kept apart from gemm_dma.h so that a kernel header (and its probe under
+// pointers, the process-wide bf16-input switches.  Kept apart from gemm_dma.h so that a kernel header (and its probe under
 // tools/probes) can be compiled without instantiating every GEMM configuration.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +29,16 @@ static inline int& bf16_mode_ref() {
   return m;
 }
 static inline int bf16_mode() { return bf16_mode_ref(); }
+
+// opt-in bf16-input mode of the tactile encoder's convolutions (forward, data gradient, weight gradient):
+// IGI_CONV_BF16=1 in the environment, or igi_conv_set_bf16_inputs().  Independent of bf16_mode(), which never applies to
+// an im2col product.
+static inline int& conv_bf16_mode_ref() {
+  static int m = -1;
+  if (m < 0) { const char* e = getenv("IGI_CONV_BF16"); m = e ? (atoi(e) != 0) : 0; }
+  return m;
+}
+static inline int conv_bf16_mode() { return conv_bf16_mode_ref(); }
 
 // EXPERIMENT (off by default): fp32 products on the bf16 matrix pipe by an EXACT three-plane split -- every operand element
 // x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (each difference is exact, 3 x 8

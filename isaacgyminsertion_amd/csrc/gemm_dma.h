@@ -497,7 +497,8 @@ __device__ __forceinline__ void epilogue_rows(float* __restrict__ ep, float* __r
 // by-value problem table to scratch (1.2 KB/lane, 37 -> 90 us).
 // HEAD: bias+tanh layer whose single n-tile holds whole rows, followed by a <= 8-wide tanh head computed from
 // the LDS-staged activated tile (the 128 -> 8 latent layer of env_mlp: one launch less per step).
-// BF16IN (opt-in, IGI_GEMM_BF16=1; SURVEY section 7 "offer bf16-input fp32-accumulate as an opt-in mode"): the
+// BF16IN (opt-in, IGI_GEMM_BF16=1 for the Linear products, IGI_CONV_BF16=1 for the tactile convolutions' im2col tiles;
+// SURVEY section 7 "offer bf16-input fp32-accumulate as an opt-in mode"): the
 // fp32 tiles land in LDS exactly as before, each lane converts the eight k it feeds to one
 // v_mfma_f32_32x32x16_bf16 (round to nearest even, v_cvt_pk_bf16_f32) -- 16x the matrix rate, ~3 significant
 // digits per product, fp32 accumulation.  NOT the arithmetic the headline number is measured in.
@@ -533,7 +534,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, int n_tiles, in
   constexpr int NW = DMA_WAVES / KG;
   constexpr int WGM = KG == 2 ? 2 : ((BN == 32) ? 8 : ((BN == 64) ? 4 : 2)), WGN = NW / WGM;
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
-  static_assert(KG == 1 || (BN == 64 && STORE_ONLY_OK<STORE_ONLY, HEAD, (BF16IN != 0), TANHGRAD_ONLY, Hook>::value),
+  static_assert(KG == 1 || (BN == 64 && (BF16IN == 0 || BF16IN == 1) && STORE_ONLY_OK<STORE_ONLY, HEAD, false, TANHGRAD_ONLY, Hook>::value),
                 "the 192-row tile is built for the plain-store weight-gradient products");
   static_assert(BN != 32 || NS == 2, "waves issue unequal DMA counts on a 32-wide tile: no counted vmcnt waits");
   constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -724,8 +725,10 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, int n_tiles, in
       }
     } else if constexpr (BF16IN != 0) {
       if (kt + NS - 1 < nk) issue(kt + NS - 1, std::integral_constant<int, (S + NS - 1) % NS>{});  // into stage (kt-1)%NS: every wave is past its reads of it
+      // (KG == 2: one half per wave group, the partial accumulators meet in the epilogue as on the fp32 path)
 #pragma unroll
-      for (int gk = 0; gk < 2; ++gk) {   // the two 16-k halves of the tile; lanes 0-31 feed k 0-7, lanes 32-63 k 8-15
+      for (int g2 = 0; g2 < 2 / KG; ++g2) {   // the two 16-k halves of the tile; lanes 0-31 feed k 0-7, lanes 32-63 k 8-15
+        const int gk = KG == 2 ? kg : g2;
         bf16x8 av[TM], bv[TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -1071,6 +1074,14 @@ __global__ __launch_bounds__(DMA_THREADS) void gemm_dma_kernel(const GemmArgs g,
   gemm_dma_body<BN, A_KC, B_KC, GATHER, NS, BM>(g, n_tiles, m_tiles, xcd_remap(blockIdx.x, gridDim.x));
 }
 
+// the im2col tiles of the tactile convolutions with bf16-rounded operands (conv_bf16_mode()): same loaders, LDS images and
+// epilogues as gemm_dma_kernel<BN, A_KC, B_KC, GATHER, NS, BM>, the BF16IN inner loop
+template <int BN, bool A_KC, bool B_KC, int GATHER, int NS, int BM>
+__global__ __launch_bounds__(DMA_THREADS) void gemm_dma_conv_bf16_kernel(const GemmArgs g, int n_tiles, int m_tiles) {
+  static_assert(GATHER != 0 && GATHER != 2, "im2col products of the tactile encoder only");
+  gemm_dma_body<BN, A_KC, B_KC, GATHER, NS, BM, false, false, 1>(g, n_tiles, m_tiles, xcd_remap(blockIdx.x, gridDim.x));
+}
+
 template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(DMA_THREADS) void gemm_dma_bf16_kernel(const GemmArgs g, int n_tiles, int m_tiles) {
   gemm_dma_body<128, A_KC, B_KC, 0, 2, DMA_BM, false, false, 1>(g, n_tiles, m_tiles, xcd_remap(blockIdx.x, gridDim.x));
@@ -1309,7 +1320,7 @@ static inline void dma_set_divs(GemmArgs& g, int n_tiles, int m_tiles) {
   g.dSK = make_fastdiv((unsigned)(g.splitk < 1 ? 1 : g.splitk));
 }
 
-template <int BN, int NS = DMA_NS, int BM = DMA_BM>
+template <int BN, int NS = DMA_NS, int BM = DMA_BM, bool BF = false>
 static hipError_t launch_dma_cfg(const GemmArgs& g, bool akc, bool bkc, hipStream_t s) {
   const int n_tiles = (g.N + BN - 1) / BN, m_tiles = (g.M + BM - 1) / BM;
   const int total = n_tiles * m_tiles * g.nbatch * g.splitk;
@@ -1336,16 +1347,27 @@ static hipError_t launch_dma_cfg(const GemmArgs& g, bool akc, bool bkc, hipStrea
   if (gg.wide_epi && shm < EPI_BYTES) shm = EPI_BYTES;
   const size_t shm_cap = shm_max > EPI_BYTES ? shm_max : EPI_BYTES;
   dim3 grid(total), block(DMA_THREADS);
-#define IGI_DMA_LAUNCH(AK, BK_, GA)                                                                    \
+#define IGI_DMA_LAUNCH_K(KERNEL)                                                                       \
   do {                                                                                                 \
     static bool attr_set = false;                                                                      \
     if (!attr_set) {                                                                                   \
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_kernel<BN, AK, BK_, GA, NS, BM>,        \
+      hipError_t e = hipFuncSetAttribute((const void*)KERNEL,                                          \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_cap);    \
       if (e != hipSuccess) return e;                                                                   \
       attr_set = true;                                                                                 \
     }                                                                                                  \
-    IGI_LAUNCH((gemm_dma_kernel<BN, AK, BK_, GA, NS, BM>), grid, block, shm, s, gg, n_tiles, m_tiles); \
+    IGI_LAUNCH((KERNEL), grid, block, shm, s, gg, n_tiles, m_tiles);                                   \
+  } while (0)
+  // BF: the bf16-input twin of the same tile (im2col products A = gather 1 / 3 with a k-contiguous weight operand only)
+#define IGI_DMA_LAUNCH(AK, BK_, GA)                                                                    \
+  do {                                                                                                 \
+    if constexpr (BF) {                                                                                \
+      if constexpr ((GA) != 0 && (GA) != 2 && ((GA) == 3 || (GA) == 5 || (BK_)))                      \
+        IGI_DMA_LAUNCH_K((gemm_dma_conv_bf16_kernel<BN, AK, BK_, GA, NS, BM>));                        \
+      else return hipErrorInvalidValue;                                                                \
+    } else {                                                                                           \
+      IGI_DMA_LAUNCH_K((gemm_dma_kernel<BN, AK, BK_, GA, NS, BM>));                                    \
+    }                                                                                                  \
   } while (0)
   if constexpr (BM == 192) {
     // three 192-tap tiles for a 576-tap weight gradient (conv3 of the tactile CNN): the position-major reduction only
@@ -1394,6 +1416,7 @@ static hipError_t launch_dma_cfg(const GemmArgs& g, bool akc, bool bkc, hipStrea
   return hipGetLastError();
   }
 #undef IGI_DMA_LAUNCH
+#undef IGI_DMA_LAUNCH_K
 }
 
 template <bool B_KC>
@@ -1462,27 +1485,51 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   const bool tall_fwd = tall && g.gather == 1 && bn == 64 && g.splitk == 1 && (long long)((g.M + 255) / 256) * g.nbatch >= 512;
   if (g.ssa_part && !(tall_fwd && g.N > 32 && g.N <= 64 && (g.M & 255) == 0 && !conv_pmajor_ok(g, bkc)))
     return hipErrorInvalidValue;   // the caller plans the fused soft-argmax with conv_ssa_fusable(): only that tile emits it
+  // conv_bf16 (the tactile encoder under conv_bf16_mode()): the SAME tile choice, the bf16-input twin of each tile and a
+  // profiler class of its own.  Only the shapes that encoder launches are built: anything else is an error, not fp32.
+  const bool cbf = g.conv_bf16 != 0;
+  if (cbf && !(g.N <= 64 && ((g.gather == 1 && akc && bkc) || (g.gather == 3 && !akc && !bkc)))) return hipErrorInvalidValue;
   if (tall_fwd) {
     // <= 32 output channels (conv1 forward, conv2 data gradient): a 32-wide tile, no padded MFMA columns
     const bool pmj = conv_pmajor_ok(g, bkc);
     if (g.N <= 32 && tall > 1) {
+      if (cbf) {
+        ProfScope ps(pmj ? PC_CONVB_PM32 : PC_CONVB_TALL32_TT, s, fl, by);
+        return launch_dma_cfg<32, 2, 256, true>(g, akc, bkc, s);
+      }
       ProfScope ps(pmj ? PC_CONV_PM32 : (bkc ? PC_CONV_TALL32_TT : PC_CONV_TALL32_TF), s, fl, by);
       return launch_dma_cfg<32, 2, 256>(g, akc, bkc, s);
+    }
+    if (cbf) {
+      ProfScope ps(pmj ? PC_CONVB_PM64 : (g.ssa_part ? PC_CONVB_TALL64_SSA : PC_CONVB_TALL64_TT), s, fl, by);
+      return launch_dma_cfg<64, 2, 256, true>(g, akc, bkc, s);
     }
     ProfScope ps(pmj ? PC_CONV_PM64 : (g.ssa_part ? PC_CONV_TALL64_SSA : (bkc ? PC_CONV_TALL64_TT : PC_CONV_TALL64_TF)), s, fl, by);
     return launch_dma_cfg<64, 2, 256>(g, akc, bkc, s);
   }
   if (tall > 1 && g.gather == 3 && g.N <= 32 && g.M % 256 == 0) {  // conv1 weight gradient: 32 output channels
+    if (cbf) {
+      ProfScope ps(conv_pw_ok(g) ? PC_CONVB_PW32 : PC_CONVB_WG_TALL32, s, fl, by);
+      return launch_dma_cfg<32, 2, 256, true>(g, akc, bkc, s);
+    }
     ProfScope ps(conv_pw_ok(g) ? PC_CONV_PW32 : PC_CONV_WG_TALL32, s, fl, by);
     return launch_dma_cfg<32, 2, 256>(g, akc, bkc, s);
   }
   if (tall > 2 && g.gather == 3 && g.N > 32 && g.N <= 64 && g.M % 192 == 0 && g.M % 256 != 0 && conv_bm192_on() && conv_pw_ok(g) &&
       aligned16(g.C) && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && (g.sCsplit & 3) == 0 && (g.N & 3) == 0 && g.epilogue == EPI_STORE) {
     // 576 taps = 3 x 192: no padded tap rows (five 128-tap tiles multiplied 640), 24 MFMAs per wave and barrier
+    if (cbf) {   // (two 16-k halves of a k-tile: one per wave group)
+      ProfScope ps(PC_CONVB_PW64_192, s, fl, by);
+      return launch_dma_cfg<64, 2, 192, true>(g, akc, bkc, s);
+    }
     ProfScope ps(PC_CONV_PW64_192, s, fl, by);
     return launch_dma_cfg<64, 2, 192>(g, akc, bkc, s);
   }
   if (tall > 2 && g.gather == 3 && g.N <= 64 && g.M % 256 == 0) {  // 64-channel weight gradients with whole 256-tap tiles
+    if (cbf) {
+      ProfScope ps(conv_pw_ok(g) ? PC_CONVB_PW64 : PC_CONVB_WG_TALL64, s, fl, by);
+      return launch_dma_cfg<64, 2, 256, true>(g, akc, bkc, s);
+    }
     ProfScope ps(conv_pw_ok(g) ? PC_CONV_PW64 : PC_CONV_WG_TALL64, s, fl, by);
     return launch_dma_cfg<64, 2, 256>(g, akc, bkc, s);
   }
@@ -1492,6 +1539,10 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   // one-k-tile products (the first trunk layer: K = 32, 67 MB of tanh outputs): the launch is epilogue + store, and the
   // 128-wide tile's 73 KB of epilogue staging allows two workgroups per CU; 64-wide tiles stage 37 KB: 20.6 -> 19.4 us
   if (bn == 128 && !g.gather && g.K <= DMA_BK) bn = 64;
+  if (cbf) {   // the 128-row, 64-wide, three-stage tile of small batches (N <= 64: checked above)
+    ProfScope ps(g.gather == 1 ? PC_CONVB_ROW64 : (conv_pw_ok(g) ? PC_CONVB_PW64_128 : PC_CONVB_WG64), s, fl, by);
+    return launch_dma_cfg<64, DMA_NS, DMA_BM, true>(g, akc, bkc, s);
+  }
   const int lay = akc ? (bkc ? 0 : 1) : (bkc ? 3 : 2);
   ProfScope ps((bn == 128 ? PC_DMA_128_TT : PC_DMA_64_TT) + lay, s, fl, by);
   if (bn == 128 && x3_mode() && !bf16_mode() && !g.gather && akc && bkc && g.K >= 256) {

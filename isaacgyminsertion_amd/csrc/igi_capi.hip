@@ -137,6 +137,12 @@ int igi_gemm_set_bf16_inputs(int on) {
   return prev;
 }
 
+int igi_conv_set_bf16_inputs(int on) {
+  const int prev = igi::conv_bf16_mode();
+  if (on >= 0) igi::conv_bf16_mode_ref() = on != 0;
+  return prev;
+}
+
 int igi_mfma_peak_probe(int shape, int blocks, int iters, uint64_t* clocks_dev, float* sink_dev, igi_stream_t stream) {
   return fail(igi::mfma_peak_probe(shape, blocks, iters, (unsigned long long*)clocks_dev, sink_dev, S(stream)), "igi_mfma_peak_probe");
 }

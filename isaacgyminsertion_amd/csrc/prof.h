@@ -23,6 +23,11 @@ enum ProfClass {
   PC_CONV_TALL64_TT, PC_CONV_TALL32_TT, PC_CONV_TALL64_TF, PC_CONV_TALL32_TF, PC_CONV_TALL64_SSA, PC_CONV_WG_TALL32, PC_CONV_WG_TALL64,
   PC_CONV_PM64, PC_CONV_PM32,   // position-major data-gradient tiles (GATHER == 4)
   PC_CONV_PW32, PC_CONV_PW64, PC_CONV_PW64_192,   // weight gradients with a position-major reduction (GATHER == 5), 256-tap tiles
+  // the same im2col tiles with bf16-rounded operands on v_mfma_f32_32x32x16_bf16 (conv_bf16_mode(): gemm_dma_conv_bf16_kernel),
+  // in the order of the fp32 classes above; ROW64 / WG64 are the 128-row tiles of small batches (forward and data
+  // gradient; weight gradient), which the fp32 path books under gemm_dma_kernel<64,...>
+  PC_CONVB_TALL64_TT, PC_CONVB_TALL32_TT, PC_CONVB_TALL64_SSA, PC_CONVB_WG_TALL32, PC_CONVB_WG_TALL64,
+  PC_CONVB_PM64, PC_CONVB_PM32, PC_CONVB_PW32, PC_CONVB_PW64, PC_CONVB_PW64_192, PC_CONVB_ROW64, PC_CONVB_WG64, PC_CONVB_PW64_128,
   PC_POINTNET_FWD, PC_POINTNET_BWD, PC_SOFTARGMAX_FWD, PC_SOFTARGMAX_BWD,
   PC_DMA_HEAD, PC_TRUNK_LOSS, PC_RB_TRUNK, PC_RB_ENV, PC_MLP_FWD, PC_POLICY_FWD, PC_FWD12, PC_ENV_FWD, PC_GEMM_GENERIC, PC_GATHER_NORMALIZE, PC_RMS_FINAL, PC_NORMALIZE,
   PC_LOSS, PC_LATENT_BWD, PC_SLAB_REDUCE, PC_SUMSQ, PC_ADAM, PC_ADAM_GATHER, PC_PREPARE, PC_OTHER, PC_COUNT
@@ -46,6 +51,14 @@ static const char* const kProfNames[PC_COUNT] = {
     "gemm_dma_kernel<32,false,false,3,2,256>", "gemm_dma_kernel<64,false,false,3,2,256>",
     "gemm_dma_kernel<64,true,true,4,2,256>", "gemm_dma_kernel<32,true,true,4,2,256>",
     "gemm_dma_kernel<32,false,false,5,2,256>", "gemm_dma_kernel<64,false,false,5,2,256>", "gemm_dma_kernel<64,false,false,5,2,192>",
+    "gemm_dma_conv_bf16_kernel<64,true,true,1,2,256>", "gemm_dma_conv_bf16_kernel<32,true,true,1,2,256>",
+    "gemm_dma_conv_bf16_kernel<64,true,true,6,2,256>",
+    "gemm_dma_conv_bf16_kernel<32,false,false,3,2,256>", "gemm_dma_conv_bf16_kernel<64,false,false,3,2,256>",
+    "gemm_dma_conv_bf16_kernel<64,true,true,4,2,256>", "gemm_dma_conv_bf16_kernel<32,true,true,4,2,256>",
+    "gemm_dma_conv_bf16_kernel<32,false,false,5,2,256>", "gemm_dma_conv_bf16_kernel<64,false,false,5,2,256>",
+    "gemm_dma_conv_bf16_kernel<64,false,false,5,2,192>",
+    "gemm_dma_conv_bf16_kernel<64,true,true,1,3,128>", "gemm_dma_conv_bf16_kernel<64,false,false,3,3,128>",
+    "gemm_dma_conv_bf16_kernel<64,false,false,5,3,128>",
     "k_pointnet_fwd", "k_pointnet_bwd", "k_softargmax_fwd", "k_softargmax_bwd",
     "gemm_dma_head_kernel<true>", "k_trunk_loss",
     "k_rb_level#trunk3: dW 256->128 x2 + dgrad 128->256 x2", "k_rb_level#env2: dW env 256->128 + env dgrad 128->256 (+ dW env 64->256 from its tiles)",

@@ -955,6 +955,34 @@ def _mlp_grad_offsets(dims):
 # ---------------------------------------------------------------------------------------------------------------
 # student encoders: tactile CNN, PointNet, depth backbone, token transformer
 # ---------------------------------------------------------------------------------------------------------------
+class conv_bf16_inputs:
+    """Opt-in bf16-input, fp32-accumulate arithmetic of the tactile CNN's convolutions (igi_conv_set_bf16_inputs; off by
+    default, ``IGI_CONV_BF16=1`` starts it on).  ``conv_bf16_inputs(True)`` sets the process-wide switch at once and
+    remembers the previous value in ``.previous``; used as a context manager it restores that value on exit::
+
+        ops.conv_bf16_inputs(True)                 # on from here
+        with ops.conv_bf16_inputs(True): ...       # on inside the block only
+
+    ``tactile_cnn_fwd`` records the setting its forward ran under and its autograd formula re-establishes it around
+    the backward op, so a switch flipped between forward and backward never mixes the two arithmetics.  Nothing but
+    the tactile convolutions reads this switch."""
+
+    def __init__(self, on):
+        self.previous = bool(_lib.lib().igi_conv_set_bf16_inputs(1 if on else 0))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().igi_conv_set_bf16_inputs(1 if self.previous else 0)
+        return False
+
+
+def conv_bf16_inputs_enabled():
+    """the current setting of the switch (igi_conv_set_bf16_inputs(-1): a query)"""
+    return bool(_lib.lib().igi_conv_set_bf16_inputs(-1))
+
+
 @_op("tactile_cnn_fwd(Tensor x, Tensor params, int latent_dim) -> (Tensor, Tensor)")
 def tactile_cnn_fwd(x: Tensor, params: Tensor, latent_dim: int) -> Tuple[Tensor, Tensor]:
     """CNNWithSpatialSoftArgmax forward (tactile_cnn.py:62-79) on (B, 3, H, W), B a multiple of 32: implicit-GEMM
@@ -1009,6 +1037,7 @@ def _tac_setup(ctx, inputs, output):
     x, params, latent_dim = inputs
     ctx.save_for_backward(params, output[1])
     ctx.hw = (x.shape[2], x.shape[3])
+    ctx.conv_bf16 = conv_bf16_inputs_enabled()     # setup_context runs right behind the forward op: still its setting
     ctx.set_materialize_grads(False)
 
 
@@ -1016,7 +1045,8 @@ def _tac_backward(ctx, dy, dws):
     params, ws = ctx.saved_tensors
     if dy is None:
         return None, None, None
-    return None, torch.ops.mi355ppo.tactile_cnn_bwd(dy.contiguous(), params, ws, ctx.hw[0], ctx.hw[1]), None
+    with conv_bf16_inputs(ctx.conv_bf16):          # the arithmetic the saved activations were computed in
+        return None, torch.ops.mi355ppo.tactile_cnn_bwd(dy.contiguous(), params, ws, ctx.hw[0], ctx.hw[1]), None
 
 
 register_autograd(f"{NS}::tactile_cnn_fwd", _tac_backward, setup_context=_tac_setup)

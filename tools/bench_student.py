@@ -6,6 +6,7 @@ resident in HBM.
 
     python tools/bench_student.py --config 3 [--hw 32 64] [--envs 2048] [--updates 2]
     python tools/bench_student.py --config 4 --envs 512        # tactile + PointNet(plug+socket) + lin
+    python tools/bench_student.py --config 3 --conv-bf16       # the tactile convolutions with bf16 inputs (opt-in mode)
 """
 import argparse
 import json
@@ -39,7 +40,7 @@ def algorithmic_macs(config, hw):
 
 
 def student_bench(config=3, envs=2048, horizon=32, hw=(32, 64), updates=2, device="cuda:0", multi_gpu=False,
-                  profile=True):
+                  profile=True, conv_bf16=False):
     """multi_gpu: one call per rank under torchrun (the process group is up): per-rank synthetic buffers (seed + rank),
     rank 0's initial student on every rank, ExtrinsicAdapt.update() with its gradient exchange; the time is the maximum
     over the ranks between barriers and the record says whether the parameter vectors ended bit-identical."""
@@ -60,6 +61,7 @@ def student_bench(config=3, envs=2048, horizon=32, hw=(32, 64), updates=2, devic
     cfg = default_config(num_envs=envs, horizon_length=horizon, rl_device=device, multi_gpu=multi_gpu, obs_info=True,
                          tactile_info=not img, pcl_info=pcl, img_info=img, seg_info=img, num_points=8)
     cfg.offline_train.tactile_width, cfg.offline_train.tactile_height = H, W
+    cfg.offline_train.model.conv_bf16_inputs = bool(conv_bf16)
     env = SyntheticInsertionEnv(envs, device=device, tactile_hw=None if img else (H, W),
                                 pcl_points=800 if pcl else 0, img_hw=(54, 96) if img else None)
     agent = ExtrinsicAdapt(env, None, cfg)
@@ -125,6 +127,8 @@ def student_bench(config=3, envs=2048, horizon=32, hw=(32, 64), updates=2, devic
            "ms_per_optimizer_step": round(1e3 * dt / steps, 2),
            "samples_per_s": round(world * envs * horizon * agent.mini_epochs_num / dt),
            "finite": bool(torch.isfinite(torch.stack(losses)).all())}
+    if conv_bf16:
+        out["conv_bf16_inputs"] = True
     if multi_gpu:
         comm = getattr(agent, "_comm", None)
         out["n_gpus"] = world
@@ -169,8 +173,11 @@ def main():
     ap.add_argument("--horizon", type=int, default=32)
     ap.add_argument("--hw", type=int, nargs=2, default=[32, 64])
     ap.add_argument("--updates", type=int, default=2)
+    ap.add_argument("--conv-bf16", action="store_true",
+                    help="offline_train.model.conv_bf16_inputs=True: bf16-input, fp32-accumulate tactile convolutions")
     args = ap.parse_args()
-    print(json.dumps(student_bench(args.config, args.envs, args.horizon, tuple(args.hw), args.updates)))
+    print(json.dumps(student_bench(args.config, args.envs, args.horizon, tuple(args.hw), args.updates,
+                                   conv_bf16=args.conv_bf16)))
 
 
 if __name__ == "__main__":
