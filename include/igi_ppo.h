@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define IGI_ABI_VERSION 5
+#define IGI_ABI_VERSION 6
 #define IGI_MAX_LAYERS 4
 #define IGI_MAX_ACT 8
 
@@ -145,6 +145,14 @@ typedef struct igi_teacher_cfg {
    * contact_points = num_points P, contact_emb = contact_mlp.units[-1] (<= 32), only_contact = train.ppo.only_contact
    * (the trunk then sees [obs | contact embedding] and env_mlp is not trained; needs contact_emb == priv_units[-1]). */
   int32_t contact_points, contact_emb, only_contact;
+  /* KL-adaptive learning rate (rl_games AdaptiveScheduler, schedule_type standard; frozen_ppo.py:624-630, 864-877 with
+   * the scheduler call of :630 live -- an opt-in beyond the reference's live code); all zero = fixed: the rate is
+   * cfg.lr.  lr_schedule 1: the rate lives in st->lr_state, Adam reads it there, and after the last optimizer step of
+   * every mini-epoch a one-wave kernel applies  lr = max(lr / 1.5, lr_min) if kl > 2 kl_threshold,
+   * lr = min(lr * 1.5, lr_max) if kl < 0.5 kl_threshold  (in double, strict inequalities) to that mini-epoch's mean KL;
+   * cfg.lr is then ignored.  The host neither reads nor writes the rate during an update. */
+  int32_t lr_schedule;
+  double kl_threshold, lr_min, lr_max;
 } igi_teacher_cfg;
 
 /* Time-major rollout arena, exactly what play_steps stores (frozen_ppo.py:655-683;
@@ -185,9 +193,17 @@ typedef struct igi_teacher_state {
   float* stats;       /* [E*E][IGI_STATS_PER_STEP] per-optimizer-step scalars, see below */
   void* workspace;
   size_t workspace_bytes;
+  /* cfg.lr_schedule != 0 only (else ignored, may be NULL): IGI_LR_STATE_DOUBLES(mini_epochs) doubles.
+   * [0] the learning rate: the caller writes it before the first update, the scheduler kernel afterwards;
+   * [1] scratch of the data-parallel updates: its first 4 bytes hold, as ONE float, this rank's mini-epoch KL, summed
+   *     over the ranks in place (the callback path hands it to the reducer as bucket 3);
+   * [2 + 2e], [3 + 2e] the record of mini-epoch e of the last update: the KL as compared, the rate after the decision. */
+  double* lr_state;
 } igi_teacher_state;
+#define IGI_LR_STATE_DOUBLES(mini_epochs) (2 + 2 * (mini_epochs))
 
-/* stats row: a_loss, c_loss, b_loss, entropy, kl, grad_total_norm (pre-clip), param_norm, 0 */
+/* stats row: a_loss, c_loss, b_loss, entropy, kl, grad_total_norm (pre-clip), param_norm, clip coefficient -- or, with
+ * cfg.lr_schedule != 0, in the last slot the (float) learning rate the step used */
 #define IGI_STATS_PER_STEP 8
 
 /* Flat parameter vector: tensors in state_dict order (sigma, env_mlp.mlp.{0,2,..}.{weight,bias},
@@ -216,6 +232,8 @@ int igi_teacher_prepare(const igi_teacher_cfg* cfg, const igi_rollout* ro,
 int igi_teacher_fwd_bwd(const igi_teacher_cfg* cfg, const igi_rollout* ro,
                         const igi_teacher_state* st, int mb_index, int step_slot,
                         igi_stream_t stream);
+/* With cfg.lr_schedule != 0 igi_teacher_apply also runs the scheduler when step_slot is the last of a mini-epoch
+ * (single rank: the mini-epoch's KL is this rank's). */
 int igi_teacher_apply(const igi_teacher_cfg* cfg, const igi_teacher_state* st, int step_slot,
                       int64_t adam_t, float grad_scale, igi_stream_t stream);
 
@@ -256,7 +274,11 @@ int igi_teacher_set_latz_fuse(int on);
  * phase 1, calls reduce(user, 1, step) for grads[0 : grad_split), then reduce(user, 2, step) -- the caller makes
  * `stream` wait (stream-ordered, no host block) for both collectives -- and enqueues clip + Adam with grad_scale
  * (= 1 / world_size).  reduce returns 0, or non-zero to abort (returned as IGI_E_CALLBACK).  The callback is the
- * only thing that is not a kernel launch: there is no per-step host <-> library round trip besides it. */
+ * only thing that is not a kernel launch: there is no per-step host <-> library round trip besides it.
+ * With cfg.lr_schedule != 0, after the last step of every mini-epoch the library writes this rank's mean KL as one
+ * float at (float*)(st->lr_state + 1) and calls reduce(user, 3, step): the caller all-reduces (SUM) that ONE float in
+ * place, in the order of `stream` (or makes `stream` wait for it); the scheduler kernel then divides by
+ * 1 / grad_scale ranks and decides -- identically on every rank (frozen_ppo.py:625-627). */
 typedef int (*igi_reduce_fn)(void* user, int bucket, int step);
 int igi_teacher_update_dp(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
                           int64_t adam_t0, float grad_scale, igi_reduce_fn reduce, void* user, igi_stream_t stream);
@@ -301,8 +323,11 @@ int igi_comm_broadcast(igi_comm_t comm, void* buf, int64_t bytes, int root, igi_
  * reference's serial schedule (one all-reduce of the whole flat gradient after backward, on `stream`).
  * stats_sum: NULL, or mini_epochs * n_minibatch * IGI_STATS_PER_STEP floats receiving st->stats summed over the
  * ranks (the per-mini-epoch KL all-reduce of frozen_ppo.py:624-627 and the loss aggregation of :387-396 as one
- * collective per update).  The learning-rate broadcast of :632-637 has nothing to send: the scheduler call is
- * commented out in the reference (:630), the rate is constant. */
+ * collective per update).  The learning-rate broadcast of :632-637 has nothing to send: under the fixed schedule the
+ * rate is constant (the scheduler call is commented out in the reference, :630); with cfg.lr_schedule != 0 every rank
+ * takes the same decision from the rank-mean KL -- one float per mini-epoch all-reduced on `stream` after the step's
+ * gradient collectives were joined there, so never two collectives of the communicator on two streams -- and holds
+ * the same rate. */
 int igi_teacher_update_dp_rccl(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
                                int64_t adam_t0, igi_comm_t comm, int overlap, float* stats_sum, igi_stream_t stream);
 

@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libigi_hip.so")
 IGI_MAX_LAYERS = 4
 IGI_MAX_ACT = 8
 IGI_STATS_PER_STEP = 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 IGI_E_BADARG, IGI_E_WORKSPACE, IGI_E_UNSUPPORTED, IGI_E_CALLBACK, IGI_E_COMM = -1, -2, -3, -5, -6   # include/igi_ppo.h
 
 EPI_STORE, EPI_BIAS_TANH, EPI_TANHGRAD, EPI_BIAS = 0, 1, 2, 3
@@ -31,6 +31,7 @@ class TeacherCfg(C.Structure):
         ("e_clip", C.c_float), ("critic_coef", C.c_float), ("entropy_coef", C.c_float),
         ("bounds_loss_coef", C.c_float), ("grad_norm", C.c_float), ("rms_eps", C.c_float),
         ("contact_points", C.c_int32), ("contact_emb", C.c_int32), ("only_contact", C.c_int32),
+        ("lr_schedule", C.c_int32), ("kl_threshold", C.c_double), ("lr_min", C.c_double), ("lr_max", C.c_double),
     ]
 
 
@@ -46,7 +47,12 @@ class TeacherState(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in
                 ("params", "grads", "adam_m", "adam_v", "rms_obs", "rms_priv", "rms_value", "perm",
                  "returns_raw", "advantages", "values_n", "returns_n", "mus_w", "sigmas_w", "stats",
-                 "workspace")] + [("workspace_bytes", C.c_size_t)]
+                 "workspace")] + [("workspace_bytes", C.c_size_t), ("lr_state", C.c_void_p)]
+
+
+def lr_state_doubles(mini_epochs):
+    """IGI_LR_STATE_DOUBLES: [rate, exchange scratch, (kl, rate after) per mini-epoch]."""
+    return 2 + 2 * int(mini_epochs)
 
 
 class TactileCfg(C.Structure):

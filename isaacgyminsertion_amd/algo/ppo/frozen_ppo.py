@@ -21,7 +21,7 @@ import torch.distributed as dist
 from ..models.models_split import ActorCriticSplit as ActorCritic
 from ..models.running_mean_std import RunningMeanStd
 from .experience import ExperienceBuffer
-from ...teacher_native import TeacherEngine
+from ...teacher_native import TeacherEngine, lr_schedule_id
 from ...utils.misc import AverageScalarMeter, multi_gpu_aggregate_stats
 
 
@@ -64,7 +64,9 @@ def _summary_writer(path):
 
 class _FusedAdam:
     """Holds what torch.optim.Adam held for the reference (frozen_ppo.py:192-194); the update itself is
-    the k_clip_adam kernel.  ``param_groups[0]['lr']`` is honoured (frozen_ppo.py:636-640)."""
+    the k_clip_adam kernel.  ``param_groups[0]['lr']`` is honoured (frozen_ppo.py:636-640); under the adaptive
+    schedule PPO.update uploads it before an update and writes the device's rate back after it, and ``load_state_dict``
+    puts the checkpoint's rate on the device as well."""
 
     def __init__(self, engine, lr, weight_decay=0.0):
         if weight_decay:
@@ -81,6 +83,7 @@ class _FusedAdam:
         self.engine.adam_v.copy_(sd["exp_avg_sq"])
         self.engine.adam_t = int(sd["step"])
         self.param_groups[0]["lr"] = float(sd["lr"])
+        self.engine.set_lr(float(sd["lr"]))
 
 
 class PPO(object):
@@ -98,6 +101,7 @@ class PPO(object):
         self.task_config = full_config.task
         self.network_config = full_config.train.network
         self.ppo_config = full_config.train.ppo
+        self.parse_lr_schedule(self.ppo_config)      # a schedule this trainer does not have: fail before anything is built
         self.env = env
         self.num_actors = self.ppo_config['num_actors']
         self.actions_num = self.task_config.env.numActions
@@ -161,6 +165,9 @@ class PPO(object):
         assert self.batch_size % self.minibatch_size == 0 or full_config.test
         self.kl_threshold = self.ppo_config['kl_threshold']
         self.scheduler = AdaptiveScheduler(self.kl_threshold)
+        # train.ppo.lr_schedule: absent / "fixed" = the reference's live code (the scheduler is never stepped);
+        # "adaptive" = its commented-out call (:630) made live, stepped on the device inside the fused update
+        self.lr_schedule = self.parse_lr_schedule(self.ppo_config)
         self.save_freq = self.ppo_config['save_frequency']
         self.save_best_after = self.ppo_config['save_best_after']
         self.it = 0
@@ -183,7 +190,9 @@ class PPO(object):
             priv_dim=self.priv_info_dim, act_dim=self.actions_num, device=self.device, perm=self.storage.indices,
             gamma=self.gamma, tau=self.tau, lr=self.last_lr, e_clip=self.e_clip, critic_coef=self.critic_coef,
             entropy_coef=self.entropy_coef, bounds_loss_coef=self.bounds_loss_coef, grad_norm=self.grad_norm,
-            truncate_grads=self.truncate_grads, normalize_value=self.normalize_value, **self.model.contact_kwargs())
+            truncate_grads=self.truncate_grads, normalize_value=self.normalize_value,
+            lr_schedule=self.lr_schedule, kl_threshold=self.kl_threshold, lr_min=self.scheduler.min_lr,
+            lr_max=self.scheduler.max_lr, **self.model.contact_kwargs())
         self.model.bind_flat_to(self.engine)
         self.model.attach_engine(self.engine)
         self.running_mean_std.bind(self.engine.rms_obs)
@@ -205,6 +214,15 @@ class PPO(object):
         self.data_collect_time = 0
         self.rl_train_time = 0
         self.all_time = 0
+
+    @staticmethod
+    def parse_lr_schedule(ppo_config):
+        """train.ppo.lr_schedule -> "fixed" (also when the key is absent) or "adaptive"; ValueError for any other name
+        (rl_games' "linear" and its per-minibatch "legacy" schedule type are not built)."""
+        name = ppo_config.get('lr_schedule', None)
+        name = 'fixed' if name is None else name
+        lr_schedule_id(name)
+        return name
 
     # ------------------------------------------------------------------------------------------
     def write_stats(self, a_losses, c_losses, b_losses, entropies, kls, grad_norms, returns_list):
@@ -359,7 +377,9 @@ class PPO(object):
         """The optimisation half of train_epoch (frozen_ppo.py:503-646) on the rollout currently in
         storage (prepare_training already run).  Returns the reference's seven lists."""
         eng = self.engine
-        eng.cfg.lr = float(self.optimizer.param_groups[0]["lr"])
+        # fixed: the rate is a host scalar of the cfg; adaptive: an asynchronous upload to the device, where Adam and
+        # the scheduler find it -- the host does not touch it again until the update is enqueued whole
+        eng.set_lr(float(self.optimizer.param_groups[0]["lr"]))
         stats_sum = None
         if self.multi_gpu and self._native_comm() is not None:
             # the library issues both bucket all-reduces itself (own RCCL communicator + communication stream) and
@@ -385,7 +405,9 @@ class PPO(object):
                 dist.all_reduce(av_kls, op=dist.ReduceOp.SUM)
                 av_kls = av_kls / self.rank_size
         kls = list(av_kls.unbind())
-        for pg in self.optimizer.param_groups:  # lr is constant: scheduler.update is commented out (:630)
+        if eng.adaptive_lr:                     # :630-640 with the scheduler live: one read per update, next to the
+            self.last_lr = eng.lr               # stats read train_epoch synchronises for
+        for pg in self.optimizer.param_groups:  # fixed: lr is constant, scheduler.update is commented out (:630)
             pg["lr"] = self.last_lr
         returns_list = [self.engine.returns_n.mean()]
         return a_losses, c_losses, b_losses, entropies, kls, grad_norms, returns_list
@@ -505,7 +527,9 @@ def policy_kl(p0_mu, p0_sigma, p1_mu, p1_sigma):
 
 
 class AdaptiveScheduler(object):
-    """frozen_ppo.py:864-877 (constructed but never stepped: SURVEY Appendix A5)."""
+    """frozen_ppo.py:864-877.  The reference constructs it and never steps it, and neither does the
+    default ``lr_schedule: fixed``; under ``lr_schedule: adaptive`` this rule runs on the device (csrc/teacher.h
+    k_lr_schedule) with this object's kl_threshold / min_lr / max_lr, and the class is the oracle the tests hold it to."""
 
     def __init__(self, kl_threshold=0.008):
         self.min_lr = 1e-6

@@ -188,8 +188,17 @@ static int teacher_update_dp_rccl(const igi_teacher_cfg* c, const igi_rollout* r
       }
       const bool more = slot + 1 < total;
       if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, scale, s, more ? ro : nullptr, (slot + 1) % p.nmb,
-                              slot + 1)))
+                              slot + 1, /*schedule_here=*/false)))
         return rc;
+      if (lr_adaptive(c) && i == p.nmb - 1) {
+        // adaptive schedule: the rank-mean KL of the mini-epoch (frozen_ppo.py:625-627) as ONE float on the compute
+        // stream.  Both gradient collectives of this step were joined on `s` before Adam and the next one on the
+        // communication stream waits for an event recorded on `s` after phase 0 of the next step: the communicator
+        // never has collectives in flight on two streams.  Every rank then takes the same decision.
+        if ((rc = teacher_lr_exchange_begin(c, p, st, slot, s))) return rc;
+        if ((rc = comm_all_reduce_sum(cm, reinterpret_cast<float*>(st->lr_state + 1), 1, s))) return rc;
+        if ((rc = teacher_lr_exchange_end(c, p, st, slot, cm->world, s))) return rc;
+      }
     }
   }
   if (stats_sum && st->stats) {

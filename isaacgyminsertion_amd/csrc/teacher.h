@@ -1891,8 +1891,10 @@ __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const
                                                const double* __restrict__ part, float scale, float max_norm, float w1,
                                                float beta2, float w2, float step_size, float bc2_sqrt, float eps,
                                                float* __restrict__ stats_row, float decay, float l2, int bid,
-                                               int nblocks, const W1Mirror* mir) {
+                                               int nblocks, const W1Mirror* mir, const double* __restrict__ lr_dev = nullptr,
+                                               double bc1 = 1.0) {
   __shared__ float s_coef;
+  __shared__ float s_step;
   __shared__ double s_part[2][64];
   if (threadIdx.x < 64) {
     // 128 partial pairs: lane b of the first wave adds pairs b and b + 64, lane 0 finishes in lane order
@@ -1917,9 +1919,16 @@ __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const
       stats_row[6] = (float)sqrt(sp);  // the reference logs the PARAMETER norm as "grad_norms"
       stats_row[7] = coef;
     }
+    if (lr_dev) {
+      // adaptive schedule: the rate is a device double; the step size is the host line's arithmetic, (float)(lr / bc1)
+      const double lr = *lr_dev;
+      s_step = (float)(lr / bc1);
+      if (bid == 0 && stats_row) stats_row[7] = (float)lr;   // the rate this step used (replaces the clip coefficient)
+    }
   }
   __syncthreads();
   const float coef = s_coef;
+  if (lr_dev) step_size = s_step;
   // one element: exactly torch's single-tensor Adam arithmetic (each line one rounding, -ffp-contract=off)
   auto one = [&](long long i, float gi, float& pi, float& mi, float& vi) {
     float g = (gi * scale) * coef;
@@ -1977,9 +1986,10 @@ __global__ __launch_bounds__(256) void k_clip_adam(float* __restrict__ params,
                                                    float scale, float max_norm, float w1, float beta2,
                                                    float w2, float step_size, float bc2_sqrt, float eps,
                                                    float* __restrict__ stats_row, float decay = 1.0f,
-                                                   float l2 = 0.0f) {
+                                                   float l2 = 0.0f, const double* __restrict__ lr_dev = nullptr,
+                                                   double bc1 = 1.0) {
   clip_adam_body(params, grads, m, v, P, part, scale, max_norm, w1, beta2, w2, step_size, bc2_sqrt, eps, stats_row,
-                 decay, l2, (int)blockIdx.x, (int)gridDim.x, nullptr);
+                 decay, l2, (int)blockIdx.x, (int)gridDim.x, nullptr, lr_dev, bc1);
 }
 
 // Tail of optimizer step s fused with the head of step s+1: blocks [0, adam_blocks) run clip + Adam (and keep the
@@ -1990,6 +2000,7 @@ __global__ __launch_bounds__(256) void k_clip_adam(float* __restrict__ params,
 struct AdamArgs {
   float* params; const float* grads; float* m; float* v; long long P; const double* part;
   float scale, max_norm, w1, beta2, w2, step_size, bc2_sqrt, eps; float* stats_row;
+  const double* lr_dev; double bc1;   // adaptive schedule: the rate's device address (NULL: step_size as given) and 1 - beta1^t
 };
 __global__ __launch_bounds__(256) void k_adam_gather(const AdamArgs a, const W1Mirror mir, const GatherArgs g,
                                                      int adam_blocks) {
@@ -2000,7 +2011,41 @@ __global__ __launch_bounds__(256) void k_adam_gather(const AdamArgs a, const W1M
     gather_normalize_body(g, (int)blockIdx.x, gblocks);
   else
     clip_adam_body(a.params, a.grads, a.m, a.v, a.P, a.part, a.scale, a.max_norm, a.w1, a.beta2, a.w2, a.step_size,
-                   a.bc2_sqrt, a.eps, a.stats_row, 1.0f, 0.0f, (int)blockIdx.x - gblocks, adam_blocks, &mir);
+                   a.bc2_sqrt, a.eps, a.stats_row, 1.0f, 0.0f, (int)blockIdx.x - gblocks, adam_blocks, &mir, a.lr_dev,
+                   a.bc1);
+}
+
+// KL-adaptive learning rate (rl_games AdaptiveScheduler.update, frozen_ppo.py:864-877, fed as at :624-630 with the call
+// of :630 live): one wave, launched once per mini-epoch behind its last optimizer step.  kl = fp32 mean of the n_mb
+// per-step KL values (stats slot 4) of the mini-epoch, as torch.mean(torch.stack(ep_kls)); the comparison and the
+// rate are doubles, as in Python.  lr_state: [0] rate, [1] scratch float of the data-parallel exchange,
+// [2 + 2e] / [3 + 2e] the record of mini-epoch e (KL as compared, rate after the decision).
+//   mode 0: one rank -- mean and decision
+//   mode 1: data parallel, before the exchange -- this rank's mean into the scratch float, no decision
+//   mode 2: data parallel, after the all-reduce (SUM) of the scratch float -- kl = sum / world (fp32, :625-627), decision
+// Every store is a plain C++ store from lane 0.
+__global__ __launch_bounds__(64) void k_lr_schedule(const float* __restrict__ stats_epoch, int nmb, int epoch, int mode,
+                                                    int world, double kl_threshold, double lr_min, double lr_max,
+                                                    double* __restrict__ lr_state) {
+  if (threadIdx.x != 0) return;
+  float* scratch = reinterpret_cast<float*>(lr_state + 1);
+  float kl;
+  if (mode != 2) {
+    float sum = 0.f;
+    for (int i = 0; i < nmb; ++i) sum += stats_epoch[(long long)i * IGI_STATS_PER_STEP + 4];
+    kl = sum / (float)nmb;
+    if (mode == 1) { *scratch = kl; return; }
+  } else {
+    kl = *scratch / (float)world;
+  }
+  const double k = (double)kl;
+  const double cur = lr_state[0];
+  double lr = cur;
+  if (k > 2.0 * kl_threshold) lr = fmax(cur / 1.5, lr_min);
+  if (k < 0.5 * kl_threshold) lr = fmin(cur * 1.5, lr_max);
+  lr_state[0] = lr;
+  lr_state[2 + 2 * epoch] = k;
+  lr_state[3 + 2 * epoch] = lr;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2009,6 +2054,14 @@ __global__ __launch_bounds__(256) void k_adam_gather(const AdamArgs a, const W1M
 static int check_state(const TeacherPlan& p, const igi_teacher_state* st) {
   if (!st || !st->params || !st->workspace) return IGI_E_BADARG;
   if (st->workspace_bytes < p.w_total) return IGI_E_WORKSPACE;
+  return 0;
+}
+static inline bool lr_adaptive(const igi_teacher_cfg* c) { return c->lr_schedule != 0; }
+static int check_lr_cfg(const igi_teacher_cfg* c, const igi_teacher_state* st) {
+  if (!lr_adaptive(c)) return 0;
+  if (c->lr_schedule != 1 || !(c->kl_threshold > 0.0) || !(c->lr_min > 0.0) || !(c->lr_max >= c->lr_min) || !st->lr_state ||
+      !st->stats)
+    return IGI_E_BADARG;
   return 0;
 }
 
@@ -2853,15 +2906,33 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   return (int)hipGetLastError();
 }
 
+// The scheduler launch behind the last optimizer step (step_slot) of a mini-epoch; mode as k_lr_schedule takes it.
+static int teacher_lr_schedule(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_teacher_state* st, int step_slot,
+                               int mode, int world, hipStream_t s) {
+  const int e = step_slot / p.nmb;
+  if (e >= p.E || step_slot % p.nmb != p.nmb - 1) return IGI_E_BADARG;
+  const float* rows = st->stats + (long long)e * p.nmb * IGI_STATS_PER_STEP;
+  ProfScope ps(PC_LR_SCHEDULE, s, 0.0, 4.0 * p.nmb + 32.0);
+  IGI_LAUNCH(k_lr_schedule, dim3(1), dim3(64), 0, s, rows, p.nmb, e, mode, world, c->kl_threshold, c->lr_min, c->lr_max,
+             st->lr_state);
+  return (int)hipGetLastError();
+}
+
 // next_ro != NULL: fuse the gather + normalise of optimizer step (next_mb, next_slot) into this step's Adam launch
 // (k_sumsq_stats computes both norms and the statistics row first)
+// schedule_here: with the adaptive schedule, run the (single-rank) scheduler when step_slot ends a mini-epoch; the
+// data-parallel updates pass false and put their KL exchange between the two halves themselves
 static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, int step_slot,
                          int64_t adam_t, float grad_scale, hipStream_t s, const igi_rollout* next_ro = nullptr,
-                         int next_mb = 0, int next_slot = 0) {
+                         int next_mb = 0, int next_slot = 0, bool schedule_here = true) {
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
   if ((rc = check_state(p, st))) return rc;
+  if ((rc = check_lr_cfg(c, st))) return rc;
+  const bool adaptive = lr_adaptive(c);
+  if (adaptive && (step_slot < 0 || step_slot >= p.E * p.nmb)) return IGI_E_BADARG;
+  const bool sched = adaptive && schedule_here && step_slot % p.nmb == p.nmb - 1;
   if (!st->grads || !st->adam_m || !st->adam_v || adam_t < 1) return IGI_E_BADARG;
   double* part = wsp<double>(st, p.w_sumsq);
   float* row = st->stats ? st->stats + (long long)step_slot * IGI_STATS_PER_STEP : nullptr;
@@ -2889,18 +2960,31 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
     aa.params = st->params; aa.grads = st->grads; aa.m = st->adam_m; aa.v = st->adam_v; aa.P = p.P; aa.part = part;
     aa.scale = grad_scale; aa.max_norm = c->grad_norm; aa.w1 = w1; aa.beta2 = (float)b2; aa.w2 = w2;
     aa.step_size = step_size; aa.bc2_sqrt = bc2_sqrt; aa.eps = (float)c->adam_eps; aa.stats_row = row;
+    aa.lr_dev = adaptive ? st->lr_state : nullptr; aa.bc1 = bc1;
     const GatherArgs ga = gather_args(p, next_ro, st, next_mb, next_slot);
     W1Mirror mir;
     mir.w1p = ga.w1p; mir.wlat = ga.wlat; mir.o_w = ga.o_w; mir.ac_block = ga.ac_block; mir.u0 = ga.u0;
     mir.u0p = ga.u0p; mir.xw = p.xw; mir.xld = p.xld; mir.obs = p.obs; mir.K2p = ga.K2p;
     IGI_LAUNCH(k_adam_gather, dim3(nb + p.gs_blocks), dim3(256), 0, s, aa, mir, ga, nb);
-    return (int)hipGetLastError();
+    if ((rc = (int)hipGetLastError())) return rc;
+  } else {
+    ProfScope ps(PC_ADAM, s, 0.0, 28.0 * (double)p.P);  // 16 B read + 12 B written per parameter
+    IGI_LAUNCH(k_clip_adam, dim3(nb), dim3(256), 0, s, st->params, st->grads, st->adam_m,
+                       st->adam_v, p.P, part, grad_scale, c->grad_norm, w1, (float)b2, w2, step_size,
+                       bc2_sqrt, (float)c->adam_eps, row, 1.0f, 0.0f, adaptive ? st->lr_state : (const double*)nullptr, bc1);
+    if ((rc = (int)hipGetLastError())) return rc;
   }
-  ProfScope ps(PC_ADAM, s, 0.0, 28.0 * (double)p.P);  // 16 B read + 12 B written per parameter
-  IGI_LAUNCH(k_clip_adam, dim3(nb), dim3(256), 0, s, st->params, st->grads, st->adam_m,
-                     st->adam_v, p.P, part, grad_scale, c->grad_norm, w1, (float)b2, w2, step_size,
-                     bc2_sqrt, (float)c->adam_eps, row, 1.0f, 0.0f);
-  return (int)hipGetLastError();
+  return sched ? teacher_lr_schedule(c, p, st, step_slot, 0, 1, s) : 0;
+}
+
+// data-parallel updates: this rank's mini-epoch KL into the exchange scratch / the decision from the rank sum
+static int teacher_lr_exchange_begin(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_teacher_state* st, int slot,
+                                     hipStream_t s) {
+  return teacher_lr_schedule(c, p, st, slot, 1, 1, s);
+}
+static int teacher_lr_exchange_end(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_teacher_state* st, int slot,
+                                   int world, hipStream_t s) {
+  return teacher_lr_schedule(c, p, st, slot, 2, world, s);
 }
 
 static int teacher_update(const igi_teacher_cfg* c, const igi_rollout* ro,
@@ -2931,6 +3015,8 @@ static int teacher_update_dp(const igi_teacher_cfg* c, const igi_rollout* ro, co
   int rc = make_plan(c, &p);
   if (rc) return rc;
   const int total = p.E * p.nmb;
+  const int world = grad_scale > 0.f ? (int)lroundf(1.0f / grad_scale) : 0;
+  if (lr_adaptive(c) && world < 1) return IGI_E_BADARG;
   int slot = 0;
   for (int e = 0; e < p.E; ++e) {
     for (int i = 0; i < p.nmb; ++i, ++slot) {
@@ -2941,8 +3027,14 @@ static int teacher_update_dp(const igi_teacher_cfg* c, const igi_rollout* ro, co
       if (reduce(user, 2, slot)) return IGI_E_CALLBACK;
       const bool more = slot + 1 < total;
       if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, grad_scale, s, more ? ro : nullptr,
-                              (slot + 1) % p.nmb, slot + 1)))
+                              (slot + 1) % p.nmb, slot + 1, /*schedule_here=*/false)))
         return rc;
+      if (lr_adaptive(c) && i == p.nmb - 1) {
+        // the rank-mean KL of the mini-epoch (frozen_ppo.py:625-627): one float through the caller's transport, bucket 3
+        if ((rc = teacher_lr_exchange_begin(c, p, st, slot, s))) return rc;
+        if (reduce(user, 3, slot)) return IGI_E_CALLBACK;
+        if ((rc = teacher_lr_exchange_end(c, p, st, slot, world, s))) return rc;
+      }
     }
   }
   return 0;

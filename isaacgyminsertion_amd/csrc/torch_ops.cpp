@@ -52,15 +52,24 @@ float* fpo(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(
 // ---- teacher marshalling: (int[] icfg, float[] fcfg) <-> struct igi_teacher_cfg, tensor lists <-> the structs
 igi_teacher_cfg unpack_cfg(at::IntArrayRef ic, at::ArrayRef<double> fc) {
   constexpr int M = IGI_MAX_LAYERS;
-  TORCH_CHECK(((int)ic.size() == 8 + 2 * M || (int)ic.size() == 11 + 2 * M) && fc.size() == 12, "teacher cfg: expected ",
-              8 + 2 * M, " (or ", 11 + 2 * M, " with contacts) ints and 12 floats, got ", ic.size(), " and ", fc.size());
+  // the adaptive learning-rate schedule appends ONE int (lr_schedule) and three floats (kl_threshold, lr_min, lr_max)
+  const bool sched = fc.size() == 15;
+  const int ni = (int)ic.size() - (sched ? 1 : 0);
+  TORCH_CHECK((ni == 8 + 2 * M || ni == 11 + 2 * M) && (fc.size() == 12 || sched), "teacher cfg: expected ",
+              8 + 2 * M, " (or ", 11 + 2 * M, " with contacts) ints and 12 floats (one more int and 15 floats with the adaptive "
+              "learning-rate schedule), got ", ic.size(), " and ", fc.size());
   igi_teacher_cfg c;
   std::memset(&c, 0, sizeof(c));
+  if (sched) {
+    c.lr_schedule = (int32_t)ic[ni]; c.kl_threshold = fc[12]; c.lr_min = fc[13]; c.lr_max = fc[14];
+    TORCH_CHECK(c.lr_schedule == 1 && c.kl_threshold > 0 && c.lr_min > 0 && c.lr_max >= c.lr_min,
+                "teacher cfg: the schedule fields need lr_schedule == 1, kl_threshold > 0 and 0 < lr_min <= lr_max");
+  }
   c.obs_dim = (int32_t)ic[0]; c.priv_dim = (int32_t)ic[1]; c.act_dim = (int32_t)ic[2]; c.n_priv_layers = (int32_t)ic[3];
   for (int i = 0; i < M; ++i) { c.priv_units[i] = (int32_t)ic[4 + i]; c.units[i] = (int32_t)ic[5 + M + i]; }
   c.n_layers = (int32_t)ic[4 + M];
   c.num_envs = (int32_t)ic[5 + 2 * M]; c.horizon = (int32_t)ic[6 + 2 * M]; c.mini_epochs = (int32_t)ic[7 + 2 * M];
-  if ((int)ic.size() == 11 + 2 * M) {   // contact mode (ops.py pack_cfg)
+  if (ni == 11 + 2 * M) {   // contact mode (ops.py pack_cfg)
     c.contact_points = (int32_t)ic[8 + 2 * M]; c.contact_emb = (int32_t)ic[9 + 2 * M]; c.only_contact = (int32_t)ic[10 + 2 * M];
     TORCH_CHECK(c.contact_points >= 1, "teacher cfg: the contact fields need contact_points >= 1");
   }
@@ -77,7 +86,8 @@ igi_teacher_state state_struct(at::TensorList st, const igi_teacher_cfg& c) {
   static const char* names[16] = {"params", "grads", "adam_m", "adam_v", "rms_obs", "rms_priv", "rms_value", "perm",
                                   "returns_raw", "advantages", "values_n", "returns_n", "mus_w", "sigmas_w", "stats",
                                   "workspace"};
-  TORCH_CHECK(st.size() == 16, "state: expected 16 tensors (struct igi_teacher_state field order), got ", st.size());
+  const size_t want_n = c.lr_schedule ? 17 : 16;   // + lr_state (float64) under the adaptive learning-rate schedule
+  TORCH_CHECK(st.size() == want_n, "state: expected ", want_n, " tensors (struct igi_teacher_state field order), got ", st.size());
   const int64_t P = igi_teacher_param_count(&c);
   TORCH_CHECK(P > 0, "teacher cfg rejected by the library: ", igi_last_error());
   const int64_t T = c.horizon, N = c.num_envs, A = c.act_dim;
@@ -100,6 +110,14 @@ igi_teacher_state state_struct(at::TensorList st, const igi_teacher_cfg& c) {
   s.returns_raw = fp(st[8]); s.advantages = fp(st[9]); s.values_n = fp(st[10]); s.returns_n = fp(st[11]);
   s.mus_w = fp(st[12]); s.sigmas_w = fp(st[13]); s.stats = fp(st[14]);
   s.workspace = st[15].data_ptr(); s.workspace_bytes = (size_t)st[15].numel();
+  s.lr_state = nullptr;
+  if (c.lr_schedule) {
+    check(st[16], "state.lr_state", at::kDouble);
+    TORCH_CHECK(st[16].device() == st[0].device(), "state.lr_state: all arguments must share one device");
+    TORCH_CHECK(st[16].numel() == IGI_LR_STATE_DOUBLES(c.mini_epochs), "state.lr_state: expected ",
+                IGI_LR_STATE_DOUBLES(c.mini_epochs), " doubles, got ", st[16].numel());
+    s.lr_state = st[16].data_ptr<double>();
+  }
   return s;
 }
 

@@ -135,15 +135,27 @@ def pack_cfg(cfg):
         icfg += [cfg.contact_points, cfg.contact_emb, cfg.only_contact]
     fcfg = [cfg.gamma, cfg.tau, cfg.lr, cfg.beta1, cfg.beta2, cfg.adam_eps, cfg.e_clip, cfg.critic_coef,
             cfg.entropy_coef, cfg.bounds_loss_coef, cfg.grad_norm, cfg.rms_eps]
+    if cfg.lr_schedule:          # adaptive learning rate: one trailing int, three trailing floats (fixed packs as before)
+        icfg += [cfg.lr_schedule]
+        fcfg += [cfg.kl_threshold, cfg.lr_min, cfg.lr_max]
     return [int(x) for x in icfg], [float(x) for x in fcfg]
 
 
 def _unpack_cfg(icfg, fcfg):
     M = _lib.IGI_MAX_LAYERS
+    sched = len(fcfg) == 15      # + lr_schedule | kl_threshold, lr_min, lr_max
+    if sched:
+        icfg, fcfg, tail = icfg[:-1], fcfg[:12], (icfg[-1], *fcfg[12:])
     if len(icfg) not in (8 + 2 * M, 11 + 2 * M) or len(fcfg) != 12:
-        raise RuntimeError(f"teacher cfg: expected {8 + 2 * M} (or {11 + 2 * M} with contacts) ints and 12 floats, "
-                           f"got {len(icfg)} and {len(fcfg)}")
+        raise RuntimeError(f"teacher cfg: expected {8 + 2 * M} (or {11 + 2 * M} with contacts) ints and 12 floats (one "
+                           f"more int and 15 floats with the adaptive learning-rate schedule), "
+                           f"got {len(icfg) + sched} and {len(fcfg) + 3 * sched}")
     c = _lib.TeacherCfg()
+    if sched:
+        c.lr_schedule, c.kl_threshold, c.lr_min, c.lr_max = tail
+        if c.lr_schedule != 1 or not c.kl_threshold > 0 or not 0 < c.lr_min <= c.lr_max:
+            raise RuntimeError("teacher cfg: the schedule fields need lr_schedule == 1, kl_threshold > 0 and "
+                               "0 < lr_min <= lr_max")
     c.obs_dim, c.priv_dim, c.act_dim, c.n_priv_layers = icfg[0:4]
     for i in range(M):
         c.priv_units[i] = icfg[4 + i]
@@ -184,8 +196,10 @@ def _teacher_args(state, icfg, fcfg):
 
 def _state_struct(state, cfg, need=()):
     """Tensor list in STATE_FIELDS order -> struct igi_teacher_state (validated)."""
-    if len(state) != len(STATE_FIELDS):
-        raise RuntimeError(f"state: expected {len(STATE_FIELDS)} tensors ({', '.join(STATE_FIELDS)}), got {len(state)}")
+    want = len(STATE_FIELDS) + (1 if cfg.lr_schedule else 0)     # + lr_state under the adaptive learning-rate schedule
+    if len(state) != want:
+        raise RuntimeError(f"state: expected {want} tensors ({', '.join(STATE_FIELDS)}"
+                           f"{', lr_state' if cfg.lr_schedule else ''}), got {len(state)}")
     dev = state[0].device
     s = _lib.TeacherState()
     T, N, A = cfg.horizon, cfg.num_envs, cfg.act_dim
@@ -201,6 +215,9 @@ def _state_struct(state, cfg, need=()):
     if state[14].dim() != 2 or state[14].shape[1] != _lib.IGI_STATS_PER_STEP:
         raise RuntimeError(f"state.stats: expected (steps, {_lib.IGI_STATS_PER_STEP}), got {tuple(state[14].shape)}")
     s.workspace_bytes = state[15].numel()
+    if cfg.lr_schedule:
+        _check(state[16], "state.lr_state", dtype=torch.float64, shape=(_lib.lr_state_doubles(cfg.mini_epochs),), device=dev)
+        s.lr_state = state[16].data_ptr()
     need_ws = int(_lib.lib().igi_teacher_workspace_bytes(C.byref(cfg)))
     if s.workspace_bytes < need_ws:
         raise RuntimeError(f"state.workspace: {s.workspace_bytes} bytes, the configuration needs {need_ws}")
@@ -287,7 +304,9 @@ _REDUCERS = {}
 
 def register_reducer(fn):
     """fn(bucket, step) -> None: bucket 0 / 1 = start the all-reduce(SUM) of the early / late ranges of state.grads
-    (igi_teacher_grad_buckets) without blocking the host; bucket 2 = make the current stream wait for both.  Returns the handle
+    (igi_teacher_grad_buckets) without blocking the host; bucket 2 = make the current stream wait for both; bucket 3
+    (adaptive learning-rate schedule only, once per mini-epoch) = all-reduce(SUM) the one float of the KL exchange
+    in the order of the current stream.  Returns the handle
     ``ppo_update_dp`` takes (ops cannot carry Python callables)."""
     h = max(_REDUCERS, default=0) + 1
     _REDUCERS[h] = fn

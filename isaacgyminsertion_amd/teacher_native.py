@@ -75,12 +75,39 @@ def teacher_param_shapes(obs_dim, priv_dim, act_dim, units, priv_units, contact_
     return shapes
 
 
+LR_SCHEDULES = ("fixed", "adaptive")
+
+
+def lr_schedule_id(name):
+    """train.ppo.lr_schedule -> igi_teacher_cfg.lr_schedule (None = absent = fixed)."""
+    name = "fixed" if name is None else name
+    if name not in LR_SCHEDULES:
+        raise ValueError(f"lr_schedule {name!r}: supported schedules are {' and '.join(map(repr, LR_SCHEDULES))}")
+    return LR_SCHEDULES.index(name)
+
+
+def adaptive_lr_rule(lr, kl, kl_threshold, lr_min=1e-6, lr_max=1e-2):
+    """The decision k_lr_schedule takes on the device, restated in Python doubles (= AdaptiveScheduler.update,
+    frozen_ppo.py:864-877): strict inequalities, clamps applied to the moved rate only."""
+    new = lr
+    if kl > 2.0 * kl_threshold:
+        new = max(lr / 1.5, lr_min)
+    if kl < 0.5 * kl_threshold:
+        new = min(lr * 1.5, lr_max)
+    return new
+
+
 def make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon, mini_epochs, contact_points=0,
-             contact_emb=0, only_contact=False, **hp):
+             contact_emb=0, only_contact=False, lr_schedule="fixed", kl_threshold=0.008, lr_min=1e-6, lr_max=1e-2, **hp):
     """contact_points > 0: the teacher with ground-truth contacts (task.env.compute_contact_gt; num_points P,
-    contact_mlp.units[-1] = contact_emb, train.ppo.only_contact)."""
+    contact_mlp.units[-1] = contact_emb, train.ppo.only_contact).  lr_schedule "adaptive": the KL-adaptive learning
+    rate scheduled on the device (kl_threshold, lr_min, lr_max as rl_games' AdaptiveScheduler); "fixed" leaves the four
+    schedule fields zero, whatever the other three arguments say."""
     h = dict(DEFAULT_HP)
     h.update(hp)
+    sched = lr_schedule_id(lr_schedule)
+    if sched and not (float(kl_threshold) > 0 and 0 < float(lr_min) <= float(lr_max)):
+        raise ValueError("the adaptive schedule needs kl_threshold > 0 and 0 < lr_min <= lr_max")
     if contact_points:
         if not 1 <= contact_emb <= 32:
             raise ValueError(f"contact embedding width {contact_emb}: 1 .. 32 supported")
@@ -106,6 +133,8 @@ def make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon, m
     c.grad_norm = float(h["grad_norm"]) if h["truncate_grads"] else 0.0
     c.rms_eps = float(h["rms_eps"])
     c.contact_points, c.contact_emb, c.only_contact = int(contact_points), int(contact_emb), int(bool(only_contact))
+    if sched:
+        c.lr_schedule, c.kl_threshold, c.lr_min, c.lr_max = sched, float(kl_threshold), float(lr_min), float(lr_max)
     return c, h
 
 
@@ -125,14 +154,16 @@ def param_layout(cfg):
 class TeacherEngine:
     def __init__(self, num_envs, horizon, mini_epochs, units=(512, 256, 128), priv_units=(256, 128, 8),
                  obs_dim=15, priv_dim=64, act_dim=6, device="cuda:0", perm=None, contact_points=0, contact_emb=0,
-                 only_contact=False, **hp):
+                 only_contact=False, lr_schedule="fixed", kl_threshold=0.008, lr_min=1e-6, lr_max=1e-2, **hp):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("TeacherEngine needs a HIP device (there is no CPU path)")
         self.L = _lib.lib()
         self.cfg, self.hp = make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon,
                                      mini_epochs, contact_points=contact_points, contact_emb=contact_emb,
-                                     only_contact=only_contact, **hp)
+                                     only_contact=only_contact, lr_schedule=lr_schedule, kl_threshold=kl_threshold,
+                                     lr_min=lr_min, lr_max=lr_max, **hp)
+        self.adaptive_lr = bool(self.cfg.lr_schedule)
         self.contact_points, self.contact_emb, self.only_contact = int(contact_points), int(contact_emb), bool(only_contact)
         self.N, self.T, self.E = num_envs, horizon, mini_epochs
         self.B = num_envs * horizon
@@ -168,6 +199,11 @@ class TeacherEngine:
                                + self.L.igi_last_error().decode())
         self.workspace = torch.zeros(wbytes, dtype=torch.uint8, device=dev)
         self.workspace_trial_ms = None      # see tune_workspace
+        # adaptive schedule: [rate, exchange scratch, (kl, rate after) per mini-epoch] as doubles (igi_teacher_state.lr_state)
+        self.lr_state = None
+        if self.adaptive_lr:
+            self.lr_state = torch.zeros(_lib.lr_state_doubles(mini_epochs), dtype=torch.float64, device=dev)
+            self.lr_state[0] = self.cfg.lr
         if perm is None:
             perm = torch.randperm(self.B, device=dev)          # experience.py:202, drawn once
         self.perm = perm.to(device=dev, dtype=torch.int64).contiguous()
@@ -198,8 +234,29 @@ class TeacherEngine:
 
     # ---- native calls (torch.ops.mi355ppo.*: schema-checked, device-guarded; see ops.py) -------------------------
     def state_list(self):
-        """The sixteen tensors of struct igi_teacher_state, in field order."""
-        return [getattr(self, k) for k in ops.STATE_FIELDS]
+        """The sixteen tensors of struct igi_teacher_state, in field order (+ lr_state under the adaptive schedule)."""
+        st = [getattr(self, k) for k in ops.STATE_FIELDS]
+        return st + [self.lr_state] if self.adaptive_lr else st
+
+    # ---- learning rate -------------------------------------------------------------------------
+    @property
+    def lr(self):
+        """The rate the next optimizer step uses.  Adaptive schedule: read from the device (synchronises)."""
+        return float(self.lr_state[0].item()) if self.adaptive_lr else float(self.cfg.lr)
+
+    def set_lr(self, lr):
+        """Fixed: cfg.lr.  Adaptive: an asynchronous fill of the device double on the current stream (no host sync)."""
+        if self.adaptive_lr:
+            self.lr_state[0:1].fill_(float(lr))
+        else:
+            self.cfg.lr = float(lr)
+
+    def lr_history(self):
+        """Adaptive schedule: the last update's record as an (E, 2) float64 CPU tensor -- per mini-epoch the mean KL as
+        the scheduler compared it and the rate after its decision (synchronises)."""
+        if not self.adaptive_lr:
+            raise RuntimeError("lr_history: the engine runs the fixed schedule")
+        return self.lr_state[2:].cpu().reshape(self.E, 2)
 
     def _cfg_args(self):
         """The packed igi_teacher_cfg, rebuilt from the struct on every call: trainers mutate ``cfg.lr`` and
@@ -234,7 +291,7 @@ class TeacherEngine:
         trials = int(os.environ.get("IGI_WS_TRIALS", "6")) if trials is None else int(trials)
         if trials <= 1 or self._ro is None or self.device.type != "cuda":
             return None
-        keys = [k for k in ops.STATE_FIELDS if k not in ("perm", "workspace")]
+        keys = [k for k in ops.STATE_FIELDS if k not in ("perm", "workspace")] + (["lr_state"] if self.adaptive_lr else [])
         snap = {k: getattr(self, k).clone() for k in keys}
         t0, cfg0 = self.adam_t, (self.cfg.gamma, self.cfg.tau, self.cfg.lr)
         cands = [self.workspace]
@@ -328,9 +385,15 @@ class TeacherEngine:
         (igi_teacher_update_dp); the library calls back between the stages of a step."""
         early, late = self.bucket_views()
         pending = []
+        kl_view = self.lr_state.view(torch.float32)[2:3] if self.adaptive_lr else None   # the float of lr_state[1]
 
         def reducer(bucket, step):
-            if bucket == 2:
+            if bucket == 3:                   # adaptive schedule: the mini-epoch's KL, one float, in stream order
+                if all_reduce_async is not None:
+                    all_reduce_async(kl_view).wait()
+                else:
+                    all_reduce(kl_view)
+            elif bucket == 2:
                 for w in pending:
                     if w is not None:
                         w.wait()
