@@ -371,52 +371,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   return (r0 + r1) + (r2 + r3);
 }
 
-// Eight wave-wide sums at once: after the call lane l holds the sum over all 64 lanes of v[l & 7].
-// Each butterfly step halves the number of live registers by keeping, per lane, only the value its low lane
-// bits select (8 -> 4 -> 2 -> 1), so the whole thing is ~30 instructions instead of 8 x 11.
-__device__ __forceinline__ float wave_sum8(const float (&v)[8], int lane) {
-  float w[4], u[2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float a = v[2 * j] + dpp_mov<0xB1>(v[2 * j]);          // lanes l, l^1
-    const float b = v[2 * j + 1] + dpp_mov<0xB1>(v[2 * j + 1]);
-    w[j] = (lane & 1) ? b : a;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const float a = w[2 * i] + dpp_mov<0x4E>(w[2 * i]);          // lanes l, l^2
-    const float b = w[2 * i + 1] + dpp_mov<0x4E>(w[2 * i + 1]);
-    u[i] = (lane & 2) ? b : a;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {                                  // the four quads of a 16-lane row
-    u[i] += dpp_mov<0x128>(u[i]);                                // row_ror:8
-    u[i] += dpp_mov<0x124>(u[i]);                                // row_ror:4
-  }
-  float z = (lane & 4) ? u[1] : u[0];
-  z += __shfl_xor(z, 16, 64);                                    // the four rows
-  z += __shfl_xor(z, 32, 64);
-  return z;
-}
-// sum over the first 16-lane row (the callers' values live in lanes 0..7, the rest of the row is zero),
-// returned wave-uniform
-__device__ __forceinline__ float row0_sum(float v) {
-  v += dpp_mov<0xB1>(v);
-  v += dpp_mov<0x4E>(v);
-  v += dpp_mov<0x128>(v);   // row_ror:8 then row_ror:4: all four quads, whatever the rotate direction
-  v += dpp_mov<0x124>(v);
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-}
-
-// the same sum for every 16-lane row at once, left in all lanes of the row (same DPP order as row0_sum)
-__device__ __forceinline__ float rows_sum_ror(float v) {
-  v += dpp_mov<0xB1>(v);
-  v += dpp_mov<0x4E>(v);
-  v += dpp_mov<0x128>(v);
-  v += dpp_mov<0x124>(v);
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 // 1. GAE + returns (experience.py:242-255): one thread per env walks T backwards over
 //    [t][env]-coalesced loads.  Also accumulates the six fp64 sums that the advantage
@@ -839,811 +793,43 @@ __global__ __launch_bounds__(256) void k_copy_rows(const float* __restrict__ obs
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// 3. heads + PPO loss + head backward (models_split.py:222-250; frozen_ppo.py:543-570, 618).
-//    One wave per minibatch row: lane l holds columns l, l+64, ... of the last hidden layer of
-//    actor and critic, so mu/value are a wave reduction, the loss scalars are computed redundantly
-//    on every lane, and d(hidden) leaves as one coalesced row.  Head weight gradients accumulate in
-//    registers over the wave's rows and leave as one per-block partial (reduced later in fixed
-//    order -> bitwise reproducible).
-// ---------------------------------------------------------------------------------------------
-struct LossArgs {
-  const float* h;        // [2][mb][ldh] last hidden (actor, critic)
-  float* dh;             // [2][mb][ldh] d(pre-activation) of the last hidden layer
-  long long net_stride;  // mb*ldh
-  int ldh, H;
-  int ld_dh;             // layout of dh (may be the interleaved [row][net][u0p] form)
-  long long net_stride_dh;
-  const float* Wmu; const float* bmu; const float* Wv; const float* bv; const float* logstd;
-  const float* actions; const float* neglogpacs;                  // rollout (time-major)
-  const float* adv; const float* values_n; const float* returns_n;  // prepared
-  float* mus_w; float* sigmas_w;
-  const int64_t* perm;
-  long long start;
-  int mb, N, T, act, rows_per_wave;
-  float e_clip, critic_coef, entropy_coef, bounds_coef;
-  double* loss_part;  // [blocks][8]
-  float* head_slab;   // [blocks][head_count]
-  int head_count;
-};
+// kernels templated on MAXJ, the number of 64-column groups of the last hidden layer (H columns) that a lane holds
+#define IGI_LAUNCH_MAXJ(kernel, H, grid, block, shm, stream, ...)                        \
+  do {                                                                                   \
+    const int _maxj = ((H) + 63) / 64;                                                   \
+    if (_maxj <= 1) IGI_LAUNCH(kernel<1>, grid, block, shm, stream, __VA_ARGS__);        \
+    else if (_maxj == 2) IGI_LAUNCH(kernel<2>, grid, block, shm, stream, __VA_ARGS__);   \
+    else IGI_LAUNCH(kernel<4>, grid, block, shm, stream, __VA_ARGS__);                   \
+  } while (0)
 
-constexpr float LOG_SQRT_2PI_F = 0.918938533204672741780329736406f;
+// ---------------------------------------------------------------------------------------------
+// 3. heads + PPO loss + head backward (models_split.py:222-250; frozen_ppo.py:543-570, 618): ppo_loss.h
+// ---------------------------------------------------------------------------------------------
+}  // namespace igi
+#include "ppo_loss.h"
+namespace igi {
 
+// One wave per row: this lane's share of the head products of a row, the value's in pv and mu[q]'s in pm[q], q < act
+// (plain multiply and add; a wave_sum of each completes it).  Shared by the inference and the rollout-step kernel so
+// that both give the same bits.
 template <int MAXJ>
-__global__ __launch_bounds__(LOSS_THREADS) void k_loss(const LossArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int H = a.H, act = a.act;
-  float wmu[IGI_MAX_ACT][MAXJ], wv[MAXJ];
-  float gmu[IGI_MAX_ACT][MAXJ], gv[MAXJ];
+__device__ __forceinline__ void head_products_row(const float* __restrict__ ha_p, const float* __restrict__ hc_p, int H,
+                                                  const float* __restrict__ Wmu, const float* __restrict__ Wv, int act,
+                                                  int lane, float (&pm)[IGI_MAX_ACT], float& pv) {
+  pv = 0.f;
 #pragma unroll
-  for (int j = 0; j < MAXJ; ++j) {
-    const int k = lane + 64 * j;
-    wv[j] = (k < H) ? a.Wv[k] : 0.f;
-    gv[j] = 0.f;
-#pragma unroll
-    for (int q = 0; q < IGI_MAX_ACT; ++q) {
-      wmu[q][j] = (q < act && k < H) ? a.Wmu[q * H + k] : 0.f;
-      gmu[q][j] = 0.f;
-    }
-  }
-  // lane q (< act) owns action dimension q for the per-action arithmetic
-  const bool alane = lane < act;
-  const float my_logstd = alane ? a.logstd[lane] : 0.f;
-  const float my_sig = expf(my_logstd);
-  const float my_logsc = logf(my_sig);  // Normal.log_prob uses scale.log() (torch/distributions/normal.py)
-  const float my_var = my_sig * my_sig;
-  const float my_bmu = alane ? a.bmu[lane] : 0.f;
-  float gbmu = 0.f, gsig = 0.f;         // lane q accumulates d(bias_mu[q]), d(sigma[q])
-  const float bv = a.bv[0];
-  float gbv = 0.f;
-  double s_a = 0, s_c = 0, s_b = 0, s_e = 0, s_kl = 0;
-  const float inv_mb = 1.0f / (float)a.mb;
-  const float lo = 1.0f - a.e_clip, hi = 1.0f + a.e_clip;
-
-  // Rows are processed four at a time: lane r fetches the permutation entry of row r, then lane q
-  // fetches the q-th per-sample scalar of each row (actions, old mu, old sigma, advantage, return,
-  // old value, old neglogp) and the hidden rows are loaded, all before any arithmetic, so a group of
-  // four rows costs two dependent memory latencies instead of eight.  Scalars reach the (redundant,
-  // wave-uniform) loss arithmetic through v_readlane.
-  const int gw = blockIdx.x * (LOSS_THREADS / 64) + wave;
-  const int row_begin = gw * a.rows_per_wave;
-  auto rl = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
-  for (int base = 0; base < a.rows_per_wave; base += 4) {
-    const int row0 = row_begin + base;
-    int nrows = a.rows_per_wave - base;
-    if (nrows > 4) nrows = 4;
-    if (nrows > a.mb - row0) nrows = a.mb - row0;
-    if (nrows <= 0) break;  // wave-uniform
-    int my_i = 0;
-    if (lane < nrows) {
-      const long long b = a.perm[a.start + row0 + lane];
-      const int n = (int)(b / a.T);
-      my_i = (int)(b - (long long)n * a.T) * a.N + n;  // b = n*T + t  ->  t*N + n
-    }
-    int irow[4];
-    float d[4];
-    float ha[4][MAXJ], hc[4][MAXJ];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      irow[r] = __builtin_amdgcn_readlane(my_i, r);
-      const long long i = irow[r];
-      // branch-free address select: ONE predicated load per row (a chain of divergent
-      // `if (lane ...) load` arms would serialise seven dependent memory round trips)
-      const float* src = a.actions + i * act + lane;
-      src = (lane >= act) ? a.mus_w + i * act + (lane - act) : src;
-      src = (lane >= 2 * act) ? a.sigmas_w + i * act + (lane - 2 * act) : src;
-      src = (lane == 3 * act) ? a.adv + i : src;
-      src = (lane == 3 * act + 1) ? a.returns_n + i : src;
-      src = (lane == 3 * act + 2) ? a.values_n + i : src;
-      src = (lane == 3 * act + 3) ? a.neglogpacs + i : src;
-      d[r] = (r < nrows && lane < 3 * act + 4) ? *src : 0.f;
-      const float* ha_p = a.h + (long long)(row0 + r) * a.ldh;
-      const float* hc_p = ha_p + a.net_stride;
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        const int k = lane + 64 * j;
-        ha[r][j] = (r < nrows && k < H) ? ha_p[k] : 0.f;
-        hc[r][j] = (r < nrows && k < H) ? hc_p[k] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (r >= nrows) break;  // wave-uniform
-      const int row = row0 + r;
-      const long long i = irow[r];
-      float pm[IGI_MAX_ACT], pv = 0.f;
-#pragma unroll
-      for (int q = 0; q < IGI_MAX_ACT; ++q) pm[q] = 0.f;
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        pv = fmaf(hc[r][j], wv[j], pv);   // explicit fma: -ffp-contract=off would issue mul + add
-#pragma unroll
-        for (int q = 0; q < IGI_MAX_ACT; ++q) pm[q] = fmaf(ha[r][j], wmu[q][j], pm[q]);
-      }
-      // lane q < act ends up with its own mu[q], lane 7 with the value (IGI_MAX_ACT == 8; act <= 7 here)
-      float red8[8];
-#pragma unroll
-      for (int q = 0; q < 7; ++q) red8[q] = pm[q];
-      red8[7] = pv;
-      float my_pm;
-      if (act <= 7) {
-        const float z = wave_sum8(red8, lane);
-        my_pm = z;
-        pv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(z), 7));
-      } else {
-        pv = wave_sum(pv);
-        my_pm = 0.f;
-#pragma unroll
-        for (int q = 0; q < IGI_MAX_ACT; ++q) {
-          const float t = wave_sum(pm[q]);
-          my_pm = (lane == q) ? t : my_pm;
-        }
-      }
-
-      const float v = pv + bv;
-      const float adv = rl(d[r], 3 * act), R = rl(d[r], 3 * act + 1), vp = rl(d[r], 3 * act + 2),
-                  old_nlp = rl(d[r], 3 * act + 3);
-      // per-action terms on lane q: select this lane's mu from the (wave-uniform) reductions and pull
-      // the old mu / sigma of action q over from lanes act+q / 2*act+q
-      const float my_mu = my_pm + my_bmu;
-      const float ac = d[r];
-      const float omu = __shfl(d[r], lane + act, 64), osig = __shfl(d[r], lane + 2 * act, 64);
-      const float x = ac - my_mu;
-      const float bh = fminf(my_mu - 1.1f, 0.f), blo = fminf(-my_mu + 1.1f, 0.f);
-      const float dm = omu - my_mu;
-      float t_nlp = (x * x) / (2.0f * my_var) + my_logsc + LOG_SQRT_2PI_F;
-      float t_ent = 0.5f + LOG_SQRT_2PI_F + my_logsc;
-      float t_bl = blo * blo + bh * bh;
-      // policy_kl(new, old) frozen_ppo.py:854-860
-      float t_kl = (logf(osig / my_sig + 1e-5f) + (my_var + dm * dm) / (2.0f * (osig * osig + 1e-5f))) - 0.5f;
-      if (!alane) { t_nlp = 0.f; t_ent = 0.f; t_bl = 0.f; t_kl = 0.f; }
-      float nlp, ent, bl, kl;
-      if (act <= 8) { nlp = row0_sum(t_nlp); ent = row0_sum(t_ent); bl = row0_sum(t_bl); kl = row0_sum(t_kl); }
-      else { nlp = wave_sum(t_nlp); ent = wave_sum(t_ent); bl = wave_sum(t_bl); kl = wave_sum(t_kl); }
-      // actor loss (frozen_ppo.py:544-547)
-      const float ratio = expf(old_nlp - nlp);
-      const float rc = fminf(fmaxf(ratio, lo), hi);
-      const float s1 = -(adv * ratio), s2 = -(adv * rc);
-      const float a_loss = fmaxf(s1, s2);
-      const float d1 = adv * ratio;  // d s1 / d nlp
-      const float d2 = (ratio >= lo && ratio <= hi) ? d1 : 0.f;
-      const float da = (s1 > s2) ? d1 : ((s1 < s2) ? d2 : 0.5f * (d1 + d2));
-      const float g_nlp = da * inv_mb;
-      // critic loss (frozen_ppo.py:549-552)
-      const float dvp = v - vp;
-      const float vclip = vp + fminf(fmaxf(dvp, -a.e_clip), a.e_clip);
-      const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-      const float c_loss = fmaxf(l1, l2);
-      const float g1 = 2.0f * (v - R);
-      const float g2 = (dvp >= -a.e_clip && dvp <= a.e_clip) ? 2.0f * (vclip - R) : 0.f;
-      const float dc = (l1 > l2) ? g1 : ((l1 < l2) ? g2 : 0.5f * (g1 + g2));
-      const float dv = dc * (0.5f * a.critic_coef * inv_mb);
-
-      float my_dmu = g_nlp * (-(x / my_var)) + (a.bounds_coef * inv_mb) * (2.0f * bh - 2.0f * blo);
-      if (!alane) my_dmu = 0.f;
-      if (alane) {
-        gsig += g_nlp * (1.0f - (x * x) / my_var) - a.entropy_coef * inv_mb;
-        gbmu += my_dmu;
-      }
-      float dmu[IGI_MAX_ACT];
-#pragma unroll
-      for (int q = 0; q < IGI_MAX_ACT; ++q) dmu[q] = rl(my_dmu, q);   // back to wave-uniform for the row products
-      gbv += dv;
-      s_a += a_loss; s_c += c_loss; s_b += bl; s_e += ent; s_kl += kl;
-
-      // d(hidden pre-activation) rows + head weight gradients
-      float* dha_p = a.dh + (long long)row * a.ld_dh;
-      float* dhc_p = dha_p + a.net_stride_dh;
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        const int k = lane + 64 * j;
-        float da3 = 0.f;
-#pragma unroll
-        for (int q = 0; q < IGI_MAX_ACT; ++q) {
-          da3 = fmaf(dmu[q], wmu[q][j], da3);
-          gmu[q][j] = fmaf(dmu[q], ha[r][j], gmu[q][j]);
-        }
-        gv[j] = fmaf(dv, hc[r][j], gv[j]);
-        if (k < H) {
-          dha_p[k] = da3 * (1.0f - ha[r][j] * ha[r][j]);
-          dhc_p[k] = (dv * wv[j]) * (1.0f - hc[r][j] * hc[r][j]);
-        }
-      }
-      // update_mu_sigma (experience.py:228-233): scatter the new mu / sigma
-      if (alane) {
-        a.mus_w[i * act + lane] = my_mu;
-        a.sigmas_w[i * act + lane] = my_sig;
-      }
-    }
-  }
-
-  // ---- block partials: [muW (act*H) | muB (act) | valW (H) | valB (1) | sigma (act)]
-  extern __shared__ __attribute__((aligned(16))) float red[];  // [4][head_count]
-  float* mine = red + wave * a.head_count;
+  for (int q = 0; q < IGI_MAX_ACT; ++q) pm[q] = 0.f;
 #pragma unroll
   for (int j = 0; j < MAXJ; ++j) {
     const int k = lane + 64 * j;
     if (k < H) {
+      const float ha = ha_p[k], hc = hc_p[k];
+      pv += hc * Wv[k];
 #pragma unroll
       for (int q = 0; q < IGI_MAX_ACT; ++q)
-        if (q < act) mine[q * H + k] = gmu[q][j];
-      mine[act * H + act + k] = gv[j];
+        if (q < act) pm[q] += ha * Wmu[q * H + k];
     }
   }
-  if (alane) {
-    mine[act * H + lane] = gbmu;
-    mine[act * H + act + H + 1 + lane] = gsig;
-  }
-  if (lane == 0) mine[act * H + act + H] = gbv;
-  __shared__ double sred[LOSS_THREADS / 64][5];
-  if (lane == 0) {
-    sred[wave][0] = s_a; sred[wave][1] = s_c; sred[wave][2] = s_b; sred[wave][3] = s_e; sred[wave][4] = s_kl;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < a.head_count; e += blockDim.x) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < LOSS_THREADS / 64; ++w) s += red[w * a.head_count + e];
-    a.head_slab[(long long)blockIdx.x * a.head_count + e] = s;
-  }
-  if (threadIdx.x < 5) {
-    double s = 0;
-    for (int w = 0; w < LOSS_THREADS / 64; ++w) s += sred[w][threadIdx.x];
-    a.loss_part[blockIdx.x * 8 + threadIdx.x] = s;
-  }
-}
-
-// k_loss with the per-sample scalar arithmetic done ONCE for a group of four rows: 16-lane row rr of the wave holds
-// row rr's actions / old mu / old sigma / advantage ..., its head sums land there straight out of wave_sum8, and the
-// row-local DPP sums give every row its neglogp / entropy / bounds / KL at once (the divisions, logs and exp of that
-// section were ~55 % of the per-row instruction count).  act <= 7.
-template <int MAXJ>
-__global__ __launch_bounds__(LOSS_THREADS) void k_loss_packed(const LossArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rr = lane >> 4, qi = lane & 15;   // scalar section: 16-lane row rr works on row rr of a group of four
-  const int H = a.H, act = a.act;
-  float wmu[IGI_MAX_ACT][MAXJ], wv[MAXJ];
-  float gmu[IGI_MAX_ACT][MAXJ], gv[MAXJ];
-#pragma unroll
-  for (int j = 0; j < MAXJ; ++j) {
-    const int k = lane + 64 * j;
-    wv[j] = (k < H) ? a.Wv[k] : 0.f;
-    gv[j] = 0.f;
-#pragma unroll
-    for (int q = 0; q < IGI_MAX_ACT; ++q) {
-      wmu[q][j] = (q < act && k < H) ? a.Wmu[q * H + k] : 0.f;
-      gmu[q][j] = 0.f;
-    }
-  }
-  // lane qi (< act) of each 16-lane row owns action dimension qi for the per-action arithmetic
-  const bool alane = qi < act;
-  const float my_logstd = alane ? a.logstd[qi] : 0.f;
-  const float my_sig = expf(my_logstd);
-  const float my_logsc = logf(my_sig);  // Normal.log_prob uses scale.log() (torch/distributions/normal.py)
-  const float my_var = my_sig * my_sig;
-  const float my_bmu = alane ? a.bmu[qi] : 0.f;
-  float gbmu = 0.f, gsig = 0.f;         // lane q accumulates d(bias_mu[q]), d(sigma[q])
-  const float bv = a.bv[0];
-  float gbv = 0.f;
-  double s_a = 0, s_c = 0, s_b = 0, s_e = 0, s_kl = 0;
-  const float inv_mb = 1.0f / (float)a.mb;
-  const float lo = 1.0f - a.e_clip, hi = 1.0f + a.e_clip;
-
-  // Rows are processed four at a time: lane r fetches the permutation entry of row r, then lane q
-  // fetches the q-th per-sample scalar of each row (actions, old mu, old sigma, advantage, return,
-  // old value, old neglogp) and the hidden rows are loaded, all before any arithmetic, so a group of
-  // four rows costs two dependent memory latencies instead of eight.  Scalars reach the (redundant,
-  // wave-uniform) loss arithmetic through v_readlane.
-  const int gw = blockIdx.x * (LOSS_THREADS / 64) + wave;
-  const int row_begin = gw * a.rows_per_wave;
-  auto rl = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
-  // One group of four rows: everything it reads.  The group AFTER the one being worked on is requested first (two
-  // register sets, the loop below is unrolled by two), so its two dependent round trips (permutation entry -> per-sample
-  // scalars; the hidden rows do not depend on it) run under the arithmetic of the current group; only the first group
-  // of a wave waits for memory.  (The mu / sigma rows written below belong to other samples than any row read later:
-  // the permutation visits each sample once per pass.)
-  struct LossRows {
-    long long ip;
-    bool okrow, aok;
-    int nrows, row0;
-    float ac, omu, osig, adv, R, vp, old_nlp;
-    float ha[4][MAXJ], hc[4][MAXJ];
-  };
-  auto load_group = [&](int base, LossRows& g) {
-    const int row0 = row_begin + base;
-    int nrows = a.rows_per_wave - base;
-    if (nrows > 4) nrows = 4;
-    if (nrows > a.mb - row0) nrows = a.mb - row0;
-    g.nrows = nrows; g.row0 = row0;
-    if (nrows <= 0) return;  // wave-uniform
-    int my_i = 0;
-    if (lane < nrows) {
-      const long long b = a.perm[a.start + row0 + lane];
-      const int n = (int)(b / a.T);
-      my_i = (int)(b - (long long)n * a.T) * a.N + n;  // b = n*T + t  ->  t*N + n
-    }
-    // the hidden rows first: their addresses do not wait for the permutation entry
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float* ha_p = a.h + (long long)(row0 + r) * a.ldh;
-      const float* hc_p = ha_p + a.net_stride;
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        const int k = lane + 64 * j;
-        g.ha[r][j] = (r < nrows && k < H) ? ha_p[k] : 0.f;
-        g.hc[r][j] = (r < nrows && k < H) ? hc_p[k] : 0.f;
-      }
-    }
-    // per-sample scalars in the packed layout: row rr of the group lives in 16-lane row rr
-    g.okrow = rr < nrows;
-    const long long ip = __shfl(my_i, rr, 64);
-    g.ip = ip;
-    g.aok = g.okrow && alane;
-    g.ac = g.aok ? a.actions[ip * act + qi] : 0.f;
-    g.omu = g.aok ? a.mus_w[ip * act + qi] : 0.f;
-    g.osig = g.aok ? a.sigmas_w[ip * act + qi] : 0.f;
-    g.adv = g.okrow ? a.adv[ip] : 0.f;
-    g.R = g.okrow ? a.returns_n[ip] : 0.f;
-    g.vp = g.okrow ? a.values_n[ip] : 0.f;
-    g.old_nlp = g.okrow ? a.neglogpacs[ip] : 0.f;
-  };
-  auto compute_group = [&](const LossRows& g) {
-    const int row0 = g.row0, nrows = g.nrows;
-    const bool okrow = g.okrow, aok = g.aok;
-    const long long ip = g.ip;
-    const float ac = g.ac, omu = g.omu, osig = g.osig, adv = g.adv, R = g.R, vp = g.vp, old_nlp = g.old_nlp;
-    const float (&ha)[4][MAXJ] = g.ha;
-    const float (&hc)[4][MAXJ] = g.hc;
-    // head dot products: after wave_sum8 EVERY lane l holds the total of value l & 7 (mu_0..mu_6, value), so row r's
-    // totals are already in place for 16-lane row r -- keep them there
-    float p_z = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float pm[IGI_MAX_ACT], pv = 0.f;
-#pragma unroll
-      for (int q = 0; q < IGI_MAX_ACT; ++q) pm[q] = 0.f;
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        pv = fmaf(hc[r][j], wv[j], pv);   // explicit fma: -ffp-contract=off would issue mul + add
-#pragma unroll
-        for (int q = 0; q < IGI_MAX_ACT; ++q) pm[q] = fmaf(ha[r][j], wmu[q][j], pm[q]);
-      }
-      float red8[8];
-#pragma unroll
-      for (int q = 0; q < 7; ++q) red8[q] = pm[q];
-      red8[7] = pv;
-      const float z = wave_sum8(red8, lane);
-      p_z = (rr == r) ? z : p_z;
-    }
-    // ---- scalar section, once for the four rows (lanes qi >= 8 of a row mirror lanes qi - 8: harmless)
-    float my_dmu, dv;
-    {
-      const float pv = __shfl(p_z, (lane & 48) | 7, 64);
-      const float v = pv + bv;
-      const float my_mu = p_z + my_bmu;
-      const float x = ac - my_mu;
-      const float bh = fminf(my_mu - 1.1f, 0.f), blo = fminf(-my_mu + 1.1f, 0.f);
-      const float dm = omu - my_mu;
-      float t_nlp = (x * x) / (2.0f * my_var) + my_logsc + LOG_SQRT_2PI_F;
-      float t_ent = 0.5f + LOG_SQRT_2PI_F + my_logsc;
-      float t_bl = blo * blo + bh * bh;
-      // policy_kl(new, old) frozen_ppo.py:854-860
-      float t_kl = (logf(osig / my_sig + 1e-5f) + (my_var + dm * dm) / (2.0f * (osig * osig + 1e-5f))) - 0.5f;
-      if (!aok) { t_nlp = 0.f; t_ent = 0.f; t_bl = 0.f; t_kl = 0.f; }
-      const float nlp = rows_sum_ror(t_nlp), ent = rows_sum_ror(t_ent), bl = rows_sum_ror(t_bl), kl = rows_sum_ror(t_kl);
-      // actor loss (frozen_ppo.py:544-547)
-      const float ratio = expf(old_nlp - nlp);
-      const float rc = fminf(fmaxf(ratio, lo), hi);
-      const float s1 = -(adv * ratio), s2 = -(adv * rc);
-      const float a_loss = fmaxf(s1, s2);
-      const float d1 = adv * ratio;  // d s1 / d nlp
-      const float d2 = (ratio >= lo && ratio <= hi) ? d1 : 0.f;
-      const float da = (s1 > s2) ? d1 : ((s1 < s2) ? d2 : 0.5f * (d1 + d2));
-      const float g_nlp = da * inv_mb;
-      // critic loss (frozen_ppo.py:549-552)
-      const float dvp = v - vp;
-      const float vclip = vp + fminf(fmaxf(dvp, -a.e_clip), a.e_clip);
-      const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-      const float c_loss = fmaxf(l1, l2);
-      const float g1 = 2.0f * (v - R);
-      const float g2 = (dvp >= -a.e_clip && dvp <= a.e_clip) ? 2.0f * (vclip - R) : 0.f;
-      const float dc = (l1 > l2) ? g1 : ((l1 < l2) ? g2 : 0.5f * (g1 + g2));
-      dv = okrow ? dc * (0.5f * a.critic_coef * inv_mb) : 0.f;
-      my_dmu = g_nlp * (-(x / my_var)) + (a.bounds_coef * inv_mb) * (2.0f * bh - 2.0f * blo);
-      if (!aok) my_dmu = 0.f;
-      if (aok) {
-        gsig += g_nlp * (1.0f - (x * x) / my_var) - a.entropy_coef * inv_mb;
-        gbmu += my_dmu;
-        // update_mu_sigma (experience.py:228-233): scatter the new mu / sigma
-        a.mus_w[ip * act + qi] = my_mu;
-        a.sigmas_w[ip * act + qi] = my_sig;
-      }
-      if (okrow && qi == 0) { s_a += a_loss; s_c += c_loss; s_b += bl; s_e += ent; s_kl += kl; gbv += dv; }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (r >= nrows) break;  // wave-uniform
-      const int row = row0 + r;
-      float dmu[IGI_MAX_ACT];
-#pragma unroll
-      for (int q = 0; q < IGI_MAX_ACT; ++q) dmu[q] = rl(my_dmu, 16 * r + q);   // wave-uniform for the row products
-      const float dvr = rl(dv, 16 * r);
-      // d(hidden pre-activation) rows + head weight gradients
-      float* dha_p = a.dh + (long long)row * a.ld_dh;
-      float* dhc_p = dha_p + a.net_stride_dh;
-#pragma unroll
-      for (int j = 0; j < MAXJ; ++j) {
-        const int k = lane + 64 * j;
-        float da3 = 0.f;
-#pragma unroll
-        for (int q = 0; q < IGI_MAX_ACT; ++q) {
-          da3 = fmaf(dmu[q], wmu[q][j], da3);
-          gmu[q][j] = fmaf(dmu[q], ha[r][j], gmu[q][j]);
-        }
-        gv[j] = fmaf(dvr, hc[r][j], gv[j]);
-        if (k < H) {
-          dha_p[k] = da3 * (1.0f - ha[r][j] * ha[r][j]);
-          dhc_p[k] = (dvr * wv[j]) * (1.0f - hc[r][j] * hc[r][j]);
-        }
-      }
-    }
-  };
-  {
-    LossRows gA, gB;
-    load_group(0, gA);
-    for (int base = 0; base < a.rows_per_wave; base += 8) {
-      if (gA.nrows <= 0) break;
-      load_group(base + 4, gB);
-      compute_group(gA);
-      if (gB.nrows <= 0) break;
-      load_group(base + 8, gA);
-      compute_group(gB);
-    }
-  }
-  // fold the four 16-lane rows' accumulators (lanes l, l ^ 16, l ^ 32, l ^ 48)
-  gbmu += __shfl_xor(gbmu, 16, 64); gbmu += __shfl_xor(gbmu, 32, 64);
-  gsig += __shfl_xor(gsig, 16, 64); gsig += __shfl_xor(gsig, 32, 64);
-  gbv += __shfl_xor(gbv, 16, 64); gbv += __shfl_xor(gbv, 32, 64);
-  s_a += __shfl_xor(s_a, 16, 64); s_a += __shfl_xor(s_a, 32, 64);
-  s_c += __shfl_xor(s_c, 16, 64); s_c += __shfl_xor(s_c, 32, 64);
-  s_b += __shfl_xor(s_b, 16, 64); s_b += __shfl_xor(s_b, 32, 64);
-  s_e += __shfl_xor(s_e, 16, 64); s_e += __shfl_xor(s_e, 32, 64);
-  s_kl += __shfl_xor(s_kl, 16, 64); s_kl += __shfl_xor(s_kl, 32, 64);
-
-  // ---- block partials: [muW (act*H) | muB (act) | valW (H) | valB (1) | sigma (act)]
-  extern __shared__ __attribute__((aligned(16))) float red[];  // [4][head_count]
-  float* mine = red + wave * a.head_count;
-#pragma unroll
-  for (int j = 0; j < MAXJ; ++j) {
-    const int k = lane + 64 * j;
-    if (k < H) {
-#pragma unroll
-      for (int q = 0; q < IGI_MAX_ACT; ++q)
-        if (q < act) mine[q * H + k] = gmu[q][j];
-      mine[act * H + act + k] = gv[j];
-    }
-  }
-  if (lane < act) {
-    mine[act * H + lane] = gbmu;
-    mine[act * H + act + H + 1 + lane] = gsig;
-  }
-  if (lane == 0) mine[act * H + act + H] = gbv;
-  __shared__ double sred[LOSS_THREADS / 64][5];
-  if (lane == 0) {
-    sred[wave][0] = s_a; sred[wave][1] = s_c; sred[wave][2] = s_b; sred[wave][3] = s_e; sred[wave][4] = s_kl;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < a.head_count; e += blockDim.x) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < LOSS_THREADS / 64; ++w) s += red[w * a.head_count + e];
-    a.head_slab[(long long)blockIdx.x * a.head_count + e] = s;
-  }
-  if (threadIdx.x < 5) {
-    double s = 0;
-    for (int w = 0; w < LOSS_THREADS / 64; ++w) s += sred[w][threadIdx.x];
-    a.loss_part[blockIdx.x * 8 + threadIdx.x] = s;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// 3b. The same loss stage fused behind the LAST trunk layer's forward (models_split.py:222-250 right behind the last
-//     Linear + Tanh of :27-38; frozen_ppo.py:543-570, 618).  k_loss re-reads the 2 x mb x 128 hidden rows that layer has
-//     just written (16.8 MB out, 16.8 MB in again, 16 MB of d(hidden) out) and spends one WAVE per row; here the
-//     64 x 128 output tile of one net (rows m0..m0+63, actor or critic; 2 x mb / 64 workgroups, two or three per CU,
-//     an actor tile paired with a critic tile) never leaves the CU:
-//       A  accumulators -> LDS (the waves' 32 x 32 slices), bias + tanh in place; the head weights -> registers
-//       B  head products on the matrix pipe (v_mfma_f32_16x16x4_f32): 16 rows x (<= 7 mu | value) per wave pair
-//       C  the results leave the pipe as (row, action) per lane: Normal log-prob / entropy / KL / bounds with the sums over
-//          the actions as 16-lane DPP sums (k_loss_packed's layout), clipped surrogate or clipped value loss with the
-//          per-row scalars requested under the last k-tile, d(loss)/d(mu) | d(loss)/d(value) -> LDS, update_mu_sigma
-//          write-back, bias / sigma gradient and fp64 loss sums per wave
-//       D  d(pre-activation) of the layer = (d(head) . W_head) * (1 - h^2): the only large thing written to HBM (16-byte
-//          row segments); head weight gradients of the tile on the matrix pipe (A = d(head)^T, B = the tanh'd tile in LDS),
-//          stored straight into the tile's partial record
-//       E  the waves' bias / sigma / loss partials in wave order -> the same record (mb / 64 records per minibatch)
-//     The hidden layer itself is not stored (nothing reads it: the data gradient below needs tanh' of the layer BELOW).
-//     Same formulas, expression by expression, as k_loss; the head sums run in the MFMA's k order.  H == 128, act <= 7;
-//     other shapes (and bf16-input mode) keep the two launches.  Same box, A/B: 21.6 + 15.4 -> 30.6 us per step.
-// ---------------------------------------------------------------------------------------------
-struct TrunkLossHook {
-  const LossArgs& a;
-  // Per-sample scalars, requested in two steps (permutation entries up front, the rows' values under the last k-tile).  Thread (wave w, q = lane & 15, fq = lane >> 4)
-  // owns action q of rows m0 + 16 (w & 3) + 4 fq + 2 (w >> 2) + r, r < 2 -- the layout in which the head products leave
-  // the matrix pipe (waves w and w + 4 both compute the 16 x 16 block of rows 16 (w & 3) .. +15 and halve its rows).
-  unsigned pb[2];                                   // permutation entries (step 0), then arena rows t*N + n
-  float ac[2], omu[2], osig[2], s0[2], s1[2];       // (s0, s1) = (advantage, old neglogp) | (return, old value)
-
-  static constexpr int TILE_M = 64;                 // rows per tile: 2 x mb / 64 workgroups, two (or three) per CU
-  static constexpr int EPLD = 36, SLICE = 32 * EPLD;
-  static constexpr int O_DM = 8 * SLICE, O_RED = O_DM + TILE_M * 8, O_LSUM = O_RED + 8 * 16, LDS_FLOATS = O_LSUM + 8 * 8;
-
-  __device__ __forceinline__ explicit TrunkLossHook(const LossArgs& a_) : a(a_) {}
-
-  // step 0, in front of the first tile's DMA requests: the permutation entries
-  __device__ __forceinline__ void prefetch(const GemmArgs& g, int m0, int batch, int tid) {
-    const int w = tid >> 6;
-    const int row0 = m0 + 16 * (w & 3) + 4 * ((tid & 63) >> 4) + 2 * (w >> 2);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) pb[r] = (unsigned)a.perm[a.start + min(row0 + r, g.M - 1)];   // < 2^31 (launcher)
-  }
-  // which k-tile carries step 1: the LAST one.  Requests return in order, so gathers issued in front of a tile's DMA
-  // hold that tile's vmcnt wait until they have landed (issued with the first tile: +3 us per launch, with the last: +1.5;
-  // measured with early exits from the kernel) -- behind the last DMA they fly under the last MFMAs and phases A / B.
-  __device__ __forceinline__ int prefetch1_at(int nk) const { return nk - 1; }
-  // step 1, behind the barrier of the k-tile prefetch1_at() names (the entries landed long ago)
-  __device__ __forceinline__ void prefetch1(const GemmArgs& g, int batch, int tid) {
-    const int q = tid & 15, act = a.act;
-    // the net is wave-uniform: its two per-row arrays are picked on the scalar unit (written as an if / else over the four
-    // loads the compiler built a table of the four pointers in SCRATCH and indexed it: a memory round trip in front of
-    // the gathers)
-    const bool actor = batch == 0;
-    const float* p0 = uniform_ptr(actor ? a.adv : a.returns_n);
-    const float* p1 = uniform_ptr(actor ? a.neglogpacs : a.values_n);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const unsigned n = pb[r] / (unsigned)a.T;
-      pb[r] = (pb[r] - n * (unsigned)a.T) * (unsigned)a.N + n;   // b = n*T + t  ->  t*N + n
-      const long long i = pb[r];
-      ac[r] = 0.f; omu[r] = 0.f; osig[r] = 1.f;
-      if (actor && q < act) {
-        ac[r] = a.actions[i * act + q];
-        omu[r] = a.mus_w[i * act + q];
-        osig[r] = a.sigmas_w[i * act + q];
-      }
-      s0[r] = p0[i];
-      s1[r] = p1[i];
-    }
-  }
-
-  __device__ __forceinline__ void epilogue(f32x16 (&acc)[1][1], float* smem, const GemmArgs& g, int m0, int mt, int batch,
-                                           int tid, int wave, int lane, int wm, int wn) {
-    typedef float f32x4r __attribute__((ext_vector_type(4)));
-    const bool actor = batch == 0;
-    const int act = a.act;
-    const int nq = actor ? act : 1;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int fm = lane & 15, fq = lane >> 4;   // MFMA 16x16x4 operand / result coordinates
-    const int c4 = lane & 7, rl = lane >> 3;    // row-major passes over a 64 x 32 slice: 16-byte column group, row
-    float* dm = smem + O_DM;                    // [64 rows][8]: d(loss)/d(head output)
-    float* red = smem + O_RED;                  // [8 waves][16]: bias / sigma gradient partials
-    double* lsum = reinterpret_cast<double*>(smem + O_LSUM);   // [8 waves][4]
-    const float* W = actor ? a.Wmu : a.Wv;      // [nq][128]
-
-    // ---- A: accumulators -> this wave's slice, bias + tanh in place; meanwhile the head weights arrive in registers
-    __syncthreads();   // every wave is done reading the ring
-    float* ep = smem + wave * SLICE;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ep[((r & 3) + 8 * (r >> 2) + 4 * h) * EPLD + l31] = acc[0][0][r];
-    // B operand of the head product: lane (n = fm = head output, fq) feeds W[n][16 kh + 4 fq + t] to step (kh, t)
-    float4 wv[8];
-#pragma unroll
-    for (int kh = 0; kh < 8; ++kh)
-      wv[kh] = (fm < nq) ? *reinterpret_cast<const float4*>(W + fm * 128 + 16 * kh + 4 * fq) : make_float4(0.f, 0.f, 0.f, 0.f);
-    // per-action constants of this lane's action
-    const bool alane = actor && fm < act;
-    const float my_logstd = alane ? a.logstd[fm] : 0.f;
-    const float my_bmu = alane ? a.bmu[fm] : 0.f;
-    const float bvv = a.bv[0];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    {
-      const float4 b = *reinterpret_cast<const float4*>(g.bias + batch * g.sBias + wn * 32 + 4 * c4);
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        float4* p = reinterpret_cast<float4*>(ep + (it * 8 + rl) * EPLD + 4 * c4);
-        float4 v = *p;
-        v.x = fast_tanh(v.x + b.x); v.y = fast_tanh(v.y + b.y); v.z = fast_tanh(v.z + b.z); v.w = fast_tanh(v.w + b.w);
-        *p = v;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-
-    // ---- B: head products of rows 16 (w & 3) .. +15 on the matrix pipe (v_mfma_f32_16x16x4_f32, k = 128):
-    //         A[m = fm][4 fq + t] = h[row 16 (w & 3) + fm][16 kh + 4 fq + t] (one 16-byte LDS read per four instructions)
-    f32x4r hacc = f32x4r{0.f, 0.f, 0.f, 0.f};
-    {
-      const int row = 16 * (wave & 3) + fm;
-      const float* hrow = smem + (row >> 5) * 4 * SLICE + (row & 31) * EPLD + 4 * fq;
-#pragma unroll
-      for (int kh = 0; kh < 8; ++kh) {
-        const float4 x = *reinterpret_cast<const float4*>(hrow + (kh >> 1) * SLICE + 16 * (kh & 1));
-        hacc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.x, wv[kh].x, hacc, 0, 0, 0);
-        hacc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.y, wv[kh].y, hacc, 0, 0, 0);
-        hacc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.z, wv[kh].z, hacc, 0, 0, 0);
-        hacc = __builtin_amdgcn_mfma_f32_16x16x4f32(x.w, wv[kh].w, hacc, 0, 0, 0);
-      }
-    }
-    // ---- C: hacc[2 (w >> 2) + r] = head output fm of row 16 (w & 3) + 4 fq + 2 (w >> 2) + r: this lane's action of its
-    //         two rows.  The sums over the actions of a row are sums over the 16-lane row (DPP), as in k_loss_packed.
-    float gb = 0.f, gs = 0.f;            // d(bias_mu[fm]) | d(bias_v), d(sigma[fm]) over this lane's rows
-    double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-    {
-      const float inv_mb = 1.0f / (float)a.mb;
-      const float my_sig = expf(my_logstd);
-      const float my_logsc = logf(my_sig);  // Normal.log_prob uses scale.log() (torch/distributions/normal.py)
-      const float my_var = my_sig * my_sig;
-      const float lo = 1.0f - a.e_clip, hi = 1.0f + a.e_clip;
-      const int hi2 = wave >> 2;
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const int rowt = 16 * (wave & 3) + 4 * fq + 2 * hi2 + r;           // row of the tile
-        const bool okrow = m0 + rowt < g.M;
-        const float hout = hi2 ? hacc[2 + r] : hacc[r];
-        float my_d = 0.f;
-        if (actor) {
-          const bool aok = okrow && alane;
-          const float my_mu = hout + my_bmu;
-          const float x = ac[r] - my_mu;
-          const float bh = fminf(my_mu - 1.1f, 0.f), blo = fminf(-my_mu + 1.1f, 0.f);
-          const float dmo = omu[r] - my_mu;
-          float t_nlp = (x * x) / (2.0f * my_var) + my_logsc + LOG_SQRT_2PI_F;
-          float t_ent = 0.5f + LOG_SQRT_2PI_F + my_logsc;
-          float t_bl = blo * blo + bh * bh;
-          // policy_kl(new, old) frozen_ppo.py:854-860
-          float t_kl = (logf(osig[r] / my_sig + 1e-5f) + (my_var + dmo * dmo) / (2.0f * (osig[r] * osig[r] + 1e-5f))) - 0.5f;
-          if (!aok) { t_nlp = 0.f; t_ent = 0.f; t_bl = 0.f; t_kl = 0.f; }
-          const float nlp = rows_sum_ror(t_nlp), ent = rows_sum_ror(t_ent), bl = rows_sum_ror(t_bl), kl = rows_sum_ror(t_kl);
-          // actor loss (frozen_ppo.py:544-547)
-          const float adv = s0[r], old_nlp = s1[r];
-          const float ratio = expf(old_nlp - nlp);
-          const float rc = fminf(fmaxf(ratio, lo), hi);
-          const float sa1 = -(adv * ratio), sa2 = -(adv * rc);
-          const float a_loss = fmaxf(sa1, sa2);
-          const float d1 = adv * ratio;  // d s1 / d nlp
-          const float d2 = (ratio >= lo && ratio <= hi) ? d1 : 0.f;
-          const float da = (sa1 > sa2) ? d1 : ((sa1 < sa2) ? d2 : 0.5f * (d1 + d2));
-          const float g_nlp = da * inv_mb;
-          if (aok) {
-            my_d = g_nlp * (-(x / my_var)) + (a.bounds_coef * inv_mb) * (2.0f * bh - 2.0f * blo);
-            gs += g_nlp * (1.0f - (x * x) / my_var) - a.entropy_coef * inv_mb;
-            gb += my_d;
-            // update_mu_sigma (experience.py:228-233): scatter the new mu / sigma
-            a.mus_w[(long long)pb[r] * act + fm] = my_mu;
-            a.sigmas_w[(long long)pb[r] * act + fm] = my_sig;
-          }
-          if (okrow && fm == 0) { t0 += a_loss; t1 += bl; t2 += ent; t3 += kl; }
-        } else {
-          // critic loss (frozen_ppo.py:549-552)
-          const float v = hout + bvv;
-          const float R = s0[r], vp = s1[r];
-          const float dvp = v - vp;
-          const float vclip = vp + fminf(fmaxf(dvp, -a.e_clip), a.e_clip);
-          const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-          const float c_loss = fmaxf(l1, l2);
-          const float g1 = 2.0f * (v - R);
-          const float g2 = (dvp >= -a.e_clip && dvp <= a.e_clip) ? 2.0f * (vclip - R) : 0.f;
-          const float dc = (l1 > l2) ? g1 : ((l1 < l2) ? g2 : 0.5f * (g1 + g2));
-          if (okrow && fm == 0) {
-            my_d = dc * (0.5f * a.critic_coef * inv_mb);
-            gb += my_d;
-            t0 += c_loss;
-          }
-        }
-        if (fm < 8) dm[rowt * 8 + fm] = my_d;
-      }
-      // this wave's 8 rows: lanes fm, fm + 16, fm + 32, fm + 48
-      gb += __shfl_xor(gb, 16, 64); gb += __shfl_xor(gb, 32, 64);
-      gs += __shfl_xor(gs, 16, 64); gs += __shfl_xor(gs, 32, 64);
-      t0 += __shfl_xor(t0, 16, 64); t0 += __shfl_xor(t0, 32, 64);
-      if (actor) {
-        t1 += __shfl_xor(t1, 16, 64); t1 += __shfl_xor(t1, 32, 64);
-        t2 += __shfl_xor(t2, 16, 64); t2 += __shfl_xor(t2, 32, 64);
-        t3 += __shfl_xor(t3, 16, 64); t3 += __shfl_xor(t3, 32, 64);
-      }
-      if (lane < 8) { red[wave * 16 + lane] = gb; red[wave * 16 + 8 + lane] = gs; }
-      if (lane == 0) { lsum[wave * 4 + 0] = t0; lsum[wave * 4 + 1] = t1; lsum[wave * 4 + 2] = t2; lsum[wave * 4 + 3] = t3; }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();   // LDS-only rendezvous: the mu / sigma stores stay in flight
-    asm volatile("" ::: "memory");
-
-    // ---- D1: d(pre-activation) of this wave's 32 x 32 slice = (d(head) . W_head) * (1 - h^2), 16-byte row segments
-    {
-      float4 w[7];
-#pragma unroll
-      for (int q = 0; q < 7; ++q)
-        w[q] = (q < nq) ? *reinterpret_cast<const float4*>(W + q * 128 + wn * 32 + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      float* dst = a.dh + batch * a.net_stride_dh + (long long)(m0 + wm * 32) * a.ld_dh + wn * 32 + 4 * c4;
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const int r = it * 8 + rl;
-        const float4 hv = *reinterpret_cast<const float4*>(ep + r * EPLD + 4 * c4);
-        const float4 d0 = *reinterpret_cast<const float4*>(dm + (wm * 32 + r) * 8);
-        const float4 d1 = *reinterpret_cast<const float4*>(dm + (wm * 32 + r) * 8 + 4);
-        const float d[7] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z};
-        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int q = 0; q < 7; ++q)
-          if (q < nq) {
-            z.x = fmaf(d[q], w[q].x, z.x); z.y = fmaf(d[q], w[q].y, z.y);
-            z.z = fmaf(d[q], w[q].z, z.z); z.w = fmaf(d[q], w[q].w, z.w);
-          }
-        z.x = z.x * (1.0f - hv.x * hv.x); z.y = z.y * (1.0f - hv.y * hv.y);
-        z.z = z.z * (1.0f - hv.z * hv.z); z.w = z.w * (1.0f - hv.w * hv.w);
-        if (m0 + wm * 32 + r < g.M) *reinterpret_cast<float4*>(dst + (long long)r * a.ld_dh) = z;
-      }
-    }
-    // ---- D2: head weight gradients of columns 16 w .. 16 w + 15 over the tile's 64 rows, on the matrix pipe:
-    //          out[q][col] = sum_row dm[row][q] * h[row][col];  A[m = q][4 fq + t] = dm[16 st + 4 fq + t][q],
-    //          B[4 fq + t][n = col] = h[16 st + 4 fq + t][16 w + n]
-    {
-      f32x4r gacc = f32x4r{0.f, 0.f, 0.f, 0.f};
-      const int col = 16 * wave + fm;
-      const float* hcol = smem + (col >> 5) * SLICE + (col & 31);
-#pragma unroll
-      for (int st = 0; st < 4; ++st) {
-        float av[4], bvv4[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int row = 16 * st + 4 * fq + t;
-          av[t] = (fm < 8) ? dm[row * 8 + fm] : 0.f;
-          bvv4[t] = hcol[(row >> 5) * 4 * SLICE + (row & 31) * EPLD];
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) gacc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t], bvv4[t], gacc, 0, 0, 0);
-      }
-      // gacc[r] = out[q = 4 fq + r][col]; record mt: [muW (act*H) | muB (act) | valW (H) | valB (1) | sigma (act)]
-      float* rec = a.head_slab + (long long)mt * a.head_count;
-      if (actor) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (4 * fq + r < act) rec[(4 * fq + r) * 128 + col] = gacc[r];
-      } else if (fq == 0) {
-        rec[act * 128 + act + col] = gacc[0];
-      }
-    }
-    // ---- E: the waves' bias / sigma / loss partials in wave order
-    if (tid < 16) {
-      float sb = 0.f;
-#pragma unroll
-      for (int w8 = 0; w8 < 8; ++w8) sb += red[w8 * 16 + tid];
-      float* rec = a.head_slab + (long long)mt * a.head_count;
-      if (actor) {
-        if (tid < act) rec[act * 128 + tid] = sb;                                          // muB
-        else if (tid >= 8 && tid - 8 < act) rec[act * 128 + act + 128 + 1 + (tid - 8)] = sb;   // sigma
-      } else if (tid == 0) {
-        rec[act * 128 + act + 128] = sb;                                                    // valB
-      }
-    } else if (tid >= 64 && tid < 68) {
-      const int j = tid - 64;
-      double sl = 0;
-#pragma unroll
-      for (int w8 = 0; w8 < 8; ++w8) sl += lsum[w8 * 4 + j];
-      double* lp = a.loss_part + (long long)mt * 8;
-      if (actor) lp[j == 0 ? 0 : j + 1] = sl;     // a_loss, bounds, entropy, kl -> slots 0, 2, 3, 4
-      else if (j == 0) lp[1] = sl;                // c_loss -> slot 1
-    }
-  }
-};
-
-__global__ __launch_bounds__(DMA_THREADS, 4) void k_trunk_loss(const GemmArgs g, const LossArgs a, int m_tiles) {
-  TrunkLossHook hook(a);
-  // no XCD remap: workgroup b and b + m_tiles (the same rows of the other net) land on the same XCD, and the round-robin
-  // placement pairs an actor tile with a critic tile on a CU (the actor's scalar section is the longer one)
-  gemm_dma_body<128, true, true, 0, 2, TrunkLossHook::TILE_M, false, false, false, false, TrunkLossHook>(
-      g, 1, m_tiles, (int)blockIdx.x, &hook);
 }
 
 // inference heads: mu (rows,act), value (rows,1)
@@ -1660,21 +846,8 @@ __global__ __launch_bounds__(256) void k_heads_infer(const float* __restrict__ h
   const int nw = (gridDim.x * blockDim.x) >> 6;
   for (int row = gw; row < rows; row += nw) {
     const float* ha_p = h + (long long)row * ldh;
-    const float* hc_p = ha_p + net_stride;
-    float pm[IGI_MAX_ACT], pv = 0.f;
-#pragma unroll
-    for (int q = 0; q < IGI_MAX_ACT; ++q) pm[q] = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-      const int k = lane + 64 * j;
-      if (k < H) {
-        const float ha = ha_p[k], hc = hc_p[k];
-        pv += hc * Wv[k];
-#pragma unroll
-        for (int q = 0; q < IGI_MAX_ACT; ++q)
-          if (q < act) pm[q] += ha * Wmu[q * H + k];
-      }
-    }
+    float pm[IGI_MAX_ACT], pv;
+    head_products_row<MAXJ>(ha_p, ha_p + net_stride, H, Wmu, Wv, act, lane, pm, pv);
     pv = wave_sum(pv);
 #pragma unroll
     for (int q = 0; q < IGI_MAX_ACT; ++q)
@@ -2593,65 +1766,9 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   // ---- heads + loss + head backward.  d(pre-activation) of the FIRST trunk layer is kept
   // interleaved [row][net][u0p] so that the dgrad into xcat is one contraction over both nets.
   const int H = p.u[p.nl - 1];
-  const int ldh = ru4(H);
   auto dz_ld = [&](int l) { return l == 0 ? 2 * p.u0p : ru4(p.u[l]); };
   auto dz_stride = [&](int l) { return l == 0 ? (long long)p.u0p : mbs * ru4(p.u[l]); };
-  if (do0) {
-    LossArgs a;
-    a.h = wsp<float>(st, p.w_h[p.nl - 1]);
-    a.dh = wsp<float>(st, p.w_dh[p.nl - 1]);
-    a.net_stride = mbs * ldh; a.ldh = ldh; a.H = H;
-    a.ld_dh = dz_ld(p.nl - 1); a.net_stride_dh = dz_stride(p.nl - 1);
-    a.Wmu = P + p.o_muW; a.bmu = P + p.o_muB; a.Wv = P + p.o_valW; a.bv = P + p.o_valB;
-    a.logstd = P + p.o_sigma;
-    a.actions = ro->actions; a.neglogpacs = ro->neglogpacs;
-    a.adv = st->advantages; a.values_n = st->values_n; a.returns_n = st->returns_n;
-    a.mus_w = st->mus_w; a.sigmas_w = st->sigmas_w;
-    a.perm = st->perm; a.start = (long long)mb_index * mb;
-    a.mb = mb; a.N = p.N; a.T = p.T; a.act = p.act; a.rows_per_wave = p.loss_rpw;
-    a.e_clip = c->e_clip; a.critic_coef = c->critic_coef; a.entropy_coef = c->entropy_coef;
-    a.bounds_coef = c->bounds_loss_coef;
-    a.loss_part = wsp<double>(st, p.w_loss_part);
-    a.head_slab = wsp<float>(st, p.w_head_slab);
-    a.head_count = p.head_count;
-    if (p.loss_fused) {
-      // last trunk layer (both nets) with the heads, the loss and the head backward in its tiles' epilogue
-      const int l = p.nl - 1, in = ac_in(p, l);
-      GemmArgs g;
-      g.A = wsp<float>(st, p.w_h[l - 1]); g.lda = ru4(in); g.sA = mbs * ru4(in);
-      g.B = P + p.o_acW[l]; g.ldb = in; g.sB = p.ac_block; g.K = in;
-      g.bias = P + p.o_acB[l]; g.sBias = p.ac_block;
-      g.M = mb; g.N = H; g.nbatch = 2;
-      g.epilogue = EPI_BIAS_TANH;
-      if (!dma_eligible(g, true, true) || !aligned16(g.bias) || (g.sBias & 3) || !aligned16(a.dh) || (a.ld_dh & 3) ||
-          (a.net_stride_dh & 3))
-        return IGI_E_UNSUPPORTED;
-      const int m_tiles = (mb + TrunkLossHook::TILE_M - 1) / TrunkLossHook::TILE_M;
-      dma_set_divs(g, 1, m_tiles);
-      constexpr size_t ring = sizeof(float) * 2 * (TrunkLossHook::TILE_M + 128) * DMA_BK;
-      constexpr size_t shm = sizeof(float) * TrunkLossHook::LDS_FLOATS > ring ? sizeof(float) * TrunkLossHook::LDS_FLOATS : ring;
-      static bool attr = false;
-      if (!attr) {
-        IGI_HIP_TRY(hipFuncSetAttribute((const void*)k_trunk_loss, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        attr = true;
-      }
-      ProfScope ps(PC_TRUNK_LOSS, s, 2.0 * 2 * (double)mbs * H * in + 2.0 * 3 * (double)mbs * H * (p.act + 1),
-                   4.0 * (2.0 * mbs * in + 2.0 * H * in + 2.0 * mbs * H + (double)mbs * (4 * p.act + 6)));
-      IGI_LAUNCH(k_trunk_loss, dim3(2 * m_tiles), dim3(DMA_THREADS), shm, s, g, a, m_tiles);
-    } else {
-    ProfScope ps(PC_LOSS, s, 2.0 * 3 * (double)mbs * H * (p.act + 1),
-                 4.0 * (double)mbs * (4.0 * ldh + 4 * p.act + 6));
-    const size_t shm = sizeof(float) * 4 * p.head_count;
-    const int maxj = (H + 63) / 64;
-    if (p.act <= 7) {   // scalar section once per four rows
-      if (maxj <= 1) IGI_LAUNCH(k_loss_packed<1>, dim3(p.loss_blocks), dim3(LOSS_THREADS), shm, s, a);
-      else if (maxj == 2) IGI_LAUNCH(k_loss_packed<2>, dim3(p.loss_blocks), dim3(LOSS_THREADS), shm, s, a);
-      else IGI_LAUNCH(k_loss_packed<4>, dim3(p.loss_blocks), dim3(LOSS_THREADS), shm, s, a);
-    } else if (maxj <= 1) IGI_LAUNCH(k_loss<1>, dim3(p.loss_blocks), dim3(LOSS_THREADS), shm, s, a);
-    else if (maxj == 2) IGI_LAUNCH(k_loss<2>, dim3(p.loss_blocks), dim3(LOSS_THREADS), shm, s, a);
-    else IGI_LAUNCH(k_loss<4>, dim3(p.loss_blocks), dim3(LOSS_THREADS), shm, s, a);
-    }
-  }
+  if (do0 && (rc = loss_stage(p, c, ro, st, mb_index, dz_ld(p.nl - 1), dz_stride(p.nl - 1), s))) return rc;
 
   // ---- backward through the actor / critic trunk.  Level fusion: the weight gradient of layer l and the data
   //      gradient INTO layer l-1 both consume dZ_l and are independent of each other, so they share one grid
@@ -3084,16 +2201,8 @@ static int teacher_infer(const igi_teacher_cfg* c, const igi_teacher_state* st, 
       const long long ns = (long long)p.mb * ldh;
       float* mo = mu ? mu + r0 * p.act : nullptr;
       float* vo = value ? value + r0 : nullptr;
-      const int maxj = (H + 63) / 64;
-      if (maxj <= 1)
-        IGI_LAUNCH(k_heads_infer<1>, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW,
-                           P + p.o_muB, P + p.o_valW, P + p.o_valB, nr, p.act, mo, vo);
-      else if (maxj == 2)
-        IGI_LAUNCH(k_heads_infer<2>, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW,
-                           P + p.o_muB, P + p.o_valW, P + p.o_valB, nr, p.act, mo, vo);
-      else
-        IGI_LAUNCH(k_heads_infer<4>, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW,
-                           P + p.o_muB, P + p.o_valW, P + p.o_valB, nr, p.act, mo, vo);
+      IGI_LAUNCH_MAXJ(k_heads_infer, H, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW, P + p.o_muB, P + p.o_valW,
+                      P + p.o_valB, nr, p.act, mo, vo);
     }
   }
   return (int)hipGetLastError();
@@ -3168,7 +2277,7 @@ struct ActStoreArgs {
   float* values_out;
 };
 
-// one wave per row: the heads exactly as k_heads_infer computes them, then lane q owns action q
+// one wave per row: the heads as k_heads_infer computes them (head_products_row), then lane q owns action q
 template <int MAXJ>
 __global__ __launch_bounds__(256) void k_heads_act_store(const float* __restrict__ h, long long net_stride, int ldh,
                                                          int H, const float* __restrict__ Wmu,
@@ -3184,21 +2293,8 @@ __global__ __launch_bounds__(256) void k_heads_act_store(const float* __restrict
   const float my_bmu = lane < act ? bmu[lane] : 0.f;
   for (int row = gw; row < rows; row += nw) {
     const float* ha_p = h + (long long)row * ldh;
-    const float* hc_p = ha_p + net_stride;
-    float pm[IGI_MAX_ACT], pv = 0.f;
-#pragma unroll
-    for (int q = 0; q < IGI_MAX_ACT; ++q) pm[q] = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-      const int k = lane + 64 * j;
-      if (k < H) {
-        const float ha = ha_p[k], hc = hc_p[k];
-        pv += hc * Wv[k];
-#pragma unroll
-        for (int q = 0; q < IGI_MAX_ACT; ++q)
-          if (q < act) pm[q] += ha * Wmu[q * H + k];
-      }
-    }
+    float pm[IGI_MAX_ACT], pv;
+    head_products_row<MAXJ>(ha_p, ha_p + net_stride, H, Wmu, Wv, act, lane, pm, pv);
     pv = wave_sum(pv);
     float my_pm = 0.f;
 #pragma unroll
@@ -3305,17 +2401,9 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
     if (hb > 1024) hb = 1024;
     const float* h = wsp<float>(st, p.w_h[p.nl - 1]);
     const long long ns = (long long)p.mb * ldh;
-    const int maxj = (H + 63) / 64;
     ProfScope ps(PC_OTHER, s, 0.0, 8.0 * nr * H);
-    if (maxj <= 1)
-      IGI_LAUNCH(k_heads_act_store<1>, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW, P + p.o_muB,
-                 P + p.o_valW, P + p.o_valB, nr, p.act, t);
-    else if (maxj == 2)
-      IGI_LAUNCH(k_heads_act_store<2>, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW, P + p.o_muB,
-                 P + p.o_valW, P + p.o_valB, nr, p.act, t);
-    else
-      IGI_LAUNCH(k_heads_act_store<4>, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW, P + p.o_muB,
-                 P + p.o_valW, P + p.o_valB, nr, p.act, t);
+    IGI_LAUNCH_MAXJ(k_heads_act_store, H, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW, P + p.o_muB, P + p.o_valW,
+                    P + p.o_valB, nr, p.act, t);
   }
   return (int)hipGetLastError();
 }

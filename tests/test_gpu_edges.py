@@ -45,13 +45,17 @@ def test_ragged_configs_match_oracle(N, T, E, units, priv_units):
     np.testing.assert_allclose(eng.packed().cpu().numpy(), orc.flat_params().numpy(), atol=slot * 2.5e-4 * 0.05)
 
 
-@pytest.mark.parametrize("obs_dim,priv_dim,act_dim", [(11, 20, 3), (15, 64, 8), (9, 33, 7)])
-def test_other_observation_and_action_widths(obs_dim, priv_dim, act_dim):
+@pytest.mark.parametrize("obs_dim,priv_dim,act_dim,units", [
+    (11, 20, 3, [48, 40, 24]), (15, 64, 8, [48, 40, 24]), (9, 33, 7, [48, 40, 24]),
+    (15, 64, 8, [48, 40, 100]), (15, 64, 8, [48, 40, 200]), (15, 64, 6, [48, 40, 200]),
+], ids=["11-20-3", "15-64-8", "9-33-7", "15-64-8-h100", "15-64-8-h200", "15-64-6-h200"])
+def test_other_observation_and_action_widths(obs_dim, priv_dim, act_dim, units):
     """Input / action widths other than the task's 15 / 64 / 6: act <= 7 runs the packed loss kernel (the scalar
-    section once per four rows), act = 8 the one-row-at-a-time kernel with its separate wave sums."""
+    section once per four rows), act = 8 the one-row-at-a-time kernel with its separate wave sums.  A last hidden layer
+    of 100 / 200 columns puts two / four columns on a lane (k_loss<2>, k_loss<4>, k_loss_packed<4>)."""
     from isaacgyminsertion_amd.teacher_native import TeacherEngine
     from oracle import synth, teacher as ot
-    N, T, E, units, pu = 96, 4, 3, [48, 40, 24], [24, 16, 8]
+    N, T, E, pu = 96, 4, 3, [24, 16, 8]
     init, ro, perm = synth.teacher_problem(N, T, units, pu, obs_dim=obs_dim, priv_dim=priv_dim, act_dim=act_dim,
                                            seed=5, done_p=0.1)
     eng = TeacherEngine(N, T, E, units=units, priv_units=pu, perm=perm, obs_dim=obs_dim, priv_dim=priv_dim,
