@@ -64,6 +64,10 @@ __device__ __forceinline__ ActionTerms action_terms(float ac, float mu, float om
   return t;
 }
 
+// the bounds term as the statistics report it (frozen_ppo.py:554-560): without a positive coefficient b_loss is 0, not the
+// sum the coefficient would have multiplied
+__device__ __forceinline__ float bounds_stat(float bl, float bounds_coef) { return bounds_coef > 0.f ? bl : 0.f; }
+
 // actor loss (frozen_ppo.py:544-547): the clipped surrogate and d(loss)/d(neglogp), with the mean of the two branches'
 // sub-gradients where they tie (torch.max's backward)
 struct ActorLoss { float loss, dnlp; };
@@ -352,7 +356,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss(const LossArgs a) {
 #pragma unroll
       for (int q = 0; q < IGI_MAX_ACT; ++q) dmu[q] = read_lane(my_dmu, q);   // back to wave-uniform for the row products
       gbv += dv;
-      s_a += al.loss; s_c += cl.loss; s_b += bl; s_e += ent; s_kl += kl;
+      s_a += al.loss; s_c += cl.loss; s_b += bounds_stat(bl, a.bounds_coef); s_e += ent; s_kl += kl;
 
       ht.backward_row(a, lane, row0 + r, ha[r], hc[r], dmu, dv);
       // update_mu_sigma (experience.py:228-233): scatter the new mu / sigma
@@ -462,7 +466,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_packed(const LossArgs a) 
         a.mus_w[g.ip * act + qi] = my_mu;
         a.sigmas_w[g.ip * act + qi] = my.sig;
       }
-      if (okrow && qi == 0) { s_a += al.loss; s_c += cl.loss; s_b += bl; s_e += ent; s_kl += kl; gbv += dv; }
+      if (okrow && qi == 0) { s_a += al.loss; s_c += cl.loss; s_b += bounds_stat(bl, a.bounds_coef); s_e += ent; s_kl += kl; gbv += dv; }
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -656,7 +660,7 @@ struct TrunkLossHook {
             a.mus_w[(long long)pb[r] * act + fm] = my_mu;
             a.sigmas_w[(long long)pb[r] * act + fm] = my.sig;
           }
-          if (okrow && fm == 0) { t0 += al.loss; t1 += bl; t2 += ent; t3 += kl; }
+          if (okrow && fm == 0) { t0 += al.loss; t1 += bounds_stat(bl, a.bounds_coef); t2 += ent; t3 += kl; }
         } else {
           const CriticLoss cl = critic_loss(hout + bvv, s0[r], s1[r], a.e_clip);
           if (okrow && fm == 0) {
