@@ -258,6 +258,47 @@ int igi_teacher_grad_buckets(const igi_teacher_cfg* cfg, int64_t* offsets, int64
  * igi_teacher_fwd_bwd / igi_teacher_apply loop and to the data-parallel updates on one rank. */
 int igi_teacher_update(const igi_teacher_cfg* cfg, const igi_rollout* ro,
                        const igi_teacher_state* st, int64_t adam_t0, igi_stream_t stream);
+/* ---- KL early stopping (frozen_ppo.py:578-581 and :642-643 made live, with the estimator of :568-569; an opt-in
+ * beyond the reference's live code -- rl_games / SB3 `target_kl`).  It rides beside the two structs above, which keep
+ * their layout (ABI 6): the three entry points below take the same arguments as their namesakes plus this record, and
+ * with ks == NULL or ks->kl_early_stop == 0 they ARE their namesakes.
+ *   approx_kl_s = mean_b((exp(d_b) - 1) - d_b), d_b = neglogp_new_b - neglogp_old_b, per sample in fp32, summed in
+ *   double (column 5 of the loss record), / mb.  Optimizer step s stops the update iff
+ *   (double)(float)approx_kl_s > 1.5 * kl_threshold (strict, in double).  The statistics block of the norm kernel
+ *   takes the decision ahead of the Adam launch of the same step; from then on both halves of the fused Adam + gather
+ *   launch, the stand-alone gather, the update_mu_sigma write-back, the statistics rows and the learning-rate
+ *   scheduler of every later mini-epoch are inert: parameters, Adam moments, first-layer copies and normaliser state are
+ *   those after step s - 1 (the normalisers have ingested minibatch s, frozen_ppo.py:521-522).  Row s of st->stats holds
+ *   slots 0 .. 4 (entropy and KL are appended before the reference's break), rows behind it are unspecified.  With
+ *   cfg.lr_schedule != 0 the scheduler of the stopping mini-epoch runs on the mean KL of its steps 0 .. s % n_mb (:630 sits
+ *   between the two breaks).  One deviation: the loss kernel of step s has written its minibatch's mus_w / sigmas_w rows
+ *   before the decision falls.
+ * stop_state: IGI_STOP_STATE_WORDS(mini_epochs * n_minibatch) 32-bit words, device memory.
+ *   [0] int32: the stop step of the last update, -1 = it ran through (step 0 of every update resets it);
+ *   [1] float: scratch of the data-parallel updates -- this rank's estimator of the step, summed over the ranks in
+ *       place;  [2 + s] float: approx_kl of step s (data parallel: the rank mean, as compared).
+ * igi_teacher_update_ks stops ENQUEUEING one mini-epoch behind the decision: after it has enqueued mini-epoch e + 1 it
+ * waits for an event recorded behind mini-epoch e and reads word 0 through a copy stream of its own that waits for
+ * that event only -- one host wait per mini-epoch, none when the switch is off.  Not capturable into a graph.
+ * Data parallel (igi_teacher_update_dp_ks, igi_teacher_update_dp_rccl_ks; declared behind their namesakes): all ranks
+ * take the decision from the rank-mean estimator.  Per optimizer step, between the norm kernel and the Adam tail, the
+ * rank's fp32 mean goes into the scratch float, that ONE float is all-reduced (SUM) -- callback path: reduce(user, 4,
+ * step), in the order of `stream`; RCCL path: on `stream`, behind the join of the step's gradient collectives -- and a
+ * one-lane kernel divides by the world size in fp32 and compares: the same bits, the same stop step and the same
+ * look-ahead boundary on every rank.  With cfg.lr_schedule != 0, ks->kl_threshold must equal cfg->kl_threshold. */
+typedef struct igi_kl_stop {
+  int32_t kl_early_stop;  /* 0 = off */
+  double kl_threshold;    /* > 0 */
+  int32_t* stop_state;
+} igi_kl_stop;
+#define IGI_STOP_STATE_WORDS(steps) (2 + (steps))
+int igi_teacher_fwd_bwd_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
+                           const igi_kl_stop* ks, int mb_index, int step_slot, igi_stream_t stream);
+int igi_teacher_apply_ks(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const igi_kl_stop* ks, int step_slot,
+                         int64_t adam_t, float grad_scale, igi_stream_t stream);
+int igi_teacher_update_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
+                          const igi_kl_stop* ks, int64_t adam_t0, igi_stream_t stream);
+
 /* Latent-gradient fusion of the teacher backward (default ON; IGI_LATZ_FUSE=0 in the environment starts it off;
  * profiles/r06_latz_ab.log): the backward of env_mlp's last (8-wide) layer -- d(latent) from the first trunk layer's row dots,
  * its rank-8 weight / bias gradient and dZ of the 128-wide layer below (autograd of models_split.py:185-232 as called from
@@ -282,6 +323,9 @@ int igi_teacher_set_latz_fuse(int on);
 typedef int (*igi_reduce_fn)(void* user, int bucket, int step);
 int igi_teacher_update_dp(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
                           int64_t adam_t0, float grad_scale, igi_reduce_fn reduce, void* user, igi_stream_t stream);
+int igi_teacher_update_dp_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
+                             const igi_kl_stop* ks, int64_t adam_t0, float grad_scale, igi_reduce_fn reduce, void* user,
+                             igi_stream_t stream);
 
 /* ---- RCCL communicator owned by the library (replaces dist.init_process_group("nccl") + the per-step
  * torch.cat / dist.all_reduce / copy-back of frozen_ppo.py:116-126, 586-603 and ext_adapt.py:833-851).
@@ -330,6 +374,9 @@ int igi_comm_broadcast(igi_comm_t comm, void* buf, int64_t bytes, int root, igi_
  * the same rate. */
 int igi_teacher_update_dp_rccl(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
                                int64_t adam_t0, igi_comm_t comm, int overlap, float* stats_sum, igi_stream_t stream);
+int igi_teacher_update_dp_rccl_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
+                                  const igi_kl_stop* ks, int64_t adam_t0, igi_comm_t comm, int overlap, float* stats_sum,
+                                  igi_stream_t stream);
 
 /* Inference forward used by model_act / act_inference (models_split.py:120-164; frozen_ppo.py:343-366).
  * normalize != 0: obs/priv are raw and are normalised with the CURRENT running stats (eval mode,

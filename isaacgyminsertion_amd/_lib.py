@@ -50,6 +50,16 @@ class TeacherState(C.Structure):
                  "workspace")] + [("workspace_bytes", C.c_size_t), ("lr_state", C.c_void_p)]
 
 
+class KlStop(C.Structure):
+    """struct igi_kl_stop: KL early stopping, beside (not inside) the teacher cfg / state structs."""
+    _fields_ = [("kl_early_stop", C.c_int32), ("kl_threshold", C.c_double), ("stop_state", C.c_void_p)]
+
+
+def stop_state_words(steps):
+    """IGI_STOP_STATE_WORDS: [stop step (int32, -1 = none), reserved, approx_kl (float bits) per optimizer step]."""
+    return 2 + int(steps)
+
+
 def lr_state_doubles(mini_epochs):
     """IGI_LR_STATE_DOUBLES: [rate, exchange scratch, (kl, rate after) per mini-epoch]."""
     return 2 + 2 * int(mini_epochs)
@@ -121,6 +131,17 @@ _EXPORTS = {
                                      C.POINTER(TeacherState), C.c_int64, C.c_void_p]),
     "igi_teacher_update_dp": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(Rollout), C.POINTER(TeacherState),
                                         C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "igi_teacher_fwd_bwd_ks": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(Rollout), C.POINTER(TeacherState),
+                                         C.POINTER(KlStop), C.c_int, C.c_int, C.c_void_p]),
+    "igi_teacher_apply_ks": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(TeacherState), C.POINTER(KlStop), C.c_int,
+                                       C.c_int64, C.c_float, C.c_void_p]),
+    "igi_teacher_update_ks": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(Rollout), C.POINTER(TeacherState),
+                                        C.POINTER(KlStop), C.c_int64, C.c_void_p]),
+    "igi_teacher_update_dp_ks": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(Rollout), C.POINTER(TeacherState),
+                                           C.POINTER(KlStop), C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "igi_teacher_update_dp_rccl_ks": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(Rollout), C.POINTER(TeacherState),
+                                                C.POINTER(KlStop), C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p]),
     "igi_comm_unique_id": (C.c_int, [C.c_void_p]),
     "igi_comm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "igi_comm_destroy": (C.c_int, [C.c_void_p]),

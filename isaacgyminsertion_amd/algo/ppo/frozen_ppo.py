@@ -21,7 +21,7 @@ import torch.distributed as dist
 from ..models.models_split import ActorCriticSplit as ActorCritic
 from ..models.running_mean_std import RunningMeanStd
 from .experience import ExperienceBuffer
-from ...teacher_native import TeacherEngine, lr_schedule_id
+from ...teacher_native import TeacherEngine, lr_schedule_id, parse_kl_early_stop, slice_update_lists
 from ...utils.misc import AverageScalarMeter, multi_gpu_aggregate_stats
 
 
@@ -102,6 +102,7 @@ class PPO(object):
         self.network_config = full_config.train.network
         self.ppo_config = full_config.train.ppo
         self.parse_lr_schedule(self.ppo_config)      # a schedule this trainer does not have: fail before anything is built
+        self.parse_kl_early_stop(self.ppo_config)    # likewise a switch value that is no boolean, or one it cannot honour
         self.env = env
         self.num_actors = self.ppo_config['num_actors']
         self.actions_num = self.task_config.env.numActions
@@ -168,6 +169,9 @@ class PPO(object):
         # train.ppo.lr_schedule: absent / "fixed" = the reference's live code (the scheduler is never stepped);
         # "adaptive" = its commented-out call (:630) made live, stepped on the device inside the fused update
         self.lr_schedule = self.parse_lr_schedule(self.ppo_config)
+        # train.ppo.kl_early_stop: absent / False = the reference's live code (every update runs E x n_mb steps); True = its
+        # commented-out breaks (:578-581, :642-643) made live on the estimator of :568-569, decided on the device
+        self.kl_early_stop = self.parse_kl_early_stop(self.ppo_config)
         self.save_freq = self.ppo_config['save_frequency']
         self.save_best_after = self.ppo_config['save_best_after']
         self.it = 0
@@ -192,7 +196,7 @@ class PPO(object):
             entropy_coef=self.entropy_coef, bounds_loss_coef=self.bounds_loss_coef, grad_norm=self.grad_norm,
             truncate_grads=self.truncate_grads, normalize_value=self.normalize_value,
             lr_schedule=self.lr_schedule, kl_threshold=self.kl_threshold, lr_min=self.scheduler.min_lr,
-            lr_max=self.scheduler.max_lr, **self.model.contact_kwargs())
+            lr_max=self.scheduler.max_lr, kl_early_stop=self.kl_early_stop, **self.model.contact_kwargs())
         self.model.bind_flat_to(self.engine)
         self.model.attach_engine(self.engine)
         self.running_mean_std.bind(self.engine.rms_obs)
@@ -224,13 +228,23 @@ class PPO(object):
         lr_schedule_id(name)
         return name
 
+    @staticmethod
+    def parse_kl_early_stop(ppo_config):
+        """train.ppo.kl_early_stop -> bool (False when the key is absent); ValueError for a value that is not a boolean
+        and for a non-positive kl_threshold under the switch."""
+        on = parse_kl_early_stop(ppo_config.get('kl_early_stop', None))
+        if on and not float(ppo_config['kl_threshold']) > 0:
+            raise ValueError("kl_early_stop needs kl_threshold > 0")
+        return on
+
     # ------------------------------------------------------------------------------------------
     def write_stats(self, a_losses, c_losses, b_losses, entropies, kls, grad_norms, returns_list):
         """frozen_ppo.py:279-318"""
         w = self.writer
         w.add_scalar('performance/RLTrainFPS', self.agent_steps / max(self.rl_train_time, 1e-9), self.agent_steps)
         w.add_scalar('performance/EnvStepFPS', self.agent_steps / max(self.data_collect_time, 1e-9), self.agent_steps)
-        mean = lambda xs: (torch.mean(torch.stack(xs)) if isinstance(xs, list) else torch.mean(xs)).item()
+        mean = lambda xs: (torch.mean(torch.stack(xs)) if isinstance(xs, list) else torch.mean(xs)).item() \
+            if len(xs) else float('nan')      # kl_early_stop at the update's first step: no loss was appended
         w.add_scalar('losses/actor_loss', mean(a_losses), self.agent_steps)
         w.add_scalar('losses/bounds_loss', mean(b_losses), self.agent_steps)
         w.add_scalar('losses/critic_loss', mean(c_losses), self.agent_steps)
@@ -405,6 +419,22 @@ class PPO(object):
                 dist.all_reduce(av_kls, op=dist.ReduceOp.SUM)
                 av_kls = av_kls / self.rank_size
         kls = list(av_kls.unbind())
+        if eng.kl_early_stop:
+            # ONE read of the stop record (engine._stop_record), next to the statistics read train_epoch synchronises
+            # for: the lists as the reference's breaks would leave them, the optimizer's step count (engine.adam_t
+            # resolves itself from the same copy) and what the update cost.  Every rank holds the same stop step.
+            stop = eng.stop_step
+            if stop is not None:
+                a_losses, c_losses, b_losses, entropies, kls, grad_norms = slice_update_lists(s, E, n_mb, stop)
+                if stats_sum is not None:       # :624-627: the rank mean, from the summed rows
+                    kls = [k / self.rank_size for k in slice_update_lists(stats_sum, E, n_mb, stop)[4]]
+                elif self.multi_gpu:
+                    t = torch.stack(kls)
+                    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+                    kls = list((t / self.rank_size).unbind())
+            akl = eng.approx_kl()
+            self.extra_info['info/approx_kl'] = float(akl[-1]) if len(akl) else float('nan')
+            self.extra_info['info/opt_steps'] = float(eng.steps_applied)
         if eng.adaptive_lr:                     # :630-640 with the scheduler live: one read per update, next to the
             self.last_lr = eng.lr               # stats read train_epoch synchronises for
         for pg in self.optimizer.param_groups:  # fixed: lr is constant, scheduler.update is commented out (:630)

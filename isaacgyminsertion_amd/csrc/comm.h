@@ -152,14 +152,30 @@ static int comm_reduce_ranges(igi_comm* c, float* grads, const long long* off, c
 // file).  stats_sum (optional, E * n_mb * IGI_STATS_PER_STEP floats): the per-step statistics summed over the ranks
 // (the KL all-reduce of frozen_ppo.py:624-627 and the loss aggregation of :387-396 ride here, once per update, on the
 // communication stream behind the last step's collectives); the per-rank values stay in st->stats.
+struct StopRcclCtx { igi_comm* cm; float* scratch; hipStream_t s; };
+// KL early stopping: the estimator's float on the COMPUTE stream, behind the join of the step's gradient collectives (the
+// rule the rate's float follows): the communicator never has collectives in flight on two streams
+static int stop_exchange_rccl(void* ctx, int) {
+  StopRcclCtx* x = static_cast<StopRcclCtx*>(ctx);
+  return comm_all_reduce_sum(x->cm, x->scratch, 1, x->s);
+}
 static int teacher_update_dp_rccl(const igi_teacher_cfg* c, const igi_rollout* ro, const igi_teacher_state* st,
-                                  int64_t adam_t0, igi_comm* cm, int overlap, float* stats_sum, hipStream_t s) {
+                                  int64_t adam_t0, igi_comm* cm, int overlap, float* stats_sum, hipStream_t s,
+                                  const igi_kl_stop* ks = nullptr) {
   if (!cm || !cm->comm) return IGI_E_BADARG;
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
   if ((rc = check_state(p, st))) return rc;
   if (!st->grads) return IGI_E_BADARG;
+  const bool stopping = kl_stop_on(ks);
+  const int32_t* stop = stopping ? ks->stop_state : nullptr;
+  StopLookahead look;
+  if (stopping) {
+    if ((rc = check_ks(ks, st, c)) || (rc = look.begin(ks))) return rc;
+  }
+  StopRcclCtx sctx{cm, stopping ? reinterpret_cast<float*>(ks->stop_state) + 1 : nullptr, s};
+  const StopExchange xch{stop_exchange_rccl, &sctx, cm->world};
   const float scale = 1.0f / (float)cm->world;
   const GradBuckets gb = grad_buckets(p);
   const int total = p.E * p.nmb;
@@ -169,12 +185,12 @@ static int teacher_update_dp_rccl(const igi_teacher_cfg* c, const igi_rollout* r
       const bool skip_gather = slot > 0;   // the previous step's fused tail gathered this minibatch
       if (overlap) {
         hipEvent_t* ev = cm->ev[slot & 1];
-        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 0, skip_gather))) return rc;
+        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 0, skip_gather, ks))) return rc;
         IGI_HIP_TRY(hipEventRecord(ev[0], s));
         IGI_HIP_TRY(hipStreamWaitEvent(cm->stream, ev[0], 0));
         if ((rc = comm_reduce_ranges(cm, st->grads, gb.off, gb.len, 2, cm->stream))) return rc;
         IGI_HIP_TRY(hipEventRecord(ev[2], cm->stream));
-        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 1))) return rc;
+        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 1, false, ks))) return rc;
         // the late bucket is on the critical path whatever stream carries it: it goes out on the compute stream (no
         // cross-stream hop behind phase 1; measured on a one-rank communicator: both buckets on the communication
         // stream cost 34 us per step of event hand-offs).  The compute stream joins the early bucket -- which finished
@@ -183,23 +199,26 @@ static int teacher_update_dp_rccl(const igi_teacher_cfg* c, const igi_rollout* r
         IGI_HIP_TRY(hipStreamWaitEvent(s, ev[2], 0));
         if ((rc = comm_reduce_ranges(cm, st->grads, gb.off + 2, gb.len + 2, 2, s))) return rc;
       } else {
-        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, -1, skip_gather))) return rc;
+        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, -1, skip_gather, ks))) return rc;
         if ((rc = comm_all_reduce_sum(cm, st->grads, p.P, s))) return rc;
       }
       const bool more = slot + 1 < total;
       if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, scale, s, more ? ro : nullptr, (slot + 1) % p.nmb,
-                              slot + 1, /*schedule_here=*/false)))
+                              slot + 1, /*schedule_here=*/false, ks, stopping ? &xch : nullptr)))
         return rc;
       if (lr_adaptive(c) && i == p.nmb - 1) {
         // adaptive schedule: the rank-mean KL of the mini-epoch (frozen_ppo.py:625-627) as ONE float on the compute
         // stream.  Both gradient collectives of this step were joined on `s` before Adam and the next one on the
         // communication stream waits for an event recorded on `s` after phase 0 of the next step: the communicator
         // never has collectives in flight on two streams.  Every rank then takes the same decision.
-        if ((rc = teacher_lr_exchange_begin(c, p, st, slot, s))) return rc;
+        if ((rc = teacher_lr_exchange_begin(c, p, st, slot, s, stop))) return rc;
         if ((rc = comm_all_reduce_sum(cm, reinterpret_cast<float*>(st->lr_state + 1), 1, s))) return rc;
-        if ((rc = teacher_lr_exchange_end(c, p, st, slot, cm->world, s))) return rc;
+        if ((rc = teacher_lr_exchange_end(c, p, st, slot, cm->world, s, stop))) return rc;
       }
     }
+    bool stopped;   // every rank reads the same word behind the same mini-epoch
+    if ((rc = look.after_mini_epoch(e, p.E, s, &stopped))) return rc;
+    if (stopped) break;
   }
   if (stats_sum && st->stats) {
     const size_t n = (size_t)total * IGI_STATS_PER_STEP;

@@ -325,9 +325,38 @@ int igi_teacher_update_dp_rccl(const igi_teacher_cfg* cfg, const igi_rollout* ro
               "igi_teacher_update_dp_rccl");
 }
 
+int igi_teacher_update_dp_rccl_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
+                                  const igi_kl_stop* ks, int64_t adam_t0, igi_comm_t comm, int overlap, float* stats_sum,
+                                  igi_stream_t stream) {
+  return fail(igi::teacher_update_dp_rccl(cfg, ro, st, adam_t0, comm, overlap, stats_sum, S(stream), ks),
+              "igi_teacher_update_dp_rccl_ks");
+}
+
 int igi_teacher_update(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
                        int64_t adam_t0, igi_stream_t stream) {
   return fail(igi::teacher_update(cfg, ro, st, adam_t0, S(stream)), "igi_teacher_update");
+}
+
+// KL early stopping: the same three calls with the stop record beside the two structs (ks NULL or off = the calls above)
+int igi_teacher_fwd_bwd_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
+                           const igi_kl_stop* ks, int mb_index, int step_slot, igi_stream_t stream) {
+  return fail(igi::teacher_fwd_bwd(cfg, ro, st, mb_index, step_slot, S(stream), -1, false, ks), "igi_teacher_fwd_bwd_ks");
+}
+int igi_teacher_apply_ks(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const igi_kl_stop* ks, int step_slot,
+                         int64_t adam_t, float grad_scale, igi_stream_t stream) {
+  return fail(igi::teacher_apply(cfg, st, step_slot, adam_t, grad_scale, S(stream), nullptr, 0, 0, true, ks),
+              "igi_teacher_apply_ks");
+}
+int igi_teacher_update_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
+                          const igi_kl_stop* ks, int64_t adam_t0, igi_stream_t stream) {
+  return fail(igi::teacher_update(cfg, ro, st, adam_t0, S(stream), ks), "igi_teacher_update_ks");
+}
+int igi_teacher_update_dp_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
+                             const igi_kl_stop* ks, int64_t adam_t0, float grad_scale, igi_reduce_fn reduce, void* user,
+                             igi_stream_t stream) {
+  if (!reduce) return fail(IGI_E_BADARG, "igi_teacher_update_dp_ks");
+  return fail(igi::teacher_update_dp(cfg, ro, st, adam_t0, grad_scale, reduce, user, S(stream), ks),
+              "igi_teacher_update_dp_ks");
 }
 
 int igi_teacher_update_dp(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,

@@ -20,7 +20,9 @@ struct LossArgs {
   long long start;
   int mb, N, T, act, rows_per_wave;
   float e_clip, critic_coef, entropy_coef, bounds_coef;
-  double* loss_part;  // [blocks][8]
+  double* loss_part;  // [blocks][8]: a_loss, c_loss, bounds, entropy, kl, approx_kl sums; two spare
+  const int32_t* stop;  // KL early stopping: the stop word (>= 0: an earlier step of this update stopped it -> no
+                        // update_mu_sigma write-back); NULL = off, and for step 0, which no step precedes
   float* head_slab;   // [blocks][head_count]
   int head_count;
 };
@@ -90,6 +92,17 @@ __device__ __forceinline__ CriticLoss critic_loss(float v, float R, float vp, fl
   const float g2 = (dvp >= -e_clip && dvp <= e_clip) ? 2.0f * (vclip - R) : 0.f;
   return {fmaxf(l1, l2), (l1 > l2) ? g1 : ((l1 < l2) ? g2 : 0.5f * (g1 + g2))};
 }
+
+// the KL estimator of frozen_ppo.py:568-569 for one sample, as written there: (exp(d) - 1) - d with
+// d = neglogp_new - neglogp_old (the reference's two "log_probs" are negative log-probabilities) and an exp of its own
+// -- actor_loss's ratio is the exp of -d
+__device__ __forceinline__ float approx_kl_term(float old_nlp, float nlp) {
+  const float d = nlp - old_nlp;
+  return (expf(d) - 1.0f) - d;
+}
+
+// update_mu_sigma write-back allowed?  (wave-uniform: one scalar load)
+__device__ __forceinline__ bool write_back_live(const int32_t* stop) { return !(stop && stop[0] >= 0); }
 
 // d(loss)/d(mu[q]) and d(loss)/d(sigma[q]) of one sample; g_nlp = d(loss)/d(neglogp), the coefficients already / mb
 __device__ __forceinline__ float d_mu(float g_nlp, const ActionTerms& t, const ActionConsts& c, float bounds_coef_mb) {
@@ -233,9 +246,9 @@ struct HeadTile {
     }
   }
   // block partials: [muW (act*H) | muB (act) | valW (H) | valB (1) | sigma (act)] and the five loss sums
-  // (actor, critic, bounds, entropy, kl).  Lane q < act brings d(bias_mu[q]) / d(sigma[q]), lane 0 d(bias_v) and the sums.
+  // (actor, critic, bounds, entropy, kl) and the approx_kl sum.  Lane q < act brings d(bias_mu[q]) / d(sigma[q]), lane 0 d(bias_v) and the sums.
   __device__ __forceinline__ void store_partials(const LossArgs& a, int lane, int wave, float gbmu, float gsig, float gbv,
-                                                 double s_a, double s_c, double s_b, double s_e, double s_kl) const {
+                                                 double s_a, double s_c, double s_b, double s_e, double s_kl, double s_ak) const {
     const int H = a.H, act = a.act;
     extern __shared__ __attribute__((aligned(16))) float red[];  // [4][head_count]
     float* mine = red + wave * a.head_count;
@@ -254,9 +267,10 @@ struct HeadTile {
       mine[act * H + act + H + 1 + lane] = gsig;
     }
     if (lane == 0) mine[act * H + act + H] = gbv;
-    __shared__ double sred[LOSS_THREADS / 64][5];
+    __shared__ double sred[LOSS_THREADS / 64][6];
     if (lane == 0) {
       sred[wave][0] = s_a; sred[wave][1] = s_c; sred[wave][2] = s_b; sred[wave][3] = s_e; sred[wave][4] = s_kl;
+      sred[wave][5] = s_ak;
     }
     __syncthreads();
     for (int e = threadIdx.x; e < a.head_count; e += blockDim.x) {
@@ -265,7 +279,7 @@ struct HeadTile {
       for (int w = 0; w < LOSS_THREADS / 64; ++w) s += red[w * a.head_count + e];
       a.head_slab[(long long)blockIdx.x * a.head_count + e] = s;
     }
-    if (threadIdx.x < 5) {
+    if (threadIdx.x < 6) {
       double s = 0;
       for (int w = 0; w < LOSS_THREADS / 64; ++w) s += sred[w][threadIdx.x];
       a.loss_part[blockIdx.x * 8 + threadIdx.x] = s;
@@ -289,7 +303,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss(const LossArgs a) {
   float gbmu = 0.f, gsig = 0.f;         // lane q accumulates d(bias_mu[q]), d(sigma[q])
   const float bv = a.bv[0];
   float gbv = 0.f;
-  double s_a = 0, s_c = 0, s_b = 0, s_e = 0, s_kl = 0;
+  double s_a = 0, s_c = 0, s_b = 0, s_e = 0, s_kl = 0, s_ak = 0;
+  const bool wb = write_back_live(a.stop);
   const float inv_mb = 1.0f / (float)a.mb;
   const float lo = 1.0f - a.e_clip, hi = 1.0f + a.e_clip;
 
@@ -357,16 +372,17 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss(const LossArgs a) {
       for (int q = 0; q < IGI_MAX_ACT; ++q) dmu[q] = read_lane(my_dmu, q);   // back to wave-uniform for the row products
       gbv += dv;
       s_a += al.loss; s_c += cl.loss; s_b += bounds_stat(bl, a.bounds_coef); s_e += ent; s_kl += kl;
+      s_ak += approx_kl_term(old_nlp, nlp);
 
       ht.backward_row(a, lane, row0 + r, ha[r], hc[r], dmu, dv);
       // update_mu_sigma (experience.py:228-233): scatter the new mu / sigma
-      if (alane) {
+      if (alane && wb) {
         a.mus_w[i * act + lane] = my_mu;
         a.sigmas_w[i * act + lane] = my.sig;
       }
     }
   }
-  ht.store_partials(a, lane, wave, gbmu, gsig, gbv, s_a, s_c, s_b, s_e, s_kl);
+  ht.store_partials(a, lane, wave, gbmu, gsig, gbv, s_a, s_c, s_b, s_e, s_kl, s_ak);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -389,7 +405,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_packed(const LossArgs a) 
   float gbmu = 0.f, gsig = 0.f;         // lane qi accumulates d(bias_mu[qi]), d(sigma[qi])
   const float bv = a.bv[0];
   float gbv = 0.f;
-  double s_a = 0, s_c = 0, s_b = 0, s_e = 0, s_kl = 0;
+  double s_a = 0, s_c = 0, s_b = 0, s_e = 0, s_kl = 0, s_ak = 0;
+  const bool wb = write_back_live(a.stop);
   const float inv_mb = 1.0f / (float)a.mb;
   const float lo = 1.0f - a.e_clip, hi = 1.0f + a.e_clip;
 
@@ -463,10 +480,15 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_packed(const LossArgs a) 
         gsig += d_sigma(g_nlp, t, my, a.entropy_coef * inv_mb);
         gbmu += my_dmu;
         // update_mu_sigma (experience.py:228-233): scatter the new mu / sigma
-        a.mus_w[g.ip * act + qi] = my_mu;
-        a.sigmas_w[g.ip * act + qi] = my.sig;
+        if (wb) {
+          a.mus_w[g.ip * act + qi] = my_mu;
+          a.sigmas_w[g.ip * act + qi] = my.sig;
+        }
       }
-      if (okrow && qi == 0) { s_a += al.loss; s_c += cl.loss; s_b += bounds_stat(bl, a.bounds_coef); s_e += ent; s_kl += kl; gbv += dv; }
+      if (okrow && qi == 0) {
+        s_a += al.loss; s_c += cl.loss; s_b += bounds_stat(bl, a.bounds_coef); s_e += ent; s_kl += kl; gbv += dv;
+        s_ak += approx_kl_term(g.old_nlp, nlp);
+      }
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -498,7 +520,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_packed(const LossArgs a) 
   s_b += __shfl_xor(s_b, 16, 64); s_b += __shfl_xor(s_b, 32, 64);
   s_e += __shfl_xor(s_e, 16, 64); s_e += __shfl_xor(s_e, 32, 64);
   s_kl += __shfl_xor(s_kl, 16, 64); s_kl += __shfl_xor(s_kl, 32, 64);
-  ht.store_partials(a, lane, wave, gbmu, gsig, gbv, s_a, s_c, s_b, s_e, s_kl);
+  s_ak += __shfl_xor(s_ak, 16, 64); s_ak += __shfl_xor(s_ak, 32, 64);
+  ht.store_partials(a, lane, wave, gbmu, gsig, gbv, s_a, s_c, s_b, s_e, s_kl, s_ak);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -531,7 +554,8 @@ struct TrunkLossHook {
 
   static constexpr int TILE_M = 64;                 // rows per tile: 2 x mb / 64 workgroups, two (or three) per CU
   static constexpr int EPLD = 36, SLICE = 32 * EPLD;
-  static constexpr int O_DM = 8 * SLICE, O_RED = O_DM + TILE_M * 8, O_LSUM = O_RED + 8 * 16, LDS_FLOATS = O_LSUM + 8 * 8;
+  static constexpr int O_DM = 8 * SLICE, O_RED = O_DM + TILE_M * 8, O_LSUM = O_RED + 8 * 16, O_LSUM5 = O_LSUM + 8 * 8,
+                        LDS_FLOATS = O_LSUM5 + 8 * 2;
 
   __device__ __forceinline__ explicit TrunkLossHook(const LossArgs& a_) : a(a_) {}
 
@@ -583,6 +607,7 @@ struct TrunkLossHook {
     float* dm = smem + O_DM;                    // [64 rows][8]: d(loss)/d(head output)
     float* red = smem + O_RED;                  // [8 waves][16]: bias / sigma gradient partials
     double* lsum = reinterpret_cast<double*>(smem + O_LSUM);   // [8 waves][4]
+    double* lsum5 = reinterpret_cast<double*>(smem + O_LSUM5); // [8 waves]: the approx_kl sums
     const float* W = actor ? a.Wmu : a.Wv;      // [nq][128]
 
     // ---- A: accumulators -> this wave's slice, bias + tanh in place; meanwhile the head weights arrive in registers
@@ -599,6 +624,7 @@ struct TrunkLossHook {
     const float my_logstd = alane ? a.logstd[fm] : 0.f;
     const float my_bmu = alane ? a.bmu[fm] : 0.f;
     const float bvv = a.bv[0];
+    const bool wb = write_back_live(a.stop);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     {
       const float4 b = *reinterpret_cast<const float4*>(g.bias + batch * g.sBias + wn * 32 + 4 * c4);
@@ -632,7 +658,7 @@ struct TrunkLossHook {
     // ---- C: hacc[2 (w >> 2) + r] = head output fm of row 16 (w & 3) + 4 fq + 2 (w >> 2) + r: this lane's action of its
     //         two rows.  The sums over the actions of a row are sums over the 16-lane row (DPP), as in k_loss_packed.
     float gb = 0.f, gs = 0.f;            // d(bias_mu[fm]) | d(bias_v), d(sigma[fm]) over this lane's rows
-    double t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+    double t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
     {
       const float inv_mb = 1.0f / (float)a.mb;
       const ActionConsts my = action_consts(my_logstd);
@@ -657,10 +683,15 @@ struct TrunkLossHook {
             gs += d_sigma(g_nlp, t, my, a.entropy_coef * inv_mb);
             gb += my_d;
             // update_mu_sigma (experience.py:228-233): scatter the new mu / sigma
-            a.mus_w[(long long)pb[r] * act + fm] = my_mu;
-            a.sigmas_w[(long long)pb[r] * act + fm] = my.sig;
+            if (wb) {
+              a.mus_w[(long long)pb[r] * act + fm] = my_mu;
+              a.sigmas_w[(long long)pb[r] * act + fm] = my.sig;
+            }
           }
-          if (okrow && fm == 0) { t0 += al.loss; t1 += bounds_stat(bl, a.bounds_coef); t2 += ent; t3 += kl; }
+          if (okrow && fm == 0) {
+            t0 += al.loss; t1 += bounds_stat(bl, a.bounds_coef); t2 += ent; t3 += kl;
+            t4 += approx_kl_term(s1[r], nlp);
+          }
         } else {
           const CriticLoss cl = critic_loss(hout + bvv, s0[r], s1[r], a.e_clip);
           if (okrow && fm == 0) {
@@ -679,9 +710,13 @@ struct TrunkLossHook {
         t1 += __shfl_xor(t1, 16, 64); t1 += __shfl_xor(t1, 32, 64);
         t2 += __shfl_xor(t2, 16, 64); t2 += __shfl_xor(t2, 32, 64);
         t3 += __shfl_xor(t3, 16, 64); t3 += __shfl_xor(t3, 32, 64);
+        t4 += __shfl_xor(t4, 16, 64); t4 += __shfl_xor(t4, 32, 64);
       }
       if (lane < 8) { red[wave * 16 + lane] = gb; red[wave * 16 + 8 + lane] = gs; }
-      if (lane == 0) { lsum[wave * 4 + 0] = t0; lsum[wave * 4 + 1] = t1; lsum[wave * 4 + 2] = t2; lsum[wave * 4 + 3] = t3; }
+      if (lane == 0) {
+        lsum[wave * 4 + 0] = t0; lsum[wave * 4 + 1] = t1; lsum[wave * 4 + 2] = t2; lsum[wave * 4 + 3] = t3;
+        lsum5[wave] = t4;
+      }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();   // LDS-only rendezvous: the mu / sigma stores stay in flight
@@ -762,6 +797,11 @@ struct TrunkLossHook {
       double* lp = a.loss_part + (long long)mt * 8;
       if (actor) lp[j == 0 ? 0 : j + 1] = sl;     // a_loss, bounds, entropy, kl -> slots 0, 2, 3, 4
       else if (j == 0) lp[1] = sl;                // c_loss -> slot 1
+    } else if (tid == 68 && actor) {
+      double sl = 0;
+#pragma unroll
+      for (int w8 = 0; w8 < 8; ++w8) sl += lsum5[w8];
+      a.loss_part[(long long)mt * 8 + 5] = sl;    // approx_kl -> slot 5
     }
   }
 };
@@ -779,7 +819,7 @@ __global__ __launch_bounds__(DMA_THREADS, 4) void k_trunk_loss(const GemmArgs g,
 //    the trunk backward reads it in.
 // ---------------------------------------------------------------------------------------------
 static int loss_stage(const TeacherPlan& p, const igi_teacher_cfg* c, const igi_rollout* ro, const igi_teacher_state* st,
-                      int mb_index, int ld_dh, long long net_stride_dh, hipStream_t s) {
+                      int mb_index, int ld_dh, long long net_stride_dh, hipStream_t s, const int32_t* stop = nullptr) {
   const float* P = st->params;
   const int mb = p.mb;
   const long long mbs = mb;
@@ -800,6 +840,7 @@ static int loss_stage(const TeacherPlan& p, const igi_teacher_cfg* c, const igi_
   a.e_clip = c->e_clip; a.critic_coef = c->critic_coef; a.entropy_coef = c->entropy_coef;
   a.bounds_coef = c->bounds_loss_coef;
   a.loss_part = wsp<double>(st, p.w_loss_part);
+  a.stop = stop;
   a.head_slab = wsp<float>(st, p.w_head_slab);
   a.head_count = p.head_count;
   if (p.loss_fused) {

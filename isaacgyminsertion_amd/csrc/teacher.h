@@ -16,6 +16,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
+
 #include "../../include/igi_ppo.h"
 #include "gemm_dma.h"
 #include "rowblock.h"
@@ -668,6 +670,7 @@ struct GatherArgs {
   const float* coef; const double* state_row; double* rms_obs; double* rms_priv;
   float* xcat; int xld, xw; float* priv_g; int pld;
   const float* params; long long o_w, ac_block; int u0, u0p; float* w1p; float* wlat; int K2p;
+  const int32_t* stop = nullptr;   // KL early stopping: the stop word; >= 0 = the update has stopped, this body is inert
 };
 
 // bid / nblocks: this body's block index and block count (it also runs as the second half of k_adam_gather)
@@ -682,6 +685,7 @@ __device__ __forceinline__ void gather_normalize_body(const GatherArgs& a, int b
   const int pld = a.pld; const float* __restrict__ params = a.params; const long long o_w = a.o_w, ac_block = a.ac_block;
   const int u0 = a.u0, u0p = a.u0p; float* __restrict__ w1p = a.w1p; float* __restrict__ wlat = a.wlat;
   const int K2p = a.K2p;
+  if (a.stop && a.stop[0] >= 0) return;   // stopped: neither the next step's running state nor its rows (block-uniform)
   if (bid >= gather_blocks) {  // W1p[net][o][c] refresh (see k_pad_w1)
     const int total = 2 * u0p * xld;
     const int nb = nblocks - gather_blocks;
@@ -880,9 +884,19 @@ struct SegTable {
                   // per-workgroup gradient records: 170 - 512 partials of 16 - 80 K floats)
 };
 
-// strided fixed-order sums of the loss partial records -> the statistics row (means over the minibatch); one block
+// KL early stopping as the statistics block sees it: state == NULL = off.  slot: this optimizer step; limit = 1.5 *
+// kl_threshold.  state[0] the stop word (int32; -1 = running), state[2 + s] approx_kl of step s (float bits).
+// exchange != 0 (data parallel): the block stores this rank's estimator in the exchange scratch, state[1], and leaves
+// the word alone -- k_stop_decide writes it from the rank sum.
+struct StopArgs { int32_t* state; int slot; double limit; int exchange; };
+
+// strided fixed-order sums of the loss partial records -> the statistics row (means over the minibatch); one block.
+// With early stopping it also takes the step's decision (frozen_ppo.py:578-581): thread 5, which holds the approx_kl
+// column, stores the estimator and the stop word -- plain stores, ahead of the Adam launch in stream order.  Step 0
+// decides whatever the word held (the previous update's result); a later step of a stopped update writes nothing.
 __device__ __forceinline__ void stats_row_block(const double* __restrict__ loss_part, int loss_blocks, int mb,
-                                                float* __restrict__ stats_row) {
+                                                float* __restrict__ stats_row, const StopArgs stop = StopArgs{nullptr, 0, 0.0, 0}) {
+  const bool live = !stop.state || stop.slot == 0 || stop.state[0] < 0;   // read before the barrier, written behind it
   // thread (q = tid&7, j = tid>>3): strided fixed-order partial sums, then a fixed tree in LDS
   __shared__ double sh[256];
   const int q = threadIdx.x & 7, j = threadIdx.x >> 3;
@@ -899,10 +913,18 @@ __device__ __forceinline__ void stats_row_block(const double* __restrict__ loss_
   }
   sh[threadIdx.x] = s;
   __syncthreads();
-  if (threadIdx.x < 5) {
+  if (threadIdx.x < 5 && live) {
     double t = 0;
     for (int jj = 0; jj < 32; ++jj) t += sh[jj * 8 + threadIdx.x];
     stats_row[threadIdx.x] = (float)(t / (double)mb);
+  }
+  if (threadIdx.x == 5 && stop.state && live) {
+    double t = 0;
+    for (int jj = 0; jj < 32; ++jj) t += sh[jj * 8 + 5];
+    const float akl = (float)(t / (double)mb);
+    reinterpret_cast<float*>(stop.state)[2 + stop.slot] = akl;
+    if (stop.exchange) reinterpret_cast<float*>(stop.state)[1] = akl;
+    else stop.state[0] = ((double)akl > stop.limit) ? stop.slot : -1;
   }
 }
 
@@ -1025,11 +1047,12 @@ __global__ __launch_bounds__(256) void k_sumsq_stats(const float* __restrict__ g
                                                      float scale, double* __restrict__ part,
                                                      const double* __restrict__ loss_part,
                                                      int loss_blocks, int mb,
-                                                     float* __restrict__ stats_row) {
+                                                     float* __restrict__ stats_row,
+                                                     const StopArgs stop = StopArgs{nullptr, 0, 0.0, 0}) {
   __shared__ double red[2][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (blockIdx.x == SUMSQ_BLOCKS) {
-    stats_row_block(loss_part, loss_blocks, mb, stats_row);
+    stats_row_block(loss_part, loss_blocks, mb, stats_row, stop);
     return;
   }
   double sg = 0, sp = 0;
@@ -1065,7 +1088,10 @@ __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const
                                                float beta2, float w2, float step_size, float bc2_sqrt, float eps,
                                                float* __restrict__ stats_row, float decay, float l2, int bid,
                                                int nblocks, const W1Mirror* mir, const double* __restrict__ lr_dev = nullptr,
-                                               double bc1 = 1.0) {
+                                               double bc1 = 1.0, const int32_t* stop = nullptr) {
+  // KL early stopping: this step's decision (or an earlier one) stopped the update -> parameters, moments, the
+  // first-layer copies and slots 5 .. 7 of the row stay as step s - 1 left them (block-uniform, ahead of any barrier)
+  if (stop && stop[0] >= 0) return;
   __shared__ float s_coef;
   __shared__ float s_step;
   __shared__ double s_part[2][64];
@@ -1160,9 +1186,9 @@ __global__ __launch_bounds__(256) void k_clip_adam(float* __restrict__ params,
                                                    float w2, float step_size, float bc2_sqrt, float eps,
                                                    float* __restrict__ stats_row, float decay = 1.0f,
                                                    float l2 = 0.0f, const double* __restrict__ lr_dev = nullptr,
-                                                   double bc1 = 1.0) {
+                                                   double bc1 = 1.0, const int32_t* stop = nullptr) {
   clip_adam_body(params, grads, m, v, P, part, scale, max_norm, w1, beta2, w2, step_size, bc2_sqrt, eps, stats_row,
-                 decay, l2, (int)blockIdx.x, (int)gridDim.x, nullptr, lr_dev, bc1);
+                 decay, l2, (int)blockIdx.x, (int)gridDim.x, nullptr, lr_dev, bc1, stop);
 }
 
 // Tail of optimizer step s fused with the head of step s+1: blocks [0, adam_blocks) run clip + Adam (and keep the
@@ -1174,6 +1200,7 @@ struct AdamArgs {
   float* params; const float* grads; float* m; float* v; long long P; const double* part;
   float scale, max_norm, w1, beta2, w2, step_size, bc2_sqrt, eps; float* stats_row;
   const double* lr_dev; double bc1;   // adaptive schedule: the rate's device address (NULL: step_size as given) and 1 - beta1^t
+  const int32_t* stop;                // KL early stopping: the stop word (NULL = off); the gather half reads GatherArgs::stop
 };
 __global__ __launch_bounds__(256) void k_adam_gather(const AdamArgs a, const W1Mirror mir, const GatherArgs g,
                                                      int adam_blocks) {
@@ -1185,7 +1212,7 @@ __global__ __launch_bounds__(256) void k_adam_gather(const AdamArgs a, const W1M
   else
     clip_adam_body(a.params, a.grads, a.m, a.v, a.P, a.part, a.scale, a.max_norm, a.w1, a.beta2, a.w2, a.step_size,
                    a.bc2_sqrt, a.eps, a.stats_row, 1.0f, 0.0f, (int)blockIdx.x - gblocks, adam_blocks, &mir, a.lr_dev,
-                   a.bc1);
+                   a.bc1, a.stop);
 }
 
 // KL-adaptive learning rate (rl_games AdaptiveScheduler.update, frozen_ppo.py:864-877, fed as at :624-630 with the call
@@ -1196,11 +1223,18 @@ __global__ __launch_bounds__(256) void k_adam_gather(const AdamArgs a, const W1M
 //   mode 0: one rank -- mean and decision
 //   mode 1: data parallel, before the exchange -- this rank's mean into the scratch float, no decision
 //   mode 2: data parallel, after the all-reduce (SUM) of the scratch float -- kl = sum / world (fp32, :625-627), decision
+// stop (KL early stopping, NULL = off): the update stopped at step *stop >= 0.  In the mini-epoch of that step the mean
+// runs over its steps 0 .. *stop % nmb (the reference's ep_kls at the inner break, :630 sits between the two breaks);
+// in every later one the launch is inert.
 // Every store is a plain C++ store from lane 0.
 __global__ __launch_bounds__(64) void k_lr_schedule(const float* __restrict__ stats_epoch, int nmb, int epoch, int mode,
                                                     int world, double kl_threshold, double lr_min, double lr_max,
-                                                    double* __restrict__ lr_state) {
+                                                    double* __restrict__ lr_state, const int32_t* stop = nullptr) {
   if (threadIdx.x != 0) return;
+  if (stop && stop[0] >= 0) {
+    if (stop[0] / nmb != epoch) return;
+    nmb = stop[0] % nmb + 1;
+  }
   float* scratch = reinterpret_cast<float*>(lr_state + 1);
   float kl;
   if (mode != 2) {
@@ -1221,6 +1255,18 @@ __global__ __launch_bounds__(64) void k_lr_schedule(const float* __restrict__ st
   lr_state[3 + 2 * epoch] = lr;
 }
 
+// KL early stopping, data parallel: the decision from the rank-mean estimator.  The statistics block left this rank's
+// fp32 mean in the scratch float, state[1]; it was all-reduced (SUM) in place; one lane divides by the world size in
+// fp32 and compares as the single-rank block does -- the same bits on every rank, so every rank stops at the same step.
+// A step behind a stop leaves the word alone (every rank is in that state alike).  Plain stores.
+__global__ __launch_bounds__(64) void k_stop_decide(int32_t* __restrict__ state, int slot, int world, double limit) {
+  if (threadIdx.x != 0) return;
+  if (slot > 0 && state[0] >= 0) return;
+  const float kl = reinterpret_cast<const float*>(state)[1] / (float)world;
+  reinterpret_cast<float*>(state)[2 + slot] = kl;
+  state[0] = ((double)kl > limit) ? slot : -1;
+}
+
 // ---------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------
@@ -1237,6 +1283,18 @@ static int check_lr_cfg(const igi_teacher_cfg* c, const igi_teacher_state* st) {
     return IGI_E_BADARG;
   return 0;
 }
+
+static inline bool kl_stop_on(const igi_kl_stop* ks) { return ks && ks->kl_early_stop != 0; }
+// one threshold: under the adaptive schedule the stop's must be the scheduler's
+static int check_ks(const igi_kl_stop* ks, const igi_teacher_state* st, const igi_teacher_cfg* c) {
+  if (!kl_stop_on(ks)) return 0;
+  if (ks->kl_early_stop != 1 || !(ks->kl_threshold > 0.0) || !ks->stop_state || !st->stats) return IGI_E_BADARG;
+  if (c->lr_schedule != 0 && c->kl_threshold != ks->kl_threshold) return IGI_E_BADARG;
+  return 0;
+}
+// the data-parallel updates' exchange of the estimator: called between the statistics block and the decision kernel,
+// it all-reduces (SUM) the scratch float in the order of the stream
+struct StopExchange { int (*fn)(void* ctx, int slot); void* ctx; int world; };
 
 static int teacher_prepare(const igi_teacher_cfg* c, const igi_rollout* ro,
                            const igi_teacher_state* st, int normalize_value, hipStream_t s) {
@@ -1729,11 +1787,15 @@ static ContactArgs contact_args(const TeacherPlan& p, const igi_teacher_state* s
 // skip_gather: the previous step's fused tail (k_adam_gather) already gathered + normalised this minibatch
 static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
                            const igi_teacher_state* st, int mb_index, int step_slot, hipStream_t s,
-                           int phase = -1, bool skip_gather = false) {
+                           int phase = -1, bool skip_gather = false, const igi_kl_stop* ks = nullptr) {
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
   if ((rc = check_state(p, st))) return rc;
+  if ((rc = check_ks(ks, st, c))) return rc;
+  // KL early stopping: what runs ahead of the step's decision looks at the word an EARLIER step left; step 0 has none
+  // (the word still holds the previous update's result)
+  const int32_t* stop = kl_stop_on(ks) && step_slot > 0 ? ks->stop_state : nullptr;
   if (!ro || !ro->obses || !ro->priv_info || !ro->actions || !ro->neglogpacs || !st->grads ||
       !st->perm || !st->rms_obs || !st->rms_priv || !st->stats || !st->advantages ||
       mb_index < 0 || mb_index >= p.nmb || step_slot < 0 || (p.ct_P > 0 && !ro->contacts))
@@ -1757,7 +1819,8 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   if (do0 && !skip_gather) {
     ProfScope ps(PC_GATHER_NORMALIZE, s, 0.0, 8.0 * (double)mbs * D + 8.0 * mbs);
     const int pad_blocks = 16;
-    const GatherArgs ga = gather_args(p, ro, st, mb_index, step_slot);
+    GatherArgs ga = gather_args(p, ro, st, mb_index, step_slot);
+    ga.stop = stop;
     IGI_LAUNCH(k_gather_normalize, dim3(p.gs_blocks + pad_blocks), dim3(GS_THREADS), 0, s, ga);
   }
   // ---- forward trunk (models_split.py:166-232)
@@ -1768,7 +1831,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   const int H = p.u[p.nl - 1];
   auto dz_ld = [&](int l) { return l == 0 ? 2 * p.u0p : ru4(p.u[l]); };
   auto dz_stride = [&](int l) { return l == 0 ? (long long)p.u0p : mbs * ru4(p.u[l]); };
-  if (do0 && (rc = loss_stage(p, c, ro, st, mb_index, dz_ld(p.nl - 1), dz_stride(p.nl - 1), s))) return rc;
+  if (do0 && (rc = loss_stage(p, c, ro, st, mb_index, dz_ld(p.nl - 1), dz_stride(p.nl - 1), s, stop))) return rc;
 
   // ---- backward through the actor / critic trunk.  Level fusion: the weight gradient of layer l and the data
   //      gradient INTO layer l-1 both consume dZ_l and are independent of each other, so they share one grid
@@ -2025,13 +2088,13 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
 
 // The scheduler launch behind the last optimizer step (step_slot) of a mini-epoch; mode as k_lr_schedule takes it.
 static int teacher_lr_schedule(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_teacher_state* st, int step_slot,
-                               int mode, int world, hipStream_t s) {
+                               int mode, int world, hipStream_t s, const int32_t* stop = nullptr) {
   const int e = step_slot / p.nmb;
   if (e >= p.E || step_slot % p.nmb != p.nmb - 1) return IGI_E_BADARG;
   const float* rows = st->stats + (long long)e * p.nmb * IGI_STATS_PER_STEP;
   ProfScope ps(PC_LR_SCHEDULE, s, 0.0, 4.0 * p.nmb + 32.0);
   IGI_LAUNCH(k_lr_schedule, dim3(1), dim3(64), 0, s, rows, p.nmb, e, mode, world, c->kl_threshold, c->lr_min, c->lr_max,
-             st->lr_state);
+             st->lr_state, stop);
   return (int)hipGetLastError();
 }
 
@@ -2041,14 +2104,17 @@ static int teacher_lr_schedule(const igi_teacher_cfg* c, const TeacherPlan& p, c
 // data-parallel updates pass false and put their KL exchange between the two halves themselves
 static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, int step_slot,
                          int64_t adam_t, float grad_scale, hipStream_t s, const igi_rollout* next_ro = nullptr,
-                         int next_mb = 0, int next_slot = 0, bool schedule_here = true) {
+                         int next_mb = 0, int next_slot = 0, bool schedule_here = true,
+                         const igi_kl_stop* ks = nullptr, const StopExchange* xch = nullptr) {
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
   if ((rc = check_state(p, st))) return rc;
   if ((rc = check_lr_cfg(c, st))) return rc;
+  if ((rc = check_ks(ks, st, c))) return rc;
   const bool adaptive = lr_adaptive(c);
-  if (adaptive && (step_slot < 0 || step_slot >= p.E * p.nmb)) return IGI_E_BADARG;
+  int32_t* stop = kl_stop_on(ks) ? ks->stop_state : nullptr;
+  if ((adaptive || stop) && (step_slot < 0 || step_slot >= p.E * p.nmb)) return IGI_E_BADARG;
   const bool sched = adaptive && schedule_here && step_slot % p.nmb == p.nmb - 1;
   if (!st->grads || !st->adam_m || !st->adam_v || adam_t < 1) return IGI_E_BADARG;
   double* part = wsp<double>(st, p.w_sumsq);
@@ -2057,7 +2123,14 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
     ProfScope ps(PC_SUMSQ, s, 0.0, 8.0 * (double)p.P);
     IGI_LAUNCH(k_sumsq_stats, dim3(SUMSQ_BLOCKS + (row ? 1 : 0)), dim3(256), 0, s, st->grads,
                        st->params, p.P, grad_scale, part, wsp<double>(st, p.w_loss_part), p.loss_blocks,
-                       p.mb, row);
+                       p.mb, row, StopArgs{stop, step_slot, stop ? 1.5 * ks->kl_threshold : 0.0, xch ? 1 : 0});
+  }
+  if (stop && xch) {   // data parallel: the rank-mean estimator decides, between the norms and the Adam tail
+    if (xch->world < 1) return IGI_E_BADARG;
+    if (xch->fn(xch->ctx, step_slot)) return IGI_E_CALLBACK;
+    ProfScope ps(PC_LR_SCHEDULE, s, 0.0, 16.0);
+    IGI_LAUNCH(k_stop_decide, dim3(1), dim3(64), 0, s, stop, step_slot, xch->world, 1.5 * ks->kl_threshold);
+    if ((rc = (int)hipGetLastError())) return rc;
   }
   // torch.optim.Adam (_single_tensor_adam): python-double scalars, cast to fp32 at the tensor op
   const double b1 = c->beta1, b2 = c->beta2;
@@ -2077,8 +2150,9 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
     aa.params = st->params; aa.grads = st->grads; aa.m = st->adam_m; aa.v = st->adam_v; aa.P = p.P; aa.part = part;
     aa.scale = grad_scale; aa.max_norm = c->grad_norm; aa.w1 = w1; aa.beta2 = (float)b2; aa.w2 = w2;
     aa.step_size = step_size; aa.bc2_sqrt = bc2_sqrt; aa.eps = (float)c->adam_eps; aa.stats_row = row;
-    aa.lr_dev = adaptive ? st->lr_state : nullptr; aa.bc1 = bc1;
-    const GatherArgs ga = gather_args(p, next_ro, st, next_mb, next_slot);
+    aa.lr_dev = adaptive ? st->lr_state : nullptr; aa.bc1 = bc1; aa.stop = stop;
+    GatherArgs ga = gather_args(p, next_ro, st, next_mb, next_slot);
+    ga.stop = stop;   // the gather blocks of a stopping step must not publish step s + 1's running state
     W1Mirror mir;
     mir.w1p = ga.w1p; mir.wlat = ga.wlat; mir.o_w = ga.o_w; mir.ac_block = ga.ac_block; mir.u0 = ga.u0;
     mir.u0p = ga.u0p; mir.xw = p.xw; mir.xld = p.xld; mir.obs = p.obs; mir.K2p = ga.K2p;
@@ -2088,71 +2162,158 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
     ProfScope ps(PC_ADAM, s, 0.0, 28.0 * (double)p.P);  // 16 B read + 12 B written per parameter
     IGI_LAUNCH(k_clip_adam, dim3(nb), dim3(256), 0, s, st->params, st->grads, st->adam_m,
                        st->adam_v, p.P, part, grad_scale, c->grad_norm, w1, (float)b2, w2, step_size,
-                       bc2_sqrt, (float)c->adam_eps, row, 1.0f, 0.0f, adaptive ? st->lr_state : (const double*)nullptr, bc1);
+                       bc2_sqrt, (float)c->adam_eps, row, 1.0f, 0.0f, adaptive ? st->lr_state : (const double*)nullptr, bc1,
+                       (const int32_t*)stop);
     if ((rc = (int)hipGetLastError())) return rc;
   }
-  return sched ? teacher_lr_schedule(c, p, st, step_slot, 0, 1, s) : 0;
+  return sched ? teacher_lr_schedule(c, p, st, step_slot, 0, 1, s, stop) : 0;
 }
 
 // data-parallel updates: this rank's mini-epoch KL into the exchange scratch / the decision from the rank sum
 static int teacher_lr_exchange_begin(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_teacher_state* st, int slot,
-                                     hipStream_t s) {
-  return teacher_lr_schedule(c, p, st, slot, 1, 1, s);
+                                     hipStream_t s, const int32_t* stop = nullptr) {
+  return teacher_lr_schedule(c, p, st, slot, 1, 1, s, stop);
 }
 static int teacher_lr_exchange_end(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_teacher_state* st, int slot,
-                                   int world, hipStream_t s) {
-  return teacher_lr_schedule(c, p, st, slot, 2, world, s);
+                                   int world, hipStream_t s, const int32_t* stop = nullptr) {
+  return teacher_lr_schedule(c, p, st, slot, 2, world, s, stop);
 }
 
+// KL early stopping, host side of the one-call updates: what reads the stop word while an update is being enqueued.
+// One per device, owned by the library for the life of the process: a non-blocking copy stream, the events behind two
+// consecutive mini-epochs, the event behind the copy, and the pinned word the copy lands in.  An update holds the
+// device's reader -- its mutex -- from its first look-ahead to its last, so two host threads that update engines on one
+// device take turns and never see each other's word.
+struct StopReader {
+  std::mutex use;
+  hipStream_t cs = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr}, done = nullptr;
+  int32_t* host = nullptr;
+};
+// built whole or not at all: a failure releases what it had created, and the next call starts afresh
+static int stop_reader_build(StopReader& r) {
+  hipStream_t cs = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  int32_t* host = nullptr;
+  hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
+  for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&host), sizeof(int32_t), hipHostMallocDefault);
+  if (e != hipSuccess) {
+    for (int i = 0; i < 3; ++i)
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+    if (cs) (void)hipStreamDestroy(cs);
+    return (int)e;
+  }
+  r.cs = cs; r.ev[0] = ev[0]; r.ev[1] = ev[1]; r.done = ev[2]; r.host = host;
+  return 0;
+}
+// the calling thread's device's reader, locked; StopLookahead's destructor unlocks it
+struct StopLookahead {
+  StopReader* rd = nullptr;
+  const igi_kl_stop* ks = nullptr;
+  ~StopLookahead() { if (rd) rd->use.unlock(); }
+  int begin(const igi_kl_stop* k) {
+    static StopReader readers[64];
+    int dev = 0;
+    IGI_HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return IGI_E_UNSUPPORTED;
+    readers[dev].use.lock();
+    rd = &readers[dev];
+    ks = k;
+    return rd->host ? 0 : stop_reader_build(*rd);
+  }
+  // behind mini-epoch e (enqueued on s, E in all): *stopped = the word as mini-epoch e - 1 left it says so
+  int after_mini_epoch(int e, int E, hipStream_t s, bool* stopped) {
+    *stopped = false;
+    if (!rd || e + 1 >= E) return 0;
+    IGI_HIP_TRY(hipEventRecord(rd->ev[e & 1], s));
+    if (e < 1) return 0;
+    IGI_HIP_TRY(hipStreamWaitEvent(rd->cs, rd->ev[(e - 1) & 1], 0));
+    IGI_HIP_TRY(hipMemcpyAsync(rd->host, ks->stop_state, sizeof(int32_t), hipMemcpyDeviceToHost, rd->cs));
+    IGI_HIP_TRY(hipEventRecord(rd->done, rd->cs));
+    IGI_HIP_TRY(hipEventSynchronize(rd->done));
+    *stopped = *rd->host >= 0;
+    return 0;
+  }
+};
+
+// ks on: the device gates every step behind the stop on its own (exact at step granularity, no host involved); the
+// host only stops ENQUEUEING, with one mini-epoch of look-ahead: mini-epoch e + 1 is in the queue before it waits for
+// the event behind mini-epoch e and reads the word through the copy stream, which waits for that event alone -- never
+// for the look-ahead work.  One host wait per mini-epoch; with the switch off there is none, as before.
 static int teacher_update(const igi_teacher_cfg* c, const igi_rollout* ro,
-                          const igi_teacher_state* st, int64_t adam_t0, hipStream_t s) {
+                          const igi_teacher_state* st, int64_t adam_t0, hipStream_t s, const igi_kl_stop* ks = nullptr) {
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
   const int total = p.E * p.nmb;
+  StopLookahead look;
+  if (kl_stop_on(ks)) {
+    if ((rc = check_state(p, st)) || (rc = check_ks(ks, st, c)) || (rc = look.begin(ks))) return rc;
+  }
   int slot = 0;
   for (int e = 0; e < p.E; ++e) {
     for (int i = 0; i < p.nmb; ++i, ++slot) {
       // from the second step on the minibatch was gathered by the previous step's fused tail
-      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, -1, slot > 0))) return rc;
+      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, -1, slot > 0, ks))) return rc;
       const bool more = slot + 1 < total;
       if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, 1.0f, s, more ? ro : nullptr, (slot + 1) % p.nmb,
-                              slot + 1)))
+                              slot + 1, /*schedule_here=*/true, ks)))
         return rc;
     }
+    bool stopped;
+    if ((rc = look.after_mini_epoch(e, p.E, s, &stopped))) return rc;
+    if (stopped) break;
   }
   return 0;
 }
 
 // data-parallel update: the same 64 steps with the two-bucket gradient exchange driven through a callback
 // (frozen_ppo.py:586-603); one host call per update, the callback only enqueues collectives / stream waits
+struct ReduceCtx { igi_reduce_fn reduce; void* user; };
+static int stop_exchange_callback(void* ctx, int slot) {   // bucket 4: the one float of the estimator exchange
+  ReduceCtx* r = static_cast<ReduceCtx*>(ctx);
+  return r->reduce(r->user, 4, slot);
+}
 static int teacher_update_dp(const igi_teacher_cfg* c, const igi_rollout* ro, const igi_teacher_state* st,
-                             int64_t adam_t0, float grad_scale, igi_reduce_fn reduce, void* user, hipStream_t s) {
+                             int64_t adam_t0, float grad_scale, igi_reduce_fn reduce, void* user, hipStream_t s,
+                             const igi_kl_stop* ks = nullptr) {
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
   const int total = p.E * p.nmb;
   const int world = grad_scale > 0.f ? (int)lroundf(1.0f / grad_scale) : 0;
-  if (lr_adaptive(c) && world < 1) return IGI_E_BADARG;
+  if ((lr_adaptive(c) || kl_stop_on(ks)) && world < 1) return IGI_E_BADARG;
+  ReduceCtx rctx{reduce, user};
+  const StopExchange xch{stop_exchange_callback, &rctx, world};
+  const bool stopping = kl_stop_on(ks);
+  const int32_t* stop = stopping ? ks->stop_state : nullptr;
+  StopLookahead look;
+  if (stopping) {
+    if ((rc = check_state(p, st)) || (rc = check_ks(ks, st, c)) || (rc = look.begin(ks))) return rc;
+  }
   int slot = 0;
   for (int e = 0; e < p.E; ++e) {
     for (int i = 0; i < p.nmb; ++i, ++slot) {
-      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 0, slot > 0))) return rc;
+      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 0, slot > 0, ks))) return rc;
       if (reduce(user, 0, slot)) return IGI_E_CALLBACK;
-      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 1))) return rc;
+      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 1, false, ks))) return rc;
       if (reduce(user, 1, slot)) return IGI_E_CALLBACK;
       if (reduce(user, 2, slot)) return IGI_E_CALLBACK;
       const bool more = slot + 1 < total;
       if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, grad_scale, s, more ? ro : nullptr,
-                              (slot + 1) % p.nmb, slot + 1, /*schedule_here=*/false)))
+                              (slot + 1) % p.nmb, slot + 1, /*schedule_here=*/false, ks, stopping ? &xch : nullptr)))
         return rc;
       if (lr_adaptive(c) && i == p.nmb - 1) {
         // the rank-mean KL of the mini-epoch (frozen_ppo.py:625-627): one float through the caller's transport, bucket 3
-        if ((rc = teacher_lr_exchange_begin(c, p, st, slot, s))) return rc;
+        if ((rc = teacher_lr_exchange_begin(c, p, st, slot, s, stop))) return rc;
         if (reduce(user, 3, slot)) return IGI_E_CALLBACK;
-        if ((rc = teacher_lr_exchange_end(c, p, st, slot, world, s))) return rc;
+        if ((rc = teacher_lr_exchange_end(c, p, st, slot, world, s, stop))) return rc;
       }
     }
+    bool stopped;   // every rank reads the same word behind the same mini-epoch: all stop enqueueing at one boundary
+    if ((rc = look.after_mini_epoch(e, p.E, s, &stopped))) return rc;
+    if (stopped) break;
   }
   return 0;
 }

@@ -121,6 +121,32 @@ igi_teacher_state state_struct(at::TensorList st, const igi_teacher_cfg& c) {
   return s;
 }
 
+// KL early stopping rides behind everything else in the three lists of ppo_minibatch_fwd_bwd, ppo_clip_adam and
+// ppo_update (ops.py pack_stop): one trailing int (kl_early_stop = 1), one trailing float (kl_threshold), one trailing
+// state tensor (stop_state, int32).  13 or 16 floats carry it; lists of today's lengths mean "off".  Takes the tail off
+// the three lists and returns whether it was there.
+bool split_stop(at::TensorList& st, at::IntArrayRef& ic, at::ArrayRef<double>& fc, igi_kl_stop* ks) {
+  std::memset(ks, 0, sizeof(*ks));
+  if (fc.size() != 13 && fc.size() != 16) return false;
+  TORCH_CHECK(ic.size() >= 1 && st.size() >= 1 && ic.back() == 1 && fc.back() > 0,
+              "teacher cfg: the early-stopping tail needs kl_early_stop == 1, kl_threshold > 0 and the stop_state tensor "
+              "behind the state list");
+  constexpr int M = IGI_MAX_LAYERS;
+  ks->kl_early_stop = 1; ks->kl_threshold = fc.back();
+  const Tensor& stop = st.back();
+  st = st.slice(0, st.size() - 1); ic = ic.slice(0, ic.size() - 1); fc = fc.slice(0, fc.size() - 1);
+  TORCH_CHECK((int)ic.size() >= 8 + 2 * M && st.size() >= 1, "teacher cfg: too short for the early-stopping tail");
+  const int64_t n_env = ic[5 + 2 * M], hor = ic[6 + 2 * M], E = ic[7 + 2 * M];
+  TORCH_CHECK(n_env >= 1 && hor >= 1 && E >= 1 && n_env * hor >= E, "teacher cfg: non-positive dimension or unsupported layer count");
+  const int64_t B = n_env * hor, steps = E * (B / (B / E));
+  check(stop, "state.stop_state", at::kInt);
+  TORCH_CHECK(stop.device() == st[0].device(), "state.stop_state: all arguments must share one device");
+  TORCH_CHECK(stop.numel() == IGI_STOP_STATE_WORDS(steps), "state.stop_state: expected ", IGI_STOP_STATE_WORDS(steps),
+              " int32 words, got ", stop.numel());
+  ks->stop_state = stop.data_ptr<int32_t>();
+  return true;
+}
+
 igi_rollout rollout_struct(at::TensorList ro, const igi_teacher_cfg& c, const at::Device& dev) {
   static const char* names[10] = {"obses", "priv_info", "rewards", "values", "neglogpacs", "dones", "actions", "mus",
                                   "sigmas", "last_values"};
@@ -158,28 +184,38 @@ void gae_advnorm(at::TensorList rollout, at::TensorList state, at::IntArrayRef i
 }
 void ppo_minibatch_fwd_bwd(at::TensorList rollout, at::TensorList state, at::IntArrayRef icfg, at::ArrayRef<double> fcfg,
                            int64_t mb_index, int64_t step_slot, int64_t phase) {
+  igi_kl_stop ks;
+  const bool stopping = split_stop(state, icfg, fcfg, &ks);
   const igi_teacher_cfg c = unpack_cfg(icfg, fcfg);
   const igi_teacher_state s = state_struct(state, c);
   const igi_rollout r = rollout_struct(rollout, c, state[0].device());
   TORCH_CHECK(phase >= -1 && phase <= 1, "phase: expected -1, 0 or 1, got ", phase);
+  TORCH_CHECK(!stopping || phase < 0, "phase: KL early stopping has no data-parallel phases (phase must be -1)");
   c10::hip::HIPGuardMasqueradingAsCUDA g(state[0].device());
-  if (phase < 0) rc(igi_teacher_fwd_bwd(&c, &r, &s, (int)mb_index, (int)step_slot, stream_of(state[0])), "igi_teacher_fwd_bwd");
+  if (stopping) rc(igi_teacher_fwd_bwd_ks(&c, &r, &s, &ks, (int)mb_index, (int)step_slot, stream_of(state[0])), "igi_teacher_fwd_bwd_ks");
+  else if (phase < 0) rc(igi_teacher_fwd_bwd(&c, &r, &s, (int)mb_index, (int)step_slot, stream_of(state[0])), "igi_teacher_fwd_bwd");
   else rc(igi_teacher_fwd_bwd_phase(&c, &r, &s, (int)mb_index, (int)step_slot, (int)phase, stream_of(state[0])),
           "igi_teacher_fwd_bwd_phase");
 }
 void ppo_clip_adam(at::TensorList state, at::IntArrayRef icfg, at::ArrayRef<double> fcfg, int64_t step_slot, int64_t adam_t,
                    double grad_scale) {
+  igi_kl_stop ks;
+  const bool stopping = split_stop(state, icfg, fcfg, &ks);
   const igi_teacher_cfg c = unpack_cfg(icfg, fcfg);
   const igi_teacher_state s = state_struct(state, c);
   c10::hip::HIPGuardMasqueradingAsCUDA g(state[0].device());
-  rc(igi_teacher_apply(&c, &s, (int)step_slot, adam_t, (float)grad_scale, stream_of(state[0])), "igi_teacher_apply");
+  if (stopping) rc(igi_teacher_apply_ks(&c, &s, &ks, (int)step_slot, adam_t, (float)grad_scale, stream_of(state[0])), "igi_teacher_apply_ks");
+  else rc(igi_teacher_apply(&c, &s, (int)step_slot, adam_t, (float)grad_scale, stream_of(state[0])), "igi_teacher_apply");
 }
 void ppo_update(at::TensorList rollout, at::TensorList state, at::IntArrayRef icfg, at::ArrayRef<double> fcfg, int64_t adam_t0) {
+  igi_kl_stop ks;
+  const bool stopping = split_stop(state, icfg, fcfg, &ks);
   const igi_teacher_cfg c = unpack_cfg(icfg, fcfg);
   const igi_teacher_state s = state_struct(state, c);
   const igi_rollout r = rollout_struct(rollout, c, state[0].device());
   c10::hip::HIPGuardMasqueradingAsCUDA g(state[0].device());
-  rc(igi_teacher_update(&c, &r, &s, adam_t0, stream_of(state[0])), "igi_teacher_update");
+  if (stopping) rc(igi_teacher_update_ks(&c, &r, &s, &ks, adam_t0, stream_of(state[0])), "igi_teacher_update_ks");
+  else rc(igi_teacher_update(&c, &r, &s, adam_t0, stream_of(state[0])), "igi_teacher_update");
 }
 std::tuple<Tensor, Tensor, Tensor> actor_critic_infer(at::TensorList state, at::IntArrayRef icfg, at::ArrayRef<double> fcfg,
                                                       const Tensor& obs, const Tensor& priv, bool normalize, bool want_latent) {

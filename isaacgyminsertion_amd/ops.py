@@ -174,6 +174,40 @@ def _unpack_cfg(icfg, fcfg):
     return c
 
 
+def pack_stop(icfg, fcfg, state, kl_threshold, stop_state):
+    """KL early stopping rides behind everything else in the three lists of ``ppo_minibatch_fwd_bwd``, ``ppo_clip_adam``,
+    ``ppo_update``, ``ppo_update_dp`` and ``ppo_update_dp_rccl``: one trailing int (kl_early_stop = 1), one trailing float (kl_threshold) and one trailing state
+    tensor (stop_state, int32).  Lists of the lengths ``pack_cfg`` / the state fields give mean "off"."""
+    return list(icfg) + [1], list(fcfg) + [float(kl_threshold)], list(state) + [stop_state]
+
+
+def _split_stop(state, icfg, fcfg):
+    """(state, icfg, fcfg, struct igi_kl_stop or None): takes the early-stopping tail off the three lists (13 or 16
+    floats carry it; 12 or 15 do not) and validates it."""
+    if len(fcfg) not in (13, 16):
+        return state, icfg, fcfg, None
+    if len(icfg) < 1 or len(state) < 1 or icfg[-1] != 1 or not fcfg[-1] > 0:
+        raise RuntimeError("teacher cfg: the early-stopping tail needs kl_early_stop == 1, kl_threshold > 0 and the "
+                           "stop_state tensor behind the state list")
+    ks = _lib.KlStop()
+    ks.kl_early_stop, ks.kl_threshold = 1, float(fcfg[-1])
+    stop, state, icfg, fcfg = state[-1], state[:-1], icfg[:-1], fcfg[:-1]
+    M = _lib.IGI_MAX_LAYERS
+    if len(icfg) < 8 + 2 * M or len(state) < 1:
+        raise RuntimeError("teacher cfg: too short for the early-stopping tail")
+    n_env, hor, E = (int(x) for x in icfg[5 + 2 * M:8 + 2 * M])
+    if min(n_env, hor, E) < 1 or n_env * hor < E:
+        raise RuntimeError("teacher cfg: non-positive dimension or unsupported layer count")
+    B = n_env * hor
+    steps = E * (B // (B // E))
+    _check(stop, "state.stop_state", dtype=torch.int32, shape=(_lib.stop_state_words(steps),), device=state[0].device)
+    ks.stop_state = stop.data_ptr()
+    if len(fcfg) == 15 and float(fcfg[12]) != ks.kl_threshold:      # one threshold: the scheduler's is the stop's
+        raise RuntimeError(f"teacher cfg: the early-stopping tail's kl_threshold {ks.kl_threshold} differs from the "
+                           f"adaptive schedule's {fcfg[12]}")
+    return state, icfg, fcfg, ks
+
+
 _STATE_CACHE = {}
 
 
@@ -262,13 +296,19 @@ def ppo_minibatch_fwd_bwd(rollout: Sequence[Tensor], state: Sequence[Tensor], ic
     """One minibatch: gather + normalise, ActorCriticSplit forward, PPO losses + KL, backward into state.grads
     (experience.py:207-226; models_split.py:166-250; frozen_ppo.py:521-584).  phase -1 = whole step; 0 / 1 = the two
     halves of the data-parallel schedule (trunk bucket final after 0) -> igi_teacher_fwd_bwd[_phase]."""
+    state, icfg, fcfg, ks = _split_stop(state, icfg, fcfg)
     cfg, st, dev = _teacher_args(state, icfg, fcfg)
     ro = _rollout_struct(rollout, cfg, dev)
     if phase not in (-1, 0, 1):
         raise RuntimeError(f"phase: expected -1, 0 or 1, got {phase}")
+    if ks is not None and phase >= 0:
+        raise RuntimeError("phase: KL early stopping has no data-parallel phases (phase must be -1)")
     with torch.cuda.device(dev):
         L = _lib.lib()
-        if phase < 0:
+        if ks is not None:
+            _rc(L.igi_teacher_fwd_bwd_ks(C.byref(cfg), C.byref(ro), C.byref(st), C.byref(ks), mb_index, step_slot,
+                                         _stream(state[0])), "igi_teacher_fwd_bwd_ks")
+        elif phase < 0:
             _rc(L.igi_teacher_fwd_bwd(C.byref(cfg), C.byref(ro), C.byref(st), mb_index, step_slot, _stream(state[0])),
                 "igi_teacher_fwd_bwd")
         else:
@@ -281,8 +321,13 @@ def ppo_clip_adam(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequence[f
                   grad_scale: float) -> None:
     """param-norm log + clip_grad_norm_ + Adam on the flat vectors, stats row ``step_slot`` (frozen_ppo.py:605-610);
     grad_scale = 1/world after an all-reduce(SUM) -> igi_teacher_apply."""
+    state, icfg, fcfg, ks = _split_stop(state, icfg, fcfg)
     cfg, st, dev = _teacher_args(state, icfg, fcfg)
     with torch.cuda.device(dev):
+        if ks is not None:
+            _rc(_lib.lib().igi_teacher_apply_ks(C.byref(cfg), C.byref(st), C.byref(ks), step_slot, adam_t,
+                                                float(grad_scale), _stream(state[0])), "igi_teacher_apply_ks")
+            return
         _rc(_lib.lib().igi_teacher_apply(C.byref(cfg), C.byref(st), step_slot, adam_t, float(grad_scale),
                                          _stream(state[0])), "igi_teacher_apply")
 
@@ -292,9 +337,14 @@ def ppo_update(rollout: Sequence[Tensor], state: Sequence[Tensor], icfg: Sequenc
                adam_t0: int) -> None:
     """mini_epochs x n_minibatch optimizer steps enqueued back to back, no host sync (frozen_ppo.py:508-640)
     -> igi_teacher_update."""
+    state, icfg, fcfg, ks = _split_stop(state, icfg, fcfg)
     cfg, st, dev = _teacher_args(state, icfg, fcfg)
     ro = _rollout_struct(rollout, cfg, dev)
     with torch.cuda.device(dev):
+        if ks is not None:
+            _rc(_lib.lib().igi_teacher_update_ks(C.byref(cfg), C.byref(ro), C.byref(st), C.byref(ks), adam_t0,
+                                                 _stream(state[0])), "igi_teacher_update_ks")
+            return
         _rc(_lib.lib().igi_teacher_update(C.byref(cfg), C.byref(ro), C.byref(st), adam_t0, _stream(state[0])),
             "igi_teacher_update")
 
@@ -306,7 +356,8 @@ def register_reducer(fn):
     """fn(bucket, step) -> None: bucket 0 / 1 = start the all-reduce(SUM) of the early / late ranges of state.grads
     (igi_teacher_grad_buckets) without blocking the host; bucket 2 = make the current stream wait for both; bucket 3
     (adaptive learning-rate schedule only, once per mini-epoch) = all-reduce(SUM) the one float of the KL exchange
-    in the order of the current stream.  Returns the handle
+    in the order of the current stream; bucket 4 (KL early stopping only, once per optimizer step, between the norm
+    kernel and the Adam tail) = the same for the one float of the estimator exchange.  Returns the handle
     ``ppo_update_dp`` takes (ops cannot carry Python callables)."""
     h = max(_REDUCERS, default=0) + 1
     _REDUCERS[h] = fn
@@ -322,7 +373,8 @@ def ppo_update_dp(rollout: Sequence[Tensor], state: Sequence[Tensor], icfg: Sequ
                   adam_t0: int, grad_scale: float, reducer: int) -> None:
     """The whole data-parallel update as ONE native call: per optimizer step, trunk backward -> reducer(0) ->
     env_mlp backward -> reducer(1) -> reducer(2) -> clip + Adam with grad_scale = 1/world
-    (frozen_ppo.py:508-640, gradient exchange :586-603) -> igi_teacher_update_dp."""
+    (frozen_ppo.py:508-640, gradient exchange :586-603) -> igi_teacher_update_dp[_ks]."""
+    state, icfg, fcfg, ks = _split_stop(state, icfg, fcfg)
     cfg, st, dev = _teacher_args(state, icfg, fcfg)
     ro = _rollout_struct(rollout, cfg, dev)
     fn = _REDUCERS.get(reducer)
@@ -340,8 +392,12 @@ def ppo_update_dp(rollout: Sequence[Tensor], state: Sequence[Tensor], icfg: Sequ
 
     cb = _lib.REDUCE_FN(trampoline)
     with torch.cuda.device(dev):
-        rc = _lib.lib().igi_teacher_update_dp(C.byref(cfg), C.byref(ro), C.byref(st), adam_t0, float(grad_scale),
-                                              C.cast(cb, C.c_void_p), None, _stream(state[0]))
+        if ks is not None:
+            rc = _lib.lib().igi_teacher_update_dp_ks(C.byref(cfg), C.byref(ro), C.byref(st), C.byref(ks), adam_t0,
+                                                     float(grad_scale), C.cast(cb, C.c_void_p), None, _stream(state[0]))
+        else:
+            rc = _lib.lib().igi_teacher_update_dp(C.byref(cfg), C.byref(ro), C.byref(st), adam_t0, float(grad_scale),
+                                                  C.cast(cb, C.c_void_p), None, _stream(state[0]))
     if err:
         raise err[0]
     _rc(rc, "igi_teacher_update_dp")
@@ -353,7 +409,8 @@ def ppo_update_dp_rccl(rollout: Sequence[Tensor], state: Sequence[Tensor], icfg:
     """The whole data-parallel update as ONE native call with the gradient exchange issued by the library over its
     own RCCL communicator (``comm`` = igi_comm_t handle from utils.dist.NativeComm): per optimizer step phase 0 ->
     all-reduce of the early bucket on the communication stream -> phase 1 -> all-reduce of the late bucket -> clip +
-    Adam with 1/world (frozen_ppo.py:508-640, 586-603) -> igi_teacher_update_dp_rccl."""
+    Adam with 1/world (frozen_ppo.py:508-640, 586-603) -> igi_teacher_update_dp_rccl[_ks]."""
+    state, icfg, fcfg, ks = _split_stop(state, icfg, fcfg)
     cfg, st, dev = _teacher_args(state, icfg, fcfg)
     ro = _rollout_struct(rollout, cfg, dev)
     if comm == 0:
@@ -363,8 +420,13 @@ def ppo_update_dp_rccl(rollout: Sequence[Tensor], state: Sequence[Tensor], icfg:
         if stats_sum.numel() != state[STATE_FIELDS.index("stats")].numel():
             raise RuntimeError("stats_sum: must have the shape of state.stats")
     with torch.cuda.device(dev):
-        rc = _lib.lib().igi_teacher_update_dp_rccl(C.byref(cfg), C.byref(ro), C.byref(st), adam_t0, C.c_void_p(comm),
-                                                   1 if overlap else 0, _p(stats_sum), _stream(state[0]))
+        if ks is not None:
+            rc = _lib.lib().igi_teacher_update_dp_rccl_ks(C.byref(cfg), C.byref(ro), C.byref(st), C.byref(ks), adam_t0,
+                                                          C.c_void_p(comm), 1 if overlap else 0, _p(stats_sum),
+                                                          _stream(state[0]))
+        else:
+            rc = _lib.lib().igi_teacher_update_dp_rccl(C.byref(cfg), C.byref(ro), C.byref(st), adam_t0, C.c_void_p(comm),
+                                                       1 if overlap else 0, _p(stats_sum), _stream(state[0]))
     if rc == -6:
         raise RuntimeError("igi_teacher_update_dp_rccl: RCCL: " +
                            _lib.lib().igi_comm_last_error(C.c_void_p(comm)).decode("utf-8", "replace"))

@@ -97,6 +97,40 @@ def adaptive_lr_rule(lr, kl, kl_threshold, lr_min=1e-6, lr_max=1e-2):
     return new
 
 
+def parse_kl_early_stop(value):
+    """train.ppo.kl_early_stop -> bool (None = absent = off); ValueError for anything that is not a boolean -- a string
+    such as "yes" or a number would otherwise switch it on silently."""
+    if value is None:
+        return False
+    if isinstance(value, bool):
+        return value
+    raise ValueError(f"kl_early_stop {value!r}: expected True or False")
+
+
+def kl_stop_rule(approx_kl, kl_threshold):
+    """The decision the statistics block takes on the device, restated in Python doubles (frozen_ppo.py:578 made live):
+    the fp32 estimator, widened, strictly above 1.5 * kl_threshold."""
+    return float(approx_kl) > 1.5 * float(kl_threshold)
+
+
+def slice_update_lists(stats, mini_epochs, n_mb, stop_step):
+    """The reference's per-update lists from the (steps, 8) statistics rows when optimizer step ``stop_step`` stopped
+    the update (frozen_ppo.py:571-581, 611-630 with the break live); ``None`` = it ran through.  At a stop at step
+    s = e * n_mb + i the losses and grad norms have s entries (appended behind the break), the entropies s + 1 (appended
+    in front of it), and the KL list e + 1: whole mini-epochs' means and, last, the mean over steps (e, 0 .. i).  Rows
+    behind s are never read.  Returns a_losses, c_losses, b_losses, entropies, kls, grad_norms as lists of 0-d tensors."""
+    total = mini_epochs * n_mb
+    s = total if stop_step is None else int(stop_step)
+    if not 0 <= s <= total or (stop_step is not None and s == total):
+        raise ValueError(f"stop_step {stop_step}: expected None or 0 .. {total - 1}")
+    n_ent = s if stop_step is None else s + 1
+    rows = stats[:total]
+    a_losses, c_losses, b_losses = (list(rows[:s, j].unbind()) for j in (0, 1, 2))
+    entropies, grad_norms = list(rows[:n_ent, 3].unbind()), list(rows[:s, 6].unbind())
+    kls = [rows[e * n_mb:min((e + 1) * n_mb, n_ent), 4].mean() for e in range((n_ent + n_mb - 1) // n_mb)]
+    return a_losses, c_losses, b_losses, entropies, kls, grad_norms
+
+
 def make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon, mini_epochs, contact_points=0,
              contact_emb=0, only_contact=False, lr_schedule="fixed", kl_threshold=0.008, lr_min=1e-6, lr_max=1e-2, **hp):
     """contact_points > 0: the teacher with ground-truth contacts (task.env.compute_contact_gt; num_points P,
@@ -154,7 +188,10 @@ def param_layout(cfg):
 class TeacherEngine:
     def __init__(self, num_envs, horizon, mini_epochs, units=(512, 256, 128), priv_units=(256, 128, 8),
                  obs_dim=15, priv_dim=64, act_dim=6, device="cuda:0", perm=None, contact_points=0, contact_emb=0,
-                 only_contact=False, lr_schedule="fixed", kl_threshold=0.008, lr_min=1e-6, lr_max=1e-2, **hp):
+                 only_contact=False, lr_schedule="fixed", kl_threshold=0.008, lr_min=1e-6, lr_max=1e-2,
+                 kl_early_stop=False, **hp):
+        """kl_early_stop: stop an update at the first optimizer step whose approx_kl exceeds 1.5 * kl_threshold, decided
+        on the device (``stop_step``, ``steps_applied``, ``approx_kl()``); data parallel: from the rank-mean estimator."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("TeacherEngine needs a HIP device (there is no CPU path)")
@@ -164,6 +201,10 @@ class TeacherEngine:
                                      only_contact=only_contact, lr_schedule=lr_schedule, kl_threshold=kl_threshold,
                                      lr_min=lr_min, lr_max=lr_max, **hp)
         self.adaptive_lr = bool(self.cfg.lr_schedule)
+        self.kl_early_stop = parse_kl_early_stop(kl_early_stop)
+        self._kl_threshold = float(kl_threshold)
+        if self.kl_early_stop and not self._kl_threshold > 0:
+            raise ValueError("kl_early_stop needs kl_threshold > 0")
         self.contact_points, self.contact_emb, self.only_contact = int(contact_points), int(contact_emb), bool(only_contact)
         self.N, self.T, self.E = num_envs, horizon, mini_epochs
         self.B = num_envs * horizon
@@ -181,7 +222,7 @@ class TeacherEngine:
         self.grads = torch.zeros(self.P, **f32)
         self.adam_m = torch.zeros(self.P, **f32)
         self.adam_v = torch.zeros(self.P, **f32)
-        self.adam_t = 0
+        self._adam_t, self._enqueued, self._stop_words = 0, None, None
         self.rms_obs = self._fresh_rms(obs_dim)
         self.rms_priv = self._fresh_rms(priv_dim)
         self.rms_value = self._fresh_rms(1)
@@ -204,6 +245,11 @@ class TeacherEngine:
         if self.adaptive_lr:
             self.lr_state = torch.zeros(_lib.lr_state_doubles(mini_epochs), dtype=torch.float64, device=dev)
             self.lr_state[0] = self.cfg.lr
+        # KL early stopping: [stop step (-1 = none), reserved, approx_kl per optimizer step] as 32-bit words (igi_kl_stop)
+        self.stop_state = None
+        if self.kl_early_stop:
+            self.stop_state = torch.zeros(_lib.stop_state_words(mini_epochs * self.n_mb), dtype=torch.int32, device=dev)
+            self.stop_state[0] = -1
         if perm is None:
             perm = torch.randperm(self.B, device=dev)          # experience.py:202, drawn once
         self.perm = perm.to(device=dev, dtype=torch.int64).contiguous()
@@ -237,6 +283,83 @@ class TeacherEngine:
         """The sixteen tensors of struct igi_teacher_state, in field order (+ lr_state under the adaptive schedule)."""
         st = [getattr(self, k) for k in ops.STATE_FIELDS]
         return st + [self.lr_state] if self.adaptive_lr else st
+
+    # ---- KL early stopping ---------------------------------------------------------------------
+    @property
+    def kl_threshold(self):
+        """The ONE threshold: the early stop compares against 1.5 x it and, under ``lr_schedule="adaptive"``, the
+        scheduler against 0.5 x and 2 x it -- setting it here sets the cfg's field too."""
+        return self._kl_threshold
+
+    @kl_threshold.setter
+    def kl_threshold(self, thr):
+        thr = float(thr)
+        if (self.kl_early_stop or self.adaptive_lr) and not thr > 0:
+            raise ValueError("kl_threshold must be > 0")
+        self._kl_threshold = thr
+        if self.adaptive_lr:
+            self.cfg.kl_threshold = thr
+
+    def _stop_record(self):
+        """The stop record of the last update as CPU int32 words, read from the device ONCE per update (the read
+        synchronises; trainers make it next to the statistics read): ``stop_step``, ``steps_applied``, ``approx_kl()``
+        and ``adam_t`` all derive from this one copy.  Enqueueing anything that writes the record drops the copy."""
+        if self._stop_words is None:
+            self._stop_words = self.stop_state.cpu()
+        return self._stop_words
+
+    @property
+    def adam_t(self):
+        """Optimizer steps applied so far.  After an update with ``kl_early_stop`` the host does not know it until it has
+        read the stop record: the first look after such an update uses ``_stop_record``."""
+        if self._enqueued is not None:
+            base, n = self._enqueued
+            s = int(self._stop_record()[0])
+            self._adam_t, self._enqueued = base + (s if 0 <= s < n else n), None
+        return self._adam_t
+
+    @adam_t.setter
+    def adam_t(self, t):
+        self._adam_t, self._enqueued = int(t), None
+
+    @property
+    def stop_step(self):
+        """The optimizer step that stopped the last update (it and every later one were not applied), or None when the
+        update ran through -- always None without ``kl_early_stop``."""
+        if not self.kl_early_stop:
+            return None
+        s = int(self._stop_record()[0])
+        return s if s >= 0 else None
+
+    @property
+    def steps_applied(self):
+        """Optimizer steps the last update applied: ``stop_step``, or all E * n_mb of them."""
+        s = self.stop_step
+        return self.E * self.n_mb if s is None else s
+
+    def approx_kl(self):
+        """The estimator mean((exp(d) - 1) - d), d = neglogp_new - neglogp_old, of every optimizer step the last update
+        evaluated -- ``stop_step`` + 1 of them, or all -- as a float32 CPU tensor (data parallel: the rank mean)."""
+        if not self.kl_early_stop:
+            raise RuntimeError("approx_kl: the engine was built without kl_early_stop")
+        w = self._stop_record()
+        s = int(w[0])
+        return w[2:].view(torch.float32)[:(s + 1 if s >= 0 else self.E * self.n_mb)].clone()
+
+    def _stop_args(self):
+        """(state list, icfg, fcfg) of the three ops that take the early-stopping tail."""
+        icfg, fcfg = self._cfg_args()
+        if not self.kl_early_stop:
+            return self.state_list(), icfg, fcfg
+        self._stop_words = None          # what is about to be enqueued rewrites the record
+        icfg, fcfg, st = ops.pack_stop(icfg, fcfg, self.state_list(), self.kl_threshold, self.stop_state)
+        return st, icfg, fcfg
+
+    def _no_stop_dp(self, what):
+        if self.kl_early_stop:
+            raise RuntimeError(f"{what}: with kl_early_stop the ranks exchange the estimator between the norm kernel and "
+                               "the Adam tail, which the step-wise two-phase loop has no place for: use update_dp / "
+                               "update_dp_native")
 
     # ---- learning rate -------------------------------------------------------------------------
     @property
@@ -291,7 +414,8 @@ class TeacherEngine:
         trials = int(os.environ.get("IGI_WS_TRIALS", "6")) if trials is None else int(trials)
         if trials <= 1 or self._ro is None or self.device.type != "cuda":
             return None
-        keys = [k for k in ops.STATE_FIELDS if k not in ("perm", "workspace")] + (["lr_state"] if self.adaptive_lr else [])
+        keys = [k for k in ops.STATE_FIELDS if k not in ("perm", "workspace")] + (["lr_state"] if self.adaptive_lr else []) \
+            + (["stop_state"] if self.kl_early_stop else [])
         snap = {k: getattr(self, k).clone() for k in keys}
         t0, cfg0 = self.adam_t, (self.cfg.gamma, self.cfg.tau, self.cfg.lr)
         cands = [self.workspace]
@@ -324,7 +448,7 @@ class TeacherEngine:
         finally:
             for k in keys:
                 getattr(self, k).copy_(snap[k])
-            self.adam_t = t0
+            self.adam_t, self._stop_words = t0, None
             self.cfg.gamma, self.cfg.tau, self.cfg.lr = cfg0
             self.workspace = cands[0]
         if len(times) == len(cands) and all(t > 0 for t in times):
@@ -340,11 +464,12 @@ class TeacherEngine:
         torch.ops.mi355ppo.gae_advnorm(self._ro, self.state_list(), *self._cfg_args(), bool(self.hp["normalize_value"]))
 
     def fwd_bwd(self, mb_index, slot):
-        torch.ops.mi355ppo.ppo_minibatch_fwd_bwd(self._ro, self.state_list(), *self._cfg_args(), mb_index, slot, -1)
+        torch.ops.mi355ppo.ppo_minibatch_fwd_bwd(self._ro, *self._stop_args(), mb_index, slot, -1)
 
     def fwd_bwd_phase(self, mb_index, slot, phase):
         """Phase 0: down to dZ of the first trunk layer (the EARLY gradient bucket is final); phase 1: latent + env_mlp
         backward and the first trunk layer's weight gradient (the LATE bucket is final).  See ``grad_buckets``."""
+        self._no_stop_dp("fwd_bwd_phase")
         torch.ops.mi355ppo.ppo_minibatch_fwd_bwd(self._ro, self.state_list(), *self._cfg_args(), mb_index, slot, phase)
 
     @property
@@ -364,15 +489,29 @@ class TeacherEngine:
         return [self.grads[o:o + n] for o, n in early], [self.grads[o:o + n] for o, n in late]
 
     def apply(self, slot, grad_scale=1.0):
+        if self.kl_early_stop:
+            # steps 0 .. slot of this update are enqueued; how many of them the device applied, the stop word says
+            base = self.adam_t if slot == 0 or self._enqueued is None else self._enqueued[0]
+            torch.ops.mi355ppo.ppo_clip_adam(*self._stop_args(), slot, base + slot + 1, float(grad_scale))
+            self._enqueued = (base, slot + 1)
+            return
         self.adam_t += 1
         torch.ops.mi355ppo.ppo_clip_adam(self.state_list(), *self._cfg_args(), slot, self.adam_t, float(grad_scale))
 
     def update(self):
         """mini_epochs x n_minibatch optimizer steps enqueued back to back (frozen_ppo.py:508-640).
         Returns the (E*n_mb, 8) stats tensor (device; no host sync here)."""
-        torch.ops.mi355ppo.ppo_update(self._ro, self.state_list(), *self._cfg_args(), self.adam_t)
-        self.adam_t += self.E * self.n_mb
+        t0 = self.adam_t
+        torch.ops.mi355ppo.ppo_update(self._ro, *self._stop_args(), t0)
+        self._count_update(t0)
         return self.stats
+
+    def _count_update(self, t0):
+        """A whole update was enqueued from step count t0: with kl_early_stop the first look at adam_t resolves it."""
+        if self.kl_early_stop:
+            self._enqueued = (t0, self.E * self.n_mb)
+        else:
+            self.adam_t = t0 + self.E * self.n_mb
 
     def update_dp(self, all_reduce, world_size, all_reduce_async=None):
         """Same loop with a gradient all-reduce between backward and the optimizer
@@ -386,9 +525,15 @@ class TeacherEngine:
         early, late = self.bucket_views()
         pending = []
         kl_view = self.lr_state.view(torch.float32)[2:3] if self.adaptive_lr else None   # the float of lr_state[1]
+        akl_view = self.stop_state.view(torch.float32)[1:2] if self.kl_early_stop else None   # the float of stop_state[1]
 
         def reducer(bucket, step):
-            if bucket == 3:                   # adaptive schedule: the mini-epoch's KL, one float, in stream order
+            if bucket == 4:                   # KL early stopping: the step's estimator, one float, in stream order
+                if all_reduce_async is not None:
+                    all_reduce_async(akl_view).wait()
+                else:
+                    all_reduce(akl_view)
+            elif bucket == 3:                   # adaptive schedule: the mini-epoch's KL, one float, in stream order
                 if all_reduce_async is not None:
                     all_reduce_async(kl_view).wait()
                 else:
@@ -406,11 +551,11 @@ class TeacherEngine:
 
         h = ops.register_reducer(reducer)
         try:
-            torch.ops.mi355ppo.ppo_update_dp(self._ro, self.state_list(), *self._cfg_args(), self.adam_t,
-                                             1.0 / world_size, h)
+            t0 = self.adam_t
+            torch.ops.mi355ppo.ppo_update_dp(self._ro, *self._stop_args(), t0, 1.0 / world_size, h)
         finally:
             ops.unregister_reducer(h)
-        self.adam_t += self.E * self.n_mb
+        self._count_update(t0)
         return self.stats
 
     def update_dp_native(self, comm, overlap=True, want_stats_sum=False):
@@ -418,9 +563,9 @@ class TeacherEngine:
         (``utils.dist.NativeComm``): one native call, no callback -- igi_teacher_update_dp_rccl.  ``want_stats_sum``:
         also returns the per-step statistics summed over the ranks (one collective per update)."""
         stats_sum = torch.empty_like(self.stats) if want_stats_sum else None
-        torch.ops.mi355ppo.ppo_update_dp_rccl(self._ro, self.state_list(), *self._cfg_args(), self.adam_t,
-                                              int(comm.handle), bool(overlap), stats_sum)
-        self.adam_t += self.E * self.n_mb
+        t0 = self.adam_t
+        torch.ops.mi355ppo.ppo_update_dp_rccl(self._ro, *self._stop_args(), t0, int(comm.handle), bool(overlap), stats_sum)
+        self._count_update(t0)
         return (self.stats, stats_sum) if want_stats_sum else self.stats
 
     def infer(self, obs, priv, want_latent=False, normalize=True):

@@ -6,6 +6,7 @@
         train.load_path=outputs/.../stage1_nn/last.pth train.ppo.tactile_info=True
     python -m isaacgyminsertion_amd.train test=True train.load_path=.../stage1_nn/last.pth
     python -m isaacgyminsertion_amd.train train.ppo.lr_schedule=adaptive train.ppo.kl_threshold=0.008
+    python -m isaacgyminsertion_amd.train train.ppo.kl_early_stop=True train.ppo.kl_threshold=0.008
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m isaacgyminsertion_amd.train train.ppo.multi_gpu=True
 
 rank / device / seed selection, ``offline_training`` -> ``Runner.run()``, environment construction, the
@@ -52,8 +53,9 @@ def build_config(config=None, overrides=()):
     # interpolations the reference resolves through Hydra (cfg/train/...PPOv2.yaml:17, cfg/config.yaml)
     cfg.train.ppo.num_actors = cfg.task.env.numEnvs
     cfg.train.ppo.multi_gpu = bool(cfg.train.ppo.multi_gpu or cfg.get('multi_gpu', False))
-    from .teacher_native import lr_schedule_id
+    from .teacher_native import lr_schedule_id, parse_kl_early_stop
     lr_schedule_id(cfg.train.ppo.get('lr_schedule', None))     # "fixed" | "adaptive": anything else stops here
+    parse_kl_early_stop(cfg.train.ppo.get('kl_early_stop', None))     # True | False: anything else stops here
     return cfg
 
 

@@ -48,7 +48,7 @@ def default_config(num_envs=4096, horizon_length=32, rl_device="cuda:0", multi_g
         "output_name": "debug", "multi_gpu": multi_gpu, "normalize_input": True, "normalize_value": True,
         "value_bootstrap": True, "shared_parameters": False, "num_actors": num_envs,
         "normalize_advantage": True, "gamma": 0.99, "tau": 0.95, "learning_rate": 2.5e-4,
-        "kl_threshold": 0.02, "lr_schedule": "fixed", "horizon_length": horizon_length, "mini_epochs": 8, "minibatch_size": 24,
+        "kl_threshold": 0.02, "lr_schedule": "fixed", "kl_early_stop": False, "horizon_length": horizon_length, "mini_epochs": 8, "minibatch_size": 24,
         "clip_value": True, "critic_coef": 4, "entropy_coef": 0.0, "e_clip": 0.2, "bounds_loss_coef": 1e-4,
         "truncate_grads": True, "grad_norm": 1, "save_best_after": 1000000, "save_frequency": 100,
         "max_agent_steps": 1500000000, "priv_info": True, "priv_info_dim": 64, "compute_contact_gt": False,
