@@ -149,16 +149,51 @@ static int comm_reduce_ranges(igi_comm* c, float* grads, const long long* off, c
 }
 
 // The whole data-parallel update as one host call with the gradient exchange issued natively (see the header of this
-// file).  stats_sum (optional, E * n_mb * IGI_STATS_PER_STEP floats): the per-step statistics summed over the ranks
-// (the KL all-reduce of frozen_ppo.py:624-627 and the loss aggregation of :387-396 ride here, once per update, on the
-// communication stream behind the last step's collectives); the per-rank values stay in st->stats.
-struct StopRcclCtx { igi_comm* cm; float* scratch; hipStream_t s; };
-// KL early stopping: the estimator's float on the COMPUTE stream, behind the join of the step's gradient collectives (the
-// rule the rate's float follows): the communicator never has collectives in flight on two streams
-static int stop_exchange_rccl(void* ctx, int) {
-  StopRcclCtx* x = static_cast<StopRcclCtx*>(ctx);
-  return comm_all_reduce_sum(x->cm, x->scratch, 1, x->s);
+// file): teacher_update_steps with the exchange below.  s is the compute stream of the update.
+struct RcclExchange {
+  igi_comm* cm;
+  const igi_teacher_state* st;
+  const igi_kl_stop* ks;
+  GradBuckets gb;
+  long long P;
+  bool overlap;
+  hipStream_t s;
+};
+static int rccl_exchange(void* ctx, int bucket, int slot) {
+  const RcclExchange* r = static_cast<const RcclExchange*>(ctx);
+  igi_comm* cm = r->cm;
+  float* grads = r->st->grads;
+  hipEvent_t* ev = cm->ev[slot & 1];
+  int rc;
+  switch (bucket) {
+    case XB_EARLY:   // overlap only
+      IGI_HIP_TRY(hipEventRecord(ev[0], r->s));
+      IGI_HIP_TRY(hipStreamWaitEvent(cm->stream, ev[0], 0));
+      if ((rc = comm_reduce_ranges(cm, grads, r->gb.off, r->gb.len, 2, cm->stream))) return rc;
+      IGI_HIP_TRY(hipEventRecord(ev[2], cm->stream));
+      return 0;
+    case XB_LATE:
+      if (!r->overlap) return comm_all_reduce_sum(cm, grads, r->P, r->s);
+      // the late bucket is on the critical path whatever stream carries it: it goes out on the compute stream (no
+      // cross-stream hop behind phase 1; measured on a one-rank communicator: both buckets on the communication
+      // stream cost 34 us per step of event hand-offs).  The compute stream joins the early bucket -- which finished
+      // under phase 1 -- FIRST: two collectives of one communicator are then never in flight on two streams at once
+      // (RCCL serialises a communicator's launches internally; the explicit order does not rely on it)
+      IGI_HIP_TRY(hipStreamWaitEvent(r->s, ev[2], 0));
+      return comm_reduce_ranges(cm, grads, r->gb.off + 2, r->gb.len + 2, 2, r->s);
+    case XB_JOIN:    // XB_LATE joined the early bucket and ran on the compute stream itself
+      return 0;
+    // One float on the COMPUTE stream.  Both gradient collectives of this step were joined on `s` before Adam and the
+    // next one on the communication stream waits for an event recorded on `s` after phase 0 of the next step: the
+    // communicator never has collectives in flight on two streams.
+    case XB_KL: return comm_all_reduce_sum(cm, reinterpret_cast<float*>(r->st->lr_state + 1), 1, r->s);
+    case XB_ESTIMATOR: return comm_all_reduce_sum(cm, reinterpret_cast<float*>(r->ks->stop_state) + 1, 1, r->s);
+  }
+  return IGI_E_BADARG;
 }
+// stats_sum (optional, E * n_mb * IGI_STATS_PER_STEP floats): the per-step statistics summed over the ranks (the KL
+// all-reduce of frozen_ppo.py:624-627 and the loss aggregation of :387-396 ride here, once per update, on the compute
+// stream behind the last step); the per-rank values stay in st->stats.
 static int teacher_update_dp_rccl(const igi_teacher_cfg* c, const igi_rollout* ro, const igi_teacher_state* st,
                                   int64_t adam_t0, igi_comm* cm, int overlap, float* stats_sum, hipStream_t s,
                                   const igi_kl_stop* ks = nullptr) {
@@ -168,60 +203,11 @@ static int teacher_update_dp_rccl(const igi_teacher_cfg* c, const igi_rollout* r
   if (rc) return rc;
   if ((rc = check_state(p, st))) return rc;
   if (!st->grads) return IGI_E_BADARG;
-  const bool stopping = kl_stop_on(ks);
-  const int32_t* stop = stopping ? ks->stop_state : nullptr;
-  StopLookahead look;
-  if (stopping) {
-    if ((rc = check_ks(ks, st, c)) || (rc = look.begin(ks))) return rc;
-  }
-  StopRcclCtx sctx{cm, stopping ? reinterpret_cast<float*>(ks->stop_state) + 1 : nullptr, s};
-  const StopExchange xch{stop_exchange_rccl, &sctx, cm->world};
-  const float scale = 1.0f / (float)cm->world;
-  const GradBuckets gb = grad_buckets(p);
-  const int total = p.E * p.nmb;
-  int slot = 0;
-  for (int e = 0; e < p.E; ++e) {
-    for (int i = 0; i < p.nmb; ++i, ++slot) {
-      const bool skip_gather = slot > 0;   // the previous step's fused tail gathered this minibatch
-      if (overlap) {
-        hipEvent_t* ev = cm->ev[slot & 1];
-        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 0, skip_gather, ks))) return rc;
-        IGI_HIP_TRY(hipEventRecord(ev[0], s));
-        IGI_HIP_TRY(hipStreamWaitEvent(cm->stream, ev[0], 0));
-        if ((rc = comm_reduce_ranges(cm, st->grads, gb.off, gb.len, 2, cm->stream))) return rc;
-        IGI_HIP_TRY(hipEventRecord(ev[2], cm->stream));
-        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 1, false, ks))) return rc;
-        // the late bucket is on the critical path whatever stream carries it: it goes out on the compute stream (no
-        // cross-stream hop behind phase 1; measured on a one-rank communicator: both buckets on the communication
-        // stream cost 34 us per step of event hand-offs).  The compute stream joins the early bucket -- which finished
-        // under phase 1 -- FIRST: two collectives of one communicator are then never in flight on two streams at once
-        // (RCCL serialises a communicator's launches internally; the explicit order does not rely on it)
-        IGI_HIP_TRY(hipStreamWaitEvent(s, ev[2], 0));
-        if ((rc = comm_reduce_ranges(cm, st->grads, gb.off + 2, gb.len + 2, 2, s))) return rc;
-      } else {
-        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, -1, skip_gather, ks))) return rc;
-        if ((rc = comm_all_reduce_sum(cm, st->grads, p.P, s))) return rc;
-      }
-      const bool more = slot + 1 < total;
-      if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, scale, s, more ? ro : nullptr, (slot + 1) % p.nmb,
-                              slot + 1, /*schedule_here=*/false, ks, stopping ? &xch : nullptr)))
-        return rc;
-      if (lr_adaptive(c) && i == p.nmb - 1) {
-        // adaptive schedule: the rank-mean KL of the mini-epoch (frozen_ppo.py:625-627) as ONE float on the compute
-        // stream.  Both gradient collectives of this step were joined on `s` before Adam and the next one on the
-        // communication stream waits for an event recorded on `s` after phase 0 of the next step: the communicator
-        // never has collectives in flight on two streams.  Every rank then takes the same decision.
-        if ((rc = teacher_lr_exchange_begin(c, p, st, slot, s, stop))) return rc;
-        if ((rc = comm_all_reduce_sum(cm, reinterpret_cast<float*>(st->lr_state + 1), 1, s))) return rc;
-        if ((rc = teacher_lr_exchange_end(c, p, st, slot, cm->world, s, stop))) return rc;
-      }
-    }
-    bool stopped;   // every rank reads the same word behind the same mini-epoch
-    if ((rc = look.after_mini_epoch(e, p.E, s, &stopped))) return rc;
-    if (stopped) break;
-  }
+  RcclExchange r{cm, st, ks, grad_buckets(p), p.P, overlap != 0, s};
+  const UpdateExchange x{cm->world, 1.0f / (float)cm->world, r.overlap, /*foreign=*/false, &r, rccl_exchange};
+  if ((rc = teacher_update_steps(c, p, ro, st, adam_t0, s, ks, &x))) return rc;
   if (stats_sum && st->stats) {
-    const size_t n = (size_t)total * IGI_STATS_PER_STEP;
+    const size_t n = (size_t)p.E * p.nmb * IGI_STATS_PER_STEP;
     IGI_HIP_TRY(hipMemcpyAsync(stats_sum, st->stats, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if ((rc = comm_all_reduce_sum(cm, stats_sum, (long long)n, s))) return rc;
   }

@@ -344,7 +344,7 @@ int igi_teacher_fwd_bwd_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, co
 }
 int igi_teacher_apply_ks(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const igi_kl_stop* ks, int step_slot,
                          int64_t adam_t, float grad_scale, igi_stream_t stream) {
-  return fail(igi::teacher_apply(cfg, st, step_slot, adam_t, grad_scale, S(stream), nullptr, 0, 0, true, ks),
+  return fail(igi::teacher_apply(cfg, st, step_slot, adam_t, grad_scale, S(stream), nullptr, 0, 0, ks),
               "igi_teacher_apply_ks");
 }
 int igi_teacher_update_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,

@@ -1292,9 +1292,27 @@ static int check_ks(const igi_kl_stop* ks, const igi_teacher_state* st, const ig
   if (c->lr_schedule != 0 && c->kl_threshold != ks->kl_threshold) return IGI_E_BADARG;
   return 0;
 }
-// the data-parallel updates' exchange of the estimator: called between the statistics block and the decision kernel,
-// it all-reduces (SUM) the scratch float in the order of the stream
-struct StopExchange { int (*fn)(void* ctx, int slot); void* ctx; int world; };
+// What a data-parallel update puts between the stages of an optimizer step (teacher_update_steps).  One hook, called
+// with the bucket of igi_reduce_fn's protocol, everything in the order of the update's stream:
+enum ExchangeBucket {
+  XB_EARLY = 0,      // behind phase 0 (two_phase only): start the all-reduce of the early ranges
+  XB_LATE = 1,       // behind phase 1 / behind the whole fwd_bwd: the late ranges / the whole flat gradient
+  XB_JOIN = 2,       // ahead of teacher_apply: the stream waits for what XB_EARLY and XB_LATE started
+  XB_KL = 3,         // all-reduce (SUM) the mini-epoch KL, the float at st->lr_state + 1, between the scheduler's halves
+  XB_ESTIMATOR = 4,  // all-reduce (SUM) the step's estimator, the float at ks->stop_state + 1, between k_sumsq_stats
+};                   // and k_stop_decide
+struct UpdateExchange {
+  int world;         // ranks; < 1 = unknown, refused where the schedule or the stop divides by it
+  float grad_scale;  // 1 / world, folded into the Adam kernel
+  bool two_phase;    // fwd_bwd in two phases with XB_EARLY between them
+  bool foreign;      // fn is a caller's callback: whatever it returns but 0 is IGI_E_CALLBACK; else fn returns our codes
+  void* ctx;
+  igi_reduce_fn fn;  // (ctx, bucket, slot)
+};
+static inline int exchange(const UpdateExchange* x, int bucket, int slot) {
+  const int rc = x->fn(x->ctx, bucket, slot);
+  return rc && x->foreign ? IGI_E_CALLBACK : rc;
+}
 
 static int teacher_prepare(const igi_teacher_cfg* c, const igi_rollout* ro,
                            const igi_teacher_state* st, int normalize_value, hipStream_t s) {
@@ -2086,26 +2104,32 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   return (int)hipGetLastError();
 }
 
-// The scheduler launch behind the last optimizer step (step_slot) of a mini-epoch; mode as k_lr_schedule takes it.
+// The scheduler launch behind the last optimizer step (step_slot) of a mini-epoch; the modes are k_lr_schedule's.
+enum LrMode {
+  LR_SINGLE = 0,  // one rank: mean and decision
+  LR_BEGIN = 1,   // data parallel, ahead of the exchange: this rank's mini-epoch KL into the scratch float
+  LR_END = 2,     // data parallel, behind it: the decision from the rank sum
+};
 static int teacher_lr_schedule(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_teacher_state* st, int step_slot,
-                               int mode, int world, hipStream_t s, const int32_t* stop = nullptr) {
+                               LrMode mode, int world, hipStream_t s, const int32_t* stop) {
   const int e = step_slot / p.nmb;
   if (e >= p.E || step_slot % p.nmb != p.nmb - 1) return IGI_E_BADARG;
   const float* rows = st->stats + (long long)e * p.nmb * IGI_STATS_PER_STEP;
   ProfScope ps(PC_LR_SCHEDULE, s, 0.0, 4.0 * p.nmb + 32.0);
-  IGI_LAUNCH(k_lr_schedule, dim3(1), dim3(64), 0, s, rows, p.nmb, e, mode, world, c->kl_threshold, c->lr_min, c->lr_max,
+  IGI_LAUNCH(k_lr_schedule, dim3(1), dim3(64), 0, s, rows, p.nmb, e, (int)mode, world, c->kl_threshold, c->lr_min, c->lr_max,
              st->lr_state, stop);
   return (int)hipGetLastError();
 }
 
 // next_ro != NULL: fuse the gather + normalise of optimizer step (next_mb, next_slot) into this step's Adam launch
 // (k_sumsq_stats computes both norms and the statistics row first)
-// schedule_here: with the adaptive schedule, run the (single-rank) scheduler when step_slot ends a mini-epoch; the
-// data-parallel updates pass false and put their KL exchange between the two halves themselves
+// x == NULL (one rank): with the adaptive schedule, run the scheduler when step_slot ends a mini-epoch.  x != NULL (data
+// parallel): the stop decides on the rank mean of the estimator, exchanged here; the scheduler is left to
+// teacher_update_steps, which puts the KL exchange between its two halves
 static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, int step_slot,
                          int64_t adam_t, float grad_scale, hipStream_t s, const igi_rollout* next_ro = nullptr,
-                         int next_mb = 0, int next_slot = 0, bool schedule_here = true,
-                         const igi_kl_stop* ks = nullptr, const StopExchange* xch = nullptr) {
+                         int next_mb = 0, int next_slot = 0, const igi_kl_stop* ks = nullptr,
+                         const UpdateExchange* x = nullptr) {
   TeacherPlan p;
   int rc = make_plan(c, &p);
   if (rc) return rc;
@@ -2115,7 +2139,8 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
   const bool adaptive = lr_adaptive(c);
   int32_t* stop = kl_stop_on(ks) ? ks->stop_state : nullptr;
   if ((adaptive || stop) && (step_slot < 0 || step_slot >= p.E * p.nmb)) return IGI_E_BADARG;
-  const bool sched = adaptive && schedule_here && step_slot % p.nmb == p.nmb - 1;
+  const bool sched = adaptive && !x && step_slot % p.nmb == p.nmb - 1;
+  const bool exchanged = stop && x;
   if (!st->grads || !st->adam_m || !st->adam_v || adam_t < 1) return IGI_E_BADARG;
   double* part = wsp<double>(st, p.w_sumsq);
   float* row = st->stats ? st->stats + (long long)step_slot * IGI_STATS_PER_STEP : nullptr;
@@ -2123,13 +2148,13 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
     ProfScope ps(PC_SUMSQ, s, 0.0, 8.0 * (double)p.P);
     IGI_LAUNCH(k_sumsq_stats, dim3(SUMSQ_BLOCKS + (row ? 1 : 0)), dim3(256), 0, s, st->grads,
                        st->params, p.P, grad_scale, part, wsp<double>(st, p.w_loss_part), p.loss_blocks,
-                       p.mb, row, StopArgs{stop, step_slot, stop ? 1.5 * ks->kl_threshold : 0.0, xch ? 1 : 0});
+                       p.mb, row, StopArgs{stop, step_slot, stop ? 1.5 * ks->kl_threshold : 0.0, exchanged ? 1 : 0});
   }
-  if (stop && xch) {   // data parallel: the rank-mean estimator decides, between the norms and the Adam tail
-    if (xch->world < 1) return IGI_E_BADARG;
-    if (xch->fn(xch->ctx, step_slot)) return IGI_E_CALLBACK;
+  if (exchanged) {   // data parallel: the rank-mean estimator decides, between the norms and the Adam tail
+    if (x->world < 1) return IGI_E_BADARG;
+    if ((rc = exchange(x, XB_ESTIMATOR, step_slot))) return rc;
     ProfScope ps(PC_LR_SCHEDULE, s, 0.0, 16.0);
-    IGI_LAUNCH(k_stop_decide, dim3(1), dim3(64), 0, s, stop, step_slot, xch->world, 1.5 * ks->kl_threshold);
+    IGI_LAUNCH(k_stop_decide, dim3(1), dim3(64), 0, s, stop, step_slot, x->world, 1.5 * ks->kl_threshold);
     if ((rc = (int)hipGetLastError())) return rc;
   }
   // torch.optim.Adam (_single_tensor_adam): python-double scalars, cast to fp32 at the tensor op
@@ -2166,17 +2191,7 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
                        (const int32_t*)stop);
     if ((rc = (int)hipGetLastError())) return rc;
   }
-  return sched ? teacher_lr_schedule(c, p, st, step_slot, 0, 1, s, stop) : 0;
-}
-
-// data-parallel updates: this rank's mini-epoch KL into the exchange scratch / the decision from the rank sum
-static int teacher_lr_exchange_begin(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_teacher_state* st, int slot,
-                                     hipStream_t s, const int32_t* stop = nullptr) {
-  return teacher_lr_schedule(c, p, st, slot, 1, 1, s, stop);
-}
-static int teacher_lr_exchange_end(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_teacher_state* st, int slot,
-                                   int world, hipStream_t s, const int32_t* stop = nullptr) {
-  return teacher_lr_schedule(c, p, st, slot, 2, world, s, stop);
+  return sched ? teacher_lr_schedule(c, p, st, step_slot, LR_SINGLE, 1, s, stop) : 0;
 }
 
 // KL early stopping, host side of the one-call updates: what reads the stop word while an update is being enqueued.
@@ -2237,29 +2252,46 @@ struct StopLookahead {
   }
 };
 
+// The minibatch loop of the three one-call updates, p = make_plan(c): E mini-epochs x n_mb optimizer steps enqueued back
+// to back on s (frozen_ppo.py:508-640).  x == NULL: one rank.  x != NULL: data parallel, the ranks' exchange goes
+// through x between the stages of a step (the gradient exchange of :586-603, the KL float of :625-627), bucket by bucket.
 // ks on: the device gates every step behind the stop on its own (exact at step granularity, no host involved); the
 // host only stops ENQUEUEING, with one mini-epoch of look-ahead: mini-epoch e + 1 is in the queue before it waits for
 // the event behind mini-epoch e and reads the word through the copy stream, which waits for that event alone -- never
-// for the look-ahead work.  One host wait per mini-epoch; with the switch off there is none, as before.
-static int teacher_update(const igi_teacher_cfg* c, const igi_rollout* ro,
-                          const igi_teacher_state* st, int64_t adam_t0, hipStream_t s, const igi_kl_stop* ks = nullptr) {
-  TeacherPlan p;
-  int rc = make_plan(c, &p);
-  if (rc) return rc;
+// for the look-ahead work.  One host wait per mini-epoch; with the switch off there is none.  Data parallel, every
+// rank reads the same word behind the same mini-epoch: all stop enqueueing at one boundary.
+static int teacher_update_steps(const igi_teacher_cfg* c, const TeacherPlan& p, const igi_rollout* ro,
+                                const igi_teacher_state* st, int64_t adam_t0, hipStream_t s, const igi_kl_stop* ks,
+                                const UpdateExchange* x) {
+  int rc;
   const int total = p.E * p.nmb;
   StopLookahead look;
   if (kl_stop_on(ks)) {
     if ((rc = check_state(p, st)) || (rc = check_ks(ks, st, c)) || (rc = look.begin(ks))) return rc;
   }
+  const int32_t* stop = kl_stop_on(ks) ? ks->stop_state : nullptr;
   int slot = 0;
   for (int e = 0; e < p.E; ++e) {
     for (int i = 0; i < p.nmb; ++i, ++slot) {
-      // from the second step on the minibatch was gathered by the previous step's fused tail
-      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, -1, slot > 0, ks))) return rc;
+      const bool gathered = slot > 0;   // by the previous step's fused tail
+      if (x && x->two_phase) {
+        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 0, gathered, ks))) return rc;
+        if ((rc = exchange(x, XB_EARLY, slot))) return rc;
+        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 1, false, ks))) return rc;
+      } else {
+        if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, -1, gathered, ks))) return rc;
+      }
+      if (x && ((rc = exchange(x, XB_LATE, slot)) || (rc = exchange(x, XB_JOIN, slot)))) return rc;
       const bool more = slot + 1 < total;
-      if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, 1.0f, s, more ? ro : nullptr, (slot + 1) % p.nmb,
-                              slot + 1, /*schedule_here=*/true, ks)))
+      if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, x ? x->grad_scale : 1.0f, s, more ? ro : nullptr,
+                              (slot + 1) % p.nmb, slot + 1, ks, x)))
         return rc;
+      if (x && lr_adaptive(c) && i == p.nmb - 1) {
+        // the rank-mean KL of the mini-epoch (frozen_ppo.py:625-627): every rank then takes the same decision
+        if ((rc = teacher_lr_schedule(c, p, st, slot, LR_BEGIN, 1, s, stop))) return rc;
+        if ((rc = exchange(x, XB_KL, slot))) return rc;
+        if ((rc = teacher_lr_schedule(c, p, st, slot, LR_END, x->world, s, stop))) return rc;
+      }
     }
     bool stopped;
     if ((rc = look.after_mini_epoch(e, p.E, s, &stopped))) return rc;
@@ -2268,54 +2300,25 @@ static int teacher_update(const igi_teacher_cfg* c, const igi_rollout* ro,
   return 0;
 }
 
-// data-parallel update: the same 64 steps with the two-bucket gradient exchange driven through a callback
-// (frozen_ppo.py:586-603); one host call per update, the callback only enqueues collectives / stream waits
-struct ReduceCtx { igi_reduce_fn reduce; void* user; };
-static int stop_exchange_callback(void* ctx, int slot) {   // bucket 4: the one float of the estimator exchange
-  ReduceCtx* r = static_cast<ReduceCtx*>(ctx);
-  return r->reduce(r->user, 4, slot);
+static int teacher_update(const igi_teacher_cfg* c, const igi_rollout* ro,
+                          const igi_teacher_state* st, int64_t adam_t0, hipStream_t s, const igi_kl_stop* ks = nullptr) {
+  TeacherPlan p;
+  const int rc = make_plan(c, &p);
+  return rc ? rc : teacher_update_steps(c, p, ro, st, adam_t0, s, ks, nullptr);
 }
+
+// data-parallel update: the same steps with the two-bucket gradient exchange driven through a callback, which sees the
+// buckets as they are; one host call per update, the callback only enqueues collectives / stream waits
 static int teacher_update_dp(const igi_teacher_cfg* c, const igi_rollout* ro, const igi_teacher_state* st,
                              int64_t adam_t0, float grad_scale, igi_reduce_fn reduce, void* user, hipStream_t s,
                              const igi_kl_stop* ks = nullptr) {
   TeacherPlan p;
-  int rc = make_plan(c, &p);
+  const int rc = make_plan(c, &p);
   if (rc) return rc;
-  const int total = p.E * p.nmb;
   const int world = grad_scale > 0.f ? (int)lroundf(1.0f / grad_scale) : 0;
   if ((lr_adaptive(c) || kl_stop_on(ks)) && world < 1) return IGI_E_BADARG;
-  ReduceCtx rctx{reduce, user};
-  const StopExchange xch{stop_exchange_callback, &rctx, world};
-  const bool stopping = kl_stop_on(ks);
-  const int32_t* stop = stopping ? ks->stop_state : nullptr;
-  StopLookahead look;
-  if (stopping) {
-    if ((rc = check_state(p, st)) || (rc = check_ks(ks, st, c)) || (rc = look.begin(ks))) return rc;
-  }
-  int slot = 0;
-  for (int e = 0; e < p.E; ++e) {
-    for (int i = 0; i < p.nmb; ++i, ++slot) {
-      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 0, slot > 0, ks))) return rc;
-      if (reduce(user, 0, slot)) return IGI_E_CALLBACK;
-      if ((rc = teacher_fwd_bwd(c, ro, st, i, slot, s, 1, false, ks))) return rc;
-      if (reduce(user, 1, slot)) return IGI_E_CALLBACK;
-      if (reduce(user, 2, slot)) return IGI_E_CALLBACK;
-      const bool more = slot + 1 < total;
-      if ((rc = teacher_apply(c, st, slot, adam_t0 + slot + 1, grad_scale, s, more ? ro : nullptr,
-                              (slot + 1) % p.nmb, slot + 1, /*schedule_here=*/false, ks, stopping ? &xch : nullptr)))
-        return rc;
-      if (lr_adaptive(c) && i == p.nmb - 1) {
-        // the rank-mean KL of the mini-epoch (frozen_ppo.py:625-627): one float through the caller's transport, bucket 3
-        if ((rc = teacher_lr_exchange_begin(c, p, st, slot, s, stop))) return rc;
-        if (reduce(user, 3, slot)) return IGI_E_CALLBACK;
-        if ((rc = teacher_lr_exchange_end(c, p, st, slot, world, s, stop))) return rc;
-      }
-    }
-    bool stopped;   // every rank reads the same word behind the same mini-epoch: all stop enqueueing at one boundary
-    if ((rc = look.after_mini_epoch(e, p.E, s, &stopped))) return rc;
-    if (stopped) break;
-  }
-  return 0;
+  const UpdateExchange x{world, grad_scale, /*two_phase=*/true, /*foreign=*/true, user, reduce};
+  return teacher_update_steps(c, p, ro, st, adam_t0, s, ks, &x);
 }
 
 static int teacher_infer(const igi_teacher_cfg* c, const igi_teacher_state* st, const float* obs,
