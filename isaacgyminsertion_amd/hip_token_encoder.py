@@ -9,7 +9,10 @@ GELU / residual-dropout kernels around them) -- the ``sa_decoder`` of the refere
 state_dicts interchange with the reference; they are never called.
 Dropout (0.1 in every layer, active in train mode exactly as in the reference) uses a counter-based mask
 seeded from torch's CPU generator, so runs are reproducible under ``torch.manual_seed`` -- the mask stream
-itself is this library's, not ATen's (no implementation reproduces another device's dropout stream).
+itself is this library's, not ATen's (no implementation reproduces another device's dropout stream).  Being a pure
+function of (seed, site, element), it is restated on the host for the tests: ``oracle/token_dropout.py`` recomputes
+every mask from the seed drawn in ``forward``, and tests/test_gpu_token_encoder.py compares train-mode outputs and
+gradients with a float64 restatement that multiplies by those masks.
 """
 import copy
 

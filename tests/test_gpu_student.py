@@ -131,6 +131,73 @@ def test_student_update_matches_reference(tag):
                        init["decoder.sa_layer.linear1.weight"]) if tag == "tac_pcl_lin" else True
 
 
+def test_student_train_mode_step0_matches_the_masked_oracle():
+    """Train mode with the stock dropout 0.1 (tactile 32 x 64 + lin, MultiLayerDecoder, minibatch 0 of the tac_lin golden's
+    buffer): the step-0 loss and the raw gradient of every parameter against oracle/student.py in float64, driven with the
+    transformer's masks as oracle/token_dropout.py recomputes them from the seed the encoder draws -- the transformer is
+    the student's only dropout, and the model's forward and the BC loss are called directly behind torch.manual_seed, so
+    that draw is the first one.  Bounds: those of test_student_update_matches_reference (loss 2e-4 relative; per tensor
+    1e-3 of its largest entry + 1e-3 relative, or 4 x the fp32 oracle's own distance from the float64 run where that is
+    larger -- computed here with the same masks instead of read from the golden file).  Measured: loss 1e-7 relative,
+    gradients <= 4.3e-5 of the tensor's largest entry, each about the fp32 oracle's own distance from float64."""
+    from isaacgyminsertion_amd.bc_loss import bc_loss
+    from oracle import student as os_
+    from oracle import token_dropout as td
+    tag = "tac_lin"
+    agent, env, (n, T, E) = _agent(tag)
+    model = agent.student.model
+    init = {k[len(tag) + 6:]: torch.from_numpy(G[k]) for k in G.files if k.startswith(f"{tag}/init/")}
+    model.load_state_dict(init)
+    layers = model.decoder.sa_decoder.layers
+    assert len(layers) == 2 and layers[0].self_attn.num_heads == 2
+    assert {float(m.p) for m in model.modules() if isinstance(m, torch.nn.Dropout)} == {0.1}
+    assert all(nm.startswith(("decoder.sa_decoder.", "decoder.sa_layer.")) for nm, m in model.named_modules()
+               if isinstance(m, torch.nn.Dropout))
+    for k in agent.storage.storage_dict:
+        agent.storage.storage_dict[k].copy_(torch.from_numpy(G[f"{tag}/in/{k}"]))
+    agent.storage.indices.copy_(torch.from_numpy(G[f"{tag}/perm"]))
+    agent.storage.prepare_training()
+    agent.set_student_train()
+    assert model.training
+    b = agent.storage[0]
+    obs, tactile, actions = b["n_student_obs"], b["n_tactile"], b["teacher_actions"]      # gathered BEFORE the seed
+    mb = actions.shape[0]
+    assert mb == n * T // E
+    for p in model.parameters():
+        p.grad = None
+    torch.manual_seed(4321)
+    latent, _ = agent.student.predict({"student_obs": obs, "tactile": tactile, "img": None, "seg": None, "pcl": None},
+                                      requires_grad=True)
+    loss = bc_loss(latent, actions, agent.loss_weights)
+    loss.backward()
+    torch.manual_seed(4321)
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    masks = td.stack_masks(mb, 2, 2, layers[0].linear1.out_features, 0.1, seed, 2)        # two tokens: tactile, lin
+    args = (init, actions, tactile.reshape(mb, 3, -1), obs)
+    loss64, g64 = os_.loss_and_grads(*args, dtype=torch.float64, masks=masks)
+    _, g32 = os_.loss_and_grads(*args, dtype=torch.float32, masks=masks)
+    loss_off, _ = os_.loss_and_grads(*args, dtype=torch.float64)
+    assert abs(loss64 - loss_off) > 1e-3 * abs(loss_off)                # the masks matter at this point
+    print(f"[train-mode student] loss {loss.item():.8g} float64 oracle {loss64:.8g} (dropout off: {loss_off:.8g})")
+    np.testing.assert_allclose(loss.item(), loss64, rtol=2e-4)
+    names = [k for k, g in g64.items() if g is not None and float(g.abs().max()) > 0]
+    got = {k: p.grad for k, p in model.named_parameters() if p.grad is not None}
+    assert len(names) >= 30 and set(names) <= set(got), set(names) - set(got)
+    gmax = max(float(g64[k].abs().max()) for k in names)
+    for k in names:
+        ref = g64[k].numpy()
+        noise = float((g32[k].double() - g64[k]).abs().max())
+        err = float(np.abs(got[k].cpu().numpy() - ref).max())
+        print(f"[train-mode student] {k}: err {err:.3e} max|g| {np.abs(ref).max():.3e} fp32-oracle err {noise:.3e}")
+    for k in names:
+        ref = g64[k].numpy()
+        noise = float((g32[k].double() - g64[k]).abs().max())
+        np.testing.assert_allclose(got[k].cpu().numpy(), ref, atol=max(1e-3 * np.abs(ref).max(), 1e-6 * gmax, 4 * noise),
+                                   rtol=1e-3, err_msg=f"train-mode grad0 {k}")
+    for k, g in got.items():                                           # nothing else received a gradient
+        assert k in names or float(g.abs().max()) == 0.0, k
+
+
 def test_student_train_epoch_with_synthetic_env(tmp_path):
     agent, env, (n, T, E) = _agent("tac_pcl_lin", out=str(tmp_path))
     with torch.no_grad():   # O(1)-scale student so losses move
