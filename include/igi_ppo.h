@@ -133,7 +133,8 @@ typedef struct igi_teacher_cfg {
   int32_t n_layers;
   int32_t units[IGI_MAX_LAYERS];      /* actor_mlp / critic_mlp widths (models_split.py:100-102) */
   int32_t num_envs, horizon, mini_epochs; /* N, T, E; minibatch = N*T/E (frozen_ppo.py:213-215) */
-  int32_t _pad0;
+  int32_t shared_parameters;          /* train.ppo.shared_parameters: 1 = no critic_mlp, value = value(actor_mlp(x))
+                                       * (models_split.py:100-102, 226-230); 0 = separate critic.  Not with contacts. */
   /* Python-float (double) hyper-parameters: the reference multiplies them as doubles before the
    * tensor op casts to fp32 (e.g. gamma*tau, experience.py:254; Adam bias corrections). */
   double gamma, tau;                  /* experience.py:242-255 */
@@ -207,7 +208,7 @@ typedef struct igi_teacher_state {
 #define IGI_STATS_PER_STEP 8
 
 /* Flat parameter vector: tensors in state_dict order (sigma, env_mlp.mlp.{0,2,..}.{weight,bias},
- * actor_mlp..., critic_mlp..., value.{weight,bias}, mu.{weight,bias}); each tensor starts at a
+ * actor_mlp..., critic_mlp... (absent with cfg.shared_parameters), value.{weight,bias}, mu.{weight,bias}); each tensor starts at a
  * multiple of 4 floats (gaps are zero and stay zero).  igi_teacher_param_count = padded length;
  * igi_teacher_param_offsets fills offsets_host[i] / sizes_host[i] for tensor i and returns the
  * number of tensors (or a negative error); either array may be NULL. */
@@ -247,6 +248,7 @@ int igi_teacher_apply(const igi_teacher_cfg* cfg, const igi_teacher_state* st, i
  *            sigma, env_mlp, actor layer 0 | critic layer 0.
  * igi_teacher_grad_buckets writes the four ranges (offset, length in floats) of the flat gradient: [0], [1] early,
  * [2], [3] late (the critic's first layer sits between the two early ranges; a length may be 0) and returns 4.
+ * With cfg.shared_parameters there is no critic block: [0] = actor layers >= 1, value, mu; [2] as above; [1], [3] empty.
  * Both phases of a step take the same (mb_index, step_slot); results equal igi_teacher_fwd_bwd bit for bit. */
 int igi_teacher_fwd_bwd_phase(const igi_teacher_cfg* cfg, const igi_rollout* ro,
                               const igi_teacher_state* st, int mb_index, int step_slot, int phase,

@@ -25,7 +25,7 @@ class TeacherCfg(C.Structure):
         ("n_priv_layers", C.c_int32), ("priv_units", C.c_int32 * IGI_MAX_LAYERS),
         ("n_layers", C.c_int32), ("units", C.c_int32 * IGI_MAX_LAYERS),
         ("num_envs", C.c_int32), ("horizon", C.c_int32), ("mini_epochs", C.c_int32),
-        ("_pad0", C.c_int32),
+        ("shared_parameters", C.c_int32),
         ("gamma", C.c_double), ("tau", C.c_double),
         ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("adam_eps", C.c_double),
         ("e_clip", C.c_float), ("critic_coef", C.c_float), ("entropy_coef", C.c_float),

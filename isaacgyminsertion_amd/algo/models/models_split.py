@@ -78,10 +78,12 @@ class ActorCriticSplit(nn.Module):
         self.priv_info_dim = kwargs['priv_info_dim']
         self.shared_parameters = kwargs.get('shared_parameters', False)
         self.vt_policy = kwargs.get('vt_policy', False)
-        if not self.priv_info or self.shared_parameters or self.vt_policy:
-            # reference defaults: priv_info True, shared_parameters False, vt_policy hard-wired False
-            # (frozen_ppo.py:139) -- the configurations on the hot path (with or without ground-truth contacts)
-            raise NotImplementedError("only priv_info=True with a separate critic is on the hot path")
+        if not self.priv_info or self.vt_policy:
+            # reference defaults: priv_info True, vt_policy hard-wired False (frozen_ppo.py:139) -- the configurations
+            # on the hot path (separate critic or shared trunk; separate critic with or without ground-truth contacts)
+            raise NotImplementedError("only priv_info=True without vt_policy is on the hot path")
+        if self.shared_parameters and self.contact_info:
+            raise NotImplementedError("shared_parameters with compute_contact_gt is not supported")
         self.obs_dim = mlp_input_shape
         self.actions_num = actions_num
         mlp_input_shape += self.priv_mlp_units[-1]
@@ -100,7 +102,8 @@ class ActorCriticSplit(nn.Module):
         elif self.only_contact:
             raise NotImplementedError("only_contact without compute_contact_gt is not a configuration of the reference")
         self.actor_mlp = MLP(units=self.units, input_size=mlp_input_shape)
-        self.critic_mlp = MLP(units=self.units, input_size=mlp_input_shape)
+        if not self.shared_parameters:                # models_split.py:100-102: the value head then reads actor_mlp's output
+            self.critic_mlp = MLP(units=self.units, input_size=mlp_input_shape)
         self.value = layer_init(torch.nn.Linear(self.units[-1], 1), std=1.0)
         self.mu = layer_init(torch.nn.Linear(self.units[-1], actions_num), std=0.01)
         self.sigma = nn.Parameter(torch.zeros(actions_num, requires_grad=True, dtype=torch.float32),
@@ -117,7 +120,7 @@ class ActorCriticSplit(nn.Module):
     def _layout(self):
         from ...teacher_native import make_cfg, param_layout
         cfg, _ = make_cfg(self.obs_dim, self.priv_info_dim, self.actions_num, self.units, self.priv_mlp_units,
-                          2, 1, 1, **self.contact_kwargs())
+                          2, 1, 1, **self.engine_kwargs())
         return param_layout(cfg)
 
     def _pack(self, device, flat=None):
@@ -146,6 +149,10 @@ class ActorCriticSplit(nn.Module):
         return dict(contact_points=self.num_contact_points, contact_emb=self.contact_emb,
                     only_contact=bool(self.only_contact))
 
+    def engine_kwargs(self):
+        """Everything of the teacher cfg that the network decides: the contact fields and the shared-trunk switch."""
+        return dict(self.contact_kwargs(), shared_parameters=bool(self.shared_parameters))
+
     @property
     def flat_params(self):
         return self._flat
@@ -171,7 +178,7 @@ class ActorCriticSplit(nn.Module):
             from ...teacher_native import TeacherEngine
             eng = TeacherEngine(4096, 1, 1, units=self.units, priv_units=self.priv_mlp_units,
                                 obs_dim=self.obs_dim, priv_dim=self.priv_info_dim, act_dim=self.actions_num,
-                                device=device, **self.contact_kwargs())
+                                device=device, **self.engine_kwargs())
             self.bind_flat_to(eng)
             self._engine = eng
         return self._engine
@@ -211,8 +218,10 @@ class ActorCriticSplit(nn.Module):
                     h = linear(h, layer.weight.detach(), layer.bias.detach(), 'tanh')
             return h
 
-        mu = linear(trunk(self.actor_mlp), self.mu.weight.detach(), self.mu.bias.detach())
-        value = linear(trunk(self.critic_mlp), self.value.weight.detach(), self.value.bias.detach())
+        h_actor = trunk(self.actor_mlp)
+        mu = linear(h_actor, self.mu.weight.detach(), self.mu.bias.detach())
+        h_critic = h_actor if self.shared_parameters else trunk(self.critic_mlp)   # models_split.py:226-230
+        value = linear(h_critic, self.value.weight.detach(), self.value.bias.detach())
         extrin_gt = None
         if 'priv_info' in obs_dict and obs_dict['priv_info'] is not None:
             with torch.no_grad():

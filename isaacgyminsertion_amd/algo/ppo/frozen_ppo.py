@@ -196,7 +196,7 @@ class PPO(object):
             entropy_coef=self.entropy_coef, bounds_loss_coef=self.bounds_loss_coef, grad_norm=self.grad_norm,
             truncate_grads=self.truncate_grads, normalize_value=self.normalize_value,
             lr_schedule=self.lr_schedule, kl_threshold=self.kl_threshold, lr_min=self.scheduler.min_lr,
-            lr_max=self.scheduler.max_lr, kl_early_stop=self.kl_early_stop, **self.model.contact_kwargs())
+            lr_max=self.scheduler.max_lr, kl_early_stop=self.kl_early_stop, **self.model.engine_kwargs())
         self.model.bind_flat_to(self.engine)
         self.model.attach_engine(self.engine)
         self.running_mean_std.bind(self.engine.rms_obs)

@@ -241,7 +241,7 @@ int igi_teacher_param_offsets(const igi_teacher_cfg* cfg, int64_t* off, int64_t*
     put(p.o_cdW1, (long long)igi::CT_HID * p.ct_E); put(p.o_cdB1, igi::CT_HID);
     put(p.o_cdW2, (long long)p.ct_P * igi::CT_HID); put(p.o_cdB2, p.ct_P);
   }
-  for (int net = 0; net < 2; ++net)
+  for (int net = 0; net < p.nets; ++net)
     for (int l = 0; l < p.nl; ++l) {
       put(p.o_acW[l] + net * p.ac_block, (long long)p.u[l] * igi::ac_in(p, l));
       put(p.o_acB[l] + net * p.ac_block, p.u[l]);

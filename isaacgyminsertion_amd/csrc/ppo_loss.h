@@ -6,9 +6,10 @@
 namespace igi {
 
 struct LossArgs {
-  const float* h;        // [2][mb][ldh] last hidden (actor, critic)
-  float* dh;             // [2][mb][ldh] d(pre-activation) of the last hidden layer
-  long long net_stride;  // mb*ldh
+  const float* h;        // [2][mb][ldh] last hidden (actor, critic); shared trunk: [mb][ldh]
+  float* dh;             // [2][mb][ldh] d(pre-activation) of the last hidden layer; shared trunk: [mb][ldh]
+  long long net_stride;  // mb*ldh; shared trunk: 0 (both heads read the one row)
+  int shared;            // 1: shared actor-critic trunk (cfg.shared_parameters) -- ONE dZ row, the sum of the heads' shares
   int ldh, H;
   int ld_dh;             // layout of dh (may be the interleaved [row][net][u0p] form)
   long long net_stride_dh;
@@ -110,6 +111,13 @@ __device__ __forceinline__ float d_mu(float g_nlp, const ActionTerms& t, const A
 }
 __device__ __forceinline__ float d_sigma(float g_nlp, const ActionTerms& t, const ActionConsts& c, float entropy_coef_mb) {
   return g_nlp * (1.0f - (t.x * t.x) / c.var) - entropy_coef_mb;
+}
+
+// Shared actor-critic trunk (models_split.py:226-230: value = value(actor_mlp(x))): d(loss)/d(hidden) of one column is
+// the mu heads' share CONTINUED by the value head's -- d_mu . Wmu[:, k] summed in action order, then + d_v * Wv[k] --
+// times tanh' of the one hidden value both heads read.  (Two trunks: each share meets its own tanh'.)
+__device__ __forceinline__ float shared_dz(float dmu_wmu, float dv, float wv, float h) {
+  return fmaf(dv, wv, dmu_wmu) * (1.0f - h * h);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -240,8 +248,12 @@ struct HeadTile {
       }
       gv[j] = fmaf(dv, hc[j], gv[j]);
       if (k < a.H) {
-        dha_p[k] = da3 * (1.0f - ha[j] * ha[j]);
-        dhc_p[k] = (dv * wv[j]) * (1.0f - hc[j] * hc[j]);
+        if (a.shared) {   // hc == ha: one row of d(pre-activation)
+          dha_p[k] = shared_dz(da3, dv, wv[j], ha[j]);
+        } else {
+          dha_p[k] = da3 * (1.0f - ha[j] * ha[j]);
+          dhc_p[k] = (dv * wv[j]) * (1.0f - hc[j] * hc[j]);
+        }
       }
     }
   }
@@ -543,21 +555,27 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_packed(const LossArgs a) 
 //     The hidden layer itself is not stored (nothing reads it: the data gradient below needs tanh' of the layer BELOW).
 //     The formulas are section 1's; the head sums run in the MFMA's k order.  H == 128, act <= 7;
 //     other shapes (and bf16-input mode) keep the two launches.  Same box, A/B: 21.6 + 15.4 -> 30.6 us per step.
+//     SHARED (cfg.shared_parameters): ONE tile per 64 rows (mb / 64 workgroups) carries both heads.  The head product has
+//     act + 1 <= 8 live outputs -- mu in columns 0 .. act - 1, the value in column act -- so lane fm == act of a 16-lane row
+//     runs the critic branch while lanes fm < act run the actor's; dm holds all act + 1 columns, D1 forms the one
+//     d(pre-activation) row from them (shared_dz's order: the mu columns, then the value's), D2 / E fill the whole record.
 // ---------------------------------------------------------------------------------------------
-struct TrunkLossHook {
+template <bool SHARED>
+struct TrunkLossHookT {
   const LossArgs& a;
   // Per-sample scalars, requested in two steps (permutation entries up front, the rows' values under the last k-tile).  Thread (wave w, q = lane & 15, fq = lane >> 4)
   // owns action q of rows m0 + 16 (w & 3) + 4 fq + 2 (w >> 2) + r, r < 2 -- the layout in which the head products leave
   // the matrix pipe (waves w and w + 4 both compute the 16 x 16 block of rows 16 (w & 3) .. +15 and halve its rows).
   unsigned pb[2];                                   // permutation entries (step 0), then arena rows t*N + n
   float ac[2], omu[2], osig[2], s0[2], s1[2];       // (s0, s1) = (advantage, old neglogp) | (return, old value)
+  float s2[2], s3[2];                               // SHARED: (s0, s1) the actor's pair, (s2, s3) = (return, old value)
 
   static constexpr int TILE_M = 64;                 // rows per tile: 2 x mb / 64 workgroups, two (or three) per CU
   static constexpr int EPLD = 36, SLICE = 32 * EPLD;
   static constexpr int O_DM = 8 * SLICE, O_RED = O_DM + TILE_M * 8, O_LSUM = O_RED + 8 * 16, O_LSUM5 = O_LSUM + 8 * 8,
-                        LDS_FLOATS = O_LSUM5 + 8 * 2;
+                        O_LSUMC = O_LSUM5 + 8 * 2, LDS_FLOATS = O_LSUMC + 8 * 2;   // (O_LSUMC: SHARED's c_loss sums)
 
-  __device__ __forceinline__ explicit TrunkLossHook(const LossArgs& a_) : a(a_) {}
+  __device__ __forceinline__ explicit TrunkLossHookT(const LossArgs& a_) : a(a_) {}
 
   // step 0, in front of the first tile's DMA requests: the permutation entries
   __device__ __forceinline__ void prefetch(const GemmArgs& g, int m0, int batch, int tid) {
@@ -576,7 +594,7 @@ struct TrunkLossHook {
     // the net is wave-uniform: its two per-row arrays are picked on the scalar unit (written as an if / else over the four
     // loads the compiler built a table of the four pointers in SCRATCH and indexed it: a memory round trip in front of
     // the gathers)
-    const bool actor = batch == 0;
+    const bool actor = SHARED || batch == 0;
     const float* p0 = uniform_ptr(actor ? a.adv : a.returns_n);
     const float* p1 = uniform_ptr(actor ? a.neglogpacs : a.values_n);
 #pragma unroll
@@ -592,15 +610,16 @@ struct TrunkLossHook {
       }
       s0[r] = p0[i];
       s1[r] = p1[i];
+      if constexpr (SHARED) { s2[r] = a.returns_n[i]; s3[r] = a.values_n[i]; }
     }
   }
 
   __device__ __forceinline__ void epilogue(f32x16 (&acc)[1][1], float* smem, const GemmArgs& g, int m0, int mt, int batch,
                                            int tid, int wave, int lane, int wm, int wn) {
     typedef float f32x4r __attribute__((ext_vector_type(4)));
-    const bool actor = batch == 0;
+    const bool actor = SHARED || batch == 0;
     const int act = a.act;
-    const int nq = actor ? act : 1;
+    const int nq = SHARED ? act + 1 : (actor ? act : 1);   // live head outputs of this tile
     const int l31 = lane & 31, h = lane >> 5;
     const int fm = lane & 15, fq = lane >> 4;   // MFMA 16x16x4 operand / result coordinates
     const int c4 = lane & 7, rl = lane >> 3;    // row-major passes over a 64 x 32 slice: 16-byte column group, row
@@ -608,7 +627,12 @@ struct TrunkLossHook {
     float* red = smem + O_RED;                  // [8 waves][16]: bias / sigma gradient partials
     double* lsum = reinterpret_cast<double*>(smem + O_LSUM);   // [8 waves][4]
     double* lsum5 = reinterpret_cast<double*>(smem + O_LSUM5); // [8 waves]: the approx_kl sums
-    const float* W = actor ? a.Wmu : a.Wv;      // [nq][128]
+    double* lsumc = reinterpret_cast<double*>(smem + O_LSUMC); // [8 waves]: SHARED, the c_loss sums
+    const float* W = actor ? a.Wmu : a.Wv;      // [nq][128] (SHARED: rows 0 .. act - 1; row act is Wv)
+    // head weight row q of this tile
+    auto wrow = [&](int q) { return (SHARED && q == act) ? a.Wv : W + q * 128; };
+    const bool vlane = SHARED && fm == act;     // SHARED: this lane owns the value of its rows
+    (void)vlane; (void)lsumc;
 
     // ---- A: accumulators -> this wave's slice, bias + tanh in place; meanwhile the head weights arrive in registers
     __syncthreads();   // every wave is done reading the ring
@@ -619,7 +643,7 @@ struct TrunkLossHook {
     float4 wv[8];
 #pragma unroll
     for (int kh = 0; kh < 8; ++kh)
-      wv[kh] = (fm < nq) ? *reinterpret_cast<const float4*>(W + fm * 128 + 16 * kh + 4 * fq) : make_float4(0.f, 0.f, 0.f, 0.f);
+      wv[kh] = (fm < nq) ? *reinterpret_cast<const float4*>(wrow(fm) + 16 * kh + 4 * fq) : make_float4(0.f, 0.f, 0.f, 0.f);
     const bool alane = actor && fm < act;   // this lane owns action fm of its rows
     const float my_logstd = alane ? a.logstd[fm] : 0.f;
     const float my_bmu = alane ? a.bmu[fm] : 0.f;
@@ -658,7 +682,7 @@ struct TrunkLossHook {
     // ---- C: hacc[2 (w >> 2) + r] = head output fm of row 16 (w & 3) + 4 fq + 2 (w >> 2) + r: this lane's action of its
     //         two rows.  The sums over the actions of a row are sums over the 16-lane row (DPP), as in k_loss_packed.
     float gb = 0.f, gs = 0.f;            // d(bias_mu[fm]) | d(bias_v), d(sigma[fm]) over this lane's rows
-    double t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+    double t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, tc = 0;
     {
       const float inv_mb = 1.0f / (float)a.mb;
       const ActionConsts my = action_consts(my_logstd);
@@ -692,6 +716,14 @@ struct TrunkLossHook {
             t0 += al.loss; t1 += bounds_stat(bl, a.bounds_coef); t2 += ent; t3 += kl;
             t4 += approx_kl_term(s1[r], nlp);
           }
+          if constexpr (SHARED) {   // the critic branch on the lane that holds the value (no action of its own: my_d == 0 so far)
+            const CriticLoss cl = critic_loss(hout + bvv, s2[r], s3[r], a.e_clip);
+            if (okrow && vlane) {
+              my_d = cl.dv * (0.5f * a.critic_coef * inv_mb);
+              gb += my_d;
+              tc += cl.loss;
+            }
+          }
         } else {
           const CriticLoss cl = critic_loss(hout + bvv, s0[r], s1[r], a.e_clip);
           if (okrow && fm == 0) {
@@ -712,11 +744,13 @@ struct TrunkLossHook {
         t3 += __shfl_xor(t3, 16, 64); t3 += __shfl_xor(t3, 32, 64);
         t4 += __shfl_xor(t4, 16, 64); t4 += __shfl_xor(t4, 32, 64);
       }
+      if constexpr (SHARED) { tc += __shfl_xor(tc, 16, 64); tc += __shfl_xor(tc, 32, 64); }
       if (lane < 8) { red[wave * 16 + lane] = gb; red[wave * 16 + 8 + lane] = gs; }
       if (lane == 0) {
         lsum[wave * 4 + 0] = t0; lsum[wave * 4 + 1] = t1; lsum[wave * 4 + 2] = t2; lsum[wave * 4 + 3] = t3;
         lsum5[wave] = t4;
       }
+      if (SHARED && lane == act) lsumc[wave] = tc;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();   // LDS-only rendezvous: the mu / sigma stores stay in flight
@@ -724,10 +758,11 @@ struct TrunkLossHook {
 
     // ---- D1: d(pre-activation) of this wave's 32 x 32 slice = (d(head) . W_head) * (1 - h^2), 16-byte row segments
     {
-      float4 w[7];
+      constexpr int NQ = SHARED ? 8 : 7;
+      float4 w[NQ];
 #pragma unroll
-      for (int q = 0; q < 7; ++q)
-        w[q] = (q < nq) ? *reinterpret_cast<const float4*>(W + q * 128 + wn * 32 + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int q = 0; q < NQ; ++q)
+        w[q] = (q < nq) ? *reinterpret_cast<const float4*>(wrow(q) + wn * 32 + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
       float* dst = a.dh + batch * a.net_stride_dh + (long long)(m0 + wm * 32) * a.ld_dh + wn * 32 + 4 * c4;
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
@@ -735,10 +770,10 @@ struct TrunkLossHook {
         const float4 hv = *reinterpret_cast<const float4*>(ep + r * EPLD + 4 * c4);
         const float4 d0 = *reinterpret_cast<const float4*>(dm + (wm * 32 + r) * 8);
         const float4 d1 = *reinterpret_cast<const float4*>(dm + (wm * 32 + r) * 8 + 4);
-        const float d[7] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z};
+        const float d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
         float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-        for (int q = 0; q < 7; ++q)
+        for (int q = 0; q < NQ; ++q)
           if (q < nq) {
             z.x = fmaf(d[q], w[q].x, z.x); z.y = fmaf(d[q], w[q].y, z.y);
             z.z = fmaf(d[q], w[q].z, z.z); z.w = fmaf(d[q], w[q].w, z.w);
@@ -771,8 +806,10 @@ struct TrunkLossHook {
       float* rec = a.head_slab + (long long)mt * a.head_count;
       if (actor) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
+        for (int r = 0; r < 4; ++r) {
           if (4 * fq + r < act) rec[(4 * fq + r) * 128 + col] = gacc[r];
+          else if (SHARED && 4 * fq + r == act) rec[act * 128 + act + col] = gacc[r];   // valW
+        }
       } else if (fq == 0) {
         rec[act * 128 + act + col] = gacc[0];
       }
@@ -785,6 +822,7 @@ struct TrunkLossHook {
       float* rec = a.head_slab + (long long)mt * a.head_count;
       if (actor) {
         if (tid < act) rec[act * 128 + tid] = sb;                                          // muB
+        else if (SHARED && tid == act) rec[act * 128 + act + 128] = sb;                    // valB (act <= 7: a lane below 8)
         else if (tid >= 8 && tid - 8 < act) rec[act * 128 + act + 128 + 1 + (tid - 8)] = sb;   // sigma
       } else if (tid == 0) {
         rec[act * 128 + act + 128] = sb;                                                    // valB
@@ -802,15 +840,22 @@ struct TrunkLossHook {
 #pragma unroll
       for (int w8 = 0; w8 < 8; ++w8) sl += lsum5[w8];
       a.loss_part[(long long)mt * 8 + 5] = sl;    // approx_kl -> slot 5
+    } else if (SHARED && tid == 69) {
+      double sl = 0;
+#pragma unroll
+      for (int w8 = 0; w8 < 8; ++w8) sl += lsumc[w8];
+      a.loss_part[(long long)mt * 8 + 1] = sl;    // c_loss -> slot 1
     }
   }
 };
+typedef TrunkLossHookT<false> TrunkLossHook;
 
+template <bool SHARED>
 __global__ __launch_bounds__(DMA_THREADS, 4) void k_trunk_loss(const GemmArgs g, const LossArgs a, int m_tiles) {
-  TrunkLossHook hook(a);
+  TrunkLossHookT<SHARED> hook(a);
   // no XCD remap: workgroup b and b + m_tiles (the same rows of the other net) land on the same XCD, and the round-robin
   // placement pairs an actor tile with a critic tile on a CU (the actor's scalar section is the longer one)
-  gemm_dma_body<128, true, true, 0, 2, TrunkLossHook::TILE_M, false, false, false, false, TrunkLossHook>(
+  gemm_dma_body<128, true, true, 0, 2, TrunkLossHook::TILE_M, false, false, false, false, TrunkLossHookT<SHARED>>(
       g, 1, m_tiles, (int)blockIdx.x, &hook);
 }
 
@@ -828,7 +873,8 @@ static int loss_stage(const TeacherPlan& p, const igi_teacher_cfg* c, const igi_
   LossArgs a;
   a.h = wsp<float>(st, p.w_h[p.nl - 1]);
   a.dh = wsp<float>(st, p.w_dh[p.nl - 1]);
-  a.net_stride = mbs * ldh; a.ldh = ldh; a.H = H;
+  a.shared = p.nets == 1;
+  a.net_stride = a.shared ? 0 : mbs * ldh; a.ldh = ldh; a.H = H;
   a.ld_dh = ld_dh; a.net_stride_dh = net_stride_dh;
   a.Wmu = P + p.o_muW; a.bmu = P + p.o_muB; a.Wv = P + p.o_valW; a.bv = P + p.o_valB;
   a.logstd = P + p.o_sigma;
@@ -850,7 +896,7 @@ static int loss_stage(const TeacherPlan& p, const igi_teacher_cfg* c, const igi_
     g.A = wsp<float>(st, p.w_h[l - 1]); g.lda = ru4(in); g.sA = mbs * ru4(in);
     g.B = P + p.o_acW[l]; g.ldb = in; g.sB = p.ac_block; g.K = in;
     g.bias = P + p.o_acB[l]; g.sBias = p.ac_block;
-    g.M = mb; g.N = H; g.nbatch = 2;
+    g.M = mb; g.N = H; g.nbatch = p.nets;
     g.epilogue = EPI_BIAS_TANH;
     if (!dma_eligible(g, true, true) || !aligned16(g.bias) || (g.sBias & 3) || !aligned16(a.dh) || (a.ld_dh & 3) ||
         (a.net_stride_dh & 3))
@@ -859,14 +905,18 @@ static int loss_stage(const TeacherPlan& p, const igi_teacher_cfg* c, const igi_
     dma_set_divs(g, 1, m_tiles);
     constexpr size_t ring = sizeof(float) * 2 * (TrunkLossHook::TILE_M + 128) * DMA_BK;
     constexpr size_t shm = sizeof(float) * TrunkLossHook::LDS_FLOATS > ring ? sizeof(float) * TrunkLossHook::LDS_FLOATS : ring;
-    static bool attr = false;
-    if (!attr) {
-      IGI_HIP_TRY(hipFuncSetAttribute((const void*)k_trunk_loss, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      attr = true;
+    static bool attr[2] = {false, false};
+    if (!attr[a.shared]) {
+      const void* fn = a.shared ? (const void*)k_trunk_loss<true> : (const void*)k_trunk_loss<false>;
+      IGI_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+      attr[a.shared] = true;
     }
-    ProfScope ps(PC_TRUNK_LOSS, s, 2.0 * 2 * (double)mbs * H * in + 2.0 * 3 * (double)mbs * H * (p.act + 1),
-                 4.0 * (2.0 * mbs * in + 2.0 * H * in + 2.0 * mbs * H + (double)mbs * (4 * p.act + 6)));
-    IGI_LAUNCH(k_trunk_loss, dim3(2 * m_tiles), dim3(DMA_THREADS), shm, s, g, a, m_tiles);
+    const double nn = p.nets;
+    ProfScope ps(PC_TRUNK_LOSS, s, 2.0 * nn * (double)mbs * H * in + 2.0 * 3 * (double)mbs * H * (p.act + 1),
+                 4.0 * (nn * mbs * in + nn * H * in + nn * mbs * H + (double)mbs * (4 * p.act + 6)));
+    // shared trunk: ONE tile per 64 rows carries both heads
+    if (a.shared) IGI_LAUNCH(k_trunk_loss<true>, dim3(m_tiles), dim3(DMA_THREADS), shm, s, g, a, m_tiles);
+    else IGI_LAUNCH(k_trunk_loss<false>, dim3(2 * m_tiles), dim3(DMA_THREADS), shm, s, g, a, m_tiles);
     return 0;
   }
   ProfScope ps(PC_LOSS, s, 2.0 * 3 * (double)mbs * H * (p.act + 1), 4.0 * (double)mbs * (4.0 * ldh + 4 * p.act + 6));

@@ -8,7 +8,8 @@
 //     so the 11 transpose-copies of prepare_training never happen;
 //   * parameters / gradients / Adam moments are single flat fp32 vectors in state_dict order;
 //   * per-minibatch activations are row-major [mb][width4] (width rounded up to 4 floats so rows
-//     are 16-byte aligned), actor and critic stacked [2][mb][width4] so one batched launch serves both.
+//     are 16-byte aligned), actor and critic stacked [nets][mb][width4] so one batched launch serves both
+//     (nets = 1 with a shared actor-critic trunk: cfg.shared_parameters).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -60,6 +61,7 @@ constexpr int ADAM_BLOCKS_MAX = 1024;
 // ---------------------------------------------------------------------------------------------
 struct TeacherPlan {
   int obs, priv, act, npl, nl;
+  int nets;             // trunks: 2 = actor_mlp + critic_mlp, 1 = shared_parameters (value reads the actor trunk's output)
   int pu[IGI_MAX_LAYERS], u[IGI_MAX_LAYERS];
   int N, T, E, mb, nmb;
   long long Bsz;
@@ -72,7 +74,7 @@ struct TeacherPlan {
   int u0p;              // first trunk width rounded up to 4
   // parameter offsets (floats) in the flat vector
   long long o_sigma, o_envW[IGI_MAX_LAYERS], o_envB[IGI_MAX_LAYERS];
-  long long o_acW[IGI_MAX_LAYERS], o_acB[IGI_MAX_LAYERS];  // actor; critic = + ac_block
+  long long o_acW[IGI_MAX_LAYERS], o_acB[IGI_MAX_LAYERS];  // actor; critic = + ac_block (nets == 2)
   long long ac_block, o_valW, o_valB, o_muW, o_muB, P;
   // workspace offsets (bytes)
   size_t w_prep_part, w_prep_coef, w_rms_part, w_norm_coef, w_priv, w_xcat, w_dxcat, w_w1p;
@@ -157,11 +159,14 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   if (p->mb < 2) return IGI_E_BADARG;
   p->nmb = (int)(p->Bsz / p->mb);
   p->latent = p->pu[p->npl - 1];
+  if (c->shared_parameters != 0 && c->shared_parameters != 1) return IGI_E_BADARG;
+  p->nets = c->shared_parameters ? 1 : 2;
   p->ct_P = c->contact_points; p->ct_E = c->contact_emb; p->ct_only = c->only_contact;
   if (p->ct_P < 0 || p->ct_E < 0 || p->ct_only < 0 || p->ct_only > 1) return IGI_E_BADARG;
   if (p->ct_P == 0 && (p->ct_E != 0 || p->ct_only)) return IGI_E_BADARG;
   if (p->ct_P > 0 && (p->ct_E < 1 || p->ct_E > CT_MAX_EMB)) return IGI_E_BADARG;
   if (p->ct_only && p->ct_E != p->latent) return IGI_E_UNSUPPORTED;   // the reference's trunk width is obs + latent
+  if (p->nets == 1 && p->ct_P > 0) return IGI_E_UNSUPPORTED;          // shared_parameters with compute_contact_gt
   p->ct_col = p->obs + (p->ct_only ? 0 : p->latent);
   p->xw = p->ct_col + p->ct_E;
   p->xld = (p->xw + 31) & ~31;  // zero-padded to the LDS-DMA kernel's k-tile
@@ -187,7 +192,7 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
     p->o_acB[l] = put(p->u[l]);
   }
   p->ac_block = o - ac0;
-  o += p->ac_block;  // critic: same shapes, same internal offsets
+  o += (p->nets - 1) * p->ac_block;  // critic: same shapes, same internal offsets
   const int H = p->u[p->nl - 1];
   p->o_valW = put(H);
   p->o_valB = put(1);
@@ -212,21 +217,21 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   p->w_traj_coef = take(sizeof(float) * 2 * D * p->E * p->nmb);
   p->w_traj_state = take(sizeof(double) * (2 * D + 2) * p->E * p->nmb);
   {
-    const int K2 = 2 * ru4(p->u[0]);
+    const int K2 = p->nets * ru4(p->u[0]);
     // LDS: transposed weight slice 8 x (K2p+4) + 32 x 260 staging tile (also hosts the 4 x (8*H2+8) final reduction)
     p->lat_fused = (p->latent == 8 && p->ct_P == 0 && p->npl >= 2 && p->pu[p->npl - 2] <= 256 && K2 <= 2048) ? 1 : 0;
     p->lat_rpw = 0;
     p->lat_blocks = (int)((mb + 31) / 32);
     p->w_lat_part = p->lat_fused ? take(sizeof(float) * (size_t)p->lat_blocks * (8 * p->pu[p->npl - 2] + 8)) : 0;
     // row dots of dZ1 with the eight latent columns, one partial per 128-column tile and net (see k_latent_bwd<., true>)
-    p->lat_tiles = 2 * ((p->u[0] + 127) / 128);
+    p->lat_tiles = p->nets * ((p->u[0] + 127) / 128);
     p->w_lat_rowdot = p->lat_fused ? take(sizeof(float) * (size_t)p->lat_tiles * mb * 8) : 0;
     p->w_wlat = p->lat_fused ? take(sizeof(float) * 8 * (size_t)((K2 + 255) / 256 * 256)) : 0;  // [8][K2p], see k_latent_bwd
   }
   p->w_priv = take(sizeof(float) * mb * ru4(p->priv));
   p->w_xcat = take(sizeof(float) * mb * p->xld);
   p->w_dxcat = take(sizeof(float) * mb * p->xld);
-  p->w_w1p = take(sizeof(float) * 2 * p->u0p * p->xld);
+  p->w_w1p = take(sizeof(float) * p->nets * p->u0p * p->xld);
   if (p->ct_P > 0) {
     p->ct_blocks = ct_bwd_blocks(p->mb);
     p->ct_rec = ct_rec_floats(p->ct_P, p->ct_E);
@@ -239,8 +244,8 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
     p->w_de[l] = (l < p->npl - 1) ? take(sizeof(float) * mb * ru4(p->pu[l])) : 0;  // last: dxcat[:, obs:]
   }
   for (int l = 0; l < p->nl; ++l) {
-    p->w_h[l] = take(sizeof(float) * 2 * mb * ru4(p->u[l]));
-    p->w_dh[l] = take(sizeof(float) * 2 * mb * ru4(p->u[l]));
+    p->w_h[l] = take(sizeof(float) * p->nets * mb * ru4(p->u[l]));
+    p->w_dh[l] = take(sizeof(float) * p->nets * mb * ru4(p->u[l]));
   }
   // loss kernel: one wave per row, loss_rpw rows per wave
   long long waves_needed = mb;
@@ -304,15 +309,15 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
     const int latz_on = latz_fuse_ref();
     // shapes only: the fused latent path with the row dots from the dZ1 tiles, the env level as the row-block kernel with the
     // first env layer's weight gradient in it, the reference's 128-wide second env layer
-    p->latz = (latz_on && p->lat_fused && p->npl == 3 && p->rb_env[1] && p->lx_env && p->pu[1] == 128 && p->lat_tiles <= 8 &&
+    p->latz = (latz_on && p->nets == 2 && p->lat_fused && p->npl == 3 && p->rb_env[1] && p->lx_env && p->pu[1] == 128 && p->lat_tiles <= 8 &&
                p->lat_blocks >= p->rb_env[1]) ? 1 : 0;
   }
   for (int l = 0; l < p->nl; ++l) {
     const int inw = (l == 0) ? p->xld : ac_in(*p, l);  // layer 0 multiplies the padded xcat
-    p->sk_ac[l] = choose_splitk(p->u[l], inw, p->mb, 2);
+    p->sk_ac[l] = choose_splitk(p->u[l], inw, p->mb, p->nets);
     // (l >= 2: the data gradient into trunk layer 0 keeps its interleaved layout and the latent row dots)
-    if (l >= 2 && rb_level_shape_ok(p->mb, p->u[l], p->u[l - 1], 2)) {
-      p->rb_ac[l] = rb_level_ranges(p->mb, p->u[l - 1], 2);
+    if (l >= 2 && rb_level_shape_ok(p->mb, p->u[l], p->u[l - 1], p->nets)) {
+      p->rb_ac[l] = rb_level_ranges(p->mb, p->u[l - 1], p->nets);
       p->sk_ac[l] = p->rb_ac[l];
     }
     if (l == 0) {
@@ -320,17 +325,18 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
       const int chain = (mt128 % 4 == 0) ? 4 : ((mt128 % 2 == 0) ? 2 : 1);
       // shapes only (the launch re-checks pointers): row dots from those tiles, 32-wide padded input with a FREE last
       // column (xw <= 31: column 31 carries the ONE of the bias gradient; obs + latent == 32 takes the separate
-      // weight-gradient launch), whole 128-row / 128-column tiles, the level-fused grid
-      if (p->nl >= 2 && p->lat_fused && p->xld == 32 && p->xw < 32 && (p->mb % DMA_BM) == 0 && (p->u[0] % 128) == 0 &&
+      // weight-gradient launch), whole 128-row / 128-column tiles, the level-fused grid; two nets (the rider's partial
+      // records and row dots are laid out per net pair: a shared trunk takes the separate weight-gradient launch)
+      if (p->nets == 2 && p->nl >= 2 && p->lat_fused && p->xld == 32 && p->xw < 32 && (p->mb % DMA_BM) == 0 && (p->u[0] % 128) == 0 &&
           !bf16_mode() && p->mb >= 4) {
         p->lw_chain = chain;
         p->lw_parts = mt128 / chain;
         p->sk_ac[0] = p->lw_parts;
       }
     }
-    // layout [split][net][...]: split stride = 2*size so the batch stride stays the net size
-    p->s_acW[l] = s; s += (long long)p->sk_ac[l] * 2 * p->u[l] * inw;
-    p->s_acB[l] = s; s += (long long)p->sk_ac[l] * 2 * p->u[l];
+    // layout [split][net][...]: split stride = nets*size so the batch stride stays the net size
+    p->s_acW[l] = s; s += (long long)p->sk_ac[l] * p->nets * p->u[l] * inw;
+    p->s_acB[l] = s; s += (long long)p->sk_ac[l] * p->nets * p->u[l];
     s = (s + 3) & ~3LL;
   }
   p->slab_floats = s;
@@ -670,6 +676,7 @@ struct GatherArgs {
   const float* coef; const double* state_row; double* rms_obs; double* rms_priv;
   float* xcat; int xld, xw; float* priv_g; int pld;
   const float* params; long long o_w, ac_block; int u0, u0p; float* w1p; float* wlat; int K2p;
+  int nets = 2;                    // trunks mirrored in w1p / wlat
   const int32_t* stop = nullptr;   // KL early stopping: the stop word; >= 0 = the update has stopped, this body is inert
 };
 
@@ -687,7 +694,7 @@ __device__ __forceinline__ void gather_normalize_body(const GatherArgs& a, int b
   const int K2p = a.K2p;
   if (a.stop && a.stop[0] >= 0) return;   // stopped: neither the next step's running state nor its rows (block-uniform)
   if (bid >= gather_blocks) {  // W1p[net][o][c] refresh (see k_pad_w1)
-    const int total = 2 * u0p * xld;
+    const int total = a.nets * u0p * xld;
     const int nb = nblocks - gather_blocks;
     for (int e = (bid - gather_blocks) * blockDim.x + threadIdx.x; e < total; e += nb * blockDim.x) {
       const int c = e % xld;
@@ -698,10 +705,10 @@ __device__ __forceinline__ void gather_normalize_body(const GatherArgs& a, int b
       // compact, transposed copy of the 8 latent columns for k_latent_bwd: wlat[j][k], k = net*u0p + o
       if (wlat && c >= obs && c < obs + 8) wlat[(long long)(c - obs) * K2p + net * u0p + o] = v;
     }
-    if (wlat) {  // zero tail k in [2*u0p, K2p)
-      const int tail = K2p - 2 * u0p;
+    if (wlat) {  // zero tail k in [nets*u0p, K2p)
+      const int tail = K2p - a.nets * u0p;
       for (int e = (bid - gather_blocks) * blockDim.x + threadIdx.x; e < 8 * tail; e += nb * blockDim.x)
-        wlat[(long long)(e / tail) * K2p + 2 * u0p + e % tail] = 0.f;
+        wlat[(long long)(e / tail) * K2p + a.nets * u0p + e % tail] = 0.f;
     }
     return;
   }
@@ -1080,6 +1087,7 @@ __global__ __launch_bounds__(256) void k_sumsq_stats(const float* __restrict__ g
 struct W1Mirror {
   float* w1p; float* wlat;
   long long o_w, ac_block; int u0, u0p, xw, xld, obs, K2p;
+  int nets;   // 1: no critic block behind the actor's (what follows it are the heads: never mirrored)
 };
 
 __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const float* __restrict__ grads,
@@ -1140,7 +1148,7 @@ __device__ __forceinline__ void clip_adam_body(float* __restrict__ params, const
     if (mir) {  // W1p[net][o][c] and the transposed latent columns follow the parameter they copy
       long long rel = i - mir->o_w;
       int net = 0;
-      if (rel >= mir->ac_block) { rel -= mir->ac_block; net = 1; }
+      if (mir->nets == 2 && rel >= mir->ac_block) { rel -= mir->ac_block; net = 1; }
       if (rel >= 0 && rel < (long long)mir->u0 * mir->xw) {
         const int o = (int)(rel / mir->xw), c = (int)(rel - (long long)o * mir->xw);
         mir->w1p[((long long)net * mir->u0p + o) * mir->xld + c] = pi;
@@ -1359,8 +1367,8 @@ static int teacher_prepare(const igi_teacher_cfg* c, const igi_rollout* ro,
 // W1p[net][o][c] = first trunk layer weight padded to xld columns (zeros) so the layer runs on
 // the LDS-DMA kernel (k-tile 32) and its dgrad / wgrad see aligned 16-byte rows.
 __global__ __launch_bounds__(256) void k_pad_w1(const float* __restrict__ params, long long o_w, long long ac_block,
-                                                int u0, int u0p, int xw, int xld, float* __restrict__ w1p) {
-  const int total = 2 * u0p * xld;
+                                                int u0, int u0p, int xw, int xld, float* __restrict__ w1p, int nets) {
+  const int total = nets * u0p * xld;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
     const int c = e % xld;
     const int o = (e / xld) % u0p;
@@ -1625,9 +1633,9 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
   float* w1p = wsp<float>(st, p.w_w1p);
   const long long mbs = p.mb;
   if (pad_w1) {
-    ProfScope ps(PC_OTHER, s, 0.0, 8.0 * 2 * p.u0p * p.xld);
-    IGI_LAUNCH(k_pad_w1, dim3((2 * p.u0p * p.xld + 255) / 256), dim3(256), 0, s, P, p.o_acW[0],
-                       p.ac_block, p.u[0], p.u0p, p.xw, p.xld, w1p);
+    ProfScope ps(PC_OTHER, s, 0.0, 8.0 * p.nets * p.u0p * p.xld);
+    IGI_LAUNCH(k_pad_w1, dim3((p.nets * p.u0p * p.xld + 255) / 256), dim3(256), 0, s, P, p.o_acW[0],
+                       p.ac_block, p.u[0], p.u0p, p.xw, p.xld, w1p, p.nets);
   }
   // env_mlp: tanh after every layer, the last one lands in xcat[:, obs:]
   const float* in = priv_g;
@@ -1638,7 +1646,8 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
   int first_trunk_layer = 0;
   // round 6: env_mlp AND the first trunk layer of both nets as one persistent launch (fwd12.h); other shapes keep
   // k_env_fwd (or the per-layer launches) + the layer's own launch below
-  if (env_fused && p.npl == 3 && p.ct_P == 0 && nl_run >= 1 && rows >= 2048 && !bf16_mode() &&
+  // (k_fwd12 runs the first trunk layer of TWO nets: a shared trunk declines it and takes the launches below)
+  if (env_fused && p.nets == 2 && p.npl == 3 && p.ct_P == 0 && nl_run >= 1 && rows >= 2048 && !bf16_mode() &&
       fwd12_supported(p.priv, p.pu[0], p.pu[1], p.pu[2], p.obs, p.xld, p.u[0]) && p.u0p == p.u[0]) {
     Fwd12Args f;
     f.priv = priv_g; f.ldp = ldin; f.xcat = xcat; f.ldx = p.xld; f.M = rows; f.obs = p.obs;
@@ -1700,7 +1709,7 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
     g.bias = P + p.o_acB[l]; g.sBias = p.ac_block;
     g.M = rows; g.N = p.u[l];
     g.C = wsp<float>(st, p.w_h[l]); g.ldc = ru4(p.u[l]); g.sC = mbs * ru4(p.u[l]);
-    g.nbatch = 2;
+    g.nbatch = p.nets;
     g.epilogue = EPI_BIAS_TANH;
     IGI_HIP_TRY(gemm(g, true, true, s));
     in = g.C; ldin = g.ldc; sIn = g.sC;
@@ -1726,6 +1735,11 @@ static GradBuckets grad_buckets(const TeacherPlan& p) {
   b.off[1] = a0 + blk + rel1;  b.len[1] = p.P - b.off[1];             // critic layers >= 1, value, mu
   b.off[2] = 0;                b.len[2] = a0 + rel1;                  // sigma, env_mlp, actor layer 0
   b.off[3] = a0 + blk;         b.len[3] = rel1;                       // critic layer 0
+  if (p.nets == 1) {   // no critic block: the early bucket is ONE range, both critic ranges are empty
+    b.len[0] = p.P - b.off[0];                                        // actor layers >= 1, value, mu
+    b.off[1] = p.P; b.len[1] = 0;
+    b.len[3] = 0;
+  }
   return b;
 }
 
@@ -1744,7 +1758,8 @@ static GatherArgs gather_args(const TeacherPlan& p, const igi_rollout* ro, const
   a.params = st->params; a.o_w = p.o_acW[0]; a.ac_block = p.ac_block; a.u0 = p.u[0]; a.u0p = p.u0p;
   a.w1p = wsp<float>(st, p.w_w1p);
   a.wlat = p.lat_fused ? wsp<float>(st, p.w_wlat) : (float*)nullptr;
-  a.K2p = (2 * p.u0p + 255) / 256 * 256;
+  a.K2p = (p.nets * p.u0p + 255) / 256 * 256;
+  a.nets = p.nets;
   return a;
 }
 
@@ -1752,7 +1767,7 @@ static GatherArgs gather_args(const TeacherPlan& p, const igi_rollout* ro, const
 // with_rowdot (l == 1): the dZ1 tiles also emit their share of dZ1 . W1[:, latent columns] (GemmArgs::rowdot_*).
 static GemmArgs trunk_dgrad_args(const TeacherPlan& p, const igi_teacher_state* st, int l, bool with_rowdot) {
   const long long mbs = p.mb;
-  auto dz_ld = [&](int k) { return k == 0 ? 2 * p.u0p : ru4(p.u[k]); };
+  auto dz_ld = [&](int k) { return k == 0 ? p.nets * p.u0p : ru4(p.u[k]); };
   auto dz_stride = [&](int k) { return k == 0 ? (long long)p.u0p : mbs * ru4(p.u[k]); };
   GemmArgs g;
   g.A = wsp<float>(st, p.w_dh[l]); g.lda = dz_ld(l); g.sA = dz_stride(l);
@@ -1760,7 +1775,7 @@ static GemmArgs trunk_dgrad_args(const TeacherPlan& p, const igi_teacher_state* 
   g.M = p.mb; g.N = ac_in(p, l); g.K = p.u[l];
   g.C = wsp<float>(st, p.w_dh[l - 1]); g.ldc = dz_ld(l - 1); g.sC = dz_stride(l - 1);
   g.aux = wsp<float>(st, p.w_h[l - 1]); g.ldaux = ru4(p.u[l - 1]); g.sAux = mbs * ru4(p.u[l - 1]);
-  g.nbatch = 2;
+  g.nbatch = p.nets;
   g.epilogue = EPI_TANHGRAD;
   if (with_rowdot) {
     g.rowdot_W = wsp<float>(st, p.w_wlat); g.rowdot_ld = (2 * p.u0p + 255) / 256 * 256; g.rowdot_kz = p.u0p;
@@ -1781,7 +1796,9 @@ static GemmArgs trunk_dgrad_args(const TeacherPlan& p, const igi_teacher_state* 
 // addresses alone, with the very predicate the launcher applies (gemm_multi_dgrad_ok), so that both halves of a phased
 // step agree and the launch can never decline row dots the plan counted on (it falls back to k_latent_bwd<., false>).
 static bool latent_rowdot(const TeacherPlan& p, const igi_teacher_state* st) {
-  if (!(p.lat_fused && p.nl >= 2 && !bf16_mode() && p.mb >= 4)) return false;
+  // (two nets only: the tiles' row dots and k_latent_bwd<., true> index the partials [tile][net]; a shared trunk's dZ1 goes
+  // through k_latent_bwd<., false>, which is generic in K2 = nets * u0p)
+  if (!(p.nets == 2 && p.lat_fused && p.nl >= 2 && !bf16_mode() && p.mb >= 4)) return false;
   GemmArgs g = trunk_dgrad_args(p, st, 1, true);
   return gemm_multi_dgrad_ok(g);
 }
@@ -1847,7 +1864,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   // ---- heads + loss + head backward.  d(pre-activation) of the FIRST trunk layer is kept
   // interleaved [row][net][u0p] so that the dgrad into xcat is one contraction over both nets.
   const int H = p.u[p.nl - 1];
-  auto dz_ld = [&](int l) { return l == 0 ? 2 * p.u0p : ru4(p.u[l]); };
+  auto dz_ld = [&](int l) { return l == 0 ? p.nets * p.u0p : ru4(p.u[l]); };
   auto dz_stride = [&](int l) { return l == 0 ? (long long)p.u0p : mbs * ru4(p.u[l]); };
   if (do0 && (rc = loss_stage(p, c, ro, st, mb_index, dz_ld(p.nl - 1), dz_stride(p.nl - 1), s, stop))) return rc;
 
@@ -1877,9 +1894,9 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
       r.W = P + p.o_acW[l]; r.ldw = in; r.sW = p.ac_block;
       r.X = x; r.ldx = ldx; r.sX = sX;
       r.dX = wsp<float>(st, p.w_dh[l - 1]); r.lddx = dz_ld(l - 1); r.sdX = dz_stride(l - 1);
-      r.dWp = slab + p.s_acW[l]; r.ldwp = in; r.sWpart = 2LL * out * in; r.sWnet = (long long)out * in;
-      r.dBp = slab + p.s_acB[l]; r.sBpart = 2LL * out; r.sBnet = out;
-      r.rows = mb; r.IN = in; r.nets = 2; r.ranges = p.rb_ac[l];
+      r.dWp = slab + p.s_acW[l]; r.ldwp = in; r.sWpart = (long long)p.nets * out * in; r.sWnet = (long long)out * in;
+      r.dBp = slab + p.s_acB[l]; r.sBpart = (long long)p.nets * out; r.sBnet = out;
+      r.rows = mb; r.IN = in; r.nets = p.nets; r.ranges = p.rb_ac[l];
       const hipError_t e = rb_level_backward(r, s, PC_RB_TRUNK);
       if (e == hipErrorNotSupported) return IGI_E_UNSUPPORTED;   // (alignment: the plan cannot see the caller's pointers)
       IGI_HIP_TRY(e);
@@ -1892,9 +1909,9 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
       g.M = out; g.N = in; g.K = mb;
       g.C = slab + p.s_acW[l]; g.ldc = in; g.sC = (long long)out * in;
       g.Cbias = slab + p.s_acB[l]; g.sCbias = out;
-      g.nbatch = 2; g.splitk = p.sk_ac[l];
+      g.nbatch = p.nets; g.splitk = p.sk_ac[l];
       if (l == 0) g.flop_credit = (double)p.xw / p.xld;   // the zero-padded input columns carry no algorithmic work
-      g.sCsplit = 2LL * out * in; g.sCbiasSplit = 2LL * out;
+      g.sCsplit = (long long)p.nets * out * in; g.sCbiasSplit = (long long)p.nets * out;
       wgrads[n_wgrads++] = g;
     }
     if (l > 0) {  // dgrad into the previous hidden layer, times tanh'
@@ -1908,7 +1925,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
       // d(xcat) = [dZ1_actor | dZ1_critic] . [W1a ; W1c] (one contraction, K = 2*u0p), times tanh'
       // of xcat: columns obs..obs+latent-1 are d(pre-activation) of the last env_mlp layer; the
       // other columns (observations, padding) are never read.
-      const int K2 = 2 * p.u0p;
+      const int K2 = p.nets * p.u0p;
       if (p.lat_fused && p.latz && latent_rowdot(p, st)) {
         // (LATZ: the env level's row-block kernel forms dZ of the second env layer from the row dots itself)
       } else if (p.lat_fused) {
@@ -2087,10 +2104,10 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
     if (!(l > 0 ? do0 : do1)) continue;
     const int out = p.u[l], in = ac_in(p, l);
     const int inw = (l == 0) ? p.xld : in;  // slab rows are inw wide; the parameter rows are `in` wide
-    for (int net = 0; net < 2; ++net) {
+    for (int net = 0; net < p.nets; ++net) {
       add(p.o_acW[l] + net * p.ac_block, slab + p.s_acW[l] + (long long)net * out * inw,
-          2LL * out * inw, out, in, inw, p.sk_ac[l]);
-      add(p.o_acB[l] + net * p.ac_block, slab + p.s_acB[l] + (long long)net * out, 2LL * out, 1, out, 0,
+          (long long)p.nets * out * inw, out, in, inw, p.sk_ac[l]);
+      add(p.o_acB[l] + net * p.ac_block, slab + p.s_acB[l] + (long long)net * out, (long long)p.nets * out, 1, out, 0,
           p.sk_ac[l]);
     }
   }
@@ -2180,7 +2197,7 @@ static int teacher_apply(const igi_teacher_cfg* c, const igi_teacher_state* st, 
     ga.stop = stop;   // the gather blocks of a stopping step must not publish step s + 1's running state
     W1Mirror mir;
     mir.w1p = ga.w1p; mir.wlat = ga.wlat; mir.o_w = ga.o_w; mir.ac_block = ga.ac_block; mir.u0 = ga.u0;
-    mir.u0p = ga.u0p; mir.xw = p.xw; mir.xld = p.xld; mir.obs = p.obs; mir.K2p = ga.K2p;
+    mir.u0p = ga.u0p; mir.xw = p.xw; mir.xld = p.xld; mir.obs = p.obs; mir.K2p = ga.K2p; mir.nets = p.nets;
     IGI_LAUNCH(k_adam_gather, dim3(nb + p.gs_blocks), dim3(256), 0, s, aa, mir, ga, nb);
     if ((rc = (int)hipGetLastError())) return rc;
   } else {
@@ -2362,7 +2379,7 @@ static int teacher_infer(const igi_teacher_cfg* c, const igi_teacher_state* st, 
       int hb = (nr + 3) / 4;
       if (hb > 1024) hb = 1024;
       const float* h = wsp<float>(st, p.w_h[p.nl - 1]);
-      const long long ns = (long long)p.mb * ldh;
+      const long long ns = p.nets == 2 ? (long long)p.mb * ldh : 0;   // shared trunk: the value head reads the actor's rows
       float* mo = mu ? mu + r0 * p.act : nullptr;
       float* vo = value ? value + r0 : nullptr;
       IGI_LAUNCH_MAXJ(k_heads_infer, H, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW, P + p.o_muB, P + p.o_valW,
@@ -2391,12 +2408,12 @@ struct PolicyStageArgs {
   float* xcat; int xld, xw; float* priv_g; int pld;
   float* obses_t; float* priv_t;            // arena slot (raw copies) or NULL
   const float* params; long long o_w, ac_block; int u0, u0p; float* w1p;
-  int stage_blocks;
+  int stage_blocks, nets;
 };
 
 __global__ __launch_bounds__(256) void k_policy_stage(const PolicyStageArgs a) {
   if ((int)blockIdx.x >= a.stage_blocks) {  // W1p[net][o][c] refresh (see k_pad_w1)
-    const int total = 2 * a.u0p * a.xld;
+    const int total = a.nets * a.u0p * a.xld;
     const int nb = (int)gridDim.x - a.stage_blocks;
     for (int e = ((int)blockIdx.x - a.stage_blocks) * blockDim.x + threadIdx.x; e < total; e += nb * blockDim.x) {
       const int c = e % a.xld;
@@ -2522,13 +2539,14 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
     long long tot = (long long)nr * D;
     int nb = (int)((tot + 255) / 256);
     if (nb > 2048) nb = 2048;
-    a.stage_blocks = nb;
+    a.stage_blocks = nb; a.nets = p.nets;
     const int pad_blocks = 16;
     {
       ProfScope ps(PC_OTHER, s, 0.0, 8.0 * tot);
       IGI_LAUNCH(k_policy_stage, dim3(nb + pad_blocks), dim3(256), 0, s, a);
     }
-    if (policy_fwd_enabled() && !bf16_mode() && policy_fwd_shape_ok(p.obs, p.priv, p.act, p.npl, p.pu, p.nl, p.u, p.xw) && p.xld == 32) {
+    // (the persistent kernel assigns one net per workgroup pair: a shared trunk takes the per-layer launches)
+    if (p.nets == 2 && policy_fwd_enabled() && !bf16_mode() && policy_fwd_shape_ok(p.obs, p.priv, p.act, p.npl, p.pu, p.nl, p.u, p.xw) && p.xld == 32) {
       // env_mlp, the contact encoder, both trunks, the heads, the sample and the arena writes (the step's raw contacts
       // among them) of these rows as ONE persistent launch (policy_fwd.h)
       PolicyFwdArgs f;
@@ -2564,7 +2582,7 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
     int hb = (nr + 3) / 4;
     if (hb > 1024) hb = 1024;
     const float* h = wsp<float>(st, p.w_h[p.nl - 1]);
-    const long long ns = (long long)p.mb * ldh;
+    const long long ns = p.nets == 2 ? (long long)p.mb * ldh : 0;
     ProfScope ps(PC_OTHER, s, 0.0, 8.0 * nr * H);
     IGI_LAUNCH_MAXJ(k_heads_act_store, H, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW, P + p.o_muB, P + p.o_valW,
                     P + p.o_valB, nr, p.act, t);

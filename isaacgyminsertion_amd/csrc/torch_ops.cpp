@@ -55,8 +55,8 @@ igi_teacher_cfg unpack_cfg(at::IntArrayRef ic, at::ArrayRef<double> fc) {
   // the adaptive learning-rate schedule appends ONE int (lr_schedule) and three floats (kl_threshold, lr_min, lr_max)
   const bool sched = fc.size() == 15;
   const int ni = (int)ic.size() - (sched ? 1 : 0);
-  TORCH_CHECK((ni == 8 + 2 * M || ni == 11 + 2 * M) && (fc.size() == 12 || sched), "teacher cfg: expected ",
-              8 + 2 * M, " (or ", 11 + 2 * M, " with contacts) ints and 12 floats (one more int and 15 floats with the adaptive "
+  TORCH_CHECK((ni == 8 + 2 * M || ni == 10 + 2 * M || ni == 11 + 2 * M) && (fc.size() == 12 || sched), "teacher cfg: expected ",
+              8 + 2 * M, " (", 10 + 2 * M, " with a shared trunk, ", 11 + 2 * M, " with contacts) ints and 12 floats (one more int and 15 floats with the adaptive "
               "learning-rate schedule), got ", ic.size(), " and ", fc.size());
   igi_teacher_cfg c;
   std::memset(&c, 0, sizeof(c));
@@ -72,6 +72,10 @@ igi_teacher_cfg unpack_cfg(at::IntArrayRef ic, at::ArrayRef<double> fc) {
   if (ni == 11 + 2 * M) {   // contact mode (ops.py pack_cfg)
     c.contact_points = (int32_t)ic[8 + 2 * M]; c.contact_emb = (int32_t)ic[9 + 2 * M]; c.only_contact = (int32_t)ic[10 + 2 * M];
     TORCH_CHECK(c.contact_points >= 1, "teacher cfg: the contact fields need contact_points >= 1");
+  }
+  if (ni == 10 + 2 * M) {   // shared actor-critic trunk (ops.py pack_cfg): two trailing ints, always (1, 0)
+    c.shared_parameters = (int32_t)ic[8 + 2 * M];
+    TORCH_CHECK(c.shared_parameters == 1 && ic[9 + 2 * M] == 0, "teacher cfg: the shared-trunk fields must be (1, 0)");
   }
   c.gamma = fc[0]; c.tau = fc[1]; c.lr = fc[2]; c.beta1 = fc[3]; c.beta2 = fc[4]; c.adam_eps = fc[5];
   c.e_clip = (float)fc[6]; c.critic_coef = (float)fc[7]; c.entropy_coef = (float)fc[8]; c.bounds_loss_coef = (float)fc[9];

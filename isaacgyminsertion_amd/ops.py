@@ -133,6 +133,8 @@ def pack_cfg(cfg):
            [cfg.n_layers] + [int(x) for x in cfg.units] + [cfg.num_envs, cfg.horizon, cfg.mini_epochs]
     if cfg.contact_points > 0:   # contact mode: three trailing ints (a contact-free cfg packs exactly as before)
         icfg += [cfg.contact_points, cfg.contact_emb, cfg.only_contact]
+    elif cfg.shared_parameters:  # shared actor-critic trunk: TWO trailing ints, (1, 0) -- never with contacts, so the lengths
+        icfg += [1, 0]           # tell the modes apart; ONE more int with twelve floats is the schedule's int without its floats
     fcfg = [cfg.gamma, cfg.tau, cfg.lr, cfg.beta1, cfg.beta2, cfg.adam_eps, cfg.e_clip, cfg.critic_coef,
             cfg.entropy_coef, cfg.bounds_loss_coef, cfg.grad_norm, cfg.rms_eps]
     if cfg.lr_schedule:          # adaptive learning rate: one trailing int, three trailing floats (fixed packs as before)
@@ -146,8 +148,8 @@ def _unpack_cfg(icfg, fcfg):
     sched = len(fcfg) == 15      # + lr_schedule | kl_threshold, lr_min, lr_max
     if sched:
         icfg, fcfg, tail = icfg[:-1], fcfg[:12], (icfg[-1], *fcfg[12:])
-    if len(icfg) not in (8 + 2 * M, 11 + 2 * M) or len(fcfg) != 12:
-        raise RuntimeError(f"teacher cfg: expected {8 + 2 * M} (or {11 + 2 * M} with contacts) ints and 12 floats (one "
+    if len(icfg) not in (8 + 2 * M, 10 + 2 * M, 11 + 2 * M) or len(fcfg) != 12:
+        raise RuntimeError(f"teacher cfg: expected {8 + 2 * M} ({10 + 2 * M} with a shared trunk, {11 + 2 * M} with contacts) ints and 12 floats (one "
                            f"more int and 15 floats with the adaptive learning-rate schedule), "
                            f"got {len(icfg) + sched} and {len(fcfg) + 3 * sched}")
     c = _lib.TeacherCfg()
@@ -166,6 +168,10 @@ def _unpack_cfg(icfg, fcfg):
         c.contact_points, c.contact_emb, c.only_contact = icfg[8 + 2 * M:11 + 2 * M]
         if c.contact_points < 1:
             raise RuntimeError("teacher cfg: the contact fields need contact_points >= 1")
+    if len(icfg) == 10 + 2 * M:
+        c.shared_parameters = icfg[8 + 2 * M]
+        if c.shared_parameters != 1 or icfg[9 + 2 * M] != 0:
+            raise RuntimeError("teacher cfg: the shared-trunk fields must be (1, 0)")
     (c.gamma, c.tau, c.lr, c.beta1, c.beta2, c.adam_eps, c.e_clip, c.critic_coef, c.entropy_coef,
      c.bounds_loss_coef, c.grad_norm, c.rms_eps) = fcfg
     if min(c.obs_dim, c.priv_dim, c.act_dim, c.num_envs, c.horizon, c.mini_epochs) < 1 or \

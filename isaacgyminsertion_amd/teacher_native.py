@@ -31,15 +31,16 @@ CONTACT_NAMES = ("contact_ae.contact_enc_mlp.0.weight", "contact_ae.contact_enc_
                  "contact_ae.contact_dec_mlp.2.weight", "contact_ae.contact_dec_mlp.2.bias")
 
 
-def teacher_param_names(n_priv_layers, n_layers, contacts=False):
+def teacher_param_names(n_priv_layers, n_layers, contacts=False, shared_parameters=False):
     """ActorCriticSplit.state_dict() key order (models_split.py:73-106); contact_ae between env_mlp
-    and actor_mlp when the teacher has ground-truth contacts (models_split.py:81-84)."""
+    and actor_mlp when the teacher has ground-truth contacts (models_split.py:81-84); no critic_mlp with a shared
+    trunk (models_split.py:100-102)."""
     names = ["sigma"]
     for i in range(n_priv_layers):
         names += [f"env_mlp.mlp.{2 * i}.weight", f"env_mlp.mlp.{2 * i}.bias"]
     if contacts:
         names += list(CONTACT_NAMES)
-    for net in ("actor_mlp", "critic_mlp"):
+    for net in ("actor_mlp",) if shared_parameters else ("actor_mlp", "critic_mlp"):
         for i in range(n_layers):
             names += [f"{net}.mlp.{2 * i}.weight", f"{net}.mlp.{2 * i}.bias"]
     names += ["value.weight", "value.bias", "mu.weight", "mu.bias"]
@@ -47,7 +48,7 @@ def teacher_param_names(n_priv_layers, n_layers, contacts=False):
 
 
 def teacher_param_shapes(obs_dim, priv_dim, act_dim, units, priv_units, contact_points=0, contact_emb=0,
-                         only_contact=False):
+                         only_contact=False, shared_parameters=False):
     shapes = OrderedDict()
     shapes["sigma"] = (act_dim,)
     d = priv_dim
@@ -62,7 +63,7 @@ def teacher_param_shapes(obs_dim, priv_dim, act_dim, units, priv_units, contact_
             shapes[k] = shp
         if not only_contact:
             trunk_in += E
-    for net in ("actor_mlp", "critic_mlp"):
+    for net in ("actor_mlp",) if shared_parameters else ("actor_mlp", "critic_mlp"):
         d = trunk_in
         for i, u in enumerate(units):
             shapes[f"{net}.mlp.{2 * i}.weight"] = (u, d)
@@ -132,8 +133,10 @@ def slice_update_lists(stats, mini_epochs, n_mb, stop_step):
 
 
 def make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon, mini_epochs, contact_points=0,
-             contact_emb=0, only_contact=False, lr_schedule="fixed", kl_threshold=0.008, lr_min=1e-6, lr_max=1e-2, **hp):
-    """contact_points > 0: the teacher with ground-truth contacts (task.env.compute_contact_gt; num_points P,
+             contact_emb=0, only_contact=False, lr_schedule="fixed", kl_threshold=0.008, lr_min=1e-6, lr_max=1e-2,
+             shared_parameters=False, **hp):
+    """shared_parameters: one actor-critic trunk, value = value(actor_mlp(x)) (train.ppo.shared_parameters; not with
+    contacts).  contact_points > 0: the teacher with ground-truth contacts (task.env.compute_contact_gt; num_points P,
     contact_mlp.units[-1] = contact_emb, train.ppo.only_contact).  lr_schedule "adaptive": the KL-adaptive learning
     rate scheduled on the device (kl_threshold, lr_min, lr_max as rl_games' AdaptiveScheduler); "fixed" leaves the four
     schedule fields zero, whatever the other three arguments say."""
@@ -142,6 +145,8 @@ def make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon, m
     sched = lr_schedule_id(lr_schedule)
     if sched and not (float(kl_threshold) > 0 and 0 < float(lr_min) <= float(lr_max)):
         raise ValueError("the adaptive schedule needs kl_threshold > 0 and 0 < lr_min <= lr_max")
+    if shared_parameters and contact_points:
+        raise NotImplementedError("shared_parameters with compute_contact_gt is not supported")
     if contact_points:
         if not 1 <= contact_emb <= 32:
             raise ValueError(f"contact embedding width {contact_emb}: 1 .. 32 supported")
@@ -160,6 +165,7 @@ def make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon, m
     for i, u in enumerate(units):
         c.units[i] = int(u)
     c.num_envs, c.horizon, c.mini_epochs = num_envs, horizon, mini_epochs
+    c.shared_parameters = int(bool(shared_parameters))
     c.gamma, c.tau = float(h["gamma"]), float(h["tau"])
     c.lr, c.beta1, c.beta2, c.adam_eps = float(h["lr"]), float(h["beta1"]), float(h["beta2"]), float(h["adam_eps"])
     c.e_clip, c.critic_coef = float(h["e_clip"]), float(h["critic_coef"])
@@ -189,8 +195,9 @@ class TeacherEngine:
     def __init__(self, num_envs, horizon, mini_epochs, units=(512, 256, 128), priv_units=(256, 128, 8),
                  obs_dim=15, priv_dim=64, act_dim=6, device="cuda:0", perm=None, contact_points=0, contact_emb=0,
                  only_contact=False, lr_schedule="fixed", kl_threshold=0.008, lr_min=1e-6, lr_max=1e-2,
-                 kl_early_stop=False, **hp):
-        """kl_early_stop: stop an update at the first optimizer step whose approx_kl exceeds 1.5 * kl_threshold, decided
+                 kl_early_stop=False, shared_parameters=False, **hp):
+        """shared_parameters: one trunk for actor and critic (train.ppo.shared_parameters; ``engine.shared_parameters``).
+        kl_early_stop: stop an update at the first optimizer step whose approx_kl exceeds 1.5 * kl_threshold, decided
         on the device (``stop_step``, ``steps_applied``, ``approx_kl()``); data parallel: from the rank-mean estimator."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -199,7 +206,8 @@ class TeacherEngine:
         self.cfg, self.hp = make_cfg(obs_dim, priv_dim, act_dim, units, priv_units, num_envs, horizon,
                                      mini_epochs, contact_points=contact_points, contact_emb=contact_emb,
                                      only_contact=only_contact, lr_schedule=lr_schedule, kl_threshold=kl_threshold,
-                                     lr_min=lr_min, lr_max=lr_max, **hp)
+                                     lr_min=lr_min, lr_max=lr_max, shared_parameters=shared_parameters, **hp)
+        self.shared_parameters = bool(self.cfg.shared_parameters)
         self.adaptive_lr = bool(self.cfg.lr_schedule)
         self.kl_early_stop = parse_kl_early_stop(kl_early_stop)
         self._kl_threshold = float(kl_threshold)
@@ -213,7 +221,7 @@ class TeacherEngine:
         self.obs_dim, self.priv_dim, self.act_dim = obs_dim, priv_dim, act_dim
         self.units, self.priv_units = list(units), list(priv_units)
         self.shapes = teacher_param_shapes(obs_dim, priv_dim, act_dim, self.units, self.priv_units, contact_points,
-                                           contact_emb, only_contact)
+                                           contact_emb, only_contact, self.shared_parameters)
         self.P, self.layout = param_layout(self.cfg)
         assert len(self.layout) == len(self.shapes)
         dev = self.device
@@ -476,7 +484,7 @@ class TeacherEngine:
     def grad_buckets(self):
         """((early ranges), (late ranges)) of the flat gradient as (offset, length) pairs, empty ranges dropped:
         early = actor layers >= 1 | critic layers >= 1 + value + mu; late = sigma + env_mlp + actor layer 0 | critic
-        layer 0 (igi_teacher_grad_buckets)."""
+        layer 0 (igi_teacher_grad_buckets).  Shared trunk: one early range (actor layers >= 1 + value + mu) and one late."""
         off, ln = (C.c_int64 * 4)(), (C.c_int64 * 4)()
         n = self.L.igi_teacher_grad_buckets(C.byref(self.cfg), off, ln)
         if n != 4:
