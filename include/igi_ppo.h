@@ -577,7 +577,9 @@ int igi_depth_backward(const igi_depth_cfg* cfg, const float* x, const float* dy
 
 /* ------------------------------------------------------------------------------------------
  * Token decoder of the student: `layers` x nn.TransformerEncoderLayer(d_model 32, nhead 2, dim_feedforward ff,
- * activation "gelu", batch_first, norm_first) over `seq` <= 8 tokens per sample
+ * activation "gelu", batch_first, norm_first) over `seq` <= 32 tokens per sample
+ * (seq <= 8: attention in registers, 16 lanes per (sample, head); 9 .. 32: one 32 x 32 MFMA tile per (sample, head);
+ * beyond 32: IGI_E_UNSUPPORTED)
  * (algo/models/transformer/tact.py:137-158: MultiLayerDecoder.sa_decoder), forward and backward.
  * x, y, dy, dx: (batch, seq, 32) fp32.  params / grads: layers x igi_token_param_count()/layers floats, each layer
  * in nn.TransformerEncoderLayer's parameter order (in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias,

@@ -121,6 +121,11 @@ class MultiModalModel(nn.Module):
             raise NotImplementedError("efficientnet image encoders are outside the scope table (SURVEY section 2)")
         if tactile_encoder != "depth" or not stack_tactile or not share_encoding or additional_lin:
             raise NotImplementedError("only the reference's default 'depth' tactile encoder path is built")
+        if include_pcl and context_size > 1:
+            raise NotImplementedError(
+                "point clouds with an observation history (context_size > 1) are not built: the reference sizes the decoder "
+                "for context_size point-cloud tokens and its pcl branch supplies one (tact.py:375, 542-583), so it cannot "
+                "run this configuration itself")
         self.context_size = context_size
         self.num_output_params = num_outputs
         self.tactile_encoding_size = tactile_encoding_size

@@ -30,7 +30,10 @@ enum ProfClass {
   PC_CONVB_PM64, PC_CONVB_PM32, PC_CONVB_PW32, PC_CONVB_PW64, PC_CONVB_PW64_192, PC_CONVB_ROW64, PC_CONVB_WG64, PC_CONVB_PW64_128,
   PC_POINTNET_FWD, PC_POINTNET_BWD, PC_SOFTARGMAX_FWD, PC_SOFTARGMAX_BWD,
   PC_DMA_HEAD, PC_TRUNK_LOSS, PC_RB_TRUNK, PC_RB_ENV, PC_MLP_FWD, PC_POLICY_FWD, PC_FWD12, PC_ENV_FWD, PC_GEMM_GENERIC, PC_GATHER_NORMALIZE, PC_RMS_FINAL, PC_NORMALIZE,
-  PC_LOSS, PC_LATENT_BWD, PC_SLAB_REDUCE, PC_SUMSQ, PC_ADAM, PC_ADAM_GATHER, PC_LR_SCHEDULE, PC_PREPARE, PC_OTHER, PC_COUNT
+  PC_LOSS, PC_LATENT_BWD, PC_SLAB_REDUCE, PC_SUMSQ, PC_ADAM, PC_ADAM_GATHER, PC_LR_SCHEDULE, PC_PREPARE,
+  // the student's token encoder: the one-launch forward (S <= 8: one symbol per S in rocprofv3, "<S>" is ours; 9 .. 32 tokens:
+  // k_token_fwd_long) and the tile attention kernels of the launch-per-operation path
+  PC_TOKEN_FWD, PC_TOKEN_FWD_LONG, PC_ATTN_TILE_FWD, PC_ATTN_TILE_BWD, PC_OTHER, PC_COUNT
 };
 
 static const char* const kProfNames[PC_COUNT] = {
@@ -64,7 +67,8 @@ static const char* const kProfNames[PC_COUNT] = {
     "k_rb_level#trunk3: dW 256->128 x2 + dgrad 128->256 x2", "k_rb_level#env2: dW env 256->128 + env dgrad 128->256 (+ dW env 64->256 from its tiles)",
     "k_mlp_fwd", "k_policy_fwd", "k_fwd12",
     "k_env_fwd", "gemm_f32_kernel<*>", "k_gather_normalize", "k_rms_final", "k_normalize",
-    "k_loss", "k_latent_bwd", "k_slab_reduce", "k_sumsq_stats", "k_clip_adam", "k_adam_gather", "k_lr_schedule", "k_gae+k_prep_final+k_prep_norm", "other"};
+    "k_loss", "k_latent_bwd", "k_slab_reduce", "k_sumsq_stats", "k_clip_adam", "k_adam_gather", "k_lr_schedule", "k_gae+k_prep_final+k_prep_norm",
+    "k_token_fwd<S>", "k_token_fwd_long", "k_attn_tile_fwd", "k_attn_tile_bwd", "other"};
 
 // which backward level the next gemm_dma_wgrad_multi_kernel launch belongs to (set by the teacher's orchestration)
 static thread_local int g_multi_level = 4;

@@ -1,5 +1,5 @@
 // Token decoder of the student: a stack of nn.TransformerEncoderLayer(d_model=32, nhead=2,
-// dim_feedforward=128, activation="gelu", batch_first=True, norm_first=True) over S <= 8 tokens
+// dim_feedforward=128, activation="gelu", batch_first=True, norm_first=True) over S <= 32 tokens
 // (algo/models/transformer/tact.py:137-158), forward and backward.
 //
 //   per layer:  x1 = x  + drop(out_proj(attn(in_proj(LN1(x)))))          (sa block,  norm_first)
@@ -12,7 +12,9 @@
 //                    wave owns a row (lane = feature), statistics by DPP row sums
 //   k_attn_fwd/bwd : softmax(q k^T / sqrt(16)) v for an S x S block per (sample, head); 16 lanes own a
 //                    (sample, head) pair, lane = head dimension, dot products are 16-lane DPP row sums;
-//                    backward recomputes the probabilities (nothing S x S is ever stored)
+//                    backward recomputes the probabilities (nothing S x S is ever stored); S <= 8
+//   k_attn_tile_fwd/bwd : the same for 9 <= S <= 32: a wave owns a (sample, head) pair, the S x S block is one padded
+//                    32 x 32 tile of v_mfma_f32_32x32x2_f32, S a runtime argument
 //   k_gelu_fwd/bwd : exact (erf) GELU + dropout
 //   k_ln_bwd       : LayerNorm backward + residual gradient add + (optionally) the dropout mask of the
 //                    branch below it; per-block partial sums for the LayerNorm weight / bias gradients,
@@ -26,10 +28,13 @@
 #include <hip/hip_runtime.h>
 
 #include "linear.h"
+#include "prof.h"
 
 namespace igi {
 
-constexpr int TOK_D = 32, TOK_DH = 16, TOK_MAX_S = 8;
+constexpr int TOK_D = 32, TOK_DH = 16;
+constexpr int TOK_MAX_S = 8;     // tokens per sample of the register attention kernels (k_attn_fwd<S>, k_token_fwd<S>)
+constexpr int TOK_MAX_SEQ = 32;  // tokens per sample of the tile attention kernels (k_attn_tile_*, k_token_fwd_long)
 constexpr float TOK_LN_EPS = 1e-5f;
 
 struct TokenPlan {
@@ -53,7 +58,7 @@ static inline long long ru4ll(long long x) { return (x + 3) & ~3LL; }
 static int make_token_plan(const igi_token_cfg* c, TokenPlan* p) {
   if (!c || c->batch < 1 || c->seq < 1 || c->layers < 1 || c->ff < 4 || c->dropout < 0.f || c->dropout >= 1.f)
     return IGI_E_BADARG;
-  if (c->d_model != TOK_D || c->nhead * TOK_DH != TOK_D || c->seq > TOK_MAX_S || (c->ff & 3) || c->layers > 8)
+  if (c->d_model != TOK_D || c->nhead * TOK_DH != TOK_D || c->seq > TOK_MAX_SEQ || (c->ff & 3) || c->layers > 8)
     return IGI_E_UNSUPPORTED;
   p->B = c->batch; p->S = c->seq; p->d = c->d_model; p->H = c->nhead; p->ff = c->ff; p->L = c->layers;
   p->R = (long long)c->batch * c->seq;
@@ -93,7 +98,7 @@ static int make_token_plan(const igi_token_cfg* c, TokenPlan* p) {
   p->bwd_grid = (int)((p->B + p->bwd_samples - 1) / p->bwd_samples);
   // one 100 KB gradient record per workgroup: beyond 1024 of them (>= 21 K samples of three tokens) the backward runs
   // launch by launch on split-row slabs instead, and no record space is reserved
-  if (p->bwd_grid > 1024) p->bwd_grid = 0;
+  if (p->bwd_grid > 1024 || p->S > TOK_MAX_S) p->bwd_grid = 0;   // (S > 8: no one-launch backward either)
   p->s_part = stake((long long)p->bwd_grid * p->per_layer * p->L);   // one gradient record per workgroup
   p->s_lin = stake(0);
   size_t lb = linear_workspace_bytes(R, d, 3 * d);
@@ -314,6 +319,236 @@ __global__ __launch_bounds__(256) void k_attn_bwd(const float* __restrict__ qkv,
   }
 }
 
+// ---- attention for 9 <= S <= 32 tokens: the S x S block of one (sample, head) pair as ONE 32 x 32 tile of
+// v_mfma_f32_32x32x2_f32, one wave per pair, S a runtime argument.  Same semantics as k_attn_fwd / k_attn_bwd (scale
+// 0.25, max-subtracted __expf softmax, dropout element ((b H + h) S + i) S + j, probabilities recomputed in the
+// backward).  The scores are formed TRANSPOSED (A = K rows, B = Q rows): lane (i, half) then owns query i and its 16
+// accumulator registers run over the keys j = tile_row(r, half), so the softmax is an in-register reduction plus one
+// exchange between the half waves, and the probabilities already sit where the A operand of P . V wants them (k-step r
+// takes key tile_row(r, 0) from the lower half wave and tile_row(r, 1) from the upper).
+// Padding: a tile row >= S is read from row S - 1 instead (always inside the sample, always finite), the scores of the
+// keys j >= S are set to -inf ONCE, so their probabilities are exact zeros and whatever they multiply drops out;
+// queries i >= S compute a copy of row S - 1 that is never written.  (Predicates per register would each hold a lane
+// mask in two SGPRs: with 16 of them alive across the routine k_token_fwd_long spilled SGPRs.)
+__device__ __forceinline__ int tile_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+// the same value behind an empty asm.  The routines below take S and the lane number through these once per pair: what
+// they derive from them (16 row offsets per operand, store offsets, lane masks) is invariant across the pairs and the
+// layers, and hoisted out of those loops it stays alive through the whole kernel -- k_token_fwd_long then spills.  A
+// comparison against a second opaque copy is not merged with the earlier ones either (whose masks would stay alive).
+__device__ __forceinline__ int tok_opaque(int x) { asm volatile("" : "+s"(x)); return x; }
+__device__ __forceinline__ int tok_opaque_lane(int x) { asm volatile("" : "+v"(x)); return x; }
+
+// probabilities of the pair: pr[r] = softmax_j(q_i . k_j / 4) at lane (i = lane & 31, half), j = tile_row(r, half)
+// (0 for j >= S).  q: the pair's first query row (this head's 16 columns), k 32 floats further on, pitch ld.
+__device__ __forceinline__ void attn_tile_probs(const float* q, int ld, int S, int lane, f32x16& pr) {
+  const int l31 = lane & 31, half = lane >> 5;
+  const float* row = q + min(l31, S - 1) * ld + 4 * half;
+  f32x4 kv[2], qv[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    kv[c] = *reinterpret_cast<const f32x4*>(row + TOK_D + 8 * c);
+    qv[c] = *reinterpret_cast<const f32x4*>(row + 8 * c);
+  }
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 2; ++c)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[c][j], qv[c][j], acc, 0, 0, 0);
+  float mx = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    acc[r] = tile_row(r, half) < S ? acc[r] * 0.25f : -INFINITY;  // 1 / sqrt(16); padded keys
+    mx = fmaxf(mx, acc[r]);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));   // finite: key 0 is valid
+  float den = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    acc[r] = __expf(acc[r] - mx);           // padded keys: exp(-inf) = 0
+    den += acc[r];
+  }
+  den += __shfl_xor(den, 32, 64);
+  const float inv = 1.0f / den;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) pr[r] = acc[r] * inv;
+  // (the dropout hashes that follow depend on nothing above: without this the scheduler starts all 16 of them under the
+  //  matrix products and the routine no longer fits k_token_fwd_long's 128 registers)
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// C[32][16] = sum_j a[r] (row i = lane & 31, column j = tile_row(r, half)) . X[j][0..15]; a is zero in the columns j >= S.
+// Result at lane (d = lane & 15, half): o[r] = C[tile_row(r, half)][d] (lanes 16 .. 31 of a half wave repeat 0 .. 15).
+// DROP: a[r] first passes the dropout of element e0 + j (the forward's P . V).
+template <bool DROP>
+__device__ __forceinline__ void attn_tile_rowmix(const f32x16& a, const float* X, int ld, int S, int lane, f32x16& o,
+                                                 const Drop& dr, unsigned int e0) {
+  const int half = lane >> 5;
+  X += lane & 15;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) o[r] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {               // four k-steps' operands at a time (registers: k_token_fwd_long has 128)
+    float xv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) xv[u] = X[min(tile_row(4 * c + u, half), S - 1) * ld];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float av = a[4 * c + u];
+      if (DROP) av = drop_apply(dr, e0 + (unsigned int)tile_row(4 * c + u, half), av);   // (padded keys: 0 stays 0)
+      o = __builtin_amdgcn_mfma_f32_32x32x2f32(av, xv[u], o, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// forward of one pair by one wave.  g: the global (sample, head) index (dropout element numbers); cl (may be null):
+// context rows in LDS, pitch ldc; cg: context rows in global memory, pitch TOK_D (both at this head's columns).
+__device__ __forceinline__ void attn_tile_fwd(const float* q, int ld, int S, long long g, const Drop& dr, float* cl, int ldc,
+                                              float* cg) {
+  S = tok_opaque(S);
+  const int lane = tok_opaque_lane(threadIdx.x & 63), l31 = lane & 31, half = lane >> 5;
+  f32x16 pr, o;
+  attn_tile_probs(q, ld, S, lane, pr);
+  const unsigned int e0 = (unsigned int)((g * S + l31) * S);
+  attn_tile_rowmix<true>(pr, q + 2 * TOK_D, ld, S, lane, o, dr, e0);
+  if (l31 < TOK_DH) {
+    const int Sw = tok_opaque(S);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = tile_row(r, half);
+      if (i < Sw) {
+        if (cl) cl[i * ldc + l31] = o[r];
+        cg[i * TOK_D + l31] = o[r];
+      }
+    }
+  }
+}
+
+constexpr int AT_LDT = 33;                      // pitch of the 32 x 32 transposition tiles of the backward
+constexpr int AT_TILE = 32 * AT_LDT;
+
+// C[32][16] = sum_i T[j][i] X[i][0..15] for the tile T (row = key j, column = query i; zero in the columns i >= S):
+// A = the tile's row (key = lane & 31), k-step t takes query 2 t + half.  Result as attn_tile_rowmix's.
+__device__ __forceinline__ void attn_tile_colmix(const float* T, const float* X, int ldx, int S, int lane, f32x16& o) {
+  const int l31 = lane & 31, half = lane >> 5;
+  X += lane & 15;
+  T += l31 * AT_LDT + half;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) o[r] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    float av[4], xv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      av[u] = T[2 * (4 * c + u)];
+      xv[u] = X[min(2 * (4 * c + u) + half, S - 1) * ldx];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) o = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], xv[u], o, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// backward of one pair by one wave: dV = (P m)^T dC, dP = (dC V^T) m, dS = P (dP - rowsum(dP P)) / 4, dQ = dS K,
+// dK = dS^T Q (m: the dropout factors).  dP is formed transposed like the scores (A = V rows, B = dC rows), so it meets
+// P register for register; dQ contracts over the keys, which the registers run over; dV and dK contract over the
+// queries, which the lanes run over: P m and dS go through two 32 x 32 LDS tiles (T, this wave's own; the columns of the
+// queries >= S written as zeros) to be read back as A operands with the query as the k index.
+// q / dc / dq: first rows of the pair at this head's columns (dq: pitch ld like q).
+__device__ __forceinline__ void attn_tile_bwd(const float* q, int ld, const float* dc, float* dq, int S, long long g,
+                                              const Drop& dr, float* T) {
+  S = tok_opaque(S);
+  const int lane = tok_opaque_lane(threadIdx.x & 63), l31 = lane & 31, half = lane >> 5;
+  f32x16 pr, dp, o;
+  attn_tile_probs(q, ld, S, lane, pr);
+  {
+    const int rowi = min(l31, S - 1);
+    f32x4 vv[2], cv[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      vv[c] = *reinterpret_cast<const f32x4*>(q + rowi * ld + 2 * TOK_D + 8 * c + 4 * half);
+      cv[c] = *reinterpret_cast<const f32x4*>(dc + rowi * TOK_D + 8 * c + 4 * half);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dp[r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[c][j], cv[c][j], dp, 0, 0, 0);
+  }
+  const unsigned int e0 = (unsigned int)((g * S + l31) * S);
+  const bool query = l31 < S;
+  float dot = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int j = tile_row(r, half);
+    // the mask factor m_ij in {0, 1/(1-p)}: P_drop = P * m
+    const float m = drop_apply(dr, e0 + (unsigned int)j, 1.0f);
+    dp[r] *= m;                               // d(loss)/dP_ij
+    dot += dp[r] * pr[r];
+    T[j * AT_LDT + l31] = query ? pr[r] * m : 0.f;          // (P m)^T: row = key, column = query
+    if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+  }
+  dot += __shfl_xor(dot, 32, 64);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    dp[r] = pr[r] * (dp[r] - dot) * 0.25f;    // dS: d(loss)/d(score_ij) incl. the 1/sqrt(dh); zero at the padded keys
+    T[AT_TILE + tile_row(r, half) * AT_LDT + l31] = query ? dp[r] : 0.f;
+  }
+  const int Sw = tok_opaque(S);
+  attn_tile_rowmix<false>(dp, q + TOK_D, ld, S, lane, o, dr, 0u);  // dQ = dS K
+  if (l31 < TOK_DH) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = tile_row(r, half);
+      if (i < Sw) dq[i * ld + l31] = o[r];
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {               // dV = (P m)^T dC (dC: pitch TOK_D), then dK = dS^T Q
+    attn_tile_colmix(T + w * AT_TILE, w == 0 ? dc : q, w == 0 ? TOK_D : ld, S, lane, o);
+    if (l31 < TOK_DH) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int j = tile_row(r, half);
+        if (j < Sw) dq[j * ld + (w == 0 ? 2 * TOK_D : TOK_D) + l31] = o[r];
+      }
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();             // the wave's next pair rewrites the tiles
+}
+
+constexpr int AT_THREADS = 256;                 // four waves, a (sample, head) pair each per step
+__global__ __launch_bounds__(AT_THREADS) void k_attn_tile_fwd(const float* __restrict__ qkv, float* __restrict__ ctx, Drop dr,
+                                                              long long pairs, int H, int S) {
+  const long long w0 = ((long long)blockIdx.x * AT_THREADS + threadIdx.x) >> 6;
+  const long long nw = ((long long)gridDim.x * AT_THREADS) >> 6;
+  for (long long g = w0; g < pairs; g += nw) {
+    const long long b = g / H;
+    const int h = (int)(g - b * H);
+    attn_tile_fwd(qkv + b * S * (3 * TOK_D) + h * TOK_DH, 3 * TOK_D, S, g, dr, nullptr, 0, ctx + b * S * TOK_D + h * TOK_DH);
+  }
+}
+
+__global__ __launch_bounds__(AT_THREADS) void k_attn_tile_bwd(const float* __restrict__ qkv, const float* __restrict__ dctx,
+                                                              float* __restrict__ dqkv, Drop dr, long long pairs, int H, int S) {
+  __shared__ float tiles[AT_THREADS / 64][2 * AT_TILE];
+  const long long w0 = ((long long)blockIdx.x * AT_THREADS + threadIdx.x) >> 6;
+  const long long nw = ((long long)gridDim.x * AT_THREADS) >> 6;
+  for (long long g = w0; g < pairs; g += nw) {
+    const long long b = g / H;
+    const int h = (int)(g - b * H);
+    attn_tile_bwd(qkv + b * S * (3 * TOK_D) + h * TOK_DH, 3 * TOK_D, dctx + b * S * TOK_D + h * TOK_DH,
+                  dqkv + b * S * (3 * TOK_D) + h * TOK_DH, S, g, dr, tiles[threadIdx.x >> 6]);
+  }
+}
+
 // h = drop(gelu(z)), exact erf form (nn.GELU default / activation="gelu")
 __global__ __launch_bounds__(256) void k_gelu_fwd(const float* __restrict__ z, float* __restrict__ h, Drop dr,
                                                   long long n) {
@@ -361,14 +596,17 @@ enum { SITE_ATTN = 0, SITE_SA = 1, SITE_FF_ACT = 2, SITE_FF = 3 };
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The whole forward as ONE launch (round 5).  As 8 launches per layer + 1 (four GEMMs, two residual + LayerNorm kernels,
-// attention, GELU) the stack was 17 launches of 4 - 8 us for ~0.15 GFLOP.  Here a workgroup of four waves carries up to
-// 128 token rows (32 samples; 16 when a sample has more than four tokens) through every layer with the residual stream,
+// attention, GELU) the stack was 17 launches of 4 - 8 us for ~0.15 GFLOP.  Here a workgroup (TF_THREADS) carries up to
+// 128 token rows = 128 / S whole samples (at most 32 of them; 14 at S = 9, 4 at S = 32) through every layer with the residual stream,
 // the LayerNorm outputs, q / k / v and the feed-forward activations in LDS; a layer's four weight matrices are brought into
 // LDS once per workgroup and layer; every activation the backward pass reads (TokenPlan::a_*) is written out once.
 // Arithmetic = the separate kernels', operation by operation: the Linears are the same fmaf chains on
 // v_mfma_f32_32x32x2_f32 in the LDS-DMA kernel's k order (K = 32 and 128 are whole k-tiles), LayerNorm is the same
-// half-wave-per-row code, attention the same 16-lanes-per-(sample, head) code, the same erf GELU, the same dropout hash on
-// the same element indices -- outputs and saved activations are bit-identical (tests/test_gpu_token_encoder.py).
+// half-wave-per-row code, attention the same code as the separate kernel's (S <= 8, k_token_fwd<S>: 16 lanes per (sample,
+// head), k_attn_fwd<S>'s arithmetic; 9 <= S <= 32, k_token_fwd_long: attn_tile_fwd, the routine k_attn_tile_fwd calls, on the
+// LDS rows, the (sample, head) pairs dealt over the waves), the same erf GELU, the same dropout hash on the same element
+// indices -- outputs and saved activations are bit-identical (tests/test_gpu_token_encoder.py, test_gpu_token_encoder_long.py).
+// Both kernels are token_fwd_body<S>; S = 0 selects the runtime-S tile attention.
 // ---------------------------------------------------------------------------------------------------------------------
 // Waves per workgroup of the two fused kernels.  A workgroup's time is its chain of ~20 phases per layer, each as wide as the
 // workgroup: at 8192 x 2 tokens the forward ran 59.5 / 43.5 / 37.6 us with 256 / 512 / 1024 threads, the backward 95 / 64.6 /
@@ -397,8 +635,9 @@ struct TokFwdArgs {
   float p; unsigned long long seed;
 };
 
+// S = 0: 9 .. 32 tokens per sample, a.S at run time, attention on the matrix-pipe tile (k_token_fwd_long)
 template <int S>
-__global__ __launch_bounds__(TF_THREADS) void k_token_fwd(const TokFwdArgs a) {
+__device__ __forceinline__ void token_fwd_body(const TokFwdArgs& a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* bx = smem;                               // residual stream [rows][36]
   float* bn = bx + TF_ROWS * TF_LDX;              // LayerNorm output / attention context / branch outputs [rows][36]
@@ -482,8 +721,17 @@ __global__ __launch_bounds__(TF_THREADS) void k_token_fwd(const TokFwdArgs a) {
     __syncthreads();
     linear(bn, TF_LDX, TOK_D, win, TF_LDX, 3 * TOK_D, P + a.o_inb, bz, TF_LDZ, A + a.a_qkv);
     __syncthreads();
-    // ---- attention: 16 lanes per (sample, head), k_attn_fwd's arithmetic on the LDS rows; context -> bn
-    {
+    if constexpr (S == 0) {
+      // ---- attention: a wave per (sample, head), k_attn_tile_fwd's routine on the LDS rows; context -> bn
+      const Drop da = make_drop_dev(a.p, a.seed, 4 * l + SITE_ATTN);
+      const int nsamp = nrows / a.S;
+      for (int g = wave; g < nsamp * a.H; g += TF_NW) {
+        const int bl = g / a.H, hh = g - bl * a.H;
+        attn_tile_fwd(bz + bl * a.S * TF_LDZ + hh * TOK_DH, TF_LDZ, a.S, (r0 / a.S + bl) * a.H + hh, da,
+                      bn + bl * a.S * TF_LDX + hh * TOK_DH, TF_LDX, A + a.a_ctx + (r0 + bl * a.S) * TOK_D + hh * TOK_DH);
+      }
+    } else {
+      // ---- attention: 16 lanes per (sample, head), k_attn_fwd's arithmetic on the LDS rows; context -> bn
       const Drop da = make_drop_dev(a.p, a.seed, 4 * l + SITE_ATTN);
       const int dl = tid & 15;
       const int nsamp = nrows / S;
@@ -565,6 +813,11 @@ __global__ __launch_bounds__(TF_THREADS) void k_token_fwd(const TokFwdArgs a) {
   }
 }
 
+template <int S>
+__global__ __launch_bounds__(TF_THREADS) void k_token_fwd(const TokFwdArgs a) { token_fwd_body<S>(a); }
+// 9 <= a.S <= 32: 128 / S whole samples per workgroup, the (sample, head) pairs dealt over the waves
+__global__ __launch_bounds__(TF_THREADS) void k_token_fwd_long(const TokFwdArgs a) { token_fwd_body<0>(a); }
+
 static inline bool token_fused_enabled() {
   const char* e = getenv("IGI_TOKEN_FUSED");   // read per call (one call per forward pass): the parity test switches it
   return !e || atoi(e) != 0;
@@ -595,6 +848,20 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
     if ((long long)samples * 256 > p.B) samples = (int)(p.B / 256 > 1 ? p.B / 256 : 1);
     a.rows_per_wg = samples * p.S;
     const int grid = (int)((p.B + samples - 1) / samples);
+    // algorithmic work of the stack: the four Linears of a row, the two S x S products of a (sample, head) pair
+    const double tok_flops = (double)p.L * (2.0 * p.R * (4.0 * TOK_D * TOK_D + 2.0 * TOK_D * TF_FF) + 4.0 * p.B * p.H * p.S * p.S * TOK_DH);
+    const double tok_bytes = 4.0 * ((double)p.L * p.a_layer + 2.0 * p.R * TOK_D + (double)p.L * p.per_layer);
+    if (p.S > TOK_MAX_S) {
+      static bool attr_long = false;
+      if (!attr_long) {
+        (void)hipFuncSetAttribute((const void*)k_token_fwd_long, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(sizeof(float) * TF_LDS_FLOATS));
+        attr_long = true;
+      }
+      ProfScope ps(PC_TOKEN_FWD_LONG, s, tok_flops, tok_bytes);
+      IGI_LAUNCH(k_token_fwd_long, dim3(grid), dim3(TF_THREADS), sizeof(float) * TF_LDS_FLOATS, s, a);
+      return (int)hipGetLastError();
+    }
     rc = attn_dispatch(p.S, [&](auto sc) {
       constexpr int SS = decltype(sc)::value;
       static bool attr = false;
@@ -603,7 +870,8 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
                                   (int)(sizeof(float) * TF_LDS_FLOATS));
         attr = true;
       }
-      hipLaunchKernelGGL((k_token_fwd<SS>), dim3(grid), dim3(TF_THREADS), sizeof(float) * TF_LDS_FLOATS, s, a);
+      ProfScope ps(PC_TOKEN_FWD, s, tok_flops, tok_bytes);
+      IGI_LAUNCH((k_token_fwd<SS>), dim3(grid), dim3(TF_THREADS), sizeof(float) * TF_LDS_FLOATS, s, a);
     });
     if (rc) return rc;
     return (int)hipGetLastError();
@@ -625,12 +893,18 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
       return rc;
     const long long pairs = (long long)p.B * p.H;
     const Drop da = make_drop(p.p, seed, 4 * l + SITE_ATTN);
-    rc = attn_dispatch(p.S, [&](auto sc) {
-      constexpr int SS = decltype(sc)::value;
-      hipLaunchKernelGGL((k_attn_fwd<SS>), dim3(tok_blocks(pairs, 16)), dim3(256), 0, s, A + p.a_qkv, A + p.a_ctx, da,
-                         pairs, p.H);
-    });
-    if (rc) return rc;
+    if (p.S > TOK_MAX_S) {
+      ProfScope ps(PC_ATTN_TILE_FWD, s, 4.0 * pairs * p.S * p.S * TOK_DH, 4.0 * R * (4.0 * d));
+      IGI_LAUNCH(k_attn_tile_fwd, dim3(tok_blocks(pairs, AT_THREADS / 64)), dim3(AT_THREADS), 0, s, A + p.a_qkv, A + p.a_ctx, da,
+                 pairs, p.H, p.S);
+    } else {
+      rc = attn_dispatch(p.S, [&](auto sc) {
+        constexpr int SS = decltype(sc)::value;
+        hipLaunchKernelGGL((k_attn_fwd<SS>), dim3(tok_blocks(pairs, 16)), dim3(256), 0, s, A + p.a_qkv, A + p.a_ctx, da,
+                           pairs, p.H);
+      });
+      if (rc) return rc;
+    }
     float* t0 = W + p.s_g0;  // sa branch output (not needed by backward)
     if ((rc = linear_forward(A + p.a_ctx, d, P + p.o_ow, P + p.o_ob, t0, d, R, d, d, LIN_NONE, s))) return rc;
     hipLaunchKernelGGL(k_resid_ln_fwd, dim3(rb), dim3(256), 0, s, A + p.a_x, t0, make_drop(p.p, seed, 4 * l + SITE_SA),
@@ -1046,12 +1320,18 @@ static int token_backward(const igi_token_cfg* c, const float* dy, const float* 
       return rc;
     const long long pairs = (long long)p.B * p.H;
     const Drop datt = make_drop(p.p, seed, 4 * l + SITE_ATTN);
-    rc = attn_dispatch(p.S, [&](auto sc) {
-      constexpr int SS = decltype(sc)::value;
-      hipLaunchKernelGGL((k_attn_bwd<SS>), dim3(tok_blocks(pairs, 16)), dim3(256), 0, s, A + p.a_qkv, g0, w1, datt,
-                         pairs, p.H);
-    });
-    if (rc) return rc;
+    if (p.S > TOK_MAX_S) {
+      ProfScope ps(PC_ATTN_TILE_BWD, s, 12.0 * pairs * p.S * p.S * TOK_DH, 4.0 * R * (7.0 * d));
+      IGI_LAUNCH(k_attn_tile_bwd, dim3(tok_blocks(pairs, AT_THREADS / 64)), dim3(AT_THREADS), 0, s, A + p.a_qkv, g0, w1, datt,
+                 pairs, p.H, p.S);
+    } else {
+      rc = attn_dispatch(p.S, [&](auto sc) {
+        constexpr int SS = decltype(sc)::value;
+        hipLaunchKernelGGL((k_attn_bwd<SS>), dim3(tok_blocks(pairs, 16)), dim3(256), 0, s, A + p.a_qkv, g0, w1, datt,
+                           pairs, p.H);
+      });
+      if (rc) return rc;
+    }
     if ((rc = linear_backward(A + p.a_xn1, d, P + p.o_inw, nullptr, 0, w1, 3 * d, g0, d, G + p.o_inw, G + p.o_inb, R, d,
                               3 * d, LIN_NONE, lin_ws_next(), p.lin_bytes, s, &sums)))
       return rc;

@@ -25,7 +25,8 @@ from .flat_params import flat_parameters
 
 class HipTransformerEncoder(nn.Module):
     """Drop-in for ``nn.TransformerEncoder(encoder_layer, num_layers, enable_nested_tensor=False)``
-    (no final norm, no masks: the reference passes neither)."""
+    (no final norm, no masks: the reference passes neither) over up to 32 tokens per sample (= sequence_length x
+    modalities of the student; more raises, there is no fallback)."""
 
     def __init__(self, encoder_layer, num_layers):
         super().__init__()

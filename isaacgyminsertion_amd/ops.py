@@ -1408,16 +1408,22 @@ def _dep_backward(ctx, dy, dws):
 register_autograd(f"{NS}::depth_backbone_fwd", _dep_backward, setup_context=_dep_setup)
 
 
+TOKEN_MAX_SEQ = 32    # csrc/token_encoder.h: TOK_MAX_SEQ, one 32 x 32 matrix-pipe tile per (sample, head)
+
+
 def _token_cfg(x, nhead, ff, layers, dropout, training):
     B, S, d = x.shape
+    if S > TOKEN_MAX_SEQ:
+        raise RuntimeError(f"token encoder: {S} tokens per sample, the native kernels take at most {TOKEN_MAX_SEQ} "
+                           f"(tokens = sequence_length x modalities; there is no fallback)")
     return _lib.TokenCfg(B, S, d, nhead, ff, layers, float(dropout), 1 if training else 0)
 
 
 @_op("token_encoder_fwd(Tensor x, Tensor params, int nhead, int ff, int layers, float dropout, bool training, int seed) -> (Tensor, Tensor)")
 def token_encoder_fwd(x: Tensor, params: Tensor, nhead: int, ff: int, layers: int, dropout: float, training: bool,
                       seed: int) -> Tuple[Tensor, Tensor]:
-    """``layers`` x TransformerEncoderLayer(d, nhead, ff, gelu, batch_first, norm_first) over (B, S <= 8, d)
-    (tact.py:143-148); dropout masks from a counter hash of ``seed`` -> igi_token_forward."""
+    """``layers`` x TransformerEncoderLayer(d, nhead, ff, gelu, batch_first, norm_first) over (B, S <= 32, d)
+    (tact.py:143-148; S <= 8: register attention kernels, 9 <= S <= 32: the matrix-pipe tile kernels); dropout masks from a counter hash of ``seed`` -> igi_token_forward."""
     _check(x, "x", dim=3)
     cfg = _token_cfg(x, nhead, ff, layers, dropout, training)
     L = _lib.lib()
