@@ -460,6 +460,33 @@ size_t igi_bc_loss_workspace_bytes(void);
 int igi_bc_loss(const float* mu, const float* teacher_actions, const float* weights, int64_t rows, int act_dim,
                 float* loss, float* dmu, void* workspace, size_t workspace_bytes, igi_stream_t stream);
 
+/* The latent student's loss (offline_train.train.latent_loss; ext_adapt.py:827 with the latent term live) in ONE launch:
+ * loss_action[0] as igi_bc_loss's loss, loss_latent[0] = mean((latent - latent_gt)^2) over (rows, latent_dim),
+ * dmu (rows, act_dim) = action_scale * d loss_action / d mu, dlatent (rows, latent_dim) = latent_scale * 2 (latent -
+ * latent_gt) / (rows * latent_dim): the gradients of action_scale * loss_action + latent_scale * loss_latent.  Every
+ * pointer is required.  Fixed-order fp64 sums. */
+int igi_distill_loss(const float* mu, const float* teacher_actions, const float* weights, int64_t rows, int act_dim,
+                     const float* latent, const float* latent_gt, int latent_dim, float action_scale, float latent_scale,
+                     float* loss_action, float* loss_latent, float* dmu, float* dlatent, igi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The frozen actor on [obs | student latent] (ActorCriticSplit.act_inference / act_with_grad with a `latent` entry:
+ * ext_adapt.py:684-690, 799-806): mu (rows, act) = mu head(actor_mlp(cat(obs_n, latent))), no value, no critic.
+ * obs_n (rows, obs_dim) normalised, latent (rows, latent_dim) with latent_dim = the teacher's own extrinsic width
+ * (priv_units[-1], plus the contact embedding of a contact teacher), IGI_E_BADARG otherwise.  With the reference's layer
+ * sizes (units 512 / 256 / 128, obs_dim + latent_dim <= 32, act <= 7) the forward is k_pad_w1 + one k_actor_latent launch
+ * per chunk of minibatch rows; every other shape runs the actor's layers one launch each.  Uses state.workspace.
+ * hsave (may be NULL): (rows, igi_actor_latent_saved_width(cfg)) = the post-tanh activations of the actor's layers side
+ * by side, each layer's width rounded up to 4 -- the caller's buffer, handed back to igi_actor_latent_backward, which
+ * writes dlatent (rows, latent_dim) = d/d latent of a loss with gradient dmu (rows, act).  No weight gradient.
+ * ---------------------------------------------------------------------------------------- */
+int igi_actor_latent_saved_width(const igi_teacher_cfg* cfg);
+int igi_actor_latent_forward(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* obs_n,
+                             const float* latent, int latent_dim, int64_t rows, float* mu, float* hsave,
+                             igi_stream_t stream);
+int igi_actor_latent_backward(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* hsave,
+                              const float* dmu, int64_t rows, float* dlatent, igi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * clip_grad_norm_ + torch.optim.Adam step on one flat fp32 vector (frozen_ppo.py:608-610;
  * ext_adapt.py:853-855): grads are scaled by grad_scale (1/world after an all-reduce SUM), clipped to

@@ -114,6 +114,13 @@ _EXPORTS = {
     "igi_bc_loss_workspace_bytes": (C.c_size_t, []),
     "igi_bc_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_size_t, C.c_void_p]),
+    "igi_distill_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "igi_actor_latent_saved_width": (C.c_int, [C.POINTER(TeacherCfg)]),
+    "igi_actor_latent_forward": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(TeacherState), C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "igi_actor_latent_backward": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(TeacherState), C.c_void_p, C.c_void_p,
+                                            C.c_int64, C.c_void_p, C.c_void_p]),
     "igi_teacher_param_count": (C.c_int64, [C.POINTER(TeacherCfg)]),
     "igi_teacher_param_offsets": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64), C.c_int]),

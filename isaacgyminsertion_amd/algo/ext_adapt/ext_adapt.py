@@ -23,6 +23,7 @@ from ..ppo.experience import StudentBuffer
 from ..ppo.frozen_ppo import _NullWriter, _summary_writer, log_test_result
 from ...bc_loss import bc_loss
 from ...optim import FlatAdam
+from ...utils.config import parse_latent_loss
 from ...utils.misc import AverageScalarMeter
 
 
@@ -114,6 +115,9 @@ class ExtrinsicAdapt(object):
         self.mean_eps_success = AverageScalarMeter(window_size=100)
         self.latent_scale = self.train_config.train.latent_scale
         self.action_scale = self.train_config.train.action_scale
+        # offline_train.train.latent_loss: absent / False = the reference's live loss, action_scale * loss_action
+        # (ext_adapt.py:827); True = that line with its comment sign removed, + latent_scale * loss_latent
+        self.latent_loss = parse_latent_loss(self.train_config.train.get('latent_loss', None), self.only_bc)
         self.best_rewards = -10000
         self.best_loss = 10000
         self.cur_reward = self.best_rewards
@@ -336,6 +340,17 @@ class ExtrinsicAdapt(object):
             'pcl': b['n_pcl'].reshape(b['n_pcl'].shape[0], -1, 3) if 'n_pcl' in b else None,
         }
         latent, _ = self.student.predict(student_dict, requires_grad=True)
+        if self.latent_loss:                                 # both terms and both gradients from one launch
+            mu, _ = self.agent.act_with_grad({'obs': b['n_obs'], 'latent': latent})
+            loss_action, loss_latent, dmu, dlatent = torch.ops.mi355ppo.distill_loss_value_grad(
+                mu.detach(), b['teacher_actions'], self.loss_weights, latent.detach().contiguous(),
+                b['latent_gt'].detach().contiguous(), float(self.action_scale), float(self.latent_scale))
+            self.optim.zero_grad()
+            # the latent collects d/d latent of both terms: latent_scale * d loss_latent directly, action_scale * d loss_action
+            # through the frozen actor
+            torch.autograd.backward([mu, latent], [dmu, dlatent])
+            self.optim.sync_grads()
+            return loss_action, loss_latent
         if not self.only_bc:                                 # act with the student latent (:799-806)
             mu, _ = self.agent.act_with_grad({'obs': b['n_obs'], 'latent': latent})
             loss_latent = torch.nn.functional.mse_loss(latent, b['latent_gt'].detach())

@@ -64,6 +64,23 @@ class ContactAE(nn.Module):
         return linear(h, l2.weight.detach(), l2.bias.detach())
 
 
+class _ActorOnLatent(torch.autograd.Function):
+    """mu = mu head(actor_mlp(cat(obs, latent))) on the native frozen-actor path (csrc/policy_fwd.h, k_actor_latent), with
+    the data gradient back into the latent.  The observation and the teacher's weights get no gradient."""
+
+    @staticmethod
+    def forward(ctx, latent, obs, engine):
+        mu, saved = engine.actor_latent(obs, latent, save=True)
+        ctx.engine = engine
+        ctx.save_for_backward(saved)
+        return mu
+
+    @staticmethod
+    def backward(ctx, dmu):
+        (saved,) = ctx.saved_tensors
+        return ctx.engine.actor_latent_backward(saved, dmu.contiguous()), None, None
+
+
 class ActorCriticSplit(nn.Module):
     def __init__(self, kwargs):
         nn.Module.__init__(self)
@@ -257,15 +274,45 @@ class ActorCriticSplit(nn.Module):
             'values': value, 'actions': selected_action, 'mus': mu, 'sigmas': sigma, 'latent_gt': latent_gt,
         }
 
+    @property
+    def latent_width(self):
+        """Columns behind the observation in the trunk's input: the privileged latent, [latent | contact embedding], or
+        the embedding alone with only_contact (models_split.py:172-183) -- the width a student latent must have."""
+        if not self.contact_info:
+            return self.priv_mlp_units[-1]
+        return self.contact_emb + (0 if self.only_contact else self.priv_mlp_units[-1])
+
+    def _mu_from_latent(self, obs_dict):
+        """mu of the frozen ACTOR on ``cat(obs, latent)`` -- what act_inference / act_with_grad keep of
+        models_split.py:187-216 when a student latent is given; the value they throw away is not computed.  One
+        k_actor_latent launch at the reference's layer sizes (csrc/policy_fwd.h), the actor's layers one by one otherwise;
+        with grad enabled and a latent that requires it, autograd carries d/d mu back into the latent."""
+        obs, latent = obs_dict['obs'], obs_dict['latent']
+        if latent.dim() != 2 or latent.shape[-1] != self.latent_width:
+            raise ValueError(f"latent of shape {tuple(latent.shape)}: width {latent.shape[-1] if latent.dim() else 0} given, "
+                             f"this teacher's actor reads an extrinsic of width {self.latent_width} behind the observation")
+        if not obs.is_cuda:
+            raise RuntimeError("ActorCriticSplit runs on the HIP device only (no CPU fallback)")
+        eng = self._infer_engine(obs.device)
+        obs = obs.detach().to(torch.float32).contiguous()
+        lat = latent.to(torch.float32).contiguous()
+        if torch.is_grad_enabled() and lat.requires_grad:
+            return _ActorOnLatent.apply(lat, obs, eng)
+        return eng.actor_latent(obs, lat.detach(), save=False)[0]
+
     @torch.no_grad()
     def act_inference(self, obs_dict):
         """models_split.py:155-159"""
+        if obs_dict.get('latent', None) is not None:
+            return self._mu_from_latent(obs_dict), obs_dict['latent']
         mu, logstd, value, latent, latent_gt = self.actor_critic(obs_dict)
         latent = latent_gt if latent is None else latent
         return mu, latent
 
     def act_with_grad(self, obs_dict):
         """models_split.py:161-164.  With a ``latent`` entry the result carries an autograd graph back to it."""
+        if obs_dict.get('latent', None) is not None:
+            return self._mu_from_latent(obs_dict), obs_dict['latent']
         mu, logstd, value, latent, _ = self.actor_critic(obs_dict)
         return mu, latent
 

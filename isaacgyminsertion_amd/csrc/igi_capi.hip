@@ -178,6 +178,32 @@ int igi_prof_read(igi_prof_entry* out, int max_entries) {
   return n;
 }
 
+int igi_distill_loss(const float* mu, const float* teacher_actions, const float* weights, int64_t rows, int act_dim,
+                     const float* latent, const float* latent_gt, int latent_dim, float action_scale, float latent_scale,
+                     float* loss_action, float* loss_latent, float* dmu, float* dlatent, igi_stream_t stream) {
+  return fail(igi::distill_loss(mu, teacher_actions, weights, rows, act_dim, latent, latent_gt, latent_dim, action_scale,
+                                latent_scale, loss_action, loss_latent, dmu, dlatent, S(stream)), "igi_distill_loss");
+}
+
+int igi_actor_latent_saved_width(const igi_teacher_cfg* cfg) {
+  igi::TeacherPlan p;
+  if (igi::make_plan(cfg, &p)) return 0;
+  return igi::actor_latent_saved_width(p);
+}
+
+int igi_actor_latent_forward(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* obs_n,
+                             const float* latent, int latent_dim, int64_t rows, float* mu, float* hsave,
+                             igi_stream_t stream) {
+  return fail(igi::teacher_actor_latent_forward(cfg, st, obs_n, latent, latent_dim, rows, mu, hsave, S(stream)),
+              "igi_actor_latent_forward");
+}
+
+int igi_actor_latent_backward(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* hsave,
+                              const float* dmu, int64_t rows, float* dlatent, igi_stream_t stream) {
+  return fail(igi::teacher_actor_latent_backward(cfg, st, hsave, dmu, rows, dlatent, S(stream)),
+              "igi_actor_latent_backward");
+}
+
 size_t igi_rms_workspace_bytes(int64_t rows, int D) {
   if (rows < 1 || D < 1) return 0;
   return igi::rms_workspace_bytes(rows, D);

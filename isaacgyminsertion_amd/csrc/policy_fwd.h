@@ -142,9 +142,13 @@ struct PfWave {
 // `aout`: N / 32 output images (another LDS region); W rows ldw floats apart.  The caller puts a workgroup barrier behind.
 // NW: the waves that compute (waves 0 .. NW - 1 own tiles wave + NW j); the others return at once.
 // NS: depth of the wave's ring (NS - 1 chunks in flight ahead of the one being multiplied).
-template <int K, int N, int NT, int NW = 8, int NS = PF_NS>
+// STORE (k_actor_latent's training forward): the wave also writes its output tiles, from the accumulators, to the row-major
+// `gout` (rows ldg floats apart; block row 0 = row m0), rows below `rows` only.  Those stores count in vmcnt like the ring's
+// requests: a later layer's counted wait can only wait longer for them, never too short (loads return in order).
+template <int K, int N, int NT, int NW = 8, int NS = PF_NS, bool STORE = false>
 __device__ __forceinline__ void pf_layer(const PfWave& w, const float* __restrict__ ain, const float* __restrict__ W, int ldw,
-                                         const float (&bias)[NT], float* __restrict__ aout) {
+                                         const float (&bias)[NT], float* __restrict__ aout, float* __restrict__ gout = nullptr,
+                                         int ldg = 0, int m0 = 0, int rows = 0) {
   constexpr int KC = K / 16, NI = KC * NT;       // items = (k-chunk c, tile j), c-major
   static_assert(K % 32 == 0 && N % 32 == 0, "whole images");
   static_assert(NT * NW * 32 >= N, "every output tile has an owner");
@@ -218,8 +222,14 @@ __device__ __forceinline__ void pf_layer(const PfWave& w, const float* __restric
   for (int j = 0; j < NT; ++j) {
     float* img = aout + (w.wave + NW * j) * PF_IMG;
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-      img[w.ib[(r >> 1) & 3] + ((r & 3) + 8 * (r >> 2)) * 32] = fast_tanh(acc[j][r] + bias[j]);
+    for (int r = 0; r < 16; ++r) {
+      const float v = fast_tanh(acc[j][r] + bias[j]);
+      img[w.ib[(r >> 1) & 3] + ((r & 3) + 8 * (r >> 2)) * 32] = v;
+      if constexpr (STORE) {   // accumulator element r of lane (l31, h): row 4 h + (r & 3) + 8 (r >> 2), column l31 of the tile
+        const int row = m0 + 4 * w.h + (r & 3) + 8 * (r >> 2);
+        if (row < rows) gout[(long long)row * ldg + 32 * (w.wave + NW * j) + w.l31] = v;
+      }
+    }
   }
 }
 
@@ -470,6 +480,112 @@ __global__ __launch_bounds__(PF_THREADS) void k_policy_fwd(const PolicyFwdArgs a
     a.values_t[grow] = v;
     a.values_out[grow] = v;
   }
+}
+
+// ---- the frozen ACTOR on [obs | student latent] (models_split.py:187-216 with a `latent` entry; ext_adapt.py:684-690,
+// 799-806): one workgroup = 32 rows of the actor's trunk and the mu head, built from the pieces above.  No env_mlp, no
+// critic, no sampling: the caller gives the normalised observation and the latent as two row-major tensors, the kernel
+// writes mu -- and, with STORE, the three post-tanh activations of the live rows for the data-gradient chain back into the
+// latent (teacher_actor_latent_backward).  Same LDS carve-up as k_policy_fwd (the env_mlp's W3 slot stays unused), same
+// trunk calls, so the trunk's bits are those of the per-layer launches and of k_policy_fwd.
+struct ActorLatentArgs {
+  const float* obs_n; const float* latent;             // [rows][obs], [rows][L]; rows need no alignment (plain loads)
+  int rows, obs, L, act;
+  const float* w1p;                                    // [512][32] zero-padded first layer of the ACTOR (k_pad_w1)
+  const float *tb1, *tW2, *tb2, *tW3, *tb3, *Wmu, *bmu;
+  float* mu;                                           // [rows][act]
+  float *h1 = nullptr, *h2 = nullptr, *h3 = nullptr;   // STORE: [rows][512 | 256 | 128], rows ldh floats apart
+  int ldh = 0;
+};
+
+static inline bool actor_latent_shape_ok(int obs, int L, int act, int nl, const int* u) {
+  return nl == 3 && u[0] == 512 && u[1] == 256 && u[2] == 128 && obs >= 1 && L >= 1 && obs + L <= 32 && act >= 1 && act <= 7;
+}
+
+template <bool STORE>
+__global__ __launch_bounds__(PF_THREADS) void k_actor_latent(const ActorLatentArgs a) {
+  extern __shared__ __attribute__((aligned(1024))) float smem[];
+  float* P = smem;
+  float* Q = P + PF_P;
+  float* ring0 = Q + PF_Q;
+  float* hws = ring0 + PF_RING + 8 * 128;   // [8][128] head rows: mu 0 .. act - 1, zeros behind
+  float* part = hws + 8 * 128;              // [2][32][8]
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int m0 = (int)blockIdx.x * PF_ROWS;
+  PfWave w;
+  w.ring = ring0 + wave * (PF_NS * PF_CH);
+  w.lane = lane; w.wave = wave; w.l31 = lane & 31; w.h = lane >> 5;
+  pf_img_bases(w.l31, w.h, w.ib);
+  w.aoff = w.l31 * 32; w.asw = (w.l31 >> 1) & 7;
+  w.boff = w.l31 * 16; w.bsw = (w.l31 >> 2) & 3;
+  const int c31 = 32 * wave + w.l31;
+  float bt1[2] = {a.tb1[c31], a.tb1[256 + c31]};
+  float bt2[1] = {a.tb2[c31]};
+  float bt3[1] = {a.tb3[min(c31, 127)]};
+  float hwv[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int e = tid + PF_THREADS * i;                               // 0 .. 1023
+    const int r = e >> 7, k = e & 127;
+    hwv[i] = r < a.act ? a.Wmu[r * 128 + k] : 0.f;
+  }
+  // ---- xcat = [obs_n | latent | 0] as ONE image in P, written whole; rows >= rows read row rows - 1
+  {
+    const int xrow = tid >> 4, xc = 2 * (tid & 15);
+    const long long grow = min(m0 + xrow, a.rows - 1);
+    const int sw = (xrow >> 1) & 7;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int c = xc + q;
+      float v = 0.f;
+      if (c < a.obs) v = a.obs_n[grow * a.obs + c];
+      else if (c < a.obs + a.L) v = a.latent[grow * a.L + (c - a.obs)];
+      P[xrow * 32 + (((c >> 2) ^ sw) << 2) + (c & 3)] = v;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) hws[tid + PF_THREADS * i] = hwv[i];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  // ---- the actor trunk: 32 -> 512 (P -> Q), 512 -> 256 (Q -> P), 256 -> 128 (P -> Q)
+  pf_layer<32, 512, 2, 8, PF_NS, STORE>(w, P, a.w1p, 32, bt1, Q, a.h1, a.ldh, m0, a.rows);
+  __syncthreads();
+  pf_layer<512, 256, 1, 8, PF_NS, STORE>(w, Q, a.tW2, 512, bt2, P, a.h2, a.ldh, m0, a.rows);
+  __syncthreads();
+  pf_layer<256, 128, 1, 8, PF_NS, STORE>(w, P, a.tW3, 256, bt3, Q, a.h3, a.ldh, m0, a.rows);
+  __syncthreads();
+  pf_dot8(Q, hws, part, tid);
+  __syncthreads();
+  const int row = tid & 31, q = tid >> 5, grow = m0 + row;
+  if (tid < 256 && q < a.act && grow < a.rows)
+    a.mu[(long long)grow * a.act + q] = (part[row * 8 + q] + part[(32 + row) * 8 + q]) + a.bmu[q];
+}
+
+template <bool STORE>
+static hipError_t actor_latent_launch(const ActorLatentArgs& a, int blocks, hipStream_t s) {
+  void (*kern)(const ActorLatentArgs) = k_actor_latent<STORE>;
+  static bool attr = false;
+  if (!attr) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * PF_LDS_FLOATS));
+    if (e != hipSuccess) return e;
+    attr = true;
+  }
+  IGI_LAUNCH(kern, dim3(blocks), dim3(PF_THREADS), sizeof(float) * PF_LDS_FLOATS, s, a);
+  return hipGetLastError();
+}
+
+// hipErrorInvalidValue: an operand the DMA rings cannot take (alignment) -- the caller runs the per-layer launches
+static hipError_t actor_latent_forward(const ActorLatentArgs& a, hipStream_t s) {
+  const bool store = a.h1 != nullptr;
+  if (a.rows < 1 || !a.obs_n || !a.latent || !a.mu || a.obs < 1 || a.L < 1 || a.obs + a.L > 32 || a.act < 1 || a.act > 7 ||
+      !aligned16(a.w1p) || !aligned16(a.tW2) || !aligned16(a.tW3) || (store && (!a.h2 || !a.h3 || a.ldh < 512)))
+    return hipErrorInvalidValue;
+  const int blocks = (a.rows + PF_ROWS - 1) / PF_ROWS;
+  const double macs = (a.obs + a.L) * 512.0 + 512.0 * 256 + 256.0 * 128 + 128.0 * a.act;
+  const double wbytes = 4.0 * (512.0 * 32 + 512.0 * 256 + 256.0 * 128 + 128.0 * a.act + 512 + 256 + 128 + a.act);
+  ProfScope ps(PC_ACTOR_LATENT, s, 2.0 * macs * a.rows,
+               4.0 * a.rows * (a.obs + a.L + a.act + (store ? 512.0 + 256 + 128 : 0.0)) + wbytes);
+  return store ? actor_latent_launch<true>(a, blocks, s) : actor_latent_launch<false>(a, blocks, s);
 }
 
 template <int CT, bool VEC>

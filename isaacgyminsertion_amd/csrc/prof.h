@@ -29,7 +29,7 @@ enum ProfClass {
   PC_CONVB_TALL64_TT, PC_CONVB_TALL32_TT, PC_CONVB_TALL64_SSA, PC_CONVB_WG_TALL32, PC_CONVB_WG_TALL64,
   PC_CONVB_PM64, PC_CONVB_PM32, PC_CONVB_PW32, PC_CONVB_PW64, PC_CONVB_PW64_192, PC_CONVB_ROW64, PC_CONVB_WG64, PC_CONVB_PW64_128,
   PC_POINTNET_FWD, PC_POINTNET_BWD, PC_SOFTARGMAX_FWD, PC_SOFTARGMAX_BWD,
-  PC_DMA_HEAD, PC_TRUNK_LOSS, PC_RB_TRUNK, PC_RB_ENV, PC_MLP_FWD, PC_POLICY_FWD, PC_FWD12, PC_ENV_FWD, PC_GEMM_GENERIC, PC_GATHER_NORMALIZE, PC_RMS_FINAL, PC_NORMALIZE,
+  PC_DMA_HEAD, PC_TRUNK_LOSS, PC_RB_TRUNK, PC_RB_ENV, PC_MLP_FWD, PC_POLICY_FWD, PC_ACTOR_LATENT, PC_FWD12, PC_ENV_FWD, PC_GEMM_GENERIC, PC_GATHER_NORMALIZE, PC_RMS_FINAL, PC_NORMALIZE,
   PC_LOSS, PC_LATENT_BWD, PC_SLAB_REDUCE, PC_SUMSQ, PC_ADAM, PC_ADAM_GATHER, PC_LR_SCHEDULE, PC_PREPARE,
   // the student's token encoder: the one-launch forward (S <= 8: one symbol per S in rocprofv3, "<S>" is ours; 9 .. 32 tokens:
   // k_token_fwd_long) and the tile attention kernels of the launch-per-operation path
@@ -65,7 +65,7 @@ static const char* const kProfNames[PC_COUNT] = {
     "k_pointnet_fwd", "k_pointnet_bwd", "k_softargmax_fwd", "k_softargmax_bwd",
     "gemm_dma_head_kernel<true>", "k_trunk_loss",
     "k_rb_level#trunk3: dW 256->128 x2 + dgrad 128->256 x2", "k_rb_level#env2: dW env 256->128 + env dgrad 128->256 (+ dW env 64->256 from its tiles)",
-    "k_mlp_fwd", "k_policy_fwd", "k_fwd12",
+    "k_mlp_fwd", "k_policy_fwd", "k_actor_latent", "k_fwd12",
     "k_env_fwd", "gemm_f32_kernel<*>", "k_gather_normalize", "k_rms_final", "k_normalize",
     "k_loss", "k_latent_bwd", "k_slab_reduce", "k_sumsq_stats", "k_clip_adam", "k_adam_gather", "k_lr_schedule", "k_gae+k_prep_final+k_prep_norm",
     "k_token_fwd<S>", "k_token_fwd_long", "k_attn_tile_fwd", "k_attn_tile_bwd", "other"};

@@ -162,4 +162,57 @@ static int bc_loss(const float* mu, const float* teacher, const float* w, int64_
   hipLaunchKernelGGL(k_bc_final, dim3(1), dim3(64), 0, s, partial, nb, loss);
   return (int)hipGetLastError();
 }
+
+// The latent student's loss (offline_train.train.latent_loss: ext_adapt.py:827 with its latent term live) and both of its
+// gradients in ONE launch of one workgroup:
+//   loss_action = sum_{row,q} w[q] (clamp(mu, +-1) - clamp(a, +-1))^2        (k_bc_partial's terms)
+//   loss_latent = mean((latent - latent_gt)^2)                                         (torch.nn.MSELoss)
+//   dmu     = action_scale * d loss_action / d mu,   dlatent = latent_scale * 2 (latent - latent_gt) / (rows * L)
+// i.e. the gradients of action_scale * loss_action + latent_scale * loss_latent.  Each thread adds its strided elements in
+// order in fp64, the waves' sums meet in wave order: a fixed order, two calls give the same bits.  One workgroup because
+// the minibatch is rows * (act + L) ~ 1e5 elements: a second launch to add per-block partials costs more than it saves.
+constexpr int DL_THREADS = 1024;
+
+__global__ __launch_bounds__(DL_THREADS) void k_distill_loss(const float* __restrict__ mu, const float* __restrict__ teacher,
+                                                             const float* __restrict__ w, long long na, int act,
+                                                             const float* __restrict__ latent, const float* __restrict__ latent_gt,
+                                                             long long nl, float action_scale, float latent_coef,
+                                                             float* __restrict__ loss_action, float* __restrict__ loss_latent,
+                                                             float* __restrict__ dmu, float* __restrict__ dlatent) {
+  __shared__ double red[2][DL_THREADS / 64];
+  double sa = 0.0, sl = 0.0;
+  for (long long e = threadIdx.x; e < na; e += DL_THREADS) {
+    const float m = mu[e];
+    const float d = fminf(fmaxf(m, -1.0f), 1.0f) - fminf(fmaxf(teacher[e], -1.0f), 1.0f);
+    const float wq = w[e % act];
+    sa += (double)((d * d) * wq);
+    dmu[e] = (m >= -1.0f && m <= 1.0f) ? action_scale * ((2.0f * d) * wq) : 0.0f;
+  }
+  for (long long e = threadIdx.x; e < nl; e += DL_THREADS) {
+    const float d = latent[e] - latent_gt[e];
+    sl += (double)(d * d);
+    dlatent[e] = latent_coef * d;
+  }
+  for (int o = 32; o > 0; o >>= 1) { sa += __shfl_xor(sa, o, 64); sl += __shfl_xor(sl, o, 64); }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sa; red[1][threadIdx.x >> 6] = sl; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double ta = 0.0, tl = 0.0;
+    for (int i = 0; i < DL_THREADS / 64; ++i) { ta += red[0][i]; tl += red[1][i]; }
+    loss_action[0] = (float)ta;
+    loss_latent[0] = (float)(tl / (double)nl);
+  }
+}
+
+static int distill_loss(const float* mu, const float* teacher, const float* w, int64_t rows, int act, const float* latent,
+                        const float* latent_gt, int L, float action_scale, float latent_scale, float* loss_action, float* loss_latent,
+                        float* dmu, float* dlatent, hipStream_t s) {
+  if (!mu || !teacher || !w || !latent || !latent_gt || !loss_action || !loss_latent || !dmu || !dlatent || rows < 1 || act < 1 || L < 1)
+    return IGI_E_BADARG;
+  const long long na = rows * (long long)act, nl = rows * (long long)L;
+  const float coef = (float)(2.0 * (double)latent_scale / (double)nl);
+  hipLaunchKernelGGL(k_distill_loss, dim3(1), dim3(DL_THREADS), 0, s, mu, teacher, w, na, act, latent, latent_gt, nl,
+                     action_scale, coef, loss_action, loss_latent, dmu, dlatent);
+  return (int)hipGetLastError();
+}
 }  // namespace igi

@@ -1382,7 +1382,9 @@ __global__ __launch_bounds__(256) void k_pad_w1(const float* __restrict__ params
 // (mb x K) . (K x 8) product: one wave per row, each lane keeps its 16 x 8 slice of the weight in
 // registers for all of its rows and the 8 row sums are wave reductions -- HBM-bound on reading dZ1
 // once (a 128 x 64 MFMA tile would spend 8x the useful FLOPs on padding here).
-template <int KQ, int LAT>
+// RAW (teacher_actor_latent_backward: the latent is the student's, there is no tanh behind it): the products themselves,
+// to the dense [mb][LAT] `dxcat`; `xcat` is not read and `w1p` may be the unpadded weight (rows xld = xw floats apart).
+template <int KQ, int LAT, bool RAW = false>
 __global__ __launch_bounds__(256) void k_latent_dgrad(const float* __restrict__ dz, int ldz,
                                                       const float* __restrict__ w1p, int xld, int obs,
                                                       const float* __restrict__ xcat, float* __restrict__ dxcat,
@@ -1426,8 +1428,12 @@ __global__ __launch_bounds__(256) void k_latent_dgrad(const float* __restrict__ 
 #pragma unroll
         for (int j = 0; j < LAT; ++j) {
           if (lane == j) {
-            const float t = xcat[(long long)row * xld + obs + j];
-            dxcat[(long long)row * xld + obs + j] = acc[j] * (1.0f - t * t);
+            if constexpr (RAW) {
+              dxcat[(long long)row * LAT + j] = acc[j];
+            } else {
+              const float t = xcat[(long long)row * xld + obs + j];
+              dxcat[(long long)row * xld + obs + j] = acc[j] * (1.0f - t * t);
+            }
           }
         }
       }
@@ -2586,6 +2592,149 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
     ProfScope ps(PC_OTHER, s, 0.0, 8.0 * nr * H);
     IGI_LAUNCH_MAXJ(k_heads_act_store, H, dim3(hb), dim3(256), 0, s, h, ns, ldh, H, P + p.o_muW, P + p.o_muB, P + p.o_valW,
                     P + p.o_valB, nr, p.act, t);
+  }
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The frozen ACTOR on [obs | student latent] (ActorCriticSplit.act_inference / act_with_grad with a `latent` entry:
+// ext_adapt.py:684-690 in the stage-2 rollout, :799-806 in the student's update, deploy_s2): mu only -- the value those
+// callers throw away is not computed -- and the data gradient of a loss on mu back into the latent.  The teacher's
+// weights are constants here: no weight gradient.
+//   forward : k_pad_w1 + ONE k_actor_latent launch per chunk of mb rows (policy_fwd.h) at the reference's layer sizes;
+//             every other shape: k_stage_obs_latent, the actor's Linear + Tanh layers (gemm, nbatch = 1), k_heads_infer.
+//             hsave (may be NULL): [rows][S], S = sum of ru4(u_l): the post-tanh activations, layer l at column
+//             offset sum of ru4(u_k), k < l -- the caller's tensor, because the backward pass runs later.
+//   backward: dZ_l = (dZ_{l+1} . W_{l+1}) * (1 - h_l^2) from dZ_{nl} = dmu and W_{nl} = Wmu, then
+//             dlatent = dZ_0 . W_0[:, obs : obs + L].
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_stage_obs_latent(const float* __restrict__ obs_n, const float* __restrict__ latent,
+                                                          int rows, int obs, int L, float* __restrict__ xcat, int xld) {
+  const long long total = (long long)rows * xld;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+    const long long r = e / xld;
+    const int c = (int)(e - r * xld);
+    xcat[e] = c < obs ? obs_n[r * obs + c] : (c < obs + L ? latent[r * L + (c - obs)] : 0.f);
+  }
+}
+
+static inline int actor_latent_saved_width(const TeacherPlan& p) {
+  int w = 0;
+  for (int l = 0; l < p.nl; ++l) w += ru4(p.u[l]);
+  return w;
+}
+
+static int teacher_actor_latent_forward(const igi_teacher_cfg* c, const igi_teacher_state* st, const float* obs_n,
+                                        const float* latent, int L, int64_t rows, float* mu, float* hsave, hipStream_t s) {
+  TeacherPlan p;
+  int rc = make_plan(c, &p);
+  if (rc) return rc;
+  if ((rc = check_state(p, st))) return rc;
+  if (!obs_n || !latent || !mu || rows < 1 || L != p.xw - p.obs) return IGI_E_BADARG;
+  const float* P = st->params;
+  float* w1p = wsp<float>(st, p.w_w1p);
+  float* xcat = wsp<float>(st, p.w_xcat);
+  const int S = actor_latent_saved_width(p);
+  const int H = p.u[p.nl - 1];
+  {
+    ProfScope ps(PC_OTHER, s, 0.0, 8.0 * p.nets * p.u0p * p.xld);
+    IGI_LAUNCH(k_pad_w1, dim3((p.nets * p.u0p * p.xld + 255) / 256), dim3(256), 0, s, P, p.o_acW[0], p.ac_block, p.u[0],
+               p.u0p, p.xw, p.xld, w1p, p.nets);
+  }
+  // (no nets == 2 term: the kernel runs the actor alone, a shared trunk's included)
+  const bool fused = policy_fwd_enabled() && !bf16_mode() && actor_latent_shape_ok(p.obs, L, p.act, p.nl, p.u) && p.xld == 32;
+  for (int64_t r0 = 0; r0 < rows; r0 += p.mb) {
+    const int nr = (int)((rows - r0 < p.mb) ? rows - r0 : p.mb);
+    float* hs = hsave ? hsave + r0 * S : nullptr;
+    if (fused) {
+      ActorLatentArgs f;
+      f.obs_n = obs_n + r0 * p.obs; f.latent = latent + r0 * L; f.rows = nr; f.obs = p.obs; f.L = L; f.act = p.act;
+      f.w1p = w1p; f.tb1 = P + p.o_acB[0]; f.tW2 = P + p.o_acW[1]; f.tb2 = P + p.o_acB[1]; f.tW3 = P + p.o_acW[2];
+      f.tb3 = P + p.o_acB[2]; f.Wmu = P + p.o_muW; f.bmu = P + p.o_muB;
+      f.mu = mu + r0 * p.act;
+      if (hs) { f.h1 = hs; f.h2 = hs + ru4(p.u[0]); f.h3 = hs + ru4(p.u[0]) + ru4(p.u[1]); f.ldh = S; }
+      const hipError_t e = actor_latent_forward(f, s);
+      if (e == hipSuccess) continue;
+      if (e != hipErrorInvalidValue) return (int)e;      // (alignment of the parameter vector: the per-layer launches below)
+    }
+    {
+      const long long tot = (long long)nr * p.xld;
+      int nb = (int)((tot + 255) / 256);
+      if (nb > 2048) nb = 2048;
+      ProfScope ps(PC_OTHER, s, 0.0, 8.0 * tot);
+      IGI_LAUNCH(k_stage_obs_latent, dim3(nb), dim3(256), 0, s, obs_n + r0 * p.obs, latent + r0 * L, nr, p.obs, L, xcat, p.xld);
+    }
+    const float* in = xcat;
+    int ldin = p.xld, col = 0;
+    for (int l = 0; l < p.nl; ++l) {
+      GemmArgs g;
+      g.A = in; g.lda = ldin;
+      if (l == 0) { g.B = w1p; g.ldb = p.xld; g.K = p.xld; g.flop_credit = (double)p.xw / p.xld; }
+      else { g.B = P + p.o_acW[l]; g.ldb = ac_in(p, l); g.K = ac_in(p, l); }
+      g.bias = P + p.o_acB[l];
+      g.M = nr; g.N = p.u[l];
+      if (hs) { g.C = hs + col; g.ldc = S; }
+      else { g.C = wsp<float>(st, p.w_h[l]); g.ldc = ru4(p.u[l]); }
+      g.epilogue = EPI_BIAS_TANH;
+      IGI_HIP_TRY(gemm(g, true, true, s));
+      in = g.C; ldin = g.ldc; col += ru4(p.u[l]);
+    }
+    int hb = (nr + 3) / 4;
+    if (hb > 1024) hb = 1024;
+    ProfScope ps(PC_OTHER, s, 0.0, 4.0 * nr * H);
+    IGI_LAUNCH_MAXJ(k_heads_infer, H, dim3(hb), dim3(256), 0, s, in, 0LL, ldin, H, P + p.o_muW, P + p.o_muB, P + p.o_valW,
+                    P + p.o_valB, nr, p.act, mu + r0 * p.act, (float*)nullptr);
+  }
+  return (int)hipGetLastError();
+}
+
+static int teacher_actor_latent_backward(const igi_teacher_cfg* c, const igi_teacher_state* st, const float* hsave,
+                                         const float* dmu, int64_t rows, float* dlatent, hipStream_t s) {
+  TeacherPlan p;
+  int rc = make_plan(c, &p);
+  if (rc) return rc;
+  if ((rc = check_state(p, st))) return rc;
+  if (!hsave || !dmu || !dlatent || rows < 1) return IGI_E_BADARG;
+  const float* P = st->params;
+  const int L = p.xw - p.obs;
+  const int S = actor_latent_saved_width(p);
+  int off[IGI_MAX_LAYERS];
+  for (int l = 0, col = 0; l < p.nl; ++l) { off[l] = col; col += ru4(p.u[l]); }
+  for (int64_t r0 = 0; r0 < rows; r0 += p.mb) {
+    const int nr = (int)((rows - r0 < p.mb) ? rows - r0 : p.mb);
+    const float* hs = hsave + r0 * S;
+    for (int l = p.nl - 1; l >= 0; --l) {       // dZ_l into the workspace's dh slot of layer l, rows ru4(u_l) floats apart
+      GemmArgs g;
+      if (l == p.nl - 1) { g.A = dmu + r0 * p.act; g.lda = p.act; g.B = P + p.o_muW; g.K = p.act; }
+      else { g.A = wsp<float>(st, p.w_dh[l + 1]); g.lda = ru4(p.u[l + 1]); g.B = P + p.o_acW[l + 1]; g.K = p.u[l + 1]; }
+      g.ldb = p.u[l];
+      g.M = nr; g.N = p.u[l];
+      g.C = wsp<float>(st, p.w_dh[l]); g.ldc = ru4(p.u[l]);
+      g.aux = hs + off[l]; g.ldaux = S;
+      g.epilogue = EPI_TANHGRAD;
+      IGI_HIP_TRY(gemm(g, true, false, s));
+    }
+    const float* dz = wsp<float>(st, p.w_dh[0]);
+    float* out = dlatent + r0 * L;
+    if (L == 8 && p.u[0] % 256 == 0 && p.u[0] <= 1024) {
+      ProfScope ps(PC_OTHER, s, 2.0 * nr * p.u[0] * 8, 4.0 * nr * p.u[0]);
+      const int rpw = 8;
+      const int nb = (nr + 4 * rpw - 1) / (4 * rpw);
+      const int kq = p.u[0] / 256;
+#define IGI_LATR(KQ_) IGI_LAUNCH((k_latent_dgrad<KQ_, 8, true>), dim3(nb), dim3(256), 0, s, dz, p.u0p, P + p.o_acW[0], p.xw, \
+                                 p.obs, (const float*)nullptr, out, nr, rpw)
+      if (kq == 1) IGI_LATR(1); else if (kq == 2) IGI_LATR(2); else if (kq == 3) IGI_LATR(3); else IGI_LATR(4);
+#undef IGI_LATR
+    } else {
+      GemmArgs g;
+      g.A = dz; g.lda = p.u0p;
+      g.B = P + p.o_acW[0] + p.obs; g.ldb = p.xw;
+      g.M = nr; g.N = L; g.K = p.u[0];
+      g.C = out; g.ldc = L;
+      g.epilogue = EPI_STORE;
+      IGI_HIP_TRY(gemm(g, true, false, s));
+    }
   }
   return (int)hipGetLastError();
 }

@@ -508,6 +508,63 @@ def _(state, icfg, fcfg, obs, priv, contacts, normalize, want_latent):
             obs.new_empty(rows if want_latent else 0, _latent_gt_width(icfg)))
 
 
+def _actor_saved_width(icfg):
+    """ru4(u_0) + ... of the actor's layers: the row width of ``actor_latent_fwd``'s saved activations."""
+    M = _lib.IGI_MAX_LAYERS
+    return sum((int(icfg[5 + M + i]) + 3) & ~3 for i in range(int(icfg[4 + M])))
+
+
+@_op("actor_latent_fwd(Tensor(a!)[] state, int[] icfg, float[] fcfg, Tensor obs, Tensor latent, bool save) -> (Tensor, Tensor)")
+def actor_latent_fwd(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequence[float], obs: Tensor, latent: Tensor,
+                     save: bool) -> Tuple[Tensor, Tensor]:
+    """The frozen actor on ``cat(obs, latent)`` (act_inference / act_with_grad with a student latent, models_split.py:
+    155-164 + 187-216; ext_adapt.py:684-690, 799-806): mu (rows, act) -- no value, no critic.  obs (rows, obs_dim)
+    normalised; latent (rows, W) with W the teacher's own extrinsic width.  ``save``: also the post-tanh activations of
+    the actor's layers, (rows, sum of the layer widths rounded up to 4) -- the caller's tensor, for ``actor_latent_bwd``
+    (empty otherwise).  Uses state.workspace as scratch -> igi_actor_latent_forward."""
+    cfg, st, dev = _teacher_args(state, icfg, fcfg)
+    rows = _check(obs, "obs", shape=(None, cfg.obs_dim), device=dev).shape[0]
+    _check(latent, "latent", shape=(rows, None), device=dev)
+    if rows < 1:
+        raise RuntimeError("actor_latent_fwd: no rows")
+    mu = torch.empty(rows, cfg.act_dim, dtype=torch.float32, device=dev)
+    saved = torch.empty(rows if save else 0, _actor_saved_width(icfg), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _rc(_lib.lib().igi_actor_latent_forward(C.byref(cfg), C.byref(st), _p(obs), _p(latent), int(latent.shape[1]), rows,
+                                                _p(mu), _p(saved) if save else None, _stream(obs)),
+            "igi_actor_latent_forward")
+    return mu, saved
+
+
+@_fake("actor_latent_fwd")
+def _(state, icfg, fcfg, obs, latent, save):
+    rows = obs.shape[0]
+    return obs.new_empty(rows, icfg[2]), obs.new_empty(rows if save else 0, _actor_saved_width(icfg))
+
+
+@_op("actor_latent_bwd(Tensor(a!)[] state, int[] icfg, float[] fcfg, Tensor saved, Tensor dmu) -> Tensor")
+def actor_latent_bwd(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequence[float], saved: Tensor,
+                     dmu: Tensor) -> Tensor:
+    """d/d latent of a loss whose gradient with respect to ``actor_latent_fwd``'s mu is ``dmu`` (rows, act), from that
+    call's saved activations: the data-gradient chain through the frozen actor, no weight gradient
+    -> igi_actor_latent_backward."""
+    cfg, st, dev = _teacher_args(state, icfg, fcfg)
+    rows = _check(dmu, "dmu", shape=(None, cfg.act_dim), device=dev).shape[0]
+    _check(saved, "saved", shape=(rows, _actor_saved_width(icfg)), device=dev)
+    if rows < 1:
+        raise RuntimeError("actor_latent_bwd: no rows")
+    dlatent = torch.empty(rows, _latent_gt_width(icfg), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _rc(_lib.lib().igi_actor_latent_backward(C.byref(cfg), C.byref(st), _p(saved), _p(dmu), rows, _p(dlatent),
+                                                 _stream(dmu)), "igi_actor_latent_backward")
+    return dlatent
+
+
+@_fake("actor_latent_bwd")
+def _(state, icfg, fcfg, saved, dmu):
+    return dmu.new_empty(dmu.shape[0], _latent_gt_width(icfg))
+
+
 @_op("rollout_policy_step_contacts(Tensor(a!)[] state, int[] icfg, float[] fcfg, Tensor obs, Tensor priv, Tensor contacts, bool normalize, Tensor noise, Tensor? rms_value, Tensor(b!)? obses_t, Tensor(c!)? priv_t, Tensor(k!)? contacts_t, Tensor(d!) actions_t, Tensor(e!) neglogp_t, Tensor(f!) values_t, Tensor(g!) mus_t, Tensor(h!) sigmas_t, Tensor(i!) actions_clamped, Tensor(j!) values_out) -> ()")
 def rollout_policy_step_contacts(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequence[float], obs: Tensor,
                                  priv: Tensor, contacts: Tensor, normalize: bool, noise: Tensor,
@@ -766,6 +823,35 @@ def bc_loss_fwd_bwd(mu: Tensor, teacher_actions: Tensor, weights: Tensor, want_g
 @_fake("bc_loss_fwd_bwd")
 def _(mu, teacher_actions, weights, want_grad):
     return mu.new_empty(()), (torch.empty_like(mu) if want_grad else mu.new_empty(0, mu.shape[1]))
+
+
+@_op("distill_loss_value_grad(Tensor mu, Tensor actions, Tensor weights, Tensor latent, Tensor latent_gt, float action_scale, float latent_scale) -> (Tensor, Tensor, Tensor, Tensor)")
+def distill_loss_value_grad(mu: Tensor, actions: Tensor, weights: Tensor, latent: Tensor, latent_gt: Tensor,
+                            action_scale: float, latent_scale: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The latent student's loss with its latent term live (ext_adapt.py:827 without the comment sign), ONE launch:
+    (loss_action = bc_loss's sum, loss_latent = MSELoss(latent, latent_gt), dmu, dlatent) with the two gradients those of
+    ``action_scale * loss_action + latent_scale * loss_latent`` -> igi_distill_loss."""
+    rows, act = _check(mu, "mu", dim=2).shape
+    dev = mu.device
+    _check(actions, "actions", shape=(rows, act), device=dev)
+    _check(weights, "weights", shape=(act,), device=dev)
+    L = _check(latent, "latent", shape=(rows, None), device=dev).shape[1]
+    _check(latent_gt, "latent_gt", shape=(rows, L), device=dev)
+    if rows < 1 or act < 1 or L < 1:
+        raise RuntimeError("distill_loss_value_grad: empty input")
+    loss_action = torch.empty((), dtype=torch.float32, device=dev)
+    loss_latent = torch.empty((), dtype=torch.float32, device=dev)
+    dmu, dlatent = torch.empty_like(mu), torch.empty_like(latent)
+    with torch.cuda.device(dev):
+        _rc(_lib.lib().igi_distill_loss(_p(mu), _p(actions), _p(weights), rows, act, _p(latent), _p(latent_gt), L,
+                                        float(action_scale), float(latent_scale), _p(loss_action), _p(loss_latent), _p(dmu), _p(dlatent),
+                                        _stream(mu)), "igi_distill_loss")
+    return loss_action, loss_latent, dmu, dlatent
+
+
+@_fake("distill_loss_value_grad")
+def _(mu, actions, weights, latent, latent_gt, action_scale, latent_scale):
+    return mu.new_empty(()), mu.new_empty(()), torch.empty_like(mu), torch.empty_like(latent)
 
 
 @_op("bc_loss(Tensor mu, Tensor teacher_actions, Tensor weights) -> Tensor")
@@ -1590,7 +1676,7 @@ for _n in ("gae_advnorm", "ppo_minibatch_fwd_bwd", "ppo_clip_adam", "ppo_update"
     register_fake(f"{NS}::{_n}")(lambda *a, **k: None)
 
 OP_NAMES = ["gae_advnorm", "ppo_minibatch_fwd_bwd", "ppo_clip_adam", "ppo_update", "ppo_update_dp", "ppo_update_dp_rccl",
-            "actor_critic_infer", "rms_update_normalize", "clip_adam_step", "rollout_act_store", "rollout_policy_step",
+            "actor_critic_infer", "actor_latent_fwd", "actor_latent_bwd", "distill_loss_value_grad", "rms_update_normalize", "clip_adam_step", "rollout_act_store", "rollout_policy_step",
             "rollout_env_store",
             "bc_loss_fwd_bwd", "bc_loss", "bc_loss_value_grad", "gemm_f32", "linear", "linear_bwd", "mlp_fwd", "mlp_bwd", "tactile_cnn_fwd", "tactile_cnn_bwd", "spatial_softargmax_fwd", "spatial_softargmax_bwd",
             "pointnet_max_fwd", "pointnet_max_bwd", "pointnet_max_fwd_multi", "pointnet_max_bwd_multi", "depth_backbone_fwd", "depth_backbone_bwd", "token_encoder_fwd",

@@ -586,6 +586,16 @@ class TeacherEngine:
                                                               bool(normalize), bool(want_latent))
         return (mu, val, lat) if want_latent else (mu, val)
 
+    def actor_latent(self, obs, latent, save=False):
+        """The frozen actor on ``cat(obs, latent)`` (act_inference / act_with_grad with a student latent): obs normalised
+        (rows, obs_dim), latent (rows, the teacher's extrinsic width), both fp32 and contiguous on the engine's device.
+        Returns (mu, saved): ``saved`` holds the actor's activations for ``actor_latent_backward`` when ``save``."""
+        return torch.ops.mi355ppo.actor_latent_fwd(self.state_list(), *self._cfg_args(), obs, latent, bool(save))
+
+    def actor_latent_backward(self, saved, dmu):
+        """d/d latent from ``actor_latent(..., save=True)``'s activations and d/d mu; the teacher's weights get nothing."""
+        return torch.ops.mi355ppo.actor_latent_bwd(self.state_list(), *self._cfg_args(), saved, dmu)
+
     def infer_contacts(self, obs, priv, contacts, want_latent=False, normalize=True):
         """``infer`` for a contact teacher: contacts (rows, P) raw; the latent is latent_gt = [priv latent | contact
         embedding] (models_split.py:172-177)."""

@@ -7,6 +7,8 @@
     python -m isaacgyminsertion_amd.train test=True train.load_path=.../stage1_nn/last.pth
     python -m isaacgyminsertion_amd.train train.ppo.lr_schedule=adaptive train.ppo.kl_threshold=0.008
     python -m isaacgyminsertion_amd.train train.ppo.kl_early_stop=True train.ppo.kl_threshold=0.008
+    python -m isaacgyminsertion_amd.train train.algo=ExtrinsicAdapt offline_train.only_bc=False \\
+        offline_train.train.latent_loss=True offline_train.train.latent_scale=0.5
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m isaacgyminsertion_amd.train train.ppo.multi_gpu=True
 
 rank / device / seed selection, ``offline_training`` -> ``Runner.run()``, environment construction, the
@@ -56,6 +58,8 @@ def build_config(config=None, overrides=()):
     from .teacher_native import lr_schedule_id, parse_kl_early_stop
     lr_schedule_id(cfg.train.ppo.get('lr_schedule', None))     # "fixed" | "adaptive": anything else stops here
     parse_kl_early_stop(cfg.train.ppo.get('kl_early_stop', None))     # True | False: anything else stops here
+    from .utils.config import parse_latent_loss
+    parse_latent_loss(cfg.offline_train.train.get('latent_loss', None), cfg.offline_train.only_bc)   # likewise
     return cfg
 
 

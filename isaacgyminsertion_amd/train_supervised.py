@@ -12,7 +12,7 @@ import yaml
 
 from .algo.models.transformer.runner import Runner
 from .algo.models.transformer.utils import set_seed
-from .utils.config import default_config, load_config, merge
+from .utils.config import default_config, load_config, merge, parse_latent_loss
 
 
 def _override(cfg, dotted, value):
@@ -36,6 +36,8 @@ def main(argv=None):
     for o in args.overrides:
         k, _, v = o.partition('=')
         cfg = _override(cfg, k, v)
+    # (read by ExtrinsicAdapt, the online stage that shares this config; the offline loss always carries both terms)
+    parse_latent_loss(cfg.offline_train.train.get('latent_loss', None), cfg.offline_train.only_bc)
     set_seed(cfg.offline_train.get('seed', 0))
     runner = Runner(cfg, agent=None)
     runner.run()

@@ -90,7 +90,7 @@ def default_config(num_envs=4096, horizon_length=32, rl_device="cuda:0", multi_g
             "tactile_patch_size": 16, "tactile_gaussian_noise": 0.001, "tactile_masking_prob": 0.0,
             "tactile_color_jitter": False, "seed": 0, "data_folder": "", "output_dir": "outputs/offline",
             # supervised learning (offline_config.yaml:28-83)
-            "train": {"latent_scale": 1.0, "action_scale": 1.0, "action_regularization": False, "epochs": 100, "train_batch_size": 64,
+            "train": {"latent_scale": 1.0, "action_scale": 1.0, "latent_loss": False, "action_regularization": False, "epochs": 100, "train_batch_size": 64,
                       "val_batch_size": 64, "learning_rate": 1e-4, "train_test_split": 0.98,
                       "scheduler": "cosine", "warmup": False, "warmup_epochs": 4,
                       "print_every": 1000, "eval_every": 1000, "test_every": 2000,
@@ -121,6 +121,20 @@ def default_config(num_envs=4096, horizon_length=32, rl_device="cuda:0", multi_g
         },
     }
     return to_attr(cfg)
+
+
+def parse_latent_loss(value, only_bc=None):
+    """offline_train.train.latent_loss -> bool (None = absent = off: the reference's live loss, action_scale * loss_action).
+    True adds latent_scale * loss_latent, the term ext_adapt.py:827 computes and comments out.  ValueError for anything
+    that is not a boolean -- a string such as "yes" or a number would otherwise switch it on silently -- and for True
+    with ``only_bc`` (the student then emits the action: there is no latent to compare)."""
+    if value is None:
+        return False
+    if not isinstance(value, bool):
+        raise ValueError(f"latent_loss {value!r}: expected True or False")
+    if value and only_bc:
+        raise ValueError("latent_loss needs offline_train.only_bc=False: with only_bc the student emits no latent")
+    return value
 
 
 def load_config(path, **overrides):
