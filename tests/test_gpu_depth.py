@@ -8,11 +8,11 @@ import sys
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from golden_io import GOLDEN, load_golden
 
 sys.path.insert(0, GOLDEN)
+from oracle import encoders as oe  # noqa: E402
 from make_golden_depth import depth_case  # noqa: E402  (seeded inputs only; the reference is not imported)
 
 pytestmark = pytest.mark.gpu
@@ -51,19 +51,15 @@ def test_matches_reference_module():
 
 
 def _aten(sd, x, dy):
-    p = {k: v.double().requires_grad_(True) for k, v in sd.items()}
-    h = F.conv2d(x.double(), p["image_compression.0.weight"], p["image_compression.0.bias"])
-    h = F.elu(F.max_pool2d(h, 2, 2))
-    h = F.elu(F.conv2d(h, p["image_compression.3.weight"], p["image_compression.3.bias"]))
-    h = F.elu(F.linear(h.flatten(1), p["image_compression.6.weight"], p["image_compression.6.bias"]))
-    y = F.linear(h, p["image_compression.8.weight"], p["image_compression.8.bias"])
-    y.backward(dy.double())
-    return y.detach(), {k: v.grad for k, v in p.items()}
+    """ATen fp64 on the CPU: oracle/encoders.py:depth_backbone (pinned to depth.npz by tests/test_oracle_encoders.py)"""
+    return oe.value_and_grads(oe.depth_backbone, x, sd, dy, dtype=torch.float64)
 
 
-@pytest.mark.parametrize("batch,latent", [(64, 32), (5, 8), (33, 32)])
+@pytest.mark.parametrize("batch,latent", [(64, 32), (5, 8), (33, 32), (96, 4), (128, 64)])
 def test_matches_aten_other_shapes(batch, latent):
-    """incl. batches that are not a multiple of 32 (padded inside the op)."""
+    """incl. batches that are not a multiple of 32 (padded inside the op); 96: three 32-image groups in the conv2
+    weight-gradient walk and the first wrap of the fc1 weight gradient's two-stage ring, with the narrowest head the plan
+    accepts (4); 128: the largest batch still on 128-row convolution tiles."""
     sd, x, dy = depth_case(latent=latent, batch=batch, seed=batch)
     m = _module(sd, latent)
     y = m(x.cuda())
