@@ -540,6 +540,31 @@ int igi_level_backward_below(const float* dz, const float* weight, const float* 
                              igi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * TEST ENTRY: the grouped weight-gradient launcher (csrc/gemm_dma.h, gemm_wgrad_group) on a list of the caller's
+ * choosing.  No product code calls it; it exists so that the launcher -- one grid for up to six (fp32) or four plus
+ * four (bf16-input mode) problems, split-K slabs, bias sums from the tiles, batched nets, a launch of its own for any
+ * problem the grid cannot take -- can be tested without a whole teacher step around it (tests/test_gpu_wgrad_group.py).
+ * `count` (1..8) problems, each built as linear_backward and the teacher's backward build theirs:
+ *     dweight[split][batch][out][in] = sum over the split's rows r of dz[batch][r][out]^T . x[batch][r][in]
+ *     dbias  [split][batch][out]     = sum over the split's rows r of dz[batch][r][out]              (dbias may be NULL)
+ * Split s covers rows [s * chunk, min(rows, (s + 1) * chunk)) with chunk = ceil(rows / splitk) rounded up to a
+ * multiple of 32; the caller adds the splitk slabs.  Both outputs are dense.  Under igi_gemm_set_bf16_inputs(1) the
+ * eligible problems with in_features > 64 that fit the four-entry table run with bf16-rounded operands; the bias sums
+ * are fp32 sums of the un-rounded dz in either mode.  The list is handed to the launcher as it is: no tile logic here.
+ * IGI_E_BADARG: count outside 1..8, a null problems / dz / x / dweight pointer, a non-positive extent, a leading
+ * dimension below the row width.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct igi_wgrad_problem {
+  const float* dz;          /* [nbatch][rows][lddz], batch stride dz_batch_stride floats */
+  const float* x;           /* [nbatch][rows][ldx],  batch stride x_batch_stride floats */
+  float* dweight;           /* [splitk][nbatch][out_features][in_features] */
+  float* dbias;             /* [splitk][nbatch][out_features], or NULL */
+  int64_t dz_batch_stride, x_batch_stride;
+  int32_t lddz, ldx, out_features, in_features, rows, nbatch, splitk;
+} igi_wgrad_problem;
+int igi_gemm_wgrad_group(const igi_wgrad_problem* problems, int count, igi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * nn.Linear with a fused activation, forward and backward, for the student's small MLPs: lin encoder
  * Linear(15,64)-ReLU-Linear(64,32) (tact.py:337-339), point-cloud compress (tact.py:367-369), MLPDecoder /
  * MultiLayerDecoder output stack (tact.py:137-158, 197-212), action head Linear(32,6)+Tanh (tact.py:407-410)

@@ -87,6 +87,14 @@ class ProfEntry(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class WgradProblem(C.Structure):
+    """struct igi_wgrad_problem (test entry igi_gemm_wgrad_group)"""
+    _fields_ = [("dz", C.c_void_p), ("x", C.c_void_p), ("dweight", C.c_void_p), ("dbias", C.c_void_p),
+                ("dz_batch_stride", C.c_int64), ("x_batch_stride", C.c_int64),
+                ("lddz", C.c_int32), ("ldx", C.c_int32), ("out_features", C.c_int32), ("in_features", C.c_int32),
+                ("rows", C.c_int32), ("nbatch", C.c_int32), ("splitk", C.c_int32)]
+
+
 _EXPORTS = {
     # name: (restype, argtypes)
     "igi_abi_version": (C.c_int, []),
@@ -105,6 +113,7 @@ _EXPORTS = {
     "igi_level_backward_parts": (C.c_int, [C.c_int64, C.c_int, C.c_int]),
     "igi_level_backward": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "igi_level_backward_below": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "igi_gemm_wgrad_group": (C.c_int, [C.POINTER(WgradProblem), C.c_int, C.c_void_p]),
     "igi_rms_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "igi_rms_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_float,
                                   C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),

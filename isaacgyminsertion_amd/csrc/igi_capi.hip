@@ -119,6 +119,28 @@ int igi_level_backward_below(const float* dz, const float* weight, const float* 
   return fail((int)e, "igi_level_backward_below");
 }
 
+// test entry: the caller's list, built as linear_backward / the teacher's backward build theirs, straight to the launcher
+int igi_gemm_wgrad_group(const igi_wgrad_problem* problems, int count, igi_stream_t stream) {
+  if (!problems || count < 1 || count > 8) return fail(IGI_E_BADARG, "igi_gemm_wgrad_group");
+  igi::GemmArgs list[8];
+  for (int i = 0; i < count; ++i) {
+    const igi_wgrad_problem& p = problems[i];
+    if (!p.dz || !p.x || !p.dweight || p.out_features < 1 || p.in_features < 1 || p.rows < 1 || p.nbatch < 1 ||
+        p.splitk < 1 || p.lddz < p.out_features || p.ldx < p.in_features || p.dz_batch_stride < 0 || p.x_batch_stride < 0)
+      return fail(IGI_E_BADARG, "igi_gemm_wgrad_group");
+    igi::GemmArgs& g = list[i];
+    const long long out = p.out_features, in = p.in_features;
+    g.A = p.dz; g.lda = p.lddz; g.sA = p.dz_batch_stride;
+    g.B = p.x; g.ldb = p.ldx; g.sB = p.x_batch_stride;
+    g.M = p.out_features; g.N = p.in_features; g.K = p.rows;
+    g.C = p.dweight; g.ldc = p.in_features; g.sC = out * in;
+    g.Cbias = p.dbias; g.sCbias = out;
+    g.nbatch = p.nbatch; g.splitk = p.splitk;
+    g.sCsplit = p.nbatch * out * in; g.sCbiasSplit = p.nbatch * out;
+  }
+  return fail((int)igi::gemm_wgrad_group(list, count, S(stream)), "igi_gemm_wgrad_group");
+}
+
 int igi_teacher_set_latz_fuse(int on) {
   const int prev = igi::latz_fuse_ref();
   igi::latz_fuse_ref() = on != 0;

@@ -1667,8 +1667,10 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
   }
   // (the fused kernel is one workgroup per 64 rows with a fixed ~20 us chain: at the rollout's 4096 rows it fills a
   // quarter of the chip and the per-layer launches win -- measured 8.4 -> 8.0 ms per 32-step rollout)
-  if (!env_done && env_fused && p.npl == 3 && rows >= 8192) {
+  if (!env_done && env_fused && p.npl == 3 && rows >= 8192 && !bf16_mode()) {
     // the whole env_mlp of a 64-row block in one workgroup (env_mlp.h); other shapes run layer by layer below
+    // (an fp32 kernel: in the bf16-input mode the layers go through gemm() like every other fused class's, so the
+    // forward of a layer and its backward products are under the switch together)
     EnvFwdArgs a;
     a.priv = priv_g; a.ldp = ldin;
     a.W1 = P + p.o_envW[0]; a.b1 = P + p.o_envB[0];

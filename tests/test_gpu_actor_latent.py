@@ -42,6 +42,9 @@ def _case(name):
     from isaacgyminsertion_amd.teacher_native import TeacherEngine
     s = SHAPES[name]
     g = torch.Generator().manual_seed(sum(ord(c) for c in name))
+    # the initialisation draws from the GLOBAL generator: seeded too, or every process tests another network (the fused
+    # against chain comparison then moved between 2.9e-6 and 3.8e-6 at 300 rows from run to run, around its bound)
+    torch.manual_seed(sum(ord(c) for c in name))
     net = ActorCriticSplit({'actions_num': s["act"], 'input_shape': (s["obs"],), 'actor_units': list(s["units"]),
                             'priv_mlp_units': [256, 128, s["L"]], 'priv_info': True, 'priv_info_dim': 64,
                             'shared_parameters': s["shared"]})

@@ -568,6 +568,66 @@ def test_bf16_input_mode_is_optin_and_close():
     assert (outs[0][1] - outs[1][1]).abs().mean() < 1e-3
 
 
+def test_bf16_input_mode_first_step_gradient_per_tensor():
+    """The teacher under igi_gemm_set_bf16_inputs(1) at 4096 envs x 8, 4 mini-epochs: minibatches of 8192 rows, the
+    smallest at which the default network's 512 -> 256 and 256 -> 128 layers exceed 128 tiles -- so the step launches
+    the bf16 forward / data-gradient kernels and gemm_dma_group_kernel<128,false,false> (the only bf16 kernel with
+    reduction-major operands on both sides), and none of the fused classes the planner switches off in the mode.
+    The raw first-step gradient, per tensor, against the fp64 oracle (its Linears computed in fp64):
+        |g - g64| <= max(2e-4 * max|g64|, 3 * e_emu)
+    e_emu = max|g_emu - g64| of a CPU run of the oracle whose Linears round BOTH operands of the forward, data-gradient
+    and weight-gradient products to bf16 (tests/bf16_emulation.py).  The device rounds a subset of those products, so
+    the emulation's own error is the yardstick; 3 is the factor this suite gives a device over an fp32 oracle
+    everywhere else.
+    Measured on an MI355X: worst |g - g64| / tolerance over the 23 tensors 0.28 (value.bias: 1.0e-3 against e_emu = 1.2e-3);
+    every tensor's error is below its e_emu."""
+    from isaacgyminsertion_amd import _lib
+    from isaacgyminsertion_amd.teacher_native import TeacherEngine
+    from oracle import synth, teacher as ot
+    from tests.bf16_emulation import bf16r, oracle_first_step_grad
+    N, T, E = 4096, 8, 4
+    units, priv_units = [512, 256, 128], [256, 128, 8]
+    init, ro, perm = synth.teacher_problem(N, T, units, priv_units, seed=77)
+    L = _lib.lib()
+    assert L.igi_gemm_set_bf16_inputs(1) == 0
+    try:
+        eng = TeacherEngine(N, T, E, units=units, priv_units=priv_units, perm=perm)
+        eng.load_params(init)
+        eng.prepare(ro)
+        torch.cuda.synchronize()
+        _lib.prof_enable(True)
+        try:
+            eng.fwd_bwd(0, 0)
+            torch.cuda.synchronize()
+            classes = {c["name"]: c["launches"] for c in _lib.prof_read()}
+        finally:
+            _lib.prof_enable(False)
+        got = {k: v.cpu().double() for k, v in eng.param_views(eng.grads).items()}
+    finally:
+        L.igi_gemm_set_bf16_inputs(0)
+    assert classes.get("gemm_dma_group_kernel<128,false,false>", 0) >= 1, classes
+    fused = [k for k in classes if k.startswith(("k_fwd12", "k_rb_level", "k_policy_fwd", "k_env_fwd"))]
+    assert not fused, classes
+
+    def oracle(rnd):
+        orc = ot.TeacherOracle(init, perm, N, T, E, units, priv_units)
+        orc.prepare(ro)
+        return oracle_first_step_grad(orc, rnd)
+
+    g64, gemu = oracle(None), oracle(bf16r)
+    assert list(got) == list(g64)
+    bad = []
+    for k in got:
+        scale = float(g64[k].abs().max())
+        err = float((got[k] - g64[k]).abs().max())
+        e_emu = float((gemu[k] - g64[k]).abs().max())
+        tol = max(2e-4 * scale, 3.0 * e_emu)
+        print(f"{k}: |g - g64| = {err:.3e}, e_emu = {e_emu:.3e}, max|g64| = {scale:.3e}, err / tol = {err / tol:.3f}")
+        if not err <= tol:
+            bad.append((k, err, e_emu, scale))
+    assert not bad, bad
+
+
 _ENV_FUSED_CHILD = r'''
 import sys, numpy as np, torch
 from isaacgyminsertion_amd.envs import synthetic_rollout as synth
