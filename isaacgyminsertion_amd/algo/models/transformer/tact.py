@@ -16,7 +16,6 @@ transformer is ``HipTransformerEncoder`` = igi_token_forward / igi_token_backwar
 The efficientnet encoders are outside the scope table and raise.
 """
 import math
-import os
 from typing import Dict, Optional
 
 import torch
@@ -26,9 +25,6 @@ from ....hip_linear import HipLinear, mlp_chain, run_chain
 from ....hip_token_encoder import HipTransformerEncoder
 from .depth_backbone import DepthOnlyFCBackbone54x96
 from .pointnets import PointNet
-
-# IGI_PCL_ONE_LAUNCH=0: one PointNet launch per object + a concatenation (A/B; read once)
-_PCL_ONE_LAUNCH = os.environ.get("IGI_PCL_ONE_LAUNCH", "1") != "0"
 from .tactile_cnn import CNNWithSpatialSoftArgmax
 
 
@@ -216,7 +212,7 @@ class MultiModalModel(nn.Module):
                                                                ('merge_socket', 'socket_encoder', 'num_sample_hole'),
                                                                ('merge_goal', 'goal_encoder', 'num_sample_goal'),
                                                                ('scene_pcl', 'scene_encoder', 'num_sample_all')) if c[flag]]
-            if _PCL_ONE_LAUNCH and 2 <= len(objs) <= 4 and obs_pcl.is_cuda and obs_pcl.dtype is torch.float32:
+            if 2 <= len(objs) <= 4 and obs_pcl.is_cuda and obs_pcl.dtype is torch.float32:
                 # every object in ONE forward (and one backward) launch, encodings written concatenated (round 6)
                 enc, _idx = torch.ops.mi355ppo.pointnet_max_fwd_multi(
                     obs_pcl, [self.pcl_encoder[name].flat_parameters() for name, _n in objs], [int(n) for _name, n in objs])

@@ -1278,10 +1278,8 @@ static inline bool dma_eligible(const GemmArgs& g, bool akc, bool bkc) {
 // Can the im2col product `g` (gather == 1) run on position-major tiles (GATHER == 4)?  A padded stride-1 correlation
 // (= the data gradient of an unpadded convolution), whole blocks of 256 images, 16-byte aligned output / aux rows.
 static inline bool conv_pmajor_ok(const GemmArgs& g, bool bkc) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("IGI_CONV_PMAJOR"); on = e ? atoi(e) : 1; }
   const ConvDesc& c = g.conv;
-  if (!on || g.gather != 1 || !bkc || c.pad <= 0 || c.KH <= 0 || c.KH * c.KW > 32 || (c.C & 31) || g.splitk > 1 ||
+  if (g.gather != 1 || !bkc || c.pad <= 0 || c.KH <= 0 || c.KH * c.KW > 32 || (c.C & 31) || g.splitk > 1 ||
       g.nbatch != 1 || c.OHW <= 0)
     return false;
   const long long images = g.M / c.OHW;
@@ -1292,20 +1290,20 @@ static inline bool conv_pmajor_ok(const GemmArgs& g, bool bkc) {
   return wide && (long long)c.OHW * g.ldc < (1 << 24) && (long long)c.OHW * g.ldaux < (1 << 24);
 }
 
-// IGI_CONV_BM192=0: the 576-tap weight gradient on five 128-tap tiles (A/B)
-static inline bool conv_bm192_on() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("IGI_CONV_BM192"); on = e ? atoi(e) : 1; }
-  return on != 0;
+// Tap-tile height (BM) of an im2col weight gradient over `taps` rows: whole 256-tap tiles where they divide the taps
+// (conv1: 256, conv2: 512), three 192-tap tiles for conv3's 576 (no padded tap rows: five 128-tap tiles multiplied 640),
+// else the 128-row tile.  gemm() picks its weight-gradient branch with it and the tactile plan sizes the split-k slabs
+// of conv2 and conv3 for the same tiles.
+constexpr int CONV_BM_TALL = 256, CONV_BM_192 = 192;
+constexpr int conv_wgrad_bm(int taps) {
+  return taps % CONV_BM_TALL == 0 ? CONV_BM_TALL : (taps % CONV_BM_192 == 0 ? CONV_BM_192 : DMA_BM);
 }
 
 // Can the weight gradient `g` (gather == 3) walk its reduction position-major (GATHER == 5)?  Unpadded convolution, whole
 // groups of 32 images, every split's k-range whole k-tiles (the launcher guarantees that already).
 static inline bool conv_pw_ok(const GemmArgs& g) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("IGI_CONV_PW"); on = e ? atoi(e) : 1; }
   const ConvDesc& c = g.conv;
-  if (!on || g.gather != 3 || c.pad != 0 || c.OHW <= 0 || (c.C & 3) || g.nbatch != 1) return false;
+  if (g.gather != 3 || c.pad != 0 || c.OHW <= 0 || (c.C & 3) || g.nbatch != 1) return false;
   const long long images = g.K / c.OHW;
   if (images * c.OHW != g.K || (images & 31)) return false;
   if (32LL * c.IH * c.IW * c.C * 4 >= (1LL << 32) || 32LL * c.OHW * g.ldb * 4 >= (1LL << 32)) return false;
@@ -1319,6 +1317,43 @@ static inline void dma_set_divs(GemmArgs& g, int n_tiles, int m_tiles) {
   g.dNT = make_fastdiv((unsigned)n_tiles); g.dMT = make_fastdiv((unsigned)m_tiles);
   g.dSK = make_fastdiv((unsigned)(g.splitk < 1 ? 1 : g.splitk));
 }
+
+// splitk >= 1, and each split's k-range whole k-tiles where the caller left kchunk open
+static inline void dma_norm_splitk(GemmArgs& g) {
+  if (g.splitk < 1) g.splitk = 1;
+  if (g.splitk > 1 && g.kchunk <= 0) {
+    int c = (g.K + g.splitk - 1) / g.splitk;
+    g.kchunk = (c + DMA_BK - 1) / DMA_BK * DMA_BK;
+  }
+}
+
+// wide (LDS-staged, 16 B per lane) epilogue: float4-aligned C for a plain store ...
+static inline bool dma_wide_store_ok(const GemmArgs& g) {
+  return aligned16(g.C) && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && (g.sCsplit & 3) == 0 && (g.N & 3) == 0;
+}
+// ... and float4-aligned bias / aux for the epilogues that read them
+static inline bool dma_wide_epi_ok(const GemmArgs& g) {
+  return dma_wide_store_ok(g) && (!g.bias || (aligned16(g.bias) && (g.sBias & 3) == 0)) &&
+         (!g.aux || (aligned16(g.aux) && (g.ldaux & 3) == 0 && (g.sAux & 3) == 0));
+}
+
+// LDS of a 128 x 128 two-stage tile: the ring, or the staging of its wide epilogue
+constexpr size_t DMA_SHM_128X2 = sizeof(float) * 2 * (DMA_BM + 128) * DMA_BK > sizeof(float) * DMA_WAVES * 64 * (32 + 4)
+                                     ? sizeof(float) * 2 * (DMA_BM + 128) * DMA_BK : sizeof(float) * DMA_WAVES * 64 * (32 + 4);
+
+// Raise the kernel's dynamic-LDS limit to SHM_CAP on its first launch from this site (one flag per expansion, and per
+// instantiation inside a template), then launch it with SHM bytes.  For functions that return hipError_t.
+#define IGI_DMA_LAUNCH_SHM(KERNEL, GRID, SHM_CAP, SHM, STREAM, ...)                                    \
+  do {                                                                                                 \
+    static bool attr_set = false;                                                                      \
+    if (!attr_set) {                                                                                   \
+      hipError_t e_ = hipFuncSetAttribute((const void*)KERNEL,                                         \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SHM_CAP)); \
+      if (e_ != hipSuccess) return e_;                                                                 \
+      attr_set = true;                                                                                 \
+    }                                                                                                  \
+    IGI_LAUNCH((KERNEL), GRID, dim3(DMA_THREADS), SHM, STREAM, __VA_ARGS__);                           \
+  } while (0)
 
 template <int BN, int NS = DMA_NS, int BM = DMA_BM, bool BF = false>
 static hipError_t launch_dma_cfg(const GemmArgs& g, bool akc, bool bkc, hipStream_t s) {
@@ -1341,23 +1376,11 @@ static hipError_t launch_dma_cfg(const GemmArgs& g, bool akc, bool bkc, hipStrea
     gg.conv.fast32 = (c.pad == 0 && images * c.IH * c.IW * c.C * 4 < (1LL << 32)) ? 1 : 0;
   }
   // wide (LDS-staged, 16 B per lane) epilogue needs float4-aligned C / bias / aux
-  gg.wide_epi = aligned16(g.C) && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && (g.sCsplit & 3) == 0 && (g.N & 3) == 0 &&
-            (!g.bias || (aligned16(g.bias) && (g.sBias & 3) == 0)) &&
-            (!g.aux || (aligned16(g.aux) && (g.ldaux & 3) == 0 && (g.sAux & 3) == 0));
+  gg.wide_epi = dma_wide_epi_ok(g);
   if (gg.wide_epi && shm < EPI_BYTES) shm = EPI_BYTES;
   const size_t shm_cap = shm_max > EPI_BYTES ? shm_max : EPI_BYTES;
-  dim3 grid(total), block(DMA_THREADS);
-#define IGI_DMA_LAUNCH_K(KERNEL)                                                                       \
-  do {                                                                                                 \
-    static bool attr_set = false;                                                                      \
-    if (!attr_set) {                                                                                   \
-      hipError_t e = hipFuncSetAttribute((const void*)KERNEL,                                          \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_cap);    \
-      if (e != hipSuccess) return e;                                                                   \
-      attr_set = true;                                                                                 \
-    }                                                                                                  \
-    IGI_LAUNCH((KERNEL), grid, block, shm, s, gg, n_tiles, m_tiles);                                   \
-  } while (0)
+  const dim3 grid(total);
+#define IGI_DMA_LAUNCH_K(KERNEL) IGI_DMA_LAUNCH_SHM(KERNEL, grid, shm_cap, shm, s, gg, n_tiles, m_tiles)
   // BF: the bf16-input twin of the same tile (im2col products A = gather 1 / 3 with a k-contiguous weight operand only)
 #define IGI_DMA_LAUNCH(AK, BK_, GA)                                                                    \
   do {                                                                                                 \
@@ -1441,34 +1464,35 @@ static hipError_t gemm_with_head(GemmArgs g, hipStream_t s) {
   const double fl = 2.0 * g.M * (double)g.N * (g.K + g.head_n);
   const double by = 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N);
   ProfScope ps(PC_DMA_HEAD, s, fl, by);
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_head_kernel<true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
-  IGI_LAUNCH((gemm_dma_head_kernel<true>), dim3(m_tiles), dim3(DMA_THREADS), shm, s, g, 1, m_tiles);
+  IGI_DMA_LAUNCH_SHM((gemm_dma_head_kernel<true>), dim3(m_tiles), shm, shm, s, g, 1, m_tiles);
   return hipGetLastError();
 }
 
-// Will gemm() run the im2col forward product (M rows, <= 64 output channels) on the tall 256 x 64 tile that can emit the
-// soft-argmax partials (GemmArgs::ssa_part)?  The tactile plan asks before it sets ssa_part.
-static inline bool conv_ssa_fusable(long long M, int N, int P) {
-  static int on = -1, tall = -1;
-  if (on < 0) { const char* e = getenv("IGI_SSA_FUSE"); on = e ? atoi(e) : 1; }
-  if (tall < 0) { const char* e = getenv("IGI_CONV_TALL"); tall = e ? atoi(e) : 3; }
-  return on && tall && N > 32 && N <= 64 && (P & 31) == 0 && (M & 255) == 0 && M / 256 >= 512;
+// Does gemm() run an im2col forward product (M rows, N <= 64 output channels, unsplit) on the tall 256-row tiles?  Enough
+// of them to fill the chip twice over.
+static inline bool conv_tall_fwd(long long M, int N, int nbatch, int splitk) {
+  return N <= 64 && splitk == 1 && (M + CONV_BM_TALL - 1) / CONV_BM_TALL * nbatch >= 512;
+}
+
+// ... and on the 256 x 64 tile that can emit the soft-argmax partials (GemmArgs::ssa_part) of maps of P positions: whole
+// tiles of whole 32-row groups, none of which straddles two images.  The ONE predicate of the tactile plan, which asks
+// before it sets ssa_part, and of gemm(), which refuses ssa_part on any other product.
+static inline bool conv_ssa_fusable(long long M, int N, int P, int nbatch = 1, int splitk = 1) {
+  return conv_tall_fwd(M, N, nbatch, splitk) && N > 32 && (P & 31) == 0 && (M & (CONV_BM_TALL - 1)) == 0;
+}
+
+// One im2col tile under its profiler class: fp32 inputs, or the bf16-input twin of the same tile (GemmArgs::conv_bf16)
+template <int BN, int NS, int BM>
+static hipError_t launch_conv_tile(const GemmArgs& g, bool akc, bool bkc, hipStream_t s, int pc_f32, int pc_bf16,
+                                   double fl, double by) {
+  ProfScope ps(g.conv_bf16 ? pc_bf16 : pc_f32, s, fl, by);
+  return g.conv_bf16 ? launch_dma_cfg<BN, NS, BM, true>(g, akc, bkc, s) : launch_dma_cfg<BN, NS, BM>(g, akc, bkc, s);
 }
 
 // Front door used by the C ABI and the teacher/student orchestration.
 static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   if (g.M <= 0 || g.N <= 0) return hipSuccess;
-  if (g.splitk < 1) g.splitk = 1;
-  if (g.splitk > 1 && g.kchunk <= 0) {
-    int c = (g.K + g.splitk - 1) / g.splitk;
-    g.kchunk = (c + DMA_BK - 1) / DMA_BK * DMA_BK;
-  }
+  dma_norm_splitk(g);
   if (!dma_eligible(g, akc, bkc)) return g.gather ? hipErrorInvalidValue : launch_gemm(g, akc, bkc, s);
   const double fl = 2.0 * g.M * g.N * (double)g.K * g.nbatch * g.flop_credit;
   const double by = 4.0 * g.nbatch * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N * g.splitk);
@@ -1480,58 +1504,36 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   // im2col forward / dgrad with <= 64 output channels (every tactile convolution): a 256 x 64 tile gives
   // each wave the same 64 x 32 sub-tile (two independent accumulator chains, 32 MFMAs per barrier) as the
   // 128 x 128 configuration; 2 stages x 40 KB so two workgroups still share a CU.
-  static int tall = -1;
-  if (tall < 0) { const char* e = getenv("IGI_CONV_TALL"); tall = e ? atoi(e) : 3; }
-  const bool tall_fwd = tall && g.gather == 1 && bn == 64 && g.splitk == 1 && (long long)((g.M + 255) / 256) * g.nbatch >= 512;
-  if (g.ssa_part && !(tall_fwd && g.N > 32 && g.N <= 64 && (g.M & 255) == 0 && !conv_pmajor_ok(g, bkc)))
+  const bool tall_fwd = g.gather == 1 && conv_tall_fwd(g.M, g.N, g.nbatch, g.splitk);
+  if (g.ssa_part && !(g.gather == 1 && conv_ssa_fusable(g.M, g.N, g.ssa_P, g.nbatch, g.splitk) && !conv_pmajor_ok(g, bkc)))
     return hipErrorInvalidValue;   // the caller plans the fused soft-argmax with conv_ssa_fusable(): only that tile emits it
   // conv_bf16 (the tactile encoder under conv_bf16_mode()): the SAME tile choice, the bf16-input twin of each tile and a
-  // profiler class of its own.  Only the shapes that encoder launches are built: anything else is an error, not fp32.
+  // profiler class of its own (launch_conv_tile).  Only the shapes that encoder launches are built: anything else is an
+  // error, not fp32.
   const bool cbf = g.conv_bf16 != 0;
   if (cbf && !(g.N <= 64 && ((g.gather == 1 && akc && bkc) || (g.gather == 3 && !akc && !bkc)))) return hipErrorInvalidValue;
   if (tall_fwd) {
-    // <= 32 output channels (conv1 forward, conv2 data gradient): a 32-wide tile, no padded MFMA columns
     const bool pmj = conv_pmajor_ok(g, bkc);
-    if (g.N <= 32 && tall > 1) {
-      if (cbf) {
-        ProfScope ps(pmj ? PC_CONVB_PM32 : PC_CONVB_TALL32_TT, s, fl, by);
-        return launch_dma_cfg<32, 2, 256, true>(g, akc, bkc, s);
-      }
-      ProfScope ps(pmj ? PC_CONV_PM32 : (bkc ? PC_CONV_TALL32_TT : PC_CONV_TALL32_TF), s, fl, by);
-      return launch_dma_cfg<32, 2, 256>(g, akc, bkc, s);
-    }
-    if (cbf) {
-      ProfScope ps(pmj ? PC_CONVB_PM64 : (g.ssa_part ? PC_CONVB_TALL64_SSA : PC_CONVB_TALL64_TT), s, fl, by);
-      return launch_dma_cfg<64, 2, 256, true>(g, akc, bkc, s);
-    }
-    ProfScope ps(pmj ? PC_CONV_PM64 : (g.ssa_part ? PC_CONV_TALL64_SSA : (bkc ? PC_CONV_TALL64_TT : PC_CONV_TALL64_TF)), s, fl, by);
-    return launch_dma_cfg<64, 2, 256>(g, akc, bkc, s);
+    if (g.N <= 32)   // conv1 forward, conv2 data gradient: a 32-wide tile, no padded MFMA columns
+      return launch_conv_tile<32, 2, CONV_BM_TALL>(g, akc, bkc, s, pmj ? PC_CONV_PM32 : (bkc ? PC_CONV_TALL32_TT : PC_CONV_TALL32_TF),
+                                                   pmj ? PC_CONVB_PM32 : PC_CONVB_TALL32_TT, fl, by);
+    return launch_conv_tile<64, 2, CONV_BM_TALL>(
+        g, akc, bkc, s, pmj ? PC_CONV_PM64 : (g.ssa_part ? PC_CONV_TALL64_SSA : (bkc ? PC_CONV_TALL64_TT : PC_CONV_TALL64_TF)),
+        pmj ? PC_CONVB_PM64 : (g.ssa_part ? PC_CONVB_TALL64_SSA : PC_CONVB_TALL64_TT), fl, by);
   }
-  if (tall > 1 && g.gather == 3 && g.N <= 32 && g.M % 256 == 0) {  // conv1 weight gradient: 32 output channels
-    if (cbf) {
-      ProfScope ps(conv_pw_ok(g) ? PC_CONVB_PW32 : PC_CONVB_WG_TALL32, s, fl, by);
-      return launch_dma_cfg<32, 2, 256, true>(g, akc, bkc, s);
-    }
-    ProfScope ps(conv_pw_ok(g) ? PC_CONV_PW32 : PC_CONV_WG_TALL32, s, fl, by);
-    return launch_dma_cfg<32, 2, 256>(g, akc, bkc, s);
-  }
-  if (tall > 2 && g.gather == 3 && g.N > 32 && g.N <= 64 && g.M % 192 == 0 && g.M % 256 != 0 && conv_bm192_on() && conv_pw_ok(g) &&
-      aligned16(g.C) && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && (g.sCsplit & 3) == 0 && (g.N & 3) == 0 && g.epilogue == EPI_STORE) {
-    // 576 taps = 3 x 192: no padded tap rows (five 128-tap tiles multiplied 640), 24 MFMAs per wave and barrier
-    if (cbf) {   // (two 16-k halves of a k-tile: one per wave group)
-      ProfScope ps(PC_CONVB_PW64_192, s, fl, by);
-      return launch_dma_cfg<64, 2, 192, true>(g, akc, bkc, s);
-    }
-    ProfScope ps(PC_CONV_PW64_192, s, fl, by);
-    return launch_dma_cfg<64, 2, 192>(g, akc, bkc, s);
-  }
-  if (tall > 2 && g.gather == 3 && g.N <= 64 && g.M % 256 == 0) {  // 64-channel weight gradients with whole 256-tap tiles
-    if (cbf) {
-      ProfScope ps(conv_pw_ok(g) ? PC_CONVB_PW64 : PC_CONVB_WG_TALL64, s, fl, by);
-      return launch_dma_cfg<64, 2, 256, true>(g, akc, bkc, s);
-    }
-    ProfScope ps(conv_pw_ok(g) ? PC_CONV_PW64 : PC_CONV_WG_TALL64, s, fl, by);
-    return launch_dma_cfg<64, 2, 256>(g, akc, bkc, s);
+  if (g.gather == 3 && g.N <= 64) {   // weight gradients: the tap tile of conv_wgrad_bm()
+    const int bm = conv_wgrad_bm(g.M);
+    const bool pw = conv_pw_ok(g);
+    if (g.N <= 32 && bm == CONV_BM_TALL)   // conv1: 32 output channels
+      return launch_conv_tile<32, 2, CONV_BM_TALL>(g, akc, bkc, s, pw ? PC_CONV_PW32 : PC_CONV_WG_TALL32,
+                                                   pw ? PC_CONVB_PW32 : PC_CONVB_WG_TALL32, fl, by);
+    // 576 taps = 3 x 192: 24 MFMAs per wave and barrier (bf16 inputs: two 16-k halves of a k-tile, one per wave group);
+    // the position-major reduction and a wide plain store only
+    if (g.N > 32 && bm == CONV_BM_192 && pw && dma_wide_store_ok(g) && g.epilogue == EPI_STORE)
+      return launch_conv_tile<64, 2, CONV_BM_192>(g, akc, bkc, s, PC_CONV_PW64_192, PC_CONVB_PW64_192, fl, by);
+    if (bm == CONV_BM_TALL)   // 64-channel weight gradients with whole 256-tap tiles
+      return launch_conv_tile<64, 2, CONV_BM_TALL>(g, akc, bkc, s, pw ? PC_CONV_PW64 : PC_CONV_WG_TALL64,
+                                                   pw ? PC_CONVB_PW64 : PC_CONVB_WG_TALL64, fl, by);
   }
   // a 128-wide grid that covers at most half the CUs (the 256 -> 128 env_mlp layer: 128 workgroups)
   // runs on 64-wide tiles instead: twice the workgroups, +1.2 % on the update.
@@ -1545,56 +1547,19 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   }
   const int lay = akc ? (bkc ? 0 : 1) : (bkc ? 3 : 2);
   ProfScope ps((bn == 128 ? PC_DMA_128_TT : PC_DMA_64_TT) + lay, s, fl, by);
-  if (bn == 128 && x3_mode() && !bf16_mode() && !g.gather && akc && bkc && g.K >= 256) {
-    // experiment: exact three-plane bf16 split (same tiles, loaders and epilogues; only the inner loop differs)
+  // the 128 x 128 two-stage tile with another inner loop (same tiles, loaders and epilogues): the exact three-plane bf16
+  // split (experiment), or the opt-in bf16-input mode
+  const bool x3 = bn == 128 && x3_mode() && !bf16_mode() && !g.gather && akc && bkc && g.K >= 256;
+  if (x3 || (bn == 128 && bf16_mode() && !g.gather && akc)) {
     const int n_tiles = (g.N + 127) / 128, m_tiles = (g.M + DMA_BM - 1) / DMA_BM;
     GemmArgs gg = g;
-    gg.wide_epi = aligned16(g.C) && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && (g.sCsplit & 3) == 0 && (g.N & 3) == 0 &&
-                  (!g.bias || (aligned16(g.bias) && (g.sBias & 3) == 0)) &&
-                  (!g.aux || (aligned16(g.aux) && (g.ldaux & 3) == 0 && (g.sAux & 3) == 0));
-    constexpr size_t ring = sizeof(float) * 2 * (DMA_BM + 128) * DMA_BK, epi = sizeof(float) * DMA_WAVES * 64 * (32 + 4);
-    constexpr size_t shm = ring > epi ? ring : epi;
+    gg.wide_epi = dma_wide_epi_ok(g);
+    constexpr size_t shm = DMA_SHM_128X2;
     const dim3 grid(n_tiles * m_tiles * g.nbatch * g.splitk);
-    static bool attr = false;
-    if (!attr) {
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_x3_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_dma_x3_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      if (e != hipSuccess) return e;
-      attr = true;
-    }
-    if (x3_mode() == 9) IGI_LAUNCH((gemm_dma_x3_kernel<9>), grid, dim3(DMA_THREADS), shm, s, gg, n_tiles, m_tiles);
-    else IGI_LAUNCH((gemm_dma_x3_kernel<6>), grid, dim3(DMA_THREADS), shm, s, gg, n_tiles, m_tiles);
-    return hipGetLastError();
-  }
-  if (bn == 128 && bf16_mode() && !g.gather && akc) {
-    // opt-in bf16-input mode: same tiles, same loaders, same epilogues
-    const int n_tiles = (g.N + 127) / 128, m_tiles = (g.M + DMA_BM - 1) / DMA_BM;
-    GemmArgs gg = g;
-    gg.wide_epi = aligned16(g.C) && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && (g.sCsplit & 3) == 0 && (g.N & 3) == 0 &&
-                  (!g.bias || (aligned16(g.bias) && (g.sBias & 3) == 0)) &&
-                  (!g.aux || (aligned16(g.aux) && (g.ldaux & 3) == 0 && (g.sAux & 3) == 0));
-    constexpr size_t ring = sizeof(float) * 2 * (DMA_BM + 128) * DMA_BK, epi = sizeof(float) * DMA_WAVES * 64 * (32 + 4);
-    constexpr size_t shm = ring > epi ? ring : epi;
-    const dim3 grid(n_tiles * m_tiles * g.nbatch * g.splitk);
-    if (bkc) {
-      static bool attr = false;
-      if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_bf16_kernel<true, true>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return e;
-        attr = true;
-      }
-      IGI_LAUNCH((gemm_dma_bf16_kernel<true, true>), grid, dim3(DMA_THREADS), shm, s, gg, n_tiles, m_tiles);
-    } else {
-      static bool attr = false;
-      if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_bf16_kernel<true, false>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return e;
-        attr = true;
-      }
-      IGI_LAUNCH((gemm_dma_bf16_kernel<true, false>), grid, dim3(DMA_THREADS), shm, s, gg, n_tiles, m_tiles);
-    }
+    if (x3 && x3_mode() == 9) IGI_DMA_LAUNCH_SHM((gemm_dma_x3_kernel<9>), grid, shm, shm, s, gg, n_tiles, m_tiles);
+    else if (x3) IGI_DMA_LAUNCH_SHM((gemm_dma_x3_kernel<6>), grid, shm, shm, s, gg, n_tiles, m_tiles);
+    else if (bkc) IGI_DMA_LAUNCH_SHM((gemm_dma_bf16_kernel<true, true>), grid, shm, shm, s, gg, n_tiles, m_tiles);
+    else IGI_DMA_LAUNCH_SHM((gemm_dma_bf16_kernel<true, false>), grid, shm, shm, s, gg, n_tiles, m_tiles);
     return hipGetLastError();
   }
   if (bn == 128) return launch_dma_cfg<128, 2>(g, akc, bkc, s);
@@ -1651,11 +1616,7 @@ static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, con
   for (int i = 0; i < count; ++i) {
     GemmArgs& g = list[i];
     if (g.M <= 0 || g.N <= 0) continue;
-    if (g.splitk < 1) g.splitk = 1;
-    if (g.splitk > 1 && g.kchunk <= 0) {
-      int c = (g.K + g.splitk - 1) / g.splitk;
-      g.kchunk = (c + DMA_BK - 1) / DMA_BK * DMA_BK;
-    }
+    dma_norm_splitk(g);
     if (!dma_eligible(g, false, false) || g.gather || mt_.n >= DMA_MULTI_MAX || g.epilogue != EPI_STORE) {
       hipError_t e = gemm(g, false, false, s);
       if (e != hipSuccess) return e;
@@ -1670,7 +1631,7 @@ static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, con
     const int nt = (g.N + bn - 1) / bn, mt = (g.M + bm - 1) / bm;
     const int tiles = nt * mt * g.nbatch * g.splitk;
     GemmArgs gg = g;
-    gg.wide_epi = aligned16(g.C) && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && (g.sCsplit & 3) == 0 && (g.N & 3) == 0;
+    gg.wide_epi = dma_wide_store_ok(g);
     dma_set_divs(gg, nt, mt);
     const int k = mt_.n++;
     mt_.g[k] = gg; mt_.n_tiles[k] = nt; mt_.m_tiles[k] = mt; mt_.kind[k] = n32 ? 3 : (bn == 64 ? 1 : 0);
@@ -1694,17 +1655,8 @@ static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, con
     mt_.g[l] = g0; mt_.n_tiles[l] = nt0; mt_.m_tiles[l] = mt0; mt_.kind[l] = k0;
     mt_.tile_end[l] = (l > 0 ? mt_.tile_end[l - 1] : 0) + t0;
   }
-  constexpr size_t ring = sizeof(float) * 2 * (DMA_BM + 128) * DMA_BK, epi = sizeof(float) * DMA_WAVES * 64 * (32 + 4);
-  constexpr size_t shm = ring > epi ? ring : epi;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_wgrad_multi_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
   ProfScope ps(PC_WGRAD_MULTI + (g_multi_level >= 0 && g_multi_level <= 5 ? g_multi_level : 4), s, fl, by);   // rocprofv3 reports one symbol; the class carries the level
-  IGI_LAUNCH(gemm_dma_wgrad_multi_kernel, dim3(mt_.tile_end[mt_.n - 1]), dim3(DMA_THREADS), shm, s, mt_);
+  IGI_DMA_LAUNCH_SHM(gemm_dma_wgrad_multi_kernel, dim3(mt_.tile_end[mt_.n - 1]), DMA_SHM_128X2, DMA_SHM_128X2, s, mt_);
   return hipGetLastError();
 }
 
@@ -1716,11 +1668,7 @@ static hipError_t gemm_wgrad_group(GemmArgs* list, int count, hipStream_t s) {
   for (int i = 0; i < count; ++i) {
     GemmArgs& g = list[i];
     if (g.M <= 0 || g.N <= 0) continue;
-    if (g.splitk < 1) g.splitk = 1;
-    if (g.splitk > 1 && g.kchunk <= 0) {
-      int c = (g.K + g.splitk - 1) / g.splitk;
-      g.kchunk = (c + DMA_BK - 1) / DMA_BK * DMA_BK;
-    }
+    dma_norm_splitk(g);
     const int bn = (g.N <= 64) ? 64 : 128;
     GemmGroup& G = grp[bn == 64 ? 1 : 0];
     if (!dma_eligible(g, false, false) || g.gather || G.n >= DMA_GROUP_MAX || g.epilogue != EPI_STORE) {
@@ -1731,7 +1679,7 @@ static hipError_t gemm_wgrad_group(GemmArgs* list, int count, hipStream_t s) {
     const int nt = (g.N + bn - 1) / bn, mt = (g.M + DMA_BM - 1) / DMA_BM;
     const int tiles = nt * mt * g.nbatch * g.splitk;
     GemmArgs gg = g;
-    gg.wide_epi = aligned16(g.C) && (g.ldc & 3) == 0 && (g.sC & 3) == 0 && (g.sCsplit & 3) == 0 && (g.N & 3) == 0;
+    gg.wide_epi = dma_wide_store_ok(g);
     dma_set_divs(gg, nt, mt);
     const int k = G.n++;
     G.g[k] = gg; G.n_tiles[k] = nt; G.m_tiles[k] = mt;
@@ -1740,31 +1688,15 @@ static hipError_t gemm_wgrad_group(GemmArgs* list, int count, hipStream_t s) {
     by[bn == 64 ? 1 : 0] += 4.0 * g.nbatch * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N * g.splitk);
   }
   if (grp[0].n > 0) {
-    constexpr size_t shm = sizeof(float) * DMA_WAVES * 64 * (32 + 4) > sizeof(float) * 2 * (DMA_BM + 128) * DMA_BK
-                               ? sizeof(float) * DMA_WAVES * 64 * (32 + 4) : sizeof(float) * 2 * (DMA_BM + 128) * DMA_BK;
-    static bool attr = false;
-    if (!attr) {
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_group_kernel<128, false, false, 2, true>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      if (e != hipSuccess) return e;
-      attr = true;
-    }
     ProfScope ps(PC_GROUP_128_FF, s, fl[0], by[0]);
-    IGI_LAUNCH((gemm_dma_group_kernel<128, false, false, 2, true>), dim3(grp[0].tile_end[grp[0].n - 1]),
-                       dim3(DMA_THREADS), shm, s, grp[0]);
+    IGI_DMA_LAUNCH_SHM((gemm_dma_group_kernel<128, false, false, 2, true>), dim3(grp[0].tile_end[grp[0].n - 1]),
+                       DMA_SHM_128X2, DMA_SHM_128X2, s, grp[0]);
   }
   if (grp[1].n > 0) {
     constexpr size_t shm = sizeof(float) * DMA_NS * (DMA_BM + 64) * DMA_BK;
-    static bool attr = false;
-    if (!attr) {
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_dma_group_kernel<64, false, false, DMA_NS>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      if (e != hipSuccess) return e;
-      attr = true;
-    }
     ProfScope ps(PC_GROUP_64_FF, s, fl[1], by[1]);
-    IGI_LAUNCH((gemm_dma_group_kernel<64, false, false, DMA_NS>), dim3(grp[1].tile_end[grp[1].n - 1]),
-                       dim3(DMA_THREADS), shm, s, grp[1]);
+    IGI_DMA_LAUNCH_SHM((gemm_dma_group_kernel<64, false, false, DMA_NS>), dim3(grp[1].tile_end[grp[1].n - 1]), shm, shm, s,
+                       grp[1]);
   }
   return hipGetLastError();
 }

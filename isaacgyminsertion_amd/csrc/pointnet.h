@@ -134,12 +134,6 @@ __device__ __forceinline__ void pn_fetch(PnStream& st, int B, int N, int ntiles,
   if (++st.tile == ntiles) { st.tile = 0; st.cloud += st.stride; st.base += cloud_step; }
 }
 
-// COLMAX (EXPERIMENT, IGI_PN_COLMAX=1, forward timing only -- VERDICT round 5 item 4(ii)): the running maximum per LANE
-// and accumulator (a v_max3 tree over the lane's 16 rows of a tile, one compare, two selects: 22 instead of 96 vector
-// instructions per tile) with only the TILE of the maximum recorded; the arg-max written is tile * 32 (the row inside the tile
-// would have to be resolved afterwards), so the backward must not be run on it.  It measures the most that variant could
-// gain in the forward before its resolve pass is paid for.
-template <bool COLMAX>
 __global__ __launch_bounds__(256, 2) void k_pointnet_fwd(const float* __restrict__ x, long long xpitch, int B,
                                                          const PnObjs o, float* __restrict__ y, long long ypitch,
                                                          int* __restrict__ argmax) {
@@ -229,8 +223,6 @@ __global__ __launch_bounds__(256, 2) void k_pointnet_fwd(const float* __restrict
     unsigned bt0[4] = {0u, 0u, 0u, 0u}, bt1[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int r = 0; r < 16; ++r) { bv0[r] = -INFINITY; bv1[r] = -INFINITY; }
-    float cm0 = -INFINITY, cm1 = -INFINITY;   // COLMAX: the lane's running maximum per accumulator and its tile
-    int ct0 = 0, ct1 = 0;
     for (int rt = 0; rt < ntiles; ++rt) {
       // the whole A fragment of this tile first (32 reads in flight; read next to their MFMAs they are reloaded into
       // one register pair and every fourth MFMA waits a full LDS latency), the production below hides the latency
@@ -261,19 +253,7 @@ __global__ __launch_bounds__(256, 2) void k_pointnet_fwd(const float* __restrict
           acc1[r] = in ? acc1[r] : -INFINITY;
         }
       }
-      if constexpr (COLMAX) {
-        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
-        auto tree = [](const f32x16& a) {
-          float m = __builtin_fmaxf(__builtin_fmaxf(a[0], a[1]), a[2]);
-#pragma unroll
-          for (int r = 3; r + 1 < 16; r += 2) m = __builtin_fmaxf(__builtin_fmaxf(m, a[r]), a[r + 1]);
-          return __builtin_fmaxf(m, a[15]);
-        };
-        const float m0 = tree(acc0), m1 = tree(acc1);
-        const bool u0 = m0 > cm0, u1 = m1 > cm1;     // strict: the first tile keeps a tie
-        cm0 = u0 ? m0 : cm0; ct0 = u0 ? rt : ct0;
-        cm1 = u1 ? m1 : cm1; ct1 = u1 ? rt : ct1;
-      } else {
+      {
         // strict '>' keeps the first tile of a slot's maximum.  Three instructions per element -- compare, select the
         // value, select the tile number into its byte (SDWA: the other three bytes of the word are preserved); the
         // compiler's form (compare, bit-field insert, two selects) takes four and keeps 32 compare masks in SGPR pairs,
@@ -305,8 +285,6 @@ __global__ __launch_bounds__(256, 2) void k_pointnet_fwd(const float* __restrict
     // merge the slots (rows ascend with r inside a tile): the first maximum in point order
     float best0 = -INFINITY, best1 = -INFINITY;
     int bi0 = 0, bi1 = 0;
-    if constexpr (COLMAX) { best0 = cm0; best1 = cm1; bi0 = ct0 * 32; bi1 = ct1 * 32; }
-    else
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int ro = (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -463,12 +441,6 @@ __global__ __launch_bounds__(PNB_THREADS) void k_pointnet_bwd(const float* __res
 }
 
 static inline int pn_blocks(int64_t B) { return (int)(B < PN_BLOCKS ? B : PN_BLOCKS); }
-// IGI_PN_COLMAX=1: the column-level running maximum (forward timing experiment: its arg-max is the TILE only, see the kernel)
-static inline bool pn_colmax_experiment() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("IGI_PN_COLMAX"); on = e ? atoi(e) != 0 : 0; }
-  return on != 0;
-}
 // workgroups per object: the chip's slots (512 forward: two per CU; 256 backward: one per CU) shared by the objects
 static inline int pn_blocks_multi(int64_t B, int nobj, int total) {
   int64_t per = total / (nobj > 0 ? nobj : 1);
@@ -510,8 +482,7 @@ static int pointnet_forward(const float* x, int64_t x_pitch, int64_t B, int N, c
     // algorithmic: 2 * (3*64 + 64*256) flop per point; 12 B/point in, 256 values + 256 indices per cloud out
     ProfScope ps(PC_POINTNET_FWD, s, 2.0 * (PN_IN * PN_H + PN_H * PN_OUT) * (double)B * N,
                  12.0 * (double)B * N + 8.0 * PN_OUT * (double)B);
-    if (pn_colmax_experiment()) IGI_LAUNCH(k_pointnet_fwd<true>, dim3(o.bpo), dim3(256), 0, s, x, (long long)x_pitch, (int)B, o, y, (long long)PN_OUT, argmax);
-    else IGI_LAUNCH(k_pointnet_fwd<false>, dim3(o.bpo), dim3(256), 0, s, x, (long long)x_pitch, (int)B, o, y, (long long)PN_OUT, argmax);
+    IGI_LAUNCH(k_pointnet_fwd, dim3(o.bpo), dim3(256), 0, s, x, (long long)x_pitch, (int)B, o, y, (long long)PN_OUT, argmax);
   }
   return (int)hipGetLastError();
 }
@@ -529,17 +500,14 @@ static int pointnet_forward_multi(int nobj, const float* x, int64_t x_pitch, int
   for (int i = 0; i < nobj; ++i) pts += (double)B * N[i];
   {
     ProfScope ps(PC_POINTNET_FWD, s, 2.0 * (PN_IN * PN_H + PN_H * PN_OUT) * pts, 12.0 * pts + 8.0 * PN_OUT * (double)B * nobj);
-    if (pn_colmax_experiment()) IGI_LAUNCH(k_pointnet_fwd<true>, dim3(o.bpo * nobj), dim3(256), 0, s, x, (long long)x_pitch, (int)B, o, y,
-                                           (long long)PN_OUT * nobj, argmax);
-    else IGI_LAUNCH(k_pointnet_fwd<false>, dim3(o.bpo * nobj), dim3(256), 0, s, x, (long long)x_pitch, (int)B, o, y,
-                    (long long)PN_OUT * nobj, argmax);
+    IGI_LAUNCH(k_pointnet_fwd, dim3(o.bpo * nobj), dim3(256), 0, s, x, (long long)x_pitch, (int)B, o, y,
+               (long long)PN_OUT * nobj, argmax);
   }
   return (int)hipGetLastError();
 }
 
 static int pn_backward_launch(const float* x, int64_t x_pitch, int64_t B, const PnObjs& o, const float* dy, int64_t dy_pitch,
                               const int* argmax, int64_t i_pitch, float* grads, void* ws, hipStream_t s) {
-  if (pn_colmax_experiment() && !getenv("IGI_PN_COLMAX_TIMING")) return IGI_E_UNSUPPORTED;   // its arg-max is the tile only: timing runs say so explicitly
   const int nb = o.bpo;
   const size_t shm = sizeof(float) * (PN_H * PN_OUT + PNB_Q * 16 * PN_OUT + PN_H + PN_OUT * 4 + 4 * PN_H);
   static bool attr = false;

@@ -92,13 +92,6 @@ static inline bool policy_fwd_shape_ok(int obs, int priv, int act, int npl, cons
          u[2] == 128 && obs >= 1 && xw > obs && xw <= 32 && act >= 1 && act <= 7;
 }
 
-// IGI_POLICY_FUSED=0: the layer-by-layer policy step (A/B)
-static inline bool policy_fwd_enabled() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("IGI_POLICY_FUSED"); on = e ? atoi(e) != 0 : 1; }
-  return on != 0;
-}
-
 // float index of accumulator element r of a lane in a k-contiguous swizzled [32][32] image: see env_img_bases (env_mlp.h)
 __device__ __forceinline__ void pf_img_bases(int l31, int h, int (&ib)[4]) {
   const int sk[4] = {0, 1, 4, 5};

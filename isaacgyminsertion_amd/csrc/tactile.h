@@ -100,28 +100,12 @@ static int make_tactile_plan(const igi_tactile_cfg* c, TactilePlan* p) {
     return (s2 > sk && K / s2 >= 32LL * DMA_BK) ? s2 : sk;
   };
   p->sk1 = two_per_cu(dma_choose_splitk(256, TC_C1, (int)p->M1, 1), p->M1, 1);
-  {
-    static int tall = -1;
-    if (tall < 0) { const char* e = getenv("IGI_CONV_TALL"); tall = e ? atoi(e) : 3; }
-    p->sk2 = two_per_cu(dma_choose_splitk(512, TC_C2, (int)p->M2, 1, tall > 2 ? 256 : DMA_BM), p->M2, tall > 2 ? 2 : 4);
-  }
-  {
-    // (576 taps: three 192-tap tiles when gemm() will take them -- whole groups of 32 images, see conv_pw_ok -- else five
-    // 128-tap tiles)
-    static int tall = -1;
-    if (tall < 0) { const char* e = getenv("IGI_CONV_TALL"); tall = e ? atoi(e) : 3; }
-    const bool t192 = tall > 2 && conv_bm192_on() && (p->B % 32) == 0;
-    p->sk3 = two_per_cu(dma_choose_splitk(576, TC_C3, (int)p->M3, 1, t192 ? 192 : DMA_BM), p->M3, t192 ? 3 : 5);
-  }
+  // conv2 and conv3 on the tap tiles gemm() takes for them (conv_wgrad_bm): two of 256 taps, three of 192 -- the batch is
+  // whole groups of 32 images (checked above), which is what conv_pw_ok asks of the 192-tap tile
+  constexpr int bm2 = conv_wgrad_bm(512), bm3 = conv_wgrad_bm(576);
+  p->sk2 = two_per_cu(dma_choose_splitk(512, TC_C2, (int)p->M2, 1, bm2), p->M2, 512 / bm2);
+  p->sk3 = two_per_cu(dma_choose_splitk(576, TC_C3, (int)p->M3, 1, bm3), p->M3, 576 / bm3);
   p->skf = dma_choose_splitk(p->L, 128, p->B, 1);
-  if (const char* e = getenv("IGI_TAC_SK")) {   // "s1,s2,s3" (0 = keep): split factors of the three weight gradients, for A/B runs
-    int v[3] = {0, 0, 0}, i = 0;
-    for (const char* q = e; *q && i < 3; ++i) { v[i] = atoi(q); while (*q && *q != ',') ++q; if (*q == ',') ++q; }
-    auto cap = [](int sk, long long rows) { const long long m = rows / 128 > 1 ? rows / 128 : 1; return (int)(sk > m ? m : sk); };
-    if (v[0] > 0) p->sk1 = cap(v[0], p->M1);
-    if (v[1] > 0) p->sk2 = cap(v[1], p->M2);
-    if (v[2] > 0) p->sk3 = cap(v[2], p->M3);
-  }
   long long s = 0;
   p->s_w1 = s; s += (long long)p->sk1 * TC_C1 * 256;
   p->s_b1 = s; s += (long long)p->sk1 * TC_C1;
@@ -584,10 +568,9 @@ static int tactile_backward(const igi_tactile_cfg* c, const float* dy, const flo
   add(grads, p.o_bf, slab + p.s_bf, p.L, p.L, p.skf);
   {
     // hundreds of partials per element at bench scale (the convolutions' reductions run over millions of rows): 64
-    // blocks per segment left the sum on a quarter of the chip (125 us at 8192 images); IGI_TAC_RED_GX blocks per segment
-    static int gx = -1;
-    if (gx < 0) { const char* e = getenv("IGI_TAC_RED_GX"); gx = e ? atoi(e) : 256; if (gx < 1) gx = 1; }
-    hipLaunchKernelGGL(k_slab_reduce, dim3(gx, t.n), dim3(RED_THREADS), 0, s, t, grads);
+    // blocks per segment left the sum on a quarter of the chip (125 us at 8192 images); one block per CU and segment
+    constexpr int RED_GX = 256;
+    hipLaunchKernelGGL(k_slab_reduce, dim3(RED_GX, t.n), dim3(RED_THREADS), 0, s, t, grads);
   }
   {
     ConvWJobs ju;

@@ -2554,7 +2554,7 @@ static int teacher_policy_step(const igi_teacher_cfg* c, const igi_teacher_state
       IGI_LAUNCH(k_policy_stage, dim3(nb + pad_blocks), dim3(256), 0, s, a);
     }
     // (the persistent kernel assigns one net per workgroup pair: a shared trunk takes the per-layer launches)
-    if (p.nets == 2 && policy_fwd_enabled() && !bf16_mode() && policy_fwd_shape_ok(p.obs, p.priv, p.act, p.npl, p.pu, p.nl, p.u, p.xw) && p.xld == 32) {
+    if (p.nets == 2 && !bf16_mode() && policy_fwd_shape_ok(p.obs, p.priv, p.act, p.npl, p.pu, p.nl, p.u, p.xw) && p.xld == 32) {
       // env_mlp, the contact encoder, both trunks, the heads, the sample and the arena writes (the step's raw contacts
       // among them) of these rows as ONE persistent launch (policy_fwd.h)
       PolicyFwdArgs f;
@@ -2645,7 +2645,7 @@ static int teacher_actor_latent_forward(const igi_teacher_cfg* c, const igi_teac
                p.u0p, p.xw, p.xld, w1p, p.nets);
   }
   // (no nets == 2 term: the kernel runs the actor alone, a shared trunk's included)
-  const bool fused = policy_fwd_enabled() && !bf16_mode() && actor_latent_shape_ok(p.obs, L, p.act, p.nl, p.u) && p.xld == 32;
+  const bool fused = !bf16_mode() && actor_latent_shape_ok(p.obs, L, p.act, p.nl, p.u) && p.xld == 32;
   for (int64_t r0 = 0; r0 < rows; r0 += p.mb) {
     const int nr = (int)((rows - r0 < p.mb) ? rows - r0 : p.mb);
     float* hs = hsave ? hsave + r0 * S : nullptr;

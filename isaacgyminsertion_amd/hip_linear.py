@@ -49,28 +49,6 @@ class HipLinear(nn.Linear):
         return super().extra_repr() + (f", act={self.act}" if self.act else "")
 
 
-def _chain_enabled():
-    """IGI_MLP_CHAIN=0: every layer under its own autograd node (A/B; read once)"""
-    global _CHAIN
-    if _CHAIN is None:
-        import os
-        _CHAIN = os.environ.get("IGI_MLP_CHAIN", "1") != "0"
-    return _CHAIN
-
-
-_CHAIN = None
-_FWD_FUSED = None
-
-
-def _fwd_fused():
-    """IGI_MLP_FWD_FUSED=0: the chain's forward as one launch per layer (A/B; read once)"""
-    global _FWD_FUSED
-    if _FWD_FUSED is None:
-        import os
-        _FWD_FUSED = os.environ.get("IGI_MLP_FWD_FUSED", "1") != "0"
-    return _FWD_FUSED
-
-
 class _MlpChain(torch.autograd.Function):
     """A chain of Linear (+ fused activation) layers: the forward is ONE launch (torch.ops.mi355ppo.mlp_fwd -> igi_mlp_forward:
     32 rows per workgroup through every layer, hidden activations in LDS; layers wider than 256 outputs: one
@@ -83,7 +61,7 @@ class _MlpChain(torch.autograd.Function):
     def forward(ctx, x, acts, *wb):
         n = len(acts)
         ws, bs = wb[:n], wb[n:]
-        if _fwd_fused() and x.shape[0] <= 8192 and all(w.shape[0] <= 256 for w in ws) and \
+        if x.shape[0] <= 8192 and all(w.shape[0] <= 256 for w in ws) and \
                 sum((w.shape[1] + 63) // 64 for w in ws) <= 40:   # (beyond one wave of 32-row workgroups the per-layer launches are faster: 75 vs 54 us at 16384 rows)
             ys = torch.ops.mi355ppo.mlp_fwd(x, list(ws), list(bs), list(acts))    # one launch for the whole chain
             h = ys[-1]
@@ -145,7 +123,7 @@ def mlp_chain(x, layers):
         return x
     if not x.is_cuda:
         raise RuntimeError("mlp_chain runs on the HIP device only (no CPU fallback)")
-    if len(layers) == 1 or len(layers) > 8 or any(m.bias is None for m in layers) or not _chain_enabled():
+    if len(layers) == 1 or len(layers) > 8 or any(m.bias is None for m in layers):
         for m in layers:
             x = m(x)
         return x

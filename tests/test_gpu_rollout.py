@@ -220,16 +220,11 @@ def test_fused_policy_step_equals_infer_plus_act_store():
             classes = {c["name"]: c["launches"] for c in _lib.prof_read()}
         finally:
             _lib.prof_enable(False)
-        import os
-        fused = os.environ.get("IGI_POLICY_FUSED", "1") != "0"
-        assert classes.get("k_policy_fwd", 0) == (1 if fused else 0), classes
+        assert classes.get("k_policy_fwd", 0) == 1, classes
         for k in ("obses", "priv", "sigmas"):
             assert torch.equal(a[k], b[k]), (N, k)
         for k in ("mus", "actions", "clamped", "values", "vout"):
-            if fused:
-                np.testing.assert_allclose(b[k].cpu().numpy(), a[k].cpu().numpy(), atol=2e-6, rtol=2e-6, err_msg=f"{N} {k}")
-            else:
-                assert torch.equal(a[k], b[k]), (N, k, float((a[k] - b[k]).abs().max()))
+            np.testing.assert_allclose(b[k].cpu().numpy(), a[k].cpu().numpy(), atol=2e-6, rtol=2e-6, err_msg=f"{N} {k}")
         np.testing.assert_allclose(b["nlp"].cpu().numpy(), a["nlp"].cpu().numpy(), rtol=2e-5, atol=2e-5, err_msg=f"{N} nlp")
         assert torch.isfinite(b["nlp"]).all() and float(b["actions"].abs().max()) > 0
 
@@ -272,8 +267,7 @@ def test_persistent_policy_kernel_on_other_widths_and_ragged_row_counts(N, obs_d
         classes = {c["name"]: c["launches"] for c in _lib.prof_read()}
     finally:
         _lib.prof_enable(False)
-    if os.environ.get("IGI_POLICY_FUSED", "1") != "0":
-        assert classes.get("k_policy_fwd", 0) == 1, classes
+    assert classes.get("k_policy_fwd", 0) == 1, classes
     for k in ("obses", "priv", "sigmas"):
         assert torch.equal(a[k], b[k]), k
     for k in ("mus", "actions", "clamped", "values", "vout"):

@@ -18,7 +18,6 @@ pytestmark = pytest.mark.gpu
 PRIV = 64
 UNITS, PRIV_UNITS = [512, 256, 128], [256, 128, 8]
 HERE = os.path.dirname(os.path.abspath(__file__))
-FUSED = os.environ.get("IGI_POLICY_FUSED", "1") != "0"
 
 
 def _classes(fn):
@@ -141,9 +140,8 @@ def test_fused_contact_step_matches_float64_and_the_layerwise_ops(rows, obs_dim,
                                          a["clamped"], a["vout"])
     classes = _classes(lambda: _step(eng, d, b, rms_v))
     chunks = (rows + eng.mb - 1) // eng.mb
-    if FUSED:
-        assert classes.get("k_policy_fwd", 0) == chunks and classes.get("other", 0) == chunks, classes
-        assert set(classes) == {"k_policy_fwd", "other"}, classes
+    assert classes.get("k_policy_fwd", 0) == chunks and classes.get("other", 0) == chunks, classes
+    assert set(classes) == {"k_policy_fwd", "other"}, classes
     # the arena slot: raw copies
     assert torch.equal(b["obses"].cpu(), x["obs"]) and torch.equal(b["priv"].cpu(), x["priv"])
     assert torch.equal(b["contacts"].cpu(), x["contacts"])
@@ -181,8 +179,7 @@ def test_the_teacher_without_contacts_still_takes_one_persistent_launch():
     rms_v = torch.tensor(RMS_V, dtype=torch.float64, device="cuda:0")
     o = _outs(rows, obs_dim, act, 0)
     classes = _classes(lambda: _step(eng, d, o, rms_v))
-    if FUSED:
-        assert classes == {"k_policy_fwd": 1, "other": 1}, classes
+    assert classes == {"k_policy_fwd": 1, "other": 1}, classes
     _assert_f64(o, ref())
 
 
@@ -209,8 +206,7 @@ def test_contact_policy_step_matches_reference_at_the_default_network(tag):
              noise=torch.from_numpy(G[f"{tag}/in/noise"]).cuda())
     o = _outs(N, 15, 6, P)
     classes = _classes(lambda: _step(eng, d, o, rms_v))
-    if FUSED:
-        assert classes == {"k_policy_fwd": 1, "other": 1}, classes
+    assert classes == {"k_policy_fwd": 1, "other": 1}, classes
     assert torch.equal(o["contacts"], d["contacts"])
     for k, gk, atol in (("mus", "mus", 2e-5), ("sigmas", "sigmas", 1e-6), ("actions", "actions", 2e-5),
                         ("values", "values", 2e-5), ("nlp", "neglogpacs", 5e-5)):
@@ -262,5 +258,4 @@ def test_ppo_play_steps_with_contacts_runs_the_persistent_kernel():
     assert torch.equal(stored[0], first)
     for t in range(1, T):
         assert torch.equal(stored[t], seen[t - 1]), t
-    if FUSED:
-        assert launches == list(range(1, T + 1)), launches
+    assert launches == list(range(1, T + 1)), launches

@@ -375,9 +375,8 @@ def _student_full_update_vs_oracle(config, envs, hw, label, os_):
     assert classes.get(TALL_FWD_64) == steps and classes.get(TALL_FWD_SSA) == steps and classes.get(PM_DGRAD_64) == steps, classes
     assert classes.get(WGRAD_192) == steps, classes
     if config == 4:
-        # plug + socket in ONE forward and ONE backward launch per step (round 6: igi_pointnet_forward_multi / _backward_multi);
-        # IGI_PCL_ONE_LAUNCH=0: one per object
-        per = 1 if os.environ.get("IGI_PCL_ONE_LAUNCH", "1") != "0" else 2
+        # plug + socket in ONE forward and ONE backward launch per step (round 6: igi_pointnet_forward_multi / _backward_multi)
+        per = 1
         assert classes.get("k_pointnet_fwd") == per * steps and classes.get("k_pointnet_bwd") == per * steps, classes
     names = [k for k, g in g64.items() if g is not None and float(g.abs().max()) > 0]
     assert len(names) >= 30 and set(names) <= set(got), set(names) - set(got)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# same-box A/B of environment switches on the student legs: ab_student.sh "IGI_MLP_CHAIN=0" "IGI_MLP_CHAIN=1" ...
+# same-box A/B of environment switches on the student legs: ab_student.sh "IGI_TOKEN_FUSED=0" "IGI_TOKEN_FUSED=1" ...
 cd "$(dirname "$0")/../.."
 for setting in "$@"; do
   for leg in "4 512 32 64" "3 2048 32 64"; do

@@ -1,12 +1,7 @@
-"""(IGI_PN_COLMAX=1: the column-level running-maximum EXPERIMENT -- forward times only are meaningful, see csrc/pointnet.h.)
-PointNet forward / backward launch times at the configs[3] per-rank size (2048 clouds x 400 points) and at 8192: the
+"""PointNet forward / backward launch times at the configs[3] per-rank size (2048 clouds x 400 points) and at 8192: the
 mean of 50 launches between two stream events, with the algorithmic rate (2 * (3*64 + 64*256) flop per point forward)."""
 import json
-import os
 import sys
-
-if os.environ.get("IGI_PN_COLMAX", "0") != "0":
-    os.environ["IGI_PN_COLMAX_TIMING"] = "1"      # the backward is timed on the experiment's (tile-only) arg-max: timing only
 
 import torch
 
