@@ -739,6 +739,27 @@ int igi_cat_cols(int n, const float* const* part, const int64_t* width, float* c
                  igi_stream_t stream);
 int igi_split_cols(int n, float* const* part, const int64_t* width, const float* cat, int64_t rows, igi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Train-time augmentation of the offline student's camera pair (csrc/augment.h), ONE launch from the resident arenas to
+ * the two batch tensors (SyncTransform of algo/models/transformer/utils.py:85-128 over a minibatch):
+ *   img, seg  : fp32 [n][t][hs][ws] depth frames and segmentation masks
+ *   rows      : [b] sample numbers; one outside [0, n) reads as a frame of zeros (never outside the arena)
+ *   offsets   : [b][2] (top, left) of the crop window, shared by a sample's t frames and by both tensors; any value is
+ *               allowed, a read outside the stored frame gives 0
+ *   angles    : [b][2] radians, column 0 rotates the depth frames, column 1 the masks, about the centre of the cropped
+ *               window: nearest resampling (round half to even), zero fill outside the WINDOW; angle 0 is a plain copy
+ *   keep      : uint8 [b*t][out_h / patch][out_w / patch] or NULL; 0 zeroes that patch of the depth frame only; rows and
+ *               columns past the last whole patch are untouched
+ *   noise_std : > 0 adds noise_std * z to both outputs, z = sqrt(-2 ln u1) cos(2 pi u2), u1 = ((h1 >> 8) + 1/2) 2^-24,
+ *               u2 = (h2 >> 8) 2^-24, h1 / h2 = the token encoder's counter hash of (seed, 2 p / 2 p + 1, e): p = 0 depth,
+ *               1 mask, e = the element's linear index in its output tensor.  A pure function: same arguments, same bits
+ *   out_img, out_seg : fp32 [b][t][out_h][out_w], out_h <= hs, out_w <= ws
+ * ---------------------------------------------------------------------------------------- */
+int igi_image_pair_augment(const float* img, const float* seg, int64_t n, int t, int hs, int ws, const int64_t* rows,
+                           int64_t b, const int32_t* offsets, const float* angles, const uint8_t* keep, int out_h,
+                           int out_w, int patch, float noise_std, uint64_t seed, float* out_img, float* out_seg,
+                           igi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

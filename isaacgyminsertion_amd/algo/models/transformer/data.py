@@ -383,22 +383,30 @@ class ResidentLoader:
     then every epoch is a ``randperm`` + row gathers on the GPU.  Iterates like the reference's
     ``DataLoader(ds, batch_size, shuffle=True)`` (runner.py:524-551): same 8-tuple per batch, last
     partial batch kept; ``len()`` = number of batches.  ``tactile_transform`` (train-time augmentation)
-    is applied per batch on the device."""
+    is applied per batch on the device.  ``sync_transform`` (utils.SyncTransform / SyncEvalTransform): the camera pair
+    (fields 1 and 2) is stored as logged and every batch of it is ONE ``sync_transform.fused`` launch -- gather, crop,
+    rotation, noise, patch masking -- instead of two ``index_select``s; its random numbers come from ``generator``."""
 
-    def __init__(self, dataset, batch_size, shuffle=True, device='cuda', generator=None, tactile_transform=None):
+    def __init__(self, dataset, batch_size, shuffle=True, device='cuda', generator=None, tactile_transform=None,
+                 sync_transform=None):
         self.batch_size, self.shuffle, self.device = int(batch_size), shuffle, device
         self.generator = generator
         self.tactile_transform = tactile_transform
+        self.sync_transform = sync_transform
         n = len(dataset)
         self.n = n
         if n == 0:
             self.fields = None
             return
         saved, dataset.tactile_transform = dataset.tactile_transform, None
+        if sync_transform is not None:                       # the arenas hold the logged frames: the transform runs per batch
+            saved_sync, dataset.sync_transform = dataset.sync_transform, None
         try:
             items = [dataset[i] for i in range(n)]
         finally:
             dataset.tactile_transform = saved
+            if sync_transform is not None:
+                dataset.sync_transform = saved_sync
         self.fields = []
         for j in range(8):
             col = [it[j] for it in items]
@@ -420,9 +428,15 @@ class ResidentLoader:
         for s in range(0, self.n, self.batch_size):
             idx = order[s:s + self.batch_size]
             batch = []
+            pair = None
+            if self.sync_transform is not None and self.fields[1] is not None and self.fields[2] is not None:
+                pair = self.sync_transform.fused(self.fields[1], self.fields[2], idx, self.generator)
             for j, f in enumerate(self.fields):
                 if f is None:
                     batch.append(torch.zeros(idx.numel(), 1, device=self.device))
+                    continue
+                if pair is not None and j in (1, 2):
+                    batch.append(pair[j - 1])
                     continue
                 x = f.index_select(0, idx)
                 if j == 0 and self.tactile_transform is not None:

@@ -31,7 +31,8 @@ from .... import ops
 from ....optim import FlatAdam
 from .data import DataNormalizer, ResidentLoader, TactileDataset
 from .tact import MultiModalModel
-from .utils import TactileTransform, define_tactile_transforms, log_output
+from .utils import (SyncCenterReshapeTransform, TactileTransform, define_img_transforms, define_tactile_transforms,
+                    log_output)
 
 
 class _Schedule:
@@ -90,7 +91,8 @@ class Runner:
         self.init_model()
 
     def _init_transforms(self):
-        """runner.py:150-192, tactile part (img / seg transforms belong to the depth branch)."""
+        """runner.py:150-192.  Camera keys beyond the sizes -- img_patch_size / img_gaussian_noise / img_masking_prob and
+        img_rotation_deg (ours; the reference hard-codes 1 degree) -- default to 16 / 0 / 0 / 0."""
         self.num_fingers = 3
         self.tactile_channel = 1 if self.cfg.tactile_type == "gray" else 3
         self.tactile_color_jitter = self.cfg.get('tactile_color_jitter', False)
@@ -104,14 +106,25 @@ class Runner:
             self.cfg.get('tactile_masking_prob', 0.0))
         self.process_tactile = TactileTransform(self.tactile_transform)
         self.eval_process_tactile = TactileTransform(self.tactile_eval_transform)
-        # external camera (runner.py:152-173): sizes only; the eval pipeline (centre crop to the crop size, resize
-        # to (img_width, img_height), centre crop) is the identity when nothing is cropped
+        # external camera (runner.py:152-173)
         self.img_channel = 1 if self.cfg.get('img_type', 'depth') == "depth" else 3
         self.img_width, self.img_height = self.cfg.get('img_width', 54), self.cfg.get('img_height', 96)
         self.crop_img_width = self.img_width - self.cfg.get('img_crop_w', 0)
         self.crop_img_height = self.img_height - self.cfg.get('img_crop_h', 0)
-        self.img_transform = self.seg_transform = self.sync_transform = None
-        self.img_eval_transform = self.sync_eval_transform = None
+        (self.img_transform, self.seg_transform, self.img_eval_transform, self.sync_transform,
+         self.sync_eval_transform) = define_img_transforms(
+            self.img_width, self.img_height, self.crop_img_width, self.crop_img_height,
+            self.cfg.get('img_patch_size', 16), self.cfg.get('img_gaussian_noise', 0.0),
+            self.cfg.get('img_masking_prob', 0.0), self.cfg.get('img_rotation_deg', 0.0))
+        # frames arrive from the environment at the cropped size (runner.py:416-423): the centre crop is then the identity
+        self.sync_eval_reshape_transform = SyncCenterReshapeTransform((self.crop_img_width, self.crop_img_height),
+                                                                      None, None)
+        # default-off: with nothing cropped, rotated, noised or masked every stage is the identity -- no transform object,
+        # the loaders gather the logged frames as they are and torch's generator is never asked
+        if self.sync_transform.is_identity:
+            self.sync_transform = None
+        if self.sync_eval_transform.is_identity:
+            self.sync_eval_transform = None
 
     def init_model(self):
         """runner.py:78-148 (model_type 'tact')."""
@@ -162,11 +175,14 @@ class Runner:
                                           self.crop_tactile_height)
         img, seg = obs_dict.get('img'), obs_dict.get('seg')
         if self.cfg.model.use_img or self.cfg.model.use_seg:
-            if (self.crop_img_width, self.crop_img_height) != (self.img_width, self.img_height):
+            cropped = (self.crop_img_width, self.crop_img_height) != (self.img_width, self.img_height)
+            if cropped and (self.crop_img_width, self.crop_img_height) != (54, 96):     # the depth backbone's input
                 raise NotImplementedError("cropped camera images (img_crop_w/h > 0) are not built")
             shp = (1, self.crop_img_width, self.crop_img_height)        # (B, T, H*W) -> (B, T, C, W, H), runner.py:419-424
             img = img.to(self.device).reshape(*img.shape[:2], *shp) if img is not None else None
             seg = seg.to(self.device).reshape(*seg.shape[:2], *shp) if seg is not None else None
+            if cropped and img is not None and seg is not None:
+                img, seg = self.sync_eval_reshape_transform(img, seg)                      # runner.py:423
         if self.cfg.model.use_lin:
             student_obs = student_obs.to(self.device)
         if self.cfg.model.use_pcl:
@@ -275,7 +291,9 @@ class Runner:
         tf = (self.tactile_transform if train else self.tactile_eval_transform) if self.cfg.model.use_tactile else None
         if tf is not None:
             tf.to(self.device)
-        return ResidentLoader(ds, batch_size, shuffle=True, device=self.device, tactile_transform=tf)
+        sync = (self.sync_transform if train else self.sync_eval_transform) \
+            if (self.cfg.model.use_img or self.cfg.model.use_seg) else None      # the dataset loads the pair for either
+        return ResidentLoader(ds, batch_size, shuffle=True, device=self.device, tactile_transform=tf, sync_transform=sync)
 
     def run_train(self, file_list, save_folder, epochs=100, train_test_split=0.9, train_batch_size=32,
                   val_batch_size=32, learning_rate=1e-4, device='cuda:0', print_every=50, eval_every=250,

@@ -11,6 +11,12 @@ device the batch lives on:
     p 0.3, 5x5 Gaussian blur sigma in (0.01, 0.1) with p 0.5, rotation <= 3 degrees with p 0.5) --
     same distributions, drawn per image from torch's generator; not sample-identical to torchvision's RNG
     stream (no parity claim is made on augmented samples).
+
+Camera pair (depth frames + segmentation masks; utils.py:12-128, 280-322, 422-454): ``define_img_transforms`` ->
+(transform, mask_transform, eval_transform, sync_transform, sync_eval_transform), ``ImageTransform``, ``SyncTransform``,
+``SyncEvalTransform``, ``SyncCenterReshapeTransform``, ``SyncRandomCrop``, ``SyncCenterCrop``.  Called on tensors they
+are torch ops on any device; ``SyncTransform.fused`` builds a minibatch from the resident arenas in one native launch
+(csrc/augment.h).  DESIGN.md section 4 has the parameter contract and the two evaluation-side deviations.
 """
 import math
 import os
@@ -20,6 +26,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from .... import ops  # noqa: F401  (registers torch.ops.mi355ppo)
 
 
 class GaussianNoise(nn.Module):
@@ -132,6 +140,289 @@ def define_tactile_transforms(width, height, crop_width, crop_height, img_patch_
     eval_transform = nn.Sequential(_Resize((width, height)), _Crop((crop_width, crop_height), False))
     eval_transform.eval()
     return transform, eval_transform
+
+
+# ---------------------------------------------------------------------------------------------
+# camera pair: depth frames + segmentation masks (utils.py:12-128, 280-322, 422-454)
+# ---------------------------------------------------------------------------------------------
+def _center_offsets(h, w, ch, cw):
+    return int(round((h - ch) / 2.0)), int(round((w - cw) / 2.0))
+
+
+def _center_crop(x, size):
+    ch, cw = size
+    h, w = x.shape[-2:]
+    if (h, w) == (ch, cw):
+        return x
+    top, left = _center_offsets(h, w, ch, cw)
+    return x[..., top:top + ch, left:left + cw]
+
+
+def _rotate(x, ang):
+    """(n, C, H, W) rotated about the image centre by ``ang`` (n,) radians: nearest resampling, zero fill (torchvision's
+    defaults) -- the arithmetic of ``_TrainAugment`` above, and the one csrc/augment.h restates per pixel."""
+    cos, sin = torch.cos(ang), torch.sin(ang)
+    H, W = x.shape[-2:]
+    zero = torch.zeros_like(cos)
+    theta = torch.stack([torch.stack([cos, -sin * H / W, zero], 1), torch.stack([sin * W / H, cos, zero], 1)], 1)
+    grid = F.affine_grid(theta.to(x.dtype), list(x.shape), align_corners=False)
+    return F.grid_sample(x, grid, mode='nearest', padding_mode='zeros', align_corners=False)
+
+
+class _RandomRotation(nn.Module):
+    """v2.RandomRotation(degrees): ONE angle per call, uniform in +-degrees, for every image of the tensor."""
+
+    def __init__(self, degrees):
+        super().__init__()
+        self.degrees = float(degrees)
+
+    def forward(self, x):
+        if not self.training or self.degrees == 0.0:
+            return x
+        ang = (torch.rand(1) * 2 - 1) * (self.degrees * math.pi / 180)
+        y = x.reshape(-1, *x.shape[-3:])
+        return _rotate(y, ang.to(x.device).expand(y.shape[0])).reshape(x.shape)
+
+
+class ImageTransform:
+    """utils.py:70-82: (B, T, C, H, W) -> the transform over (B*T, C, H, W) -> (B, T, C, h, w)."""
+
+    def __init__(self, image_transform=None):
+        self.image_transform = image_transform
+
+    def __call__(self, img_input):
+        B, T, C, H, W = img_input.shape
+        y = img_input.reshape(-1, C, H, W)
+        if self.image_transform is not None:
+            y = self.image_transform(y)
+        return y.reshape(B, T, C, *y.shape[2:])
+
+
+class SyncRandomCrop(nn.Module):
+    """utils.py:422-443: one random window for the image and its mask; kept until ``reset()``."""
+
+    def __init__(self, crop_size):
+        super().__init__()
+        self.crop_size = tuple(crop_size)
+        self.crop_params = None
+
+    def forward(self, img, mask):
+        if self.crop_params is None:
+            h, w = img.shape[-2:]
+            ch, cw = self.crop_size
+            if ch > h or cw > w:
+                raise ValueError(f"crop size {self.crop_size} larger than the image {(h, w)}")
+            i = int(torch.randint(0, h - ch + 1, (1,))) if h > ch else 0
+            j = int(torch.randint(0, w - cw + 1, (1,))) if w > cw else 0
+            self.crop_params = (i, j, ch, cw)
+        i, j, ch, cw = self.crop_params
+        return img[..., i:i + ch, j:j + cw], mask[..., i:i + ch, j:j + cw]
+
+    def reset(self):
+        self.crop_params = None
+
+
+class SyncCenterCrop(nn.Module):
+    """utils.py:446-454"""
+
+    def __init__(self, crop_size):
+        super().__init__()
+        self.crop_size = tuple(crop_size)
+
+    def forward(self, img, mask):
+        return _center_crop(img, self.crop_size), _center_crop(mask, self.crop_size)
+
+
+def _stage(transform, kind):
+    if transform is None:
+        return None
+    return next((m for m in transform.modules() if isinstance(m, kind)), None)
+
+
+class SyncTransform(nn.Module):
+    """utils.py:85-106 with the reference's constructor: resize both, ONE random crop for the image and its mask, then
+    each through its own chain (``img_transform``: rotation, noise, patch masking; ``mask_transform``: rotation, noise).
+
+    The random numbers of a call are separated from the arithmetic:
+      ``draw(B, T, generator)``  -> (offsets, angles, keep, seed) on the CPU, one crop window and one angle pair per
+                                    sample (all its T frames), one patch mask per frame;
+      ``apply(img, mask, ...)``  -> the transform of a (B, T, C, H, W) pair with those draws, in plain torch ops on any
+                                    device (the noise is ``torch.randn``);
+      ``fused(arena, arena, rows)`` -> draw + torch.ops.mi355ppo.image_pair_augment: the gather from the resident arenas
+                                    and the whole transform in one launch (the noise is the kernel's counter hash of
+                                    ``seed``).
+    ``forward(img, mask)`` is draw + apply from torch's default generator, on one item (T, C, H, W) as the dataset calls
+    it, or on a batch."""
+
+    def __init__(self, crop_size, downsample, img_transform, mask_transform):
+        super().__init__()
+        self.crop_size = tuple(crop_size)
+        self.sync_crop = SyncRandomCrop(crop_size)
+        self.downsample = downsample
+        self.img_transform = img_transform
+        self.mask_transform = mask_transform
+        self.generator = None
+        rot, noise, mask = (_stage(img_transform, k) for k in (_RandomRotation, GaussianNoise, Masking))
+        self.rotation_deg = rot.degrees if rot is not None else 0.0
+        self.noise_std = float(noise.std) if noise is not None else 0.0
+        self.masking_prob = float(mask.img_masking_prob) if mask is not None else 0.0
+        self.patch = int(mask.img_patch_size) if mask is not None else 1
+
+    @property
+    def size(self):
+        """(rows, columns) the crop is taken from: the resize target."""
+        return self.downsample.size
+
+    @property
+    def is_identity(self):
+        return (self.crop_size == tuple(self.size) and self.rotation_deg == 0.0 and self.noise_std == 0.0
+                and self.masking_prob == 0.0)
+
+    def draw(self, B, T, generator=None):
+        """The random numbers of one batch, from ``generator`` (torch's default when None), as CPU tensors: ``offsets``
+        int32 (B, 2) uniform over the valid (top, left); ``angles`` fp32 (B, 2) radians uniform in +-rotation_deg, column
+        0 the image's and column 1 the mask's; ``keep`` uint8 (B*T, gh, gw) or None; ``seed`` a 63-bit int (0 without
+        noise).  A stage that is off draws nothing."""
+        (h, w), (ch, cw) = self.size, self.crop_size
+        offsets = torch.zeros(B, 2, dtype=torch.int32)
+        if h > ch:
+            offsets[:, 0] = torch.randint(0, h - ch + 1, (B,), generator=generator, dtype=torch.int32)
+        if w > cw:
+            offsets[:, 1] = torch.randint(0, w - cw + 1, (B,), generator=generator, dtype=torch.int32)
+        angles = torch.zeros(B, 2)
+        if self.rotation_deg > 0.0:
+            angles = (torch.rand(B, 2, generator=generator) * 2 - 1) * (self.rotation_deg * math.pi / 180)
+        keep = None
+        if self.masking_prob > 0.0:
+            drop = torch.rand(B * T, ch // self.patch, cw // self.patch, generator=generator) < self.masking_prob
+            keep = (~drop).to(torch.uint8)
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator)) if self.noise_std > 0.0 else 0
+        return offsets, angles, keep, seed
+
+    def apply(self, img, mask, offsets, angles, keep=None, noise_std=0.0):
+        """(B, T, C, H, W) pair at the resize target -> cropped, rotated, noised, masked pair: batched torch ops."""
+        B, T, C = img.shape[:3]
+        ch, cw = self.crop_size
+        dev = img.device
+        off = offsets.to(dev).long()
+        bi = torch.arange(B, device=dev)[:, None, None]
+        ri = (off[:, :1] + torch.arange(ch, device=dev))[:, :, None]
+        ci = (off[:, 1:] + torch.arange(cw, device=dev))[:, None, :]
+        turned = (angles != 0).any(0).tolist()            # on the draw's (CPU) tensor: no device read-back
+        ang = angles.to(dev)
+        outs = []
+        for k, x in enumerate((img, mask)):
+            y = x.permute(0, 3, 4, 1, 2)[bi, ri, ci].permute(0, 3, 4, 1, 2).reshape(B * T, C, ch, cw)
+            if turned[k]:
+                y = _rotate(y, ang[:, k].repeat_interleave(T))
+            if noise_std > 0.0:
+                y = y + torch.randn_like(y) * noise_std
+            if k == 0 and keep is not None:
+                p = self.patch
+                gh, gw = ch // p, cw // p
+                m = keep.to(dev).to(y.dtype).repeat_interleave(p, 1).repeat_interleave(p, 2)
+                y = y.clone()
+                y[:, :, :gh * p, :gw * p] *= m.unsqueeze(1)
+            outs.append(y.reshape(B, T, C, ch, cw))
+        return outs[0], outs[1]
+
+    def forward(self, img, mask):
+        item = img.dim() == 4
+        if item:
+            img, mask = img[None], mask[None]
+        B, T, C = img.shape[:3]
+        img = self.downsample(img.reshape(-1, *img.shape[2:])).reshape(B, T, C, *self.size)
+        mask = self.downsample(mask.reshape(-1, *mask.shape[2:])).reshape(B, T, C, *self.size)
+        offsets, angles, keep, _ = self.draw(B, T, self.generator)
+        img, mask = self.apply(img, mask, offsets, angles, keep, self.noise_std if self.training else 0.0)
+        return (img[0], mask[0]) if item else (img, mask)
+
+    def _pair_op(self, img_arena, seg_arena, rows, offsets, angles, keep, noise_std, seed):
+        if tuple(img_arena.shape[-2:]) != tuple(self.size):
+            # stored at another size: resize the gathered batch, then the op reads it row by row
+            B, T, C = rows.numel(), img_arena.shape[1], img_arena.shape[2]
+            img_arena, seg_arena = (self.downsample(a.index_select(0, rows).reshape(B * T, C, *a.shape[-2:]))
+                                    .reshape(B, T, C, *self.size).contiguous() for a in (img_arena, seg_arena))
+            rows = torch.arange(B, device=rows.device)
+        dev = img_arena.device
+        return torch.ops.mi355ppo.image_pair_augment(
+            img_arena, seg_arena, rows, offsets.to(dev), angles.to(dev),
+            keep.to(dev) if keep is not None else None, self.crop_size[0], self.crop_size[1],
+            self.patch, noise_std, seed)
+
+    def fused(self, img_arena, seg_arena, rows, generator=None):
+        """``(arena.index_select(0, rows) for both) -> forward`` as one native launch: the arenas are the loader's resident
+        (N, T, 1, H, W) fields, ``rows`` the batch's int64 sample numbers on their device."""
+        offsets, angles, keep, seed = self.draw(rows.numel(), img_arena.shape[1],
+                                                generator if generator is not None else self.generator)
+        return self._pair_op(img_arena, seg_arena, rows, offsets, angles, keep, self.noise_std, seed)
+
+
+class SyncEvalTransform(SyncTransform):
+    """utils.py:109-128, deterministic: resize, centre crop, nothing random.  (The reference sends the mask through the
+    TRAIN-time ``mask_transform`` here -- a random rotation at validation -- and resizes the cropped pair a second time;
+    neither is copied: DESIGN.md.)  Same constructor; ``fused`` is the centre-crop gather in one launch."""
+
+    @property
+    def is_identity(self):
+        return self.crop_size == tuple(self.size)
+
+    def draw(self, B, T, generator=None):
+        top, left = _center_offsets(*self.size, *self.crop_size)
+        return torch.tensor([[top, left]], dtype=torch.int32).repeat(B, 1), torch.zeros(B, 2), None, 0
+
+    def forward(self, img, mask):
+        lead = img.shape[:-3]
+        img = self.downsample(img.reshape(-1, *img.shape[-3:]))
+        mask = self.downsample(mask.reshape(-1, *mask.shape[-3:]))
+        img, mask = _center_crop(img, self.crop_size), _center_crop(mask, self.crop_size)
+        return img.reshape(*lead, *img.shape[-3:]), mask.reshape(*lead, *mask.shape[-3:])
+
+    def fused(self, img_arena, seg_arena, rows, generator=None):
+        offsets, angles, _, _ = self.draw(rows.numel(), img_arena.shape[1])
+        return self._pair_op(img_arena, seg_arena, rows, offsets, angles, None, 0.0, 0)
+
+
+class SyncCenterReshapeTransform(nn.Module):
+    """utils.py:12-37: (B, T, C, H, W) pair -> centre crop to ``crop_size`` -> each through its transform (None = none)."""
+
+    def __init__(self, crop_size, img_transform, mask_transform):
+        super().__init__()
+        self.crop_size = tuple(crop_size)
+        self.img_transform, self.mask_transform = img_transform, mask_transform
+
+    def forward(self, img, mask):
+        B, T, C, H, W = img.shape
+        img = _center_crop(img.reshape(-1, C, H, W), self.crop_size)
+        mask = _center_crop(mask.reshape(-1, C, H, W), self.crop_size)
+        if self.img_transform is not None:
+            img = self.img_transform(img)
+        if self.mask_transform is not None:
+            mask = self.mask_transform(mask)
+        return img.reshape(B, T, C, *img.shape[2:]), mask.reshape(B, T, C, *mask.shape[2:])
+
+
+def define_img_transforms(width, height, crop_width, crop_height, img_patch_size=16, img_gaussian_noise=0.0,
+                          img_masking_prob=0.0, rotation_deg=0.0):
+    """utils.py:280-322 -> (transform, mask_transform, eval_transform, sync_transform, sync_eval_transform).  The
+    reference hard-codes ``RandomRotation(degrees=1)`` in both chains; here it is ``rotation_deg`` (0 = no rotation
+    stage), so a run that never rotated keeps its random stream."""
+    downsample = _Resize((width, height))
+    chain, mask_chain = [], []
+    if rotation_deg > 0.0:
+        chain.append(_RandomRotation(rotation_deg))
+        mask_chain.append(_RandomRotation(rotation_deg))
+    if img_gaussian_noise > 0.0:
+        chain.append(GaussianNoise(img_gaussian_noise))
+        mask_chain.append(GaussianNoise(img_gaussian_noise))
+    if img_masking_prob > 0.0:
+        chain.append(Masking(img_patch_size, img_masking_prob))
+    transform, mask_transform = nn.Sequential(*chain), nn.Sequential(*mask_chain)
+    eval_transform = nn.Sequential(downsample, _Crop((crop_width, crop_height), False))
+    eval_transform.eval()
+    sync_transform = SyncTransform((crop_width, crop_height), downsample, transform, mask_transform)
+    sync_eval_transform = SyncEvalTransform((crop_width, crop_height), downsample, eval_transform, mask_transform)
+    return transform, mask_transform, eval_transform, sync_transform, sync_eval_transform
 
 
 class TactileTransform:

@@ -18,6 +18,7 @@
 #include "depth.h"
 #include "comm.h"
 #include "glue.h"
+#include "augment.h"
 #include "peak_probe.h"
 
 namespace {
@@ -690,6 +691,14 @@ int igi_cat_cols(int n, const float* const* part, const int64_t* width, float* c
 
 int igi_split_cols(int n, float* const* part, const int64_t* width, const float* cat, int64_t rows, igi_stream_t stream) {
   return fail(igi::cat_cols(n, part, width, const_cast<float*>(cat), nullptr, rows, true, S(stream)), "igi_split_cols");
+}
+
+int igi_image_pair_augment(const float* img, const float* seg, int64_t n, int t, int hs, int ws, const int64_t* rows,
+                           int64_t b, const int32_t* offsets, const float* angles, const uint8_t* keep, int out_h,
+                           int out_w, int patch, float noise_std, uint64_t seed, float* out_img, float* out_seg,
+                           igi_stream_t stream) {
+  return fail(igi::image_pair_augment(img, seg, n, t, hs, ws, rows, b, offsets, angles, keep, out_h, out_w, patch,
+                                      noise_std, seed, out_img, out_seg, S(stream)), "igi_image_pair_augment");
 }
 
 size_t igi_pointnet_workspace_bytes(int64_t batch) { return batch < 1 ? 0 : igi::pointnet_workspace_bytes(batch); }

@@ -29,6 +29,7 @@
 
 #include "linear.h"
 #include "prof.h"
+#include "tok_hash.h"
 
 namespace igi {
 
@@ -112,18 +113,7 @@ static int make_token_plan(const igi_token_cfg* c, TokenPlan* p) {
   return 0;
 }
 
-// ---- dropout: keep iff hash(seed, site, index) >= p * 2^32; kept values are scaled by 1/(1-p)
-__device__ __forceinline__ unsigned int tok_hash(unsigned long long seed, unsigned int site, unsigned int idx) {
-  unsigned int x = idx * 0x9E3779B1u ^ (unsigned int)seed ^ (site * 0x85EBCA77u);
-  x ^= x >> 16; x *= 0x7FEB352Du;
-  x ^= x >> 15; x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  x += (unsigned int)(seed >> 32);
-  x ^= x >> 15; x *= 0x2C1B3C6Du;
-  x ^= x >> 12; x *= 0x297A2D39u;
-  x ^= x >> 15;
-  return x;
-}
+// ---- dropout: keep iff tok_hash(seed, site, index) >= p * 2^32 (tok_hash.h); kept values are scaled by 1/(1-p)
 struct Drop {
   unsigned long long seed;
   unsigned int site, thresh;  // thresh = 0: no dropout

@@ -1604,6 +1604,77 @@ def _(arenas, rows):
     return [a.new_empty((rows.numel(),) + tuple(a.shape[1:])) for a in arenas]
 
 
+def _check_layout(t, name, dtype, dim):
+    """dtype / rank / contiguity of an argument, looked at BEFORE its device, so a wrong argument is named as such on any
+    host; the device is checked last (``_check``)."""
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
+    if t.dim() != dim:
+        raise RuntimeError(f"{name}: expected {dim} dimensions, got shape {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous tensor, got strides {tuple(t.stride())}")
+
+
+@_op("image_pair_augment(Tensor img, Tensor seg, Tensor rows, Tensor offsets, Tensor angles, Tensor? keep, int out_h, "
+     "int out_w, int patch, float noise_std, int seed) -> (Tensor, Tensor)")
+def image_pair_augment(img: Tensor, seg: Tensor, rows: Tensor, offsets: Tensor, angles: Tensor, keep: Optional[Tensor],
+                       out_h: int, out_w: int, patch: int, noise_std: float, seed: int) -> Tuple[Tensor, Tensor]:
+    """The camera pair of a minibatch, augmented, in ONE launch from the resident arenas (igi_image_pair_augment; replaces
+    two ``index_select``s + ``SyncTransform``, utils.py:85-128): ``img`` / ``seg`` fp32 (N, T, 1, Hs, Ws); ``rows`` int64
+    (B,); ``offsets`` int32 (B, 2) crop (top, left) per sample; ``angles`` fp32 (B, 2) radians for (img, seg); ``keep``
+    uint8 (B*T, out_h // patch, out_w // patch) or None (0 zeroes that patch of img); ``noise_std`` > 0 adds hash-drawn
+    Gaussian noise of ``seed`` to both -> two fp32 (B, T, 1, out_h, out_w).  The inputs are data: no autograd."""
+    _check_layout(img, "img", torch.float32, 5)
+    _check_layout(seg, "seg", torch.float32, 5)
+    _check_layout(rows, "rows", torch.int64, 1)
+    _check_layout(offsets, "offsets", torch.int32, 2)
+    _check_layout(angles, "angles", torch.float32, 2)
+    if img.shape != seg.shape:
+        raise RuntimeError(f"seg: expected img's shape {tuple(img.shape)}, got {tuple(seg.shape)}")
+    N, T, ch, Hs, Ws = img.shape
+    if ch != 1 or img.numel() == 0:
+        raise RuntimeError(f"img: expected (N, T, 1, Hs, Ws) non-empty, got {tuple(img.shape)}")
+    B = rows.numel()
+    for t, nm in ((offsets, "offsets"), (angles, "angles")):
+        if tuple(t.shape) != (B, 2):
+            raise RuntimeError(f"{nm}: expected shape {(B, 2)}, got {tuple(t.shape)}")
+    if out_h < 1 or out_h > Hs:
+        raise RuntimeError(f"out_h: expected 1..{Hs} (the stored height), got {out_h}")
+    if out_w < 1 or out_w > Ws:
+        raise RuntimeError(f"out_w: expected 1..{Ws} (the stored width), got {out_w}")
+    if not noise_std >= 0:
+        raise RuntimeError(f"noise_std: expected >= 0, got {noise_std}")
+    if keep is not None:
+        if patch < 1:
+            raise RuntimeError(f"patch: expected >= 1 with a keep mask, got {patch}")
+        _check_layout(keep, "keep", torch.uint8, 3)
+        want = (B * T, out_h // patch, out_w // patch)
+        if tuple(keep.shape) != want:
+            raise RuntimeError(f"keep: expected shape {want}, got {tuple(keep.shape)}")
+    dev = img.device
+    for t, nm in ((img, "img"), (seg, "seg"), (rows, "rows"), (offsets, "offsets"), (angles, "angles"), (keep, "keep")):
+        if t is not None:
+            _check(t, nm, dtype=t.dtype, device=dev)
+    outs = (torch.empty((B, T, 1, out_h, out_w), dtype=torch.float32, device=dev),
+            torch.empty((B, T, 1, out_h, out_w), dtype=torch.float32, device=dev))
+    if B == 0:
+        return outs
+    with torch.cuda.device(dev):
+        _rc(_lib.lib().igi_image_pair_augment(_p(img), _p(seg), N, T, Hs, Ws, _p(rows), B, _p(offsets), _p(angles),
+                                              _p(keep), out_h, out_w, patch, noise_std,
+                                              C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), _p(outs[0]), _p(outs[1]),
+                                              _stream(img)), "igi_image_pair_augment")
+    return outs
+
+
+@_fake("image_pair_augment")
+def _(img, seg, rows, offsets, angles, keep, out_h, out_w, patch, noise_std, seed):
+    shape = (rows.numel(), img.shape[1], 1, out_h, out_w)
+    return img.new_empty(shape), img.new_empty(shape)
+
+
 @_op("cat_cols(Tensor[] parts, Tensor? add) -> Tensor")
 def cat_cols(parts: List[Tensor], add: Optional[Tensor]) -> Tensor:
     """``torch.cat(parts, dim=1) (+ add)`` for 2-D fp32 parts with the same number of rows, ``add`` one row of the
@@ -1680,4 +1751,4 @@ OP_NAMES = ["gae_advnorm", "ppo_minibatch_fwd_bwd", "ppo_clip_adam", "ppo_update
             "rollout_env_store",
             "bc_loss_fwd_bwd", "bc_loss", "bc_loss_value_grad", "gemm_f32", "linear", "linear_bwd", "mlp_fwd", "mlp_bwd", "tactile_cnn_fwd", "tactile_cnn_bwd", "spatial_softargmax_fwd", "spatial_softargmax_bwd",
             "pointnet_max_fwd", "pointnet_max_bwd", "pointnet_max_fwd_multi", "pointnet_max_bwd_multi", "depth_backbone_fwd", "depth_backbone_bwd", "token_encoder_fwd",
-            "token_encoder_bwd", "gather_rows", "cat_cols", "split_cols"]
+            "token_encoder_bwd", "gather_rows", "cat_cols", "split_cols", "image_pair_augment"]

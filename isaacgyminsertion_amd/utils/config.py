@@ -87,6 +87,8 @@ def default_config(num_envs=4096, horizon_length=32, rl_device="cuda:0", multi_g
                                       "output_size": 8, "lin_encoding_size": 32, "tactile_encoding_size": 32,
                                       "img_encoding_size": 32, "seg_encoding_size": 32, "load_tact": False}},
             "img_type": "depth", "img_width": 54, "img_height": 96, "img_crop_w": 0, "img_crop_h": 0,
+            # camera augmentation (offline_config.yaml img_*; img_rotation_deg is ours: the reference hard-codes 1 degree)
+            "img_patch_size": 16, "img_gaussian_noise": 0.0, "img_masking_prob": 0.0, "img_rotation_deg": 0.0,
             "tactile_patch_size": 16, "tactile_gaussian_noise": 0.001, "tactile_masking_prob": 0.0,
             "tactile_color_jitter": False, "seed": 0, "data_folder": "", "output_dir": "outputs/offline",
             # supervised learning (offline_config.yaml:28-83)
