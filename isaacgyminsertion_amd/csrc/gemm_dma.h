@@ -1573,7 +1573,7 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s);
 // (shorter) tiles follow the weight-gradient tiles, see below.  Returns hipErrorNotSupported when dgrad cannot ride (the caller launches it on its own).
 // Can the data-gradient product `g` (k-contiguous dZ times reduction-major W, tanh' epilogue) ride in the grid of
 // gemm_dma_wgrad_multi_kernel -- and, when it carries rowdot_out, emit the row dots from its tiles?  The ONE predicate
-// the launcher below and the teacher's planner (latent_rowdot) both use, so a plan never asks for row dots the launch
+// the launcher below and the teacher's step (resolve_paths) both use, so a plan never asks for row dots the launch
 // would decline.  Sets g.wide_epi.
 static inline bool gemm_multi_dgrad_ok(GemmArgs& g) {
   const long long mtl = (g.M + DMA_BM - 1) / DMA_BM, ntl = (g.N + 127) / 128;
@@ -1586,7 +1586,9 @@ static inline bool gemm_multi_dgrad_ok(GemmArgs& g) {
   return true;
 }
 
-static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, const GemmArgs* dgrad = nullptr) {
+// level: which backward level of the teacher's step the launch is booked under (PC_WGRAD_MULTI + level: rocprofv3 reports
+// one symbol, the profiler class carries the level); 4 = "other", every caller but the teacher's orchestration
+static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, const GemmArgs* dgrad = nullptr, int level = 4) {
   GemmMulti mt_;
   double fl = 0, by = 0;
   if (dgrad) {
@@ -1655,14 +1657,14 @@ static hipError_t gemm_wgrad_multi(GemmArgs* list, int count, hipStream_t s, con
     mt_.g[l] = g0; mt_.n_tiles[l] = nt0; mt_.m_tiles[l] = mt0; mt_.kind[l] = k0;
     mt_.tile_end[l] = (l > 0 ? mt_.tile_end[l - 1] : 0) + t0;
   }
-  ProfScope ps(PC_WGRAD_MULTI + (g_multi_level >= 0 && g_multi_level <= 5 ? g_multi_level : 4), s, fl, by);   // rocprofv3 reports one symbol; the class carries the level
+  ProfScope ps(PC_WGRAD_MULTI + (level >= 0 && level <= 5 ? level : 4), s, fl, by);
   IGI_DMA_LAUNCH_SHM(gemm_dma_wgrad_multi_kernel, dim3(mt_.tile_end[mt_.n - 1]), DMA_SHM_128X2, DMA_SHM_128X2, s, mt_);
   return hipGetLastError();
 }
 
 // fp32 inputs: one gemm_wgrad_multi grid; bf16-input mode: the grouped kernels below
-static hipError_t gemm_wgrad_group(GemmArgs* list, int count, hipStream_t s) {
-  if (!bf16_mode()) return gemm_wgrad_multi(list, count, s);
+static hipError_t gemm_wgrad_group(GemmArgs* list, int count, hipStream_t s, int level = 4) {
+  if (!bf16_mode()) return gemm_wgrad_multi(list, count, s, nullptr, level);
   GemmGroup grp[2];   // [0]: 128-wide two-stage tiles (bf16 inputs), [1]: 64-wide three-stage tiles
   double fl[2] = {0, 0}, by[2] = {0, 0};
   for (int i = 0; i < count; ++i) {
@@ -1704,15 +1706,15 @@ static hipError_t gemm_wgrad_group(GemmArgs* list, int count, hipStream_t s) {
 // One level of a backward chain: the data gradient `dgrad` (k-contiguous dZ times reduction-major W, tanh' epilogue)
 // together with the weight-gradient products that are ready at this point, in one grid when the shapes allow it (not in
 // bf16-input mode).
-static hipError_t gemm_level(const GemmArgs& dgrad, GemmArgs* wgrads, int count, hipStream_t s) {
+static hipError_t gemm_level(const GemmArgs& dgrad, GemmArgs* wgrads, int count, hipStream_t s, int level = 4) {
   if (!bf16_mode() && count > 0) {
-    hipError_t e = gemm_wgrad_multi(wgrads, count, s, &dgrad);
+    hipError_t e = gemm_wgrad_multi(wgrads, count, s, &dgrad, level);
     if (e != hipErrorNotSupported) return e;
   }
   if (dgrad.rowdot_out) return hipErrorNotSupported;   // only the fused tile emits the row dots: the caller planned for them
   hipError_t e = gemm(dgrad, true, false, s);
   if (e != hipSuccess) return e;
-  return count > 0 ? gemm_wgrad_group(wgrads, count, s) : hipSuccess;
+  return count > 0 ? gemm_wgrad_group(wgrads, count, s, level) : hipSuccess;
 }
 
 }  // namespace igi

@@ -70,9 +70,6 @@ static const char* const kProfNames[PC_COUNT] = {
     "k_loss", "k_latent_bwd", "k_slab_reduce", "k_sumsq_stats", "k_clip_adam", "k_adam_gather", "k_lr_schedule", "k_gae+k_prep_final+k_prep_norm",
     "k_token_fwd<S>", "k_token_fwd_long", "k_attn_tile_fwd", "k_attn_tile_bwd", "other"};
 
-// which backward level the next gemm_dma_wgrad_multi_kernel launch belongs to (set by the teacher's orchestration)
-static thread_local int g_multi_level = 4;
-
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes; };
 
 struct Profiler {

@@ -46,7 +46,7 @@ constexpr int LOSS_THREADS = 256;
 constexpr int LOSS_BLOCKS_DEFAULT = 512;  // measured: 256 -> 55 us, 512 -> 35 us, 1024 -> 37 us per launch
 constexpr int RED_THREADS = 256;
 constexpr int SUMSQ_BLOCKS = 512;
-// Segments of the flat-gradient assembly (teacher_fwd_bwd), worst case of what make_plan accepts, for L layers per MLP:
+// Segments of the flat-gradient assembly (assemble_gradient), worst case of what make_plan accepts, for L layers per MLP:
 // 4 heads (mu W, b; value W, b) + 1 sigma + 2 per env_mlp layer (W, b; the fused latent level's two records stand in for the
 // last layer's) + 4 contact encoder (W1, b1, W2, b2) + 4 per trunk layer (W, b of actor and critic) = 9 + 6 L; L = 4: 33.
 constexpr int teacher_max_segments(int max_layers) { return 4 + 1 + 2 * max_layers + 4 + 4 * max_layers; }
@@ -102,6 +102,10 @@ struct TeacherPlan {
 
 static inline int env_in(const TeacherPlan& p, int l) { return l == 0 ? p.priv : p.pu[l - 1]; }
 static inline int ac_in(const TeacherPlan& p, int l) { return l == 0 ? p.xw : p.u[l - 1]; }
+// d(pre-activation) of trunk layer l: stacked [net][mb][width4] like the activations, except the FIRST layer's, which is
+// kept interleaved [row][net][u0p] so that the data gradient into xcat is one contraction over both nets
+static inline int dz_ld(const TeacherPlan& p, int l) { return l == 0 ? p.nets * p.u0p : ru4(p.u[l]); }
+static inline long long dz_stride(const TeacherPlan& p, int l) { return l == 0 ? (long long)p.u0p : (long long)p.mb * ru4(p.u[l]); }
 static inline bool H_last_is_128(const TeacherPlan* p) { return p->u[p->nl - 1] == 128; }
 
 static int choose_splitk(int M, int N, int K, int nbatch) {
@@ -138,6 +142,13 @@ static int choose_splitk(int M, int N, int K, int nbatch) {
 static inline int& latz_fuse_ref() {
   static int on = -1;
   if (on < 0) { const char* e = getenv("IGI_LATZ_FUSE"); on = e ? (atoi(e) != 0) : 1; }
+  return on;
+}
+// IGI_ENV_FUSED=0, a test seam (the bit-equality tests run both settings in child processes): the env_mlp forward layer by
+// layer instead of k_env_fwd / k_fwd12
+static inline int env_fused() {
+  static int on = -1;
+  if (on < 0) { const char* e = getenv("IGI_ENV_FUSED"); on = e ? atoi(e) : 1; }
   return on;
 }
 
@@ -275,7 +286,7 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
   // workgroup slots exactly once: 84 -> ~40 MB of slabs) was measured and is SLOWER: 141 us + 14 us reduce against
   // 131.5 + 18.5 (`tools/scratch`-style sweep over slot targets 256..2048): uneven k-chunks lose the
   // per-problem XCD grouping and long workgroups run below the k-loop's steady rate.
-  long long s = 0;
+  // env_mlp: the factors of every layer first (lx_env moves the first layer's), then ONE pass lays the slab out
   for (int l = 0; l < p->npl; ++l) {
     int sk = choose_splitk(p->pu[l], env_in(*p, l), p->mb, 1);
     // the first env layer's weight gradient is a launch of its own and has to fill the chip; the later ones share the
@@ -289,21 +300,17 @@ static int make_plan(const igi_teacher_cfg* c, TeacherPlan* p) {
       p->rb_env[l] = rb_level_ranges(p->mb, p->pu[l - 1], 1);
       p->sk_env[l] = p->rb_env[l];
     }
+  }
+  if (p->npl >= 2 && p->rb_env[1] && p->priv == 64) {
+    // env layer 0's weight gradient from the data-gradient tiles of the level above: rb_env[1] partial records
+    p->lx_env = 1;
+    p->sk_env[0] = p->rb_env[1];
+  }
+  long long s = 0;
+  for (int l = 0; l < p->npl; ++l) {
     p->s_envW[l] = s; s += (long long)p->sk_env[l] * p->pu[l] * env_in(*p, l);
     p->s_envB[l] = s; s += (long long)p->sk_env[l] * p->pu[l];
     s = (s + 3) & ~3LL;
-  }
-  if (p->npl >= 2 && p->rb_env[1] && p->priv == 64) {
-    // env layer 0's weight gradient from the data-gradient tiles of the level above: rb_env[1] partial records; the slab
-    // offsets of the layers behind it move accordingly (recomputed below)
-    p->lx_env = 1;
-    p->sk_env[0] = p->rb_env[1];
-    s = 0;
-    for (int l = 0; l < p->npl; ++l) {
-      p->s_envW[l] = s; s += (long long)p->sk_env[l] * p->pu[l] * env_in(*p, l);
-      p->s_envB[l] = s; s += (long long)p->sk_env[l] * p->pu[l];
-      s = (s + 3) & ~3LL;
-    }
   }
   {
     const int latz_on = latz_fuse_ref();
@@ -1646,14 +1653,12 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
   // env_mlp: tanh after every layer, the last one lands in xcat[:, obs:]
   const float* in = priv_g;
   int ldin = ru4(p.priv);
-  static int env_fused = -1;
-  if (env_fused < 0) { const char* e = getenv("IGI_ENV_FUSED"); env_fused = e ? atoi(e) : 1; }
   bool env_done = p.ct_only != 0;   // only_contact: the privileged embedding is not used (models_split.py:176-177)
   int first_trunk_layer = 0;
   // round 6: env_mlp AND the first trunk layer of both nets as one persistent launch (fwd12.h); other shapes keep
   // k_env_fwd (or the per-layer launches) + the layer's own launch below
   // (k_fwd12 runs the first trunk layer of TWO nets: a shared trunk declines it and takes the launches below)
-  if (env_fused && p.nets == 2 && p.npl == 3 && p.ct_P == 0 && nl_run >= 1 && rows >= 2048 && !bf16_mode() &&
+  if (env_fused() && p.nets == 2 && p.npl == 3 && p.ct_P == 0 && nl_run >= 1 && rows >= 2048 && !bf16_mode() &&
       fwd12_supported(p.priv, p.pu[0], p.pu[1], p.pu[2], p.obs, p.xld, p.u[0]) && p.u0p == p.u[0]) {
     Fwd12Args f;
     f.priv = priv_g; f.ldp = ldin; f.xcat = xcat; f.ldx = p.xld; f.M = rows; f.obs = p.obs;
@@ -1667,7 +1672,7 @@ static int trunk_forward(const TeacherPlan& p, const igi_teacher_state* st, int 
   }
   // (the fused kernel is one workgroup per 64 rows with a fixed ~20 us chain: at the rollout's 4096 rows it fills a
   // quarter of the chip and the per-layer launches win -- measured 8.4 -> 8.0 ms per 32-step rollout)
-  if (!env_done && env_fused && p.npl == 3 && rows >= 8192 && !bf16_mode()) {
+  if (!env_done && env_fused() && p.npl == 3 && rows >= 8192 && !bf16_mode()) {
     // the whole env_mlp of a 64-row block in one workgroup (env_mlp.h); other shapes run layer by layer below
     // (an fp32 kernel: in the bf16-input mode the layers go through gemm() like every other fused class's, so the
     // forward of a layer and its backward products are under the switch together)
@@ -1775,13 +1780,11 @@ static GatherArgs gather_args(const TeacherPlan& p, const igi_rollout* ro, const
 // with_rowdot (l == 1): the dZ1 tiles also emit their share of dZ1 . W1[:, latent columns] (GemmArgs::rowdot_*).
 static GemmArgs trunk_dgrad_args(const TeacherPlan& p, const igi_teacher_state* st, int l, bool with_rowdot) {
   const long long mbs = p.mb;
-  auto dz_ld = [&](int k) { return k == 0 ? p.nets * p.u0p : ru4(p.u[k]); };
-  auto dz_stride = [&](int k) { return k == 0 ? (long long)p.u0p : mbs * ru4(p.u[k]); };
   GemmArgs g;
-  g.A = wsp<float>(st, p.w_dh[l]); g.lda = dz_ld(l); g.sA = dz_stride(l);
+  g.A = wsp<float>(st, p.w_dh[l]); g.lda = dz_ld(p, l); g.sA = dz_stride(p, l);
   g.B = st->params + p.o_acW[l]; g.ldb = ac_in(p, l); g.sB = p.ac_block;
   g.M = p.mb; g.N = ac_in(p, l); g.K = p.u[l];
-  g.C = wsp<float>(st, p.w_dh[l - 1]); g.ldc = dz_ld(l - 1); g.sC = dz_stride(l - 1);
+  g.C = wsp<float>(st, p.w_dh[l - 1]); g.ldc = dz_ld(p, l - 1); g.sC = dz_stride(p, l - 1);
   g.aux = wsp<float>(st, p.w_h[l - 1]); g.ldaux = ru4(p.u[l - 1]); g.sAux = mbs * ru4(p.u[l - 1]);
   g.nbatch = p.nets;
   g.epilogue = EPI_TANHGRAD;
@@ -1799,17 +1802,44 @@ static GemmArgs trunk_dgrad_args(const TeacherPlan& p, const igi_teacher_state* 
   return g;
 }
 
-// The latent gradient's K = 2*u0 contraction can ride in the tiles of the data gradient that produces dZ1 (no second
-// pass over its 67 MB): needs the level-fused multi kernel for that product.  Decided from the plan and the state's
-// addresses alone, with the very predicate the launcher applies (gemm_multi_dgrad_ok), so that both halves of a phased
-// step agree and the launch can never decline row dots the plan counted on (it falls back to k_latent_bwd<., false>).
-static bool latent_rowdot(const TeacherPlan& p, const igi_teacher_state* st) {
+// What one step launches where the plan alone does not say: resolved ONCE per call of teacher_fwd_bwd, every stage reads it.
+// The backward through the last env layer into the latent, in order of precedence: inside the env level's row-block kernel
+// (rowblock.h, LATZ: no launch of its own) | k_latent_bwd<., true> from the row dots the dZ1 tiles emitted | k_latent_bwd<., false>
+// over dZ1 itself | k_latent_dgrad<KQ, 8> | the EPI_TANHGRAD product over all xld columns
+enum LatentPath { LAT_ENV_LEVEL, LAT_BWD_PARTS, LAT_BWD_DZ1, LAT_DGRAD, LAT_GENERIC };
+struct StepPaths {
+  bool rowdot, latz, lw;   // the dZ1 tiles emit the latent row dots; the plan's latz / lw_parts, live only with them
+  LatentPath latent;
+  // profiler class (PC_WGRAD_MULTI + .) of the level launch of trunk / env layer l and of the closing weight-gradient group
+  int cls_trunk[IGI_MAX_LAYERS], cls_env[IGI_MAX_LAYERS], cls_closing;
+};
+static StepPaths resolve_paths(const TeacherPlan& p, const igi_teacher_state* st) {
+  StepPaths q;
+  // The latent gradient's K = 2*u0 contraction can ride in the tiles of the data gradient that produces dZ1 (no second
+  // pass over its 67 MB): needs the level-fused multi kernel for that product.  Decided from the plan and the state's
+  // addresses alone, with the very predicate the launcher applies (gemm_multi_dgrad_ok), so that both halves of a phased
+  // step agree and the launch can never decline row dots the plan counted on (it falls back to k_latent_bwd<., false>).
   // (two nets only: the tiles' row dots and k_latent_bwd<., true> index the partials [tile][net]; a shared trunk's dZ1 goes
   // through k_latent_bwd<., false>, which is generic in K2 = nets * u0p)
-  if (!(p.nets == 2 && p.lat_fused && p.nl >= 2 && !bf16_mode() && p.mb >= 4)) return false;
-  GemmArgs g = trunk_dgrad_args(p, st, 1, true);
-  return gemm_multi_dgrad_ok(g);
+  q.rowdot = false;
+  if (p.nets == 2 && p.lat_fused && p.nl >= 2 && !bf16_mode() && p.mb >= 4) {
+    GemmArgs g = trunk_dgrad_args(p, st, 1, true);
+    q.rowdot = gemm_multi_dgrad_ok(g);
+  }
+  q.latz = p.latz && q.rowdot;
+  q.lw = p.lw_parts > 0 && q.rowdot;
+  const int K2 = p.nets * p.u0p;
+  q.latent = p.lat_fused ? (q.latz ? LAT_ENV_LEVEL : q.rowdot ? LAT_BWD_PARTS : LAT_BWD_DZ1)
+                         : (p.latent == 8 && p.ct_P == 0 && K2 % 256 == 0 && K2 <= 1024) ? LAT_DGRAD : LAT_GENERIC;
+  for (int l = 0; l < IGI_MAX_LAYERS; ++l) {
+    q.cls_trunk[l] = (p.nl == 3) ? (l == 2 ? 0 : 1) : 4;
+    q.cls_env[l] = (p.npl == 3 && l == 1) ? 2 : 4;
+  }
+  q.cls_closing = (p.npl == 3) ? ((p.rb_env[1] && !q.lw) ? 5 : 3) : 4;   // (launched by the phase that runs the env stage)
+  return q;
 }
+// the weight-gradient products that wait for the next level launch: they cross the trunk, latent and env stages
+struct PendingWgrads { GemmArgs g[2 * IGI_MAX_LAYERS]; int n = 0; };
 
 // the contact encoder of a minibatch (perm != nullptr: rows start.. of the permutation over the (T, N, P) arena) or of
 // `rows` plain rows (perm == nullptr, T = 1)
@@ -1827,73 +1857,39 @@ static ContactArgs contact_args(const TeacherPlan& p, const igi_teacher_state* s
   return a;
 }
 
-// skip_gather: the previous step's fused tail (k_adam_gather) already gathered + normalised this minibatch
-static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
-                           const igi_teacher_state* st, int mb_index, int step_slot, hipStream_t s,
-                           int phase = -1, bool skip_gather = false, const igi_kl_stop* ks = nullptr) {
-  TeacherPlan p;
-  int rc = make_plan(c, &p);
-  if (rc) return rc;
-  if ((rc = check_state(p, st))) return rc;
-  if ((rc = check_ks(ks, st, c))) return rc;
-  // KL early stopping: what runs ahead of the step's decision looks at the word an EARLIER step left; step 0 has none
-  // (the word still holds the previous update's result)
-  const int32_t* stop = kl_stop_on(ks) && step_slot > 0 ? ks->stop_state : nullptr;
-  if (!ro || !ro->obses || !ro->priv_info || !ro->actions || !ro->neglogpacs || !st->grads ||
-      !st->perm || !st->rms_obs || !st->rms_priv || !st->stats || !st->advantages ||
-      mb_index < 0 || mb_index >= p.nmb || step_slot < 0 || (p.ct_P > 0 && !ro->contacts))
-    return IGI_E_BADARG;
+// ---- the stages of one step (teacher_fwd_bwd below), each on (plan, paths, state, ...) -------------------------------
+// gather + normalise with this step's pre-scanned running statistics (experience.py:207-226; frozen_ppo.py:521-522)
+// + publish the running state + refresh the padded first-layer weight
+static void gather_stage(const TeacherPlan& p, const igi_rollout* ro, const igi_teacher_state* st, int mb_index, int step_slot,
+                         const int32_t* stop, hipStream_t s) {
+  ProfScope ps(PC_GATHER_NORMALIZE, s, 0.0, 8.0 * (double)p.mb * (p.obs + p.priv) + 8.0 * p.mb);
+  const int pad_blocks = 16;
+  GatherArgs ga = gather_args(p, ro, st, mb_index, step_slot);
+  ga.stop = stop;
+  IGI_LAUNCH(k_gather_normalize, dim3(p.gs_blocks + pad_blocks), dim3(GS_THREADS), 0, s, ga);
+}
+
+// backward through the actor / critic trunk.  Level fusion: the weight gradient of layer l and the data
+// gradient INTO layer l-1 both consume dZ_l and are independent of each other, so they share one grid
+// (gemm_level -> gemm_dma_wgrad_multi_kernel: the data-gradient tiles lead, the weight-gradient workgroups fill
+// their fill / drain bubbles).  The first trunk layer's weight gradient rides with the env_mlp data gradient: it is left
+// pending here (phase 1; the levels above it are phase 0).
+static int trunk_backward(const TeacherPlan& p, const StepPaths& q, const igi_teacher_state* st, bool do0, bool do1,
+                          PendingWgrads& pend, hipStream_t s) {
   const float* P = st->params;
   const int mb = p.mb;
-  const ContactArgs cta = p.ct_P > 0 ? contact_args(p, st, ro->contacts, st->perm, (long long)mb_index * p.mb, p.mb) : ContactArgs();
-  const long long mbs = mb;
-  float* priv_g = wsp<float>(st, p.w_priv);
-  float* xcat = wsp<float>(st, p.w_xcat);
-  float* dxcat = wsp<float>(st, p.w_dxcat);
-  float* w1p = wsp<float>(st, p.w_w1p);
-  const int pld = ru4(p.priv);
-  const int D = p.obs + p.priv;
-
-  // ---- gather + normalise with this step's pre-scanned running statistics (experience.py:207-226;
-  //      frozen_ppo.py:521-522) + publish the running state + refresh the padded first-layer weight
-  if (mb_index != step_slot % p.nmb || step_slot >= p.E * p.nmb) return IGI_E_BADARG;  // canonical step order
-  if (phase < -1 || phase > 1) return IGI_E_BADARG;
-  const bool do0 = phase != 1, do1 = phase != 0;
-  if (do0 && !skip_gather) {
-    ProfScope ps(PC_GATHER_NORMALIZE, s, 0.0, 8.0 * (double)mbs * D + 8.0 * mbs);
-    const int pad_blocks = 16;
-    GatherArgs ga = gather_args(p, ro, st, mb_index, step_slot);
-    ga.stop = stop;
-    IGI_LAUNCH(k_gather_normalize, dim3(p.gs_blocks + pad_blocks), dim3(GS_THREADS), 0, s, ga);
-  }
-  // ---- forward trunk (models_split.py:166-232)
-  if (do0 && (rc = trunk_forward(p, st, mb, false, s, p.loss_fused ? p.nl - 1 : p.nl, p.ct_P > 0 ? &cta : nullptr))) return rc;
-
-  // ---- heads + loss + head backward.  d(pre-activation) of the FIRST trunk layer is kept
-  // interleaved [row][net][u0p] so that the dgrad into xcat is one contraction over both nets.
-  const int H = p.u[p.nl - 1];
-  auto dz_ld = [&](int l) { return l == 0 ? p.nets * p.u0p : ru4(p.u[l]); };
-  auto dz_stride = [&](int l) { return l == 0 ? (long long)p.u0p : mbs * ru4(p.u[l]); };
-  if (do0 && (rc = loss_stage(p, c, ro, st, mb_index, dz_ld(p.nl - 1), dz_stride(p.nl - 1), s, stop))) return rc;
-
-  // ---- backward through the actor / critic trunk.  Level fusion: the weight gradient of layer l and the data
-  //      gradient INTO layer l-1 both consume dZ_l and are independent of each other, so they share one grid
-  //      (gemm_level -> gemm_dma_wgrad_multi_kernel: the data-gradient tiles lead, the weight-gradient workgroups fill
-  //      their fill / drain bubbles).  The first trunk layer's weight gradient rides with the env_mlp data gradient.
   float* slab = wsp<float>(st, p.w_slab);
-  GemmArgs wgrads[2 * IGI_MAX_LAYERS];
-  int n_wgrads = 0;
   for (int l = p.nl - 1; l >= 0; --l) {
     if (l > 0 && !do0) continue;
     const bool do_wgrad = l > 0 ? do0 : do1;   // the first layer's weight gradient belongs to phase 1 (env level's grid)
     const int out = p.u[l];
     const int in = (l == 0) ? p.xld : ac_in(p, l);  // layer 0 sees the zero-padded xcat
     const float* dz = wsp<float>(st, p.w_dh[l]);
-    const int ldz = dz_ld(l);
-    const long long sZ = dz_stride(l);
-    const float* x = (l == 0) ? xcat : wsp<float>(st, p.w_h[l - 1]);
+    const int ldz = dz_ld(p, l);
+    const long long sZ = dz_stride(p, l);
+    const float* x = (l == 0) ? wsp<float>(st, p.w_xcat) : wsp<float>(st, p.w_h[l - 1]);
     const int ldx = (l == 0) ? p.xld : ru4(p.u[l - 1]);
-    const long long sX = (l == 0) ? 0 : mbs * ldx;
+    const long long sX = (l == 0) ? 0 : (long long)mb * ldx;
     if (p.rb_ac[l]) {
       // this level as one persistent row-block kernel: dZ_l and h_{l-1} cross the chip once, the weight gradient leaves
       // as rb_ac[l] partials per net (rowblock.h)
@@ -1901,7 +1897,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
       r.dZ = dz; r.ldz = ldz; r.sZ = sZ;
       r.W = P + p.o_acW[l]; r.ldw = in; r.sW = p.ac_block;
       r.X = x; r.ldx = ldx; r.sX = sX;
-      r.dX = wsp<float>(st, p.w_dh[l - 1]); r.lddx = dz_ld(l - 1); r.sdX = dz_stride(l - 1);
+      r.dX = wsp<float>(st, p.w_dh[l - 1]); r.lddx = dz_ld(p, l - 1); r.sdX = dz_stride(p, l - 1);
       r.dWp = slab + p.s_acW[l]; r.ldwp = in; r.sWpart = (long long)p.nets * out * in; r.sWnet = (long long)out * in;
       r.dBp = slab + p.s_acB[l]; r.sBpart = (long long)p.nets * out; r.sBnet = out;
       r.rows = mb; r.IN = in; r.nets = p.nets; r.ranges = p.rb_ac[l];
@@ -1910,7 +1906,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
       IGI_HIP_TRY(e);
       continue;
     }
-    if (do_wgrad && !(l == 0 && p.lw_parts > 0 && latent_rowdot(p, st))) {  // wgrad: dW[out][in] = dZ^T X, bias = column sums of dZ
+    if (do_wgrad && !(l == 0 && q.lw)) {  // wgrad: dW[out][in] = dZ^T X, bias = column sums of dZ
       GemmArgs g;
       g.A = dz; g.lda = ldz; g.sA = sZ;
       g.B = x; g.ldb = ldx; g.sB = sX;
@@ -1920,92 +1916,103 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
       g.nbatch = p.nets; g.splitk = p.sk_ac[l];
       if (l == 0) g.flop_credit = (double)p.xw / p.xld;   // the zero-padded input columns carry no algorithmic work
       g.sCsplit = (long long)p.nets * out * in; g.sCbiasSplit = (long long)p.nets * out;
-      wgrads[n_wgrads++] = g;
+      pend.g[pend.n++] = g;
     }
     if (l > 0) {  // dgrad into the previous hidden layer, times tanh'
       // (l == 1 with row dots: the dZ1 tiles also emit their share of dZ1 . W1[:, latent columns])
-      const GemmArgs g = trunk_dgrad_args(p, st, l, l == 1 && latent_rowdot(p, st));
+      const GemmArgs g = trunk_dgrad_args(p, st, l, l == 1 && q.rowdot);
       // this layer's weight gradient needs the same dZ: it shares the data gradient's launch (gemm_level)
-      g_multi_level = (p.nl == 3) ? (l == 2 ? 0 : 1) : 4;
-      IGI_HIP_TRY(gemm_level(g, wgrads, n_wgrads, s));
-      n_wgrads = 0;
-    } else if (do1) {
-      // d(xcat) = [dZ1_actor | dZ1_critic] . [W1a ; W1c] (one contraction, K = 2*u0p), times tanh'
-      // of xcat: columns obs..obs+latent-1 are d(pre-activation) of the last env_mlp layer; the
-      // other columns (observations, padding) are never read.
-      const int K2 = p.nets * p.u0p;
-      if (p.lat_fused && p.latz && latent_rowdot(p, st)) {
-        // (LATZ: the env level's row-block kernel forms dZ of the second env layer from the row dots itself)
-      } else if (p.lat_fused) {
-        const int H2 = p.pu[p.npl - 2];
-        const bool parts_path = latent_rowdot(p, st);   // the K2-wide contraction then happened in the dZ1 tiles
-        ProfScope ps(PC_LATENT_BWD, s, (parts_path ? 0.0 : 2.0 * mbs * K2 * 8) + 6.0 * mbs * 8 * H2,
-                     4.0 * mbs * ((parts_path ? 8.0 * p.lat_tiles : (double)K2) + 3 * H2));
-        const int maxj = (H2 + 63) / 64;
-        const int K2p = (K2 + LATB_CH - 1) / LATB_CH * LATB_CH;
-        size_t tile_f = (size_t)LATB_ROWS * LATB_LD;
-        if (tile_f < (size_t)4 * (8 * H2 + 8)) tile_f = (size_t)4 * (8 * H2 + 8);
-        const size_t shm = sizeof(float) * (8 * (size_t)(K2p + 4) + tile_f + LATB_ROWS * 8);
-        float* part = wsp<float>(st, p.w_lat_part);
-#define IGI_LATB(MJ_)                                                                                        \
-  do {                                                                                                       \
-    static bool attr = false;                                                                                \
-    if (!attr) {                                                                                             \
-      IGI_HIP_TRY(hipFuncSetAttribute((const void*)k_latent_bwd<MJ_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      160 * 1024));                                                          \
-      attr = true;                                                                                           \
-    }                                                                                                        \
-    IGI_LAUNCH((k_latent_bwd<MJ_>), dim3(p.lat_blocks), dim3(256), shm, s, dz, ldz, K2,               \
-                       wsp<float>(st, p.w_wlat), p.xld,                                                      \
-                       p.obs, xcat, dxcat, wsp<float>(st, p.w_e[p.npl - 2]), ru4(H2), H2,                    \
-                       P + p.o_envW[p.npl - 1], wsp<float>(st, p.w_de[p.npl - 2]), part, mb);                \
-  } while (0)
-        if (parts_path) {
-          const float* parts = wsp<float>(st, p.w_lat_rowdot);
-#define IGI_LATP(MJ_)                                                                                        \
-  do {                                                                                                       \
-    static bool attr = false;                                                                                \
-    if (!attr) {                                                                                             \
-      IGI_HIP_TRY(hipFuncSetAttribute((const void*)k_latent_bwd<MJ_, true>,                                  \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));              \
-      attr = true;                                                                                           \
-    }                                                                                                        \
-    IGI_LAUNCH((k_latent_bwd<MJ_, true>), dim3(p.lat_blocks), dim3(256), shm, s, parts, p.lat_tiles, K2,     \
-                       wsp<float>(st, p.w_wlat), p.xld,                                                      \
-                       p.obs, xcat, dxcat, wsp<float>(st, p.w_e[p.npl - 2]), ru4(H2), H2,                    \
-                       P + p.o_envW[p.npl - 1], wsp<float>(st, p.w_de[p.npl - 2]), part, mb);                \
-  } while (0)
-          if (maxj <= 2) IGI_LATP(2); else IGI_LATP(4);
-#undef IGI_LATP
-        } else if (maxj <= 2) IGI_LATB(2); else IGI_LATB(4);
-#undef IGI_LATB
-      } else if (p.latent == 8 && p.ct_P == 0 && K2 % 256 == 0 && K2 <= 1024) {
-        ProfScope ps(PC_OTHER, s, 2.0 * mbs * K2 * 8, 4.0 * mbs * K2);
-        const int rpw = 8;
-        const int nb = (mb + 4 * rpw - 1) / (4 * rpw);
-        const int kq = K2 / 256;
-#define IGI_LAT(KQ_) IGI_LAUNCH((k_latent_dgrad<KQ_, 8>), dim3(nb), dim3(256), 0, s, dz, ldz, w1p, p.xld, \
-                                        p.obs, xcat, dxcat, mb, rpw)
-        if (kq == 1) IGI_LAT(1); else if (kq == 2) IGI_LAT(2); else if (kq == 3) IGI_LAT(3); else IGI_LAT(4);
-#undef IGI_LAT
-      } else {
-        GemmArgs g;
-        g.A = dz; g.lda = ldz;
-        g.B = w1p; g.ldb = p.xld;
-        g.M = mb; g.N = p.xld; g.K = K2;
-        g.C = dxcat; g.ldc = p.xld;
-        g.aux = xcat; g.ldaux = p.xld;
-        g.epilogue = EPI_TANHGRAD;
-        IGI_HIP_TRY(gemm(g, true, false, s));
-      }
-      if (p.ct_P > 0) {   // contact encoder backward from d(pre-tanh) of its columns of dxcat
-        const hipError_t e = contact_backward(cta, s);
-        if (e != hipSuccess) return (int)e;
-      }
+      IGI_HIP_TRY(gemm_level(g, pend.g, pend.n, s, q.cls_trunk[l]));
+      pend.n = 0;
     }
   }
-  // ---- backward through env_mlp (its last layer is already done when k_latent_bwd ran)
-  for (int l = p.npl - 1 - p.lat_fused; l >= 0 && do1 && !p.ct_only; --l) {
+  return 0;
+}
+
+// k_latent_bwd<MAXJ, PARTS> from src = dZ1 (src_ld its leading dimension) or, PARTS, the dZ1 tiles' row-dot partials
+// (src_ld = their number); the LDS limit of an instantiation is raised once
+template <int MAXJ, bool PARTS>
+static int launch_latent_bwd(const TeacherPlan& p, const igi_teacher_state* st, const float* src, int src_ld, hipStream_t s) {
+  static bool attr = false;
+  if (!attr) {
+    IGI_HIP_TRY(hipFuncSetAttribute((const void*)k_latent_bwd<MAXJ, PARTS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr = true;
+  }
+  const int H2 = p.pu[p.npl - 2], K2 = p.nets * p.u0p, K2p = (K2 + LATB_CH - 1) / LATB_CH * LATB_CH;
+  size_t tile_f = (size_t)LATB_ROWS * LATB_LD;
+  if (tile_f < (size_t)4 * (8 * H2 + 8)) tile_f = (size_t)4 * (8 * H2 + 8);
+  const size_t shm = sizeof(float) * (8 * (size_t)(K2p + 4) + tile_f + LATB_ROWS * 8);
+  IGI_LAUNCH((k_latent_bwd<MAXJ, PARTS>), dim3(p.lat_blocks), dim3(256), shm, s, src, src_ld, K2, wsp<float>(st, p.w_wlat), p.xld,
+             p.obs, wsp<float>(st, p.w_xcat), wsp<float>(st, p.w_dxcat), wsp<float>(st, p.w_e[p.npl - 2]), ru4(H2), H2,
+             st->params + p.o_envW[p.npl - 1], wsp<float>(st, p.w_de[p.npl - 2]), wsp<float>(st, p.w_lat_part), p.mb);
+  return 0;
+}
+
+// d(xcat) = [dZ1_actor | dZ1_critic] . [W1a ; W1c] (one contraction, K = 2*u0p), times tanh' of xcat: columns
+// obs..obs+latent-1 are d(pre-activation) of the last env_mlp layer; the other columns (observations, padding) are never
+// read.  Then the contact encoder's backward from its columns.
+static int latent_backward(const TeacherPlan& p, const StepPaths& q, const igi_teacher_state* st, const ContactArgs& cta,
+                           hipStream_t s) {
+  const int mb = p.mb, K2 = p.nets * p.u0p, ldz = dz_ld(p, 0);
+  const long long mbs = mb;
+  const float* dz = wsp<float>(st, p.w_dh[0]);
+  float *xcat = wsp<float>(st, p.w_xcat), *dxcat = wsp<float>(st, p.w_dxcat), *w1p = wsp<float>(st, p.w_w1p);
+  switch (q.latent) {
+    case LAT_ENV_LEVEL:   // (LATZ: the env level's row-block kernel forms dZ of the second env layer from the row dots itself)
+      break;
+    case LAT_BWD_PARTS:
+    case LAT_BWD_DZ1: {
+      const int H2 = p.pu[p.npl - 2], tiles = p.lat_tiles;
+      const bool parts_path = q.latent == LAT_BWD_PARTS;   // the K2-wide contraction then happened in the dZ1 tiles
+      ProfScope ps(PC_LATENT_BWD, s, (parts_path ? 0.0 : 2.0 * mbs * K2 * 8) + 6.0 * mbs * 8 * H2,
+                   4.0 * mbs * ((parts_path ? 8.0 * tiles : (double)K2) + 3 * H2));
+      const bool j2 = (H2 + 63) / 64 <= 2;
+      const float* parts = wsp<float>(st, p.w_lat_rowdot);
+      int rc;
+      if (parts_path) rc = j2 ? launch_latent_bwd<2, true>(p, st, parts, tiles, s) : launch_latent_bwd<4, true>(p, st, parts, tiles, s);
+      else rc = j2 ? launch_latent_bwd<2, false>(p, st, dz, ldz, s) : launch_latent_bwd<4, false>(p, st, dz, ldz, s);
+      if (rc) return rc;
+      break;
+    }
+    case LAT_DGRAD: {
+      ProfScope ps(PC_OTHER, s, 2.0 * mbs * K2 * 8, 4.0 * mbs * K2);
+      const int rpw = 8;
+      const int nb = (mb + 4 * rpw - 1) / (4 * rpw);
+      const int kq = K2 / 256;
+#define IGI_LAT(KQ_) IGI_LAUNCH((k_latent_dgrad<KQ_, 8>), dim3(nb), dim3(256), 0, s, dz, ldz, w1p, p.xld, \
+                                        p.obs, xcat, dxcat, mb, rpw)
+      if (kq == 1) IGI_LAT(1); else if (kq == 2) IGI_LAT(2); else if (kq == 3) IGI_LAT(3); else IGI_LAT(4);
+#undef IGI_LAT
+      break;
+    }
+    case LAT_GENERIC: {
+      GemmArgs g;
+      g.A = dz; g.lda = ldz;
+      g.B = w1p; g.ldb = p.xld;
+      g.M = mb; g.N = p.xld; g.K = K2;
+      g.C = dxcat; g.ldc = p.xld;
+      g.aux = xcat; g.ldaux = p.xld;
+      g.epilogue = EPI_TANHGRAD;
+      IGI_HIP_TRY(gemm(g, true, false, s));
+      break;
+    }
+  }
+  if (p.ct_P > 0) {   // contact encoder backward from d(pre-tanh) of its columns of dxcat
+    const hipError_t e = contact_backward(cta, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+// backward through env_mlp (its last layer is already done when k_latent_bwd ran), then the closing group: the weight
+// gradients still pending (the first env layer's, the first trunk layer's)
+static int env_backward(const TeacherPlan& p, const StepPaths& q, const igi_teacher_state* st, PendingWgrads& pend,
+                        hipStream_t s) {
+  const float* P = st->params;
+  const int mb = p.mb, pld = ru4(p.priv);
+  float *priv_g = wsp<float>(st, p.w_priv), *xcat = wsp<float>(st, p.w_xcat), *dxcat = wsp<float>(st, p.w_dxcat);
+  float* slab = wsp<float>(st, p.w_slab);
+  for (int l = p.npl - 1 - p.lat_fused; l >= 0 && !p.ct_only; --l) {
     const int out = p.pu[l], in = env_in(p, l);
     const bool last = (l == p.npl - 1);
     const float* dz = last ? dxcat + p.obs : wsp<float>(st, p.w_de[l]);
@@ -2026,7 +2033,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
         r.lx_X = priv_g; r.lx_ld = pld;
         r.lx_W = slab + p.s_envW[0]; r.lx_ldw = env_in(p, 0); r.lx_sPart = (long long)p.pu[0] * env_in(p, 0);
         r.lx_B = slab + p.s_envB[0]; r.lx_bsPart = p.pu[0];
-        if (p.latz && latent_rowdot(p, st)) {
+        if (q.latz) {
           // dZ of this layer is formed in the kernel from the latent row dots: it stages the layer's OUTPUT activations instead
           r.dZ = wsp<float>(st, p.w_e[1]); r.ldz = ru4(p.pu[1]);
           r.lz_parts = wsp<float>(st, p.w_lat_rowdot); r.lz_tiles = p.lat_tiles; r.lz_tstride = (long long)mb * 8;
@@ -2049,7 +2056,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
       g.Cbias = slab + p.s_envB[l];
       g.splitk = p.sk_env[l];
       g.sCsplit = (long long)out * in; g.sCbiasSplit = out;
-      wgrads[n_wgrads++] = g;
+      pend.g[pend.n++] = g;
     }
     if (l > 0) {
       GemmArgs g;
@@ -2059,16 +2066,20 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
       g.C = wsp<float>(st, p.w_de[l - 1]); g.ldc = ru4(in);
       g.aux = wsp<float>(st, p.w_e[l - 1]); g.ldaux = ru4(in);
       g.epilogue = EPI_TANHGRAD;
-      g_multi_level = (p.npl == 3 && l == 1) ? 2 : 4;
-      IGI_HIP_TRY(gemm_level(g, wgrads, n_wgrads, s));   // + this layer's (and the first trunk layer's) weight gradient
-      n_wgrads = 0;
+      IGI_HIP_TRY(gemm_level(g, pend.g, pend.n, s, q.cls_env[l]));   // + this layer's (and the first trunk layer's) weight gradient
+      pend.n = 0;
     }
   }
+  IGI_HIP_TRY(gemm_wgrad_group(pend.g, pend.n, s, q.cls_closing));
+  pend.n = 0;
+  return 0;
+}
 
-  g_multi_level = (p.npl == 3 && phase != 0) ? ((p.rb_env[1] && !(p.lw_parts > 0 && latent_rowdot(p, st))) ? 5 : 3) : 4;
-  IGI_HIP_TRY(gemm_wgrad_group(wgrads, n_wgrads, s));
-
-  // ---- assemble the flat gradient
+// assemble the flat gradient: the segment table of this phase's partial sets, summed by k_slab_reduce
+static int assemble_gradient(const TeacherPlan& p, const StepPaths& q, const igi_teacher_state* st, bool do0, bool do1,
+                             hipStream_t s) {
+  const int H = p.u[p.nl - 1];
+  const float* slab = wsp<float>(st, p.w_slab);
   SegTable t;
   t.n = 0;
   bool seg_overflow = false;   // a table that is full refuses the step: nothing is ever written past s[MAX_SEG - 1]
@@ -2096,7 +2107,7 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
   if (p.lat_fused && do1) {
     const int H2 = p.pu[p.npl - 2], pc = 8 * H2 + 8;
     const float* part = wsp<float>(st, p.w_lat_part);
-    const int nrec = (p.latz && latent_rowdot(p, st)) ? p.rb_env[1] : p.lat_blocks;   // LATZ: one record per row range
+    const int nrec = q.latz ? p.rb_env[1] : p.lat_blocks;   // LATZ: one record per row range
     add(p.o_envW[p.npl - 1], part, pc, 1, 8 * H2, 0, nrec);
     add(p.o_envB[p.npl - 1], part + 8 * H2, pc, 1, 8, 0, nrec);
   }
@@ -2127,6 +2138,38 @@ static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro,
     IGI_LAUNCH(k_slab_reduce, dim3(SLAB_GX, t.n), dim3(RED_THREADS), 0, s, t, st->grads);
   }
   return (int)hipGetLastError();
+}
+
+// skip_gather: the previous step's fused tail (k_adam_gather) already gathered + normalised this minibatch
+static int teacher_fwd_bwd(const igi_teacher_cfg* c, const igi_rollout* ro, const igi_teacher_state* st, int mb_index, int step_slot,
+                           hipStream_t s, int phase = -1, bool skip_gather = false, const igi_kl_stop* ks = nullptr) {
+  TeacherPlan p;
+  int rc = make_plan(c, &p);
+  if (rc) return rc;
+  if ((rc = check_state(p, st))) return rc;
+  if ((rc = check_ks(ks, st, c))) return rc;
+  if (!ro || !ro->obses || !ro->priv_info || !ro->actions || !ro->neglogpacs || !st->grads ||
+      !st->perm || !st->rms_obs || !st->rms_priv || !st->stats || !st->advantages ||
+      mb_index < 0 || mb_index >= p.nmb || step_slot < 0 || (p.ct_P > 0 && !ro->contacts))
+    return IGI_E_BADARG;
+  if (mb_index != step_slot % p.nmb || step_slot >= p.E * p.nmb) return IGI_E_BADARG;  // canonical step order
+  if (phase < -1 || phase > 1) return IGI_E_BADARG;
+  const bool do0 = phase != 1, do1 = phase != 0;
+  // KL early stopping: what runs ahead of the step's decision looks at the word an EARLIER step left; step 0 has none
+  // (the word still holds the previous update's result)
+  const int32_t* stop = kl_stop_on(ks) && step_slot > 0 ? ks->stop_state : nullptr;
+  const ContactArgs cta = p.ct_P > 0 ? contact_args(p, st, ro->contacts, st->perm, (long long)mb_index * p.mb, p.mb) : ContactArgs();
+  // (from the plan and the state's addresses alone: phase 0 and phase 1 of a step resolve the same paths)
+  const StepPaths q = resolve_paths(p, st);
+  PendingWgrads pend;
+  if (do0 && !skip_gather) gather_stage(p, ro, st, mb_index, step_slot, stop, s);
+  // forward trunk (models_split.py:166-232), then heads + loss + head backward
+  if (do0 && (rc = trunk_forward(p, st, p.mb, false, s, p.loss_fused ? p.nl - 1 : p.nl, p.ct_P > 0 ? &cta : nullptr))) return rc;
+  if (do0 && (rc = loss_stage(p, c, ro, st, mb_index, dz_ld(p, p.nl - 1), dz_stride(p, p.nl - 1), s, stop))) return rc;
+  if ((rc = trunk_backward(p, q, st, do0, do1, pend, s))) return rc;
+  if (do1 && (rc = latent_backward(p, q, st, cta, s))) return rc;
+  if (do1 && (rc = env_backward(p, q, st, pend, s))) return rc;
+  return assemble_gradient(p, q, st, do0, do1, s);
 }
 
 // The scheduler launch behind the last optimizer step (step_slot) of a mini-epoch; the modes are k_lr_schedule's.
