@@ -614,7 +614,7 @@ int64_t igi_token_param_count(const igi_token_cfg* cfg) {
   igi::TokenPlan p;
   int rc = igi::make_token_plan(cfg, &p);
   if (rc) return fail(rc, "igi_token_param_count");
-  return p.per_layer * p.L;
+  return p.lay.per_layer * p.L;
 }
 
 size_t igi_token_workspace_bytes(const igi_token_cfg* cfg) {

@@ -7,18 +7,21 @@
 //
 // Rows are tokens, sample-major (row = b * S + s); every Linear is a row-wise product and runs on the
 // MFMA GEMMs (linear.h: igi_linear_forward / backward with deterministic split sums for the weight
-// gradients); everything else is a handful of small fused kernels:
-//   k_resid_ln_fwd : residual add (+ dropout of the branch) fused with the NEXT LayerNorm; a 32-lane half
-//                    wave owns a row (lane = feature), statistics by DPP row sums
-//   k_attn_fwd/bwd : softmax(q k^T / sqrt(16)) v for an S x S block per (sample, head); 16 lanes own a
-//                    (sample, head) pair, lane = head dimension, dot products are 16-lane DPP row sums;
-//                    backward recomputes the probabilities (nothing S x S is ever stored); S <= 8
+// gradients); everything else is a handful of small fused kernels around the routines of token_math.h:
+//   k_resid_ln_fwd : residual add (+ dropout of the branch) fused with the NEXT LayerNorm (ln_fwd); a 32-lane
+//                    half wave owns a row (lane = feature), statistics by DPP row sums
+//   k_attn_fwd/bwd : softmax(q k^T / sqrt(16)) v for an S x S block per (sample, head) (attn_ctx_row / attn_bwd);
+//                    16 lanes own a (sample, head) pair, lane = head dimension; backward recomputes the
+//                    probabilities (nothing S x S is ever stored); S <= 8
 //   k_attn_tile_fwd/bwd : the same for 9 <= S <= 32: a wave owns a (sample, head) pair, the S x S block is one padded
 //                    32 x 32 tile of v_mfma_f32_32x32x2_f32, S a runtime argument
-//   k_gelu_fwd/bwd : exact (erf) GELU + dropout
-//   k_ln_bwd       : LayerNorm backward + residual gradient add + (optionally) the dropout mask of the
+//   k_gelu_fwd/bwd : exact (erf) GELU + dropout (gelu / gelu_grad)
+//   k_ln_bwd       : LayerNorm backward + residual gradient add (ln_bwd) + (optionally) the dropout mask of the
 //                    branch below it; per-block partial sums for the LayerNorm weight / bias gradients,
 //                    reduced in fixed order
+// The one-launch kernels further down (k_token_fwd<S>, k_token_fwd_long, k_token_bwd<S>) carry whole samples through
+// every layer in LDS and call the SAME routines: a kernel of either path only decides where operands are loaded from
+// and where results go (one exception, for registers: step 7 of k_token_bwd).
 // Dropout masks are a counter-based hash of (seed, site, element): backward regenerates them, nothing is stored.
 // Parameter vector per layer, in nn.TransformerEncoderLayer's registration order:
 //   in_proj_weight [3d][d], in_proj_bias [3d], out_proj.weight [d][d], out_proj.bias [d],
@@ -29,23 +32,25 @@
 
 #include "linear.h"
 #include "prof.h"
-#include "tok_hash.h"
+#include "token_math.h"
 
 namespace igi {
 
-constexpr int TOK_D = 32, TOK_DH = 16;
 constexpr int TOK_MAX_S = 8;     // tokens per sample of the register attention kernels (k_attn_fwd<S>, k_token_fwd<S>)
 constexpr int TOK_MAX_SEQ = 32;  // tokens per sample of the tile attention kernels (k_attn_tile_*, k_token_fwd_long)
-constexpr float TOK_LN_EPS = 1e-5f;
 
+// float offsets of a layer's parameters and saved activations: filled once by make_token_plan, handed whole to the kernels
+struct TokLayout {
+  long long per_layer;   // parameters per layer
+  long long o_inw, o_inb, o_ow, o_ob, o_w1, o_b1, o_w2, o_b2, o_n1w, o_n1b, o_n2w, o_n2b;
+  // saved activations per layer (inside a layer's slab of a_layer floats)
+  long long a_x, a_st1, a_xn1, a_qkv, a_ctx, a_x1, a_st2, a_xn2, a_z, a_h, a_layer;
+};
 struct TokenPlan {
   int B, S, d, H, ff, L;
   long long R;           // token rows
   float p;               // dropout probability (0 when not training)
-  long long per_layer;   // parameters per layer
-  long long o_inw, o_inb, o_ow, o_ob, o_w1, o_b1, o_w2, o_b2, o_n1w, o_n1b, o_n2w, o_n2b;
-  // saved activations per layer (float offsets inside a layer's slab)
-  long long a_x, a_st1, a_xn1, a_qkv, a_ctx, a_x1, a_st2, a_xn2, a_z, a_h, a_layer;
+  TokLayout lay;
   // backward scratch (float offsets after the L slabs)
   long long s_g0, s_g1, s_rA, s_rB, s_wide0, s_wide1, s_lnpart, s_lin;
   size_t lin_bytes, total_bytes;
@@ -66,27 +71,28 @@ static int make_token_plan(const igi_token_cfg* c, TokenPlan* p) {
   if (p->R > (1LL << 26)) return IGI_E_UNSUPPORTED;
   p->p = c->training ? c->dropout : 0.f;
   const int d = p->d, ff = p->ff;
+  TokLayout& ly = p->lay;
   long long o = 0;
-  p->o_inw = o; o += 3LL * d * d;
-  p->o_inb = o; o += 3 * d;
-  p->o_ow = o; o += (long long)d * d;
-  p->o_ob = o; o += d;
-  p->o_w1 = o; o += (long long)ff * d;
-  p->o_b1 = o; o += ff;
-  p->o_w2 = o; o += (long long)d * ff;
-  p->o_b2 = o; o += d;
-  p->o_n1w = o; o += d;
-  p->o_n1b = o; o += d;
-  p->o_n2w = o; o += d;
-  p->o_n2b = o; o += d;
-  p->per_layer = o;
+  ly.o_inw = o; o += 3LL * d * d;
+  ly.o_inb = o; o += 3 * d;
+  ly.o_ow = o; o += (long long)d * d;
+  ly.o_ob = o; o += d;
+  ly.o_w1 = o; o += (long long)ff * d;
+  ly.o_b1 = o; o += ff;
+  ly.o_w2 = o; o += (long long)d * ff;
+  ly.o_b2 = o; o += d;
+  ly.o_n1w = o; o += d;
+  ly.o_n1b = o; o += d;
+  ly.o_n2w = o; o += d;
+  ly.o_n2b = o; o += d;
+  ly.per_layer = o;
   const long long R = p->R;
   long long a = 0;
   auto take = [&](long long n) { long long r = a; a += ru4ll(n); return r; };
-  p->a_x = take(R * d); p->a_st1 = take(R * 2); p->a_xn1 = take(R * d); p->a_qkv = take(R * 3 * d);
-  p->a_ctx = take(R * d); p->a_x1 = take(R * d); p->a_st2 = take(R * 2); p->a_xn2 = take(R * d);
-  p->a_z = take(R * ff); p->a_h = take(R * ff);
-  p->a_layer = a;
+  ly.a_x = take(R * d); ly.a_st1 = take(R * 2); ly.a_xn1 = take(R * d); ly.a_qkv = take(R * 3 * d);
+  ly.a_ctx = take(R * d); ly.a_x1 = take(R * d); ly.a_st2 = take(R * 2); ly.a_xn2 = take(R * d);
+  ly.a_z = take(R * ff); ly.a_h = take(R * ff);
+  ly.a_layer = a;
   long long s = a * p->L;
   auto stake = [&](long long n) { long long r = s; s += ru4ll(n); return r; };
   p->ln_blocks = (int)((R + 63) / 64 < 256 ? (R + 63) / 64 : 256);
@@ -100,7 +106,7 @@ static int make_token_plan(const igi_token_cfg* c, TokenPlan* p) {
   // one 100 KB gradient record per workgroup: beyond 1024 of them (>= 21 K samples of three tokens) the backward runs
   // launch by launch on split-row slabs instead, and no record space is reserved
   if (p->bwd_grid > 1024 || p->S > TOK_MAX_S) p->bwd_grid = 0;   // (S > 8: no one-launch backward either)
-  p->s_part = stake((long long)p->bwd_grid * p->per_layer * p->L);   // one gradient record per workgroup
+  p->s_part = stake((long long)p->bwd_grid * ly.per_layer * p->L);   // one gradient record per workgroup
   p->s_lin = stake(0);
   size_t lb = linear_workspace_bytes(R, d, 3 * d);
   const size_t c1 = linear_workspace_bytes(R, d, d), c2 = linear_workspace_bytes(R, d, ff),
@@ -111,43 +117,6 @@ static int make_token_plan(const igi_token_cfg* c, TokenPlan* p) {
   p->lin_bytes = lb;
   p->total_bytes = sizeof(float) * (size_t)s + lb * 4 * (size_t)p->L + 64;   // one Linear workspace per call (deferred sums)
   return 0;
-}
-
-// ---- dropout: keep iff tok_hash(seed, site, index) >= p * 2^32 (tok_hash.h); kept values are scaled by 1/(1-p)
-struct Drop {
-  unsigned long long seed;
-  unsigned int site, thresh;  // thresh = 0: no dropout
-  float scale;
-};
-static inline Drop make_drop(float p, unsigned long long seed, unsigned int site) {
-  Drop d;
-  d.seed = seed; d.site = site;
-  d.thresh = p > 0.f ? (unsigned int)((double)p * 4294967296.0) : 0u;
-  d.scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
-  return d;
-}
-__device__ __forceinline__ Drop make_drop_dev(float p, unsigned long long seed, unsigned int site) {   // = make_drop on the device
-  Drop d;
-  d.seed = seed; d.site = site;
-  d.thresh = p > 0.f ? (unsigned int)((double)p * 4294967296.0) : 0u;
-  d.scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
-  return d;
-}
-__device__ __forceinline__ float drop_apply(const Drop& d, unsigned int idx, float v) {
-  if (d.thresh == 0u) return v;
-  return tok_hash(d.seed, d.site, idx) >= d.thresh ? v * d.scale : 0.f;
-}
-
-__device__ __forceinline__ float row16_sum(float v) {  // sum over the 16-lane DPP row, in every lane
-  v += dpp_mov<0xB1>(v);
-  v += dpp_mov<0x4E>(v);
-  v += dpp_mov<0x141>(v);
-  v += dpp_mov<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ float half32_sum(float v) {  // sum over 32 consecutive lanes
-  v = row16_sum(v);
-  return v + __shfl_xor(v, 16, 64);
 }
 
 // x_out = x_prev + drop(delta)  (delta may be null: x_out = x_prev), then xn = LN(x_out) (gamma may be
@@ -165,11 +134,8 @@ __global__ __launch_bounds__(256) void k_resid_ln_fwd(const float* __restrict__ 
     if (delta) v += drop_apply(dr, (unsigned int)i, delta[i]);
     if (xout) xout[i] = v;
     if (gamma) {
-      const float mean = half32_sum(v) * (1.0f / TOK_D);
-      const float c = v - mean;
-      const float var = half32_sum(c * c) * (1.0f / TOK_D);
-      const float rstd = 1.0f / sqrtf(var + TOK_LN_EPS);
-      xn[i] = c * rstd * gamma[f] + beta[f];
+      float mean, rstd;
+      xn[i] = ln_fwd(v, gamma[f], beta[f], mean, rstd);
       if (f == 0) { stats[2 * r] = mean; stats[2 * r + 1] = rstd; }
     }
   }
@@ -190,15 +156,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd(const float* __restrict__ dxn, c
   float sg = 0.f, sb = 0.f;
   for (long long r = hw; r < R; r += nhw) {
     const long long i = r * TOK_D + f;
-    const float mean = stats[2 * r], rstd = stats[2 * r + 1];
-    const float xhat = (x[i] - mean) * rstd;
-    const float d = dxn[i];
-    sg += d * xhat;
-    sb += d;
-    const float g = d * gm;
-    const float m1 = half32_sum(g) * (1.0f / TOK_D);
-    const float m2 = half32_sum(g * xhat) * (1.0f / TOK_D);
-    const float v = dres[i] + rstd * (g - m1 - xhat * m2);
+    const float v = ln_bwd(dxn[i], x[i], stats[2 * r], stats[2 * r + 1], gm, dres[i], sg, sb);
     dx[i] = v;
     if (dmask) dmask[i] = drop_apply(dr, (unsigned int)i, v);
   }
@@ -220,14 +178,14 @@ __global__ __launch_bounds__(256) void k_drop_copy(const float* __restrict__ src
     dst[i] = drop_apply(dr, (unsigned int)i, src[i]);
 }
 
-// attention core.  16 lanes per (sample, head); lane = head dimension.  qkv row = [q(32) | k(32) | v(32)].
+// attention core (token_math.h: attn_ctx_row / attn_bwd).  16 lanes per (sample, head); lane = head dimension.
+// qkv row = [q(32) | k(32) | v(32)].
 template <int S>
 __global__ __launch_bounds__(256) void k_attn_fwd(const float* __restrict__ qkv, float* __restrict__ ctx, Drop dr,
                                                   long long pairs, int H) {
   const int dl = threadIdx.x & 15;
   const long long g0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
   const long long ng = ((long long)gridDim.x * blockDim.x) >> 4;
-  const float scale = 0.25f;  // 1 / sqrt(16)
   for (long long g = g0; g < pairs; g += ng) {
     const long long b = g / H;
     const int h = (int)(g - b * H);
@@ -238,22 +196,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const float* __restrict__ qkv,
       q[s] = row[0]; k[s] = row[TOK_D]; v[s] = row[2 * TOK_D];
     }
 #pragma unroll
-    for (int i = 0; i < S; ++i) {
-      float sc[S], mx = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < S; ++j) { sc[j] = row16_sum(q[i] * k[j]) * scale; mx = fmaxf(mx, sc[j]); }
-      float den = 0.f;
-#pragma unroll
-      for (int j = 0; j < S; ++j) { sc[j] = __expf(sc[j] - mx); den += sc[j]; }
-      const float inv = 1.0f / den;
-      float o = 0.f;
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-        const float pij = drop_apply(dr, (unsigned int)((g * S + i) * S + j), sc[j] * inv);
-        o += pij * v[j];
-      }
-      ctx[(b * S + i) * TOK_D + h * TOK_DH + dl] = o;
-    }
+    for (int i = 0; i < S; ++i) ctx[(b * S + i) * TOK_D + h * TOK_DH + dl] = attn_ctx_row<S>(q, k, v, i, dr, g);
   }
 }
 
@@ -263,7 +206,6 @@ __global__ __launch_bounds__(256) void k_attn_bwd(const float* __restrict__ qkv,
   const int dl = threadIdx.x & 15;
   const long long g0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
   const long long ng = ((long long)gridDim.x * blockDim.x) >> 4;
-  const float scale = 0.25f;
   for (long long g = g0; g < pairs; g += ng) {
     const long long b = g / H;
     const int h = (int)(g - b * H);
@@ -273,34 +215,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd(const float* __restrict__ qkv,
       const float* row = qkv + (b * S + s) * (3 * TOK_D) + h * TOK_DH + dl;
       q[s] = row[0]; k[s] = row[TOK_D]; v[s] = row[2 * TOK_D];
       dc[s] = dctx[(b * S + s) * TOK_D + h * TOK_DH + dl];
-      dq[s] = 0.f; dk[s] = 0.f; dv[s] = 0.f;
     }
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-      float pr[S], mx = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < S; ++j) { pr[j] = row16_sum(q[i] * k[j]) * scale; mx = fmaxf(mx, pr[j]); }
-      float den = 0.f;
-#pragma unroll
-      for (int j = 0; j < S; ++j) { pr[j] = __expf(pr[j] - mx); den += pr[j]; }
-      const float inv = 1.0f / den;
-      float dp[S], dot = 0.f;
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-        pr[j] *= inv;
-        // the mask factor m_ij in {0, 1/(1-p)}: P_drop = P * m
-        const float m = drop_apply(dr, (unsigned int)((g * S + i) * S + j), 1.0f);
-        dv[j] += pr[j] * m * dc[i];
-        dp[j] = row16_sum(dc[i] * v[j]) * m;     // d(loss)/dP_ij
-        dot += dp[j] * pr[j];
-      }
-#pragma unroll
-      for (int j = 0; j < S; ++j) {
-        const float ds = pr[j] * (dp[j] - dot) * scale;  // d(loss)/d(score_ij) incl. the 1/sqrt(dh)
-        dq[i] += ds * k[j];
-        dk[j] += ds * q[i];
-      }
-    }
+    attn_bwd<S>(q, k, v, dc, dr, g, dq, dk, dv);
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       float* row = dqkv + (b * S + s) * (3 * TOK_D) + h * TOK_DH + dl;
@@ -542,18 +458,15 @@ __global__ __launch_bounds__(AT_THREADS) void k_attn_tile_bwd(const float* __res
 // h = drop(gelu(z)), exact erf form (nn.GELU default / activation="gelu")
 __global__ __launch_bounds__(256) void k_gelu_fwd(const float* __restrict__ z, float* __restrict__ h, Drop dr,
                                                   long long n) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float x = z[i];
-    h[i] = drop_apply(dr, (unsigned int)i, 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)));
-  }
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    h[i] = drop_apply(dr, (unsigned int)i, gelu(z[i]));
 }
 __global__ __launch_bounds__(256) void k_gelu_bwd(const float* __restrict__ dh, const float* __restrict__ z,
                                                   float* __restrict__ dz, Drop dr, long long n) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float x = z[i];
-    const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
-    const float pdf = 0.39894228040143268f * __expf(-0.5f * x * x);
-    dz[i] = drop_apply(dr, (unsigned int)i, dh[i]) * (cdf + x * pdf);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+  {
+    const float gd = gelu_grad(z[i]);
+    dz[i] = drop_apply(dr, (unsigned int)i, dh[i]) * gd;
   }
 }
 
@@ -590,12 +503,12 @@ enum { SITE_ATTN = 0, SITE_SA = 1, SITE_FF_ACT = 2, SITE_FF = 3 };
 // 128 token rows = 128 / S whole samples (at most 32 of them; 14 at S = 9, 4 at S = 32) through every layer with the residual stream,
 // the LayerNorm outputs, q / k / v and the feed-forward activations in LDS; a layer's four weight matrices are brought into
 // LDS once per workgroup and layer; every activation the backward pass reads (TokenPlan::a_*) is written out once.
-// Arithmetic = the separate kernels', operation by operation: the Linears are the same fmaf chains on
-// v_mfma_f32_32x32x2_f32 in the LDS-DMA kernel's k order (K = 32 and 128 are whole k-tiles), LayerNorm is the same
-// half-wave-per-row code, attention the same code as the separate kernel's (S <= 8, k_token_fwd<S>: 16 lanes per (sample,
-// head), k_attn_fwd<S>'s arithmetic; 9 <= S <= 32, k_token_fwd_long: attn_tile_fwd, the routine k_attn_tile_fwd calls, on the
-// LDS rows, the (sample, head) pairs dealt over the waves), the same erf GELU, the same dropout hash on the same element
-// indices -- outputs and saved activations are bit-identical (tests/test_gpu_token_encoder.py, test_gpu_token_encoder_long.py).
+// Arithmetic = the separate kernels', operation by operation, because both call the same routines: the Linears are fmaf
+// chains on v_mfma_f32_32x32x2_f32 in the LDS-DMA kernel's k order (tile32_kdot; K = 32 and 128 are whole k-tiles), LayerNorm
+// is ln_fwd on a half wave per row, attention is attn_ctx_row on 16 lanes per (sample, head) (S <= 8, k_token_fwd<S>) or
+// attn_tile_fwd on the LDS rows, the (sample, head) pairs dealt over the waves (9 <= S <= 32, k_token_fwd_long), GELU is gelu,
+// dropout is drop_apply on the same element indices -- outputs and saved activations are bit-identical
+// (tests/test_gpu_token_encoder.py, test_gpu_token_encoder_long.py).
 // Both kernels are token_fwd_body<S>; S = 0 selects the runtime-S tile attention.
 // ---------------------------------------------------------------------------------------------------------------------
 // Waves per workgroup of the two fused kernels.  A workgroup's time is its chain of ~20 phases per layer, each as wide as the
@@ -618,9 +531,8 @@ constexpr int TF_LDS_FLOATS = 2 * TF_ROWS * TF_LDX + TF_ROWS * TF_LDZ + TF_W_FLO
 
 struct TokFwdArgs {
   const float* x; const float* params; float* y; float* W;   // W: the (aligned) workspace base
-  long long R, per_layer, a_layer;
-  long long o_inw, o_inb, o_ow, o_ob, o_w1, o_b1, o_w2, o_b2, o_n1w, o_n1b, o_n2w, o_n2b;
-  long long a_x, a_st1, a_xn1, a_qkv, a_ctx, a_x1, a_st2, a_xn2, a_z, a_h;
+  long long R;
+  TokLayout lay;
   int S, H, L, rows_per_wg;
   float p; unsigned long long seed;
 };
@@ -652,14 +564,7 @@ __device__ __forceinline__ void token_fwd_body(const TokFwdArgs& a) {
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const float* ap = A + (32 * mt + l31) * lda + 4 * h;
-      const float* bp = Wimg + (32 * nt + l31) * ldw + 4 * h;
-      for (int c = 0; c < K; c += 8) {            // the LDS-DMA kernel's order: k = 8 c + 4 h + j at step j
-        const f32x4 av = *reinterpret_cast<const f32x4*>(ap + c);
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(bp + c);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
-      }
+      tile32_kdot(A + (32 * mt + l31) * lda + 4 * h, Wimg + (32 * nt + l31) * ldw + 4 * h, K, acc);
       const int n = 32 * nt + l31;
       const float b = bias[n];
 #pragma unroll
@@ -671,61 +576,58 @@ __device__ __forceinline__ void token_fwd_body(const TokFwdArgs& a) {
       }
     }
   };
-  // xout = xprev (+ drop(delta)) ; xn = LN(xout): k_resid_ln_fwd's arithmetic on LDS rows
-  auto resid_ln = [&](const float* xprev_g, bool have_delta, const Drop& dr, float* xout_g, const float* gamma, const float* beta,
-                      float* xn_g, float* stats_g) {
+  // bx = xout = xprev (+ drop(delta)), bn = xn = LN(xout) (ln_fwd).  xprev: global rows, or null: bx; delta: LDS rows of pitch
+  // ldd, or null
+  auto resid_ln = [&](const float* xprev_g, const float* delta, int ldd, const Drop& dr, float* xout_g, const float* gamma,
+                      const float* beta, float* xn_g, float* stats_g) __attribute__((always_inline)) {
     for (int row = hw; row < nrows; row += TF_HW) {
       const long long i = (r0 + row) * TOK_D + f;
       float v = xprev_g ? xprev_g[i] : bx[row * TF_LDX + f];
-      if (have_delta) v += drop_apply(dr, (unsigned int)i, bn[row * TF_LDX + f]);
+      if (delta) v += drop_apply(dr, (unsigned int)i, delta[row * ldd + f]);
       bx[row * TF_LDX + f] = v;
-      if (xout_g) xout_g[i] = v;
-      if (gamma) {
-        const float mean = half32_sum(v) * (1.0f / TOK_D);
-        const float c = v - mean;
-        const float var = half32_sum(c * c) * (1.0f / TOK_D);
-        const float rstd = 1.0f / sqrtf(var + TOK_LN_EPS);
-        const float o = c * rstd * gamma[f] + beta[f];
-        bn[row * TF_LDX + f] = o;
-        xn_g[i] = o;
-        if (f == 0) { stats_g[2 * (r0 + row)] = mean; stats_g[2 * (r0 + row) + 1] = rstd; }
-      }
+      xout_g[i] = v;
+      float mean, rstd;
+      const float o = ln_fwd(v, gamma[f], beta[f], mean, rstd);
+      bn[row * TF_LDX + f] = o;
+      xn_g[i] = o;
+      if (f == 0) { stats_g[2 * (r0 + row)] = mean; stats_g[2 * (r0 + row) + 1] = rstd; }
     }
   };
 
-  Drop pending = make_drop_dev(0.f, a.seed, 0);
+  const TokLayout& ly = a.lay;
+  Drop pending = make_drop(0.f, a.seed, 0);
   for (int l = 0; l < a.L; ++l) {
-    const float* P = a.params + (long long)l * a.per_layer;
-    float* A = a.W + (long long)l * a.a_layer;
+    const float* P = a.params + (long long)l * ly.per_layer;
+    float* A = a.W + (long long)l * ly.a_layer;
     // ---- this layer's weights -> LDS (coalesced 16-byte loads); the previous layer's readers are behind its last barrier
     for (int u = tid; u < 3 * TOK_D * 8; u += TF_THREADS)
-      *reinterpret_cast<float4*>(win + (u >> 3) * TF_LDX + 4 * (u & 7)) = *reinterpret_cast<const float4*>(P + a.o_inw + 4 * u);
+      *reinterpret_cast<float4*>(win + (u >> 3) * TF_LDX + 4 * (u & 7)) = *reinterpret_cast<const float4*>(P + ly.o_inw + 4 * u);
     for (int u = tid; u < TOK_D * 8; u += TF_THREADS)
-      *reinterpret_cast<float4*>(wout + (u >> 3) * TF_LDX + 4 * (u & 7)) = *reinterpret_cast<const float4*>(P + a.o_ow + 4 * u);
+      *reinterpret_cast<float4*>(wout + (u >> 3) * TF_LDX + 4 * (u & 7)) = *reinterpret_cast<const float4*>(P + ly.o_ow + 4 * u);
     for (int u = tid; u < TF_FF * 8; u += TF_THREADS)
-      *reinterpret_cast<float4*>(w1 + (u >> 3) * TF_LDX + 4 * (u & 7)) = *reinterpret_cast<const float4*>(P + a.o_w1 + 4 * u);
+      *reinterpret_cast<float4*>(w1 + (u >> 3) * TF_LDX + 4 * (u & 7)) = *reinterpret_cast<const float4*>(P + ly.o_w1 + 4 * u);
     for (int u = tid; u < TOK_D * 32; u += TF_THREADS)
-      *reinterpret_cast<float4*>(w2 + (u >> 5) * TF_LDZ + 4 * (u & 31)) = *reinterpret_cast<const float4*>(P + a.o_w2 + 4 * u);
+      *reinterpret_cast<float4*>(w2 + (u >> 5) * TF_LDZ + 4 * (u & 31)) = *reinterpret_cast<const float4*>(P + ly.o_w2 + 4 * u);
     // ---- x_l = x_{l-1} + drop(ff branch of l - 1) (l == 0: the input), xn1 = LN1(x_l)
-    resid_ln(l == 0 ? a.x : nullptr, l > 0, pending, A + a.a_x, P + a.o_n1w, P + a.o_n1b, A + a.a_xn1, A + a.a_st1);
+    resid_ln(l == 0 ? a.x : nullptr, l > 0 ? bn : nullptr, TF_LDX, pending, A + ly.a_x, P + ly.o_n1w, P + ly.o_n1b, A + ly.a_xn1,
+             A + ly.a_st1);
     __syncthreads();
-    linear(bn, TF_LDX, TOK_D, win, TF_LDX, 3 * TOK_D, P + a.o_inb, bz, TF_LDZ, A + a.a_qkv);
+    linear(bn, TF_LDX, TOK_D, win, TF_LDX, 3 * TOK_D, P + ly.o_inb, bz, TF_LDZ, A + ly.a_qkv);
     __syncthreads();
     if constexpr (S == 0) {
-      // ---- attention: a wave per (sample, head), k_attn_tile_fwd's routine on the LDS rows; context -> bn
-      const Drop da = make_drop_dev(a.p, a.seed, 4 * l + SITE_ATTN);
+      // ---- attention: a wave per (sample, head), attn_tile_fwd on the LDS rows; context -> bn
+      const Drop da = make_drop(a.p, a.seed, 4 * l + SITE_ATTN);
       const int nsamp = nrows / a.S;
       for (int g = wave; g < nsamp * a.H; g += TF_NW) {
         const int bl = g / a.H, hh = g - bl * a.H;
         attn_tile_fwd(bz + bl * a.S * TF_LDZ + hh * TOK_DH, TF_LDZ, a.S, (r0 / a.S + bl) * a.H + hh, da,
-                      bn + bl * a.S * TF_LDX + hh * TOK_DH, TF_LDX, A + a.a_ctx + (r0 + bl * a.S) * TOK_D + hh * TOK_DH);
+                      bn + bl * a.S * TF_LDX + hh * TOK_DH, TF_LDX, A + ly.a_ctx + (r0 + bl * a.S) * TOK_D + hh * TOK_DH);
       }
     } else {
-      // ---- attention: 16 lanes per (sample, head), k_attn_fwd's arithmetic on the LDS rows; context -> bn
-      const Drop da = make_drop_dev(a.p, a.seed, 4 * l + SITE_ATTN);
+      // ---- attention: 16 lanes per (sample, head), attn_ctx_row on the LDS rows; context -> bn
+      const Drop da = make_drop(a.p, a.seed, 4 * l + SITE_ATTN);
       const int dl = tid & 15;
       const int nsamp = nrows / S;
-      const float scale = 0.25f;
       for (int g = tid >> 4; g < nsamp * a.H; g += TF_THREADS / 16) {
         const int bl = g / a.H, hh = g - bl * a.H;
         const long long gg = (r0 / S + bl) * a.H + hh;       // the global (sample, head) index: dropout element indices
@@ -737,64 +639,37 @@ __device__ __forceinline__ void token_fwd_body(const TokFwdArgs& a) {
         }
 #pragma unroll
         for (int i = 0; i < S; ++i) {
-          float sc[S], mx = -INFINITY;
-#pragma unroll
-          for (int j = 0; j < S; ++j) { sc[j] = row16_sum(q[i] * k[j]) * scale; mx = fmaxf(mx, sc[j]); }
-          float den = 0.f;
-#pragma unroll
-          for (int j = 0; j < S; ++j) { sc[j] = __expf(sc[j] - mx); den += sc[j]; }
-          const float inv = 1.0f / den;
-          float o = 0.f;
-#pragma unroll
-          for (int j = 0; j < S; ++j) {
-            const float pij = drop_apply(da, (unsigned int)((gg * S + i) * S + j), sc[j] * inv);
-            o += pij * v[j];
-          }
+          const float o = attn_ctx_row<S>(q, k, v, i, da, gg);
           bn[(bl * S + i) * TF_LDX + hh * TOK_DH + dl] = o;
-          A[a.a_ctx + (r0 + bl * S + i) * TOK_D + hh * TOK_DH + dl] = o;
+          A[ly.a_ctx + (r0 + bl * S + i) * TOK_D + hh * TOK_DH + dl] = o;
         }
       }
     }
     __syncthreads();
-    linear(bn, TF_LDX, TOK_D, wout, TF_LDX, TOK_D, P + a.o_ob, bz, TF_LDZ, nullptr);    // sa branch -> bz[:, 0..31]
+    linear(bn, TF_LDX, TOK_D, wout, TF_LDX, TOK_D, P + ly.o_ob, bz, TF_LDZ, nullptr);    // sa branch -> bz[:, 0..31]
     __syncthreads();
     // ---- x1 = x + drop(sa branch), xn2 = LN2(x1)   (the branch is read from bz here)
-    {
-      const Drop ds = make_drop_dev(a.p, a.seed, 4 * l + SITE_SA);
-      for (int row = hw; row < nrows; row += TF_HW) {
-        const long long i = (r0 + row) * TOK_D + f;
-        float v = bx[row * TF_LDX + f] + drop_apply(ds, (unsigned int)i, bz[row * TF_LDZ + f]);
-        bx[row * TF_LDX + f] = v;
-        A[a.a_x1 + i] = v;
-        const float mean = half32_sum(v) * (1.0f / TOK_D);
-        const float c = v - mean;
-        const float var = half32_sum(c * c) * (1.0f / TOK_D);
-        const float rstd = 1.0f / sqrtf(var + TOK_LN_EPS);
-        const float o = c * rstd * P[a.o_n2w + f] + P[a.o_n2b + f];
-        bn[row * TF_LDX + f] = o;
-        A[a.a_xn2 + i] = o;
-        if (f == 0) { A[a.a_st2 + 2 * (r0 + row)] = mean; A[a.a_st2 + 2 * (r0 + row) + 1] = rstd; }
-      }
-    }
+    resid_ln(nullptr, bz, TF_LDZ, make_drop(a.p, a.seed, 4 * l + SITE_SA), A + ly.a_x1, P + ly.o_n2w, P + ly.o_n2b, A + ly.a_xn2,
+             A + ly.a_st2);
     __syncthreads();
-    linear(bn, TF_LDX, TOK_D, w1, TF_LDX, TF_FF, P + a.o_b1, bz, TF_LDZ, A + a.a_z);
+    linear(bn, TF_LDX, TOK_D, w1, TF_LDX, TF_FF, P + ly.o_b1, bz, TF_LDZ, A + ly.a_z);
     __syncthreads();
     // ---- h = drop(gelu(z)), in place
     {
-      const Drop dg = make_drop_dev(a.p, a.seed, 4 * l + SITE_FF_ACT);
+      const Drop dg = make_drop(a.p, a.seed, 4 * l + SITE_FF_ACT);
       for (int e = tid; e < nrows * TF_FF; e += TF_THREADS) {
         const int row = e >> 7, c = e & 127;
         const float xz = bz[row * TF_LDZ + c];
         const long long i = (r0 + row) * TF_FF + c;
-        const float hv = drop_apply(dg, (unsigned int)i, 0.5f * xz * (1.0f + erff(xz * 0.70710678118654752f)));
+        const float hv = drop_apply(dg, (unsigned int)i, gelu(xz));
         bz[row * TF_LDZ + c] = hv;
-        A[a.a_h + i] = hv;
+        A[ly.a_h + i] = hv;
       }
     }
     __syncthreads();
-    linear(bz, TF_LDZ, TF_FF, w2, TF_LDZ, TOK_D, P + a.o_b2, bn, TF_LDX, nullptr);      // ff branch -> bn
+    linear(bz, TF_LDZ, TF_FF, w2, TF_LDZ, TOK_D, P + ly.o_b2, bn, TF_LDX, nullptr);      // ff branch -> bn
     __syncthreads();
-    pending = make_drop_dev(a.p, a.seed, 4 * l + SITE_FF);
+    pending = make_drop(a.p, a.seed, 4 * l + SITE_FF);
   }
   // ---- y = x1_{L-1} + drop(ff branch)
   for (int row = hw; row < nrows; row += TF_HW) {
@@ -807,6 +682,18 @@ template <int S>
 __global__ __launch_bounds__(TF_THREADS) void k_token_fwd(const TokFwdArgs a) { token_fwd_body<S>(a); }
 // 9 <= a.S <= 32: 128 / S whole samples per workgroup, the (sample, head) pairs dealt over the waves
 __global__ __launch_bounds__(TF_THREADS) void k_token_fwd_long(const TokFwdArgs a) { token_fwd_body<0>(a); }
+
+// Launch of a one-launch kernel: its dynamic LDS is beyond the default limit, so the attribute is set before the first launch
+// (one flag per kernel instantiation).  Inside a ProfScope the launch carries the scope's events (IGI_LAUNCH).
+template <auto KERNEL, typename Args>
+static void tok_launch_lds(int grid, int threads, size_t lds_bytes, hipStream_t s, const Args& a) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    attr = true;
+  }
+  IGI_LAUNCH(KERNEL, dim3(grid), dim3(threads), lds_bytes, s, a);
+}
 
 static inline bool token_fused_enabled() {
   const char* e = getenv("IGI_TOKEN_FUSED");   // read per call (one call per forward pass): the parity test switches it
@@ -821,16 +708,13 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
   if (!x || !params || !y || !workspace) return IGI_E_BADARG;
   if (workspace_bytes < p.total_bytes) return IGI_E_WORKSPACE;
   float* W = tok_ws(workspace);
+  const TokLayout& ly = p.lay;
   // (the alignment terms are linear_forward's conditions for the LDS-DMA kernel, whose k order the fused kernel reproduces)
   if (token_fused_enabled() && p.ff == TF_FF && p.d == TOK_D && p.R >= 4 && aligned16(params) && !bf16_mode() &&
-      ((p.per_layer | p.o_inw | p.o_ow | p.o_w1 | p.o_w2 | p.a_layer | p.a_xn1 | p.a_ctx | p.a_xn2 | p.a_h) & 3) == 0) {
+      ((ly.per_layer | ly.o_inw | ly.o_ow | ly.o_w1 | ly.o_w2 | ly.a_layer | ly.a_xn1 | ly.a_ctx | ly.a_xn2 | ly.a_h) & 3) == 0) {
     TokFwdArgs a;
     a.x = x; a.params = params; a.y = y; a.W = W;
-    a.R = p.R; a.per_layer = p.per_layer; a.a_layer = p.a_layer;
-    a.o_inw = p.o_inw; a.o_inb = p.o_inb; a.o_ow = p.o_ow; a.o_ob = p.o_ob; a.o_w1 = p.o_w1; a.o_b1 = p.o_b1;
-    a.o_w2 = p.o_w2; a.o_b2 = p.o_b2; a.o_n1w = p.o_n1w; a.o_n1b = p.o_n1b; a.o_n2w = p.o_n2w; a.o_n2b = p.o_n2b;
-    a.a_x = p.a_x; a.a_st1 = p.a_st1; a.a_xn1 = p.a_xn1; a.a_qkv = p.a_qkv; a.a_ctx = p.a_ctx; a.a_x1 = p.a_x1;
-    a.a_st2 = p.a_st2; a.a_xn2 = p.a_xn2; a.a_z = p.a_z; a.a_h = p.a_h;
+    a.R = p.R; a.lay = ly;
     a.S = p.S; a.H = p.H; a.L = p.L; a.p = p.p; a.seed = seed;
     // samples per workgroup: up to 128 token rows, but no fewer than one workgroup per CU while the batch allows it (2048
     // samples x 3 tokens as 64 workgroups of 96 rows ran 78 us; a workgroup's time is its serial chain of phases)
@@ -840,28 +724,15 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
     const int grid = (int)((p.B + samples - 1) / samples);
     // algorithmic work of the stack: the four Linears of a row, the two S x S products of a (sample, head) pair
     const double tok_flops = (double)p.L * (2.0 * p.R * (4.0 * TOK_D * TOK_D + 2.0 * TOK_D * TF_FF) + 4.0 * p.B * p.H * p.S * p.S * TOK_DH);
-    const double tok_bytes = 4.0 * ((double)p.L * p.a_layer + 2.0 * p.R * TOK_D + (double)p.L * p.per_layer);
+    const double tok_bytes = 4.0 * ((double)p.L * ly.a_layer + 2.0 * p.R * TOK_D + (double)p.L * ly.per_layer);
     if (p.S > TOK_MAX_S) {
-      static bool attr_long = false;
-      if (!attr_long) {
-        (void)hipFuncSetAttribute((const void*)k_token_fwd_long, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(sizeof(float) * TF_LDS_FLOATS));
-        attr_long = true;
-      }
       ProfScope ps(PC_TOKEN_FWD_LONG, s, tok_flops, tok_bytes);
-      IGI_LAUNCH(k_token_fwd_long, dim3(grid), dim3(TF_THREADS), sizeof(float) * TF_LDS_FLOATS, s, a);
+      tok_launch_lds<k_token_fwd_long>(grid, TF_THREADS, sizeof(float) * TF_LDS_FLOATS, s, a);
       return (int)hipGetLastError();
     }
     rc = attn_dispatch(p.S, [&](auto sc) {
-      constexpr int SS = decltype(sc)::value;
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_token_fwd<SS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(sizeof(float) * TF_LDS_FLOATS));
-        attr = true;
-      }
       ProfScope ps(PC_TOKEN_FWD, s, tok_flops, tok_bytes);
-      IGI_LAUNCH((k_token_fwd<SS>), dim3(grid), dim3(TF_THREADS), sizeof(float) * TF_LDS_FLOATS, s, a);
+      tok_launch_lds<k_token_fwd<decltype(sc)::value>>(grid, TF_THREADS, sizeof(float) * TF_LDS_FLOATS, s, a);
     });
     if (rc) return rc;
     return (int)hipGetLastError();
@@ -874,37 +745,37 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
   const float* branch = nullptr;  // pending residual branch (ff output of the previous layer)
   Drop pending = make_drop(0.f, seed, 0);
   for (int l = 0; l < p.L; ++l) {
-    const float* P = params + (long long)l * p.per_layer;
-    float* A = W + (long long)l * p.a_layer;
+    const float* P = params + (long long)l * ly.per_layer;
+    float* A = W + (long long)l * ly.a_layer;
     // x_l = x_{l-1} + drop(ff branch of l-1)  (l == 0: copy of the input), xn1 = LN1(x_l)
-    hipLaunchKernelGGL(k_resid_ln_fwd, dim3(rb), dim3(256), 0, s, xin, branch, pending, A + p.a_x, P + p.o_n1w,
-                       P + p.o_n1b, A + p.a_xn1, A + p.a_st1, R);
-    if ((rc = linear_forward(A + p.a_xn1, d, P + p.o_inw, P + p.o_inb, A + p.a_qkv, 3 * d, R, d, 3 * d, LIN_NONE, s)))
+    hipLaunchKernelGGL(k_resid_ln_fwd, dim3(rb), dim3(256), 0, s, xin, branch, pending, A + ly.a_x, P + ly.o_n1w,
+                       P + ly.o_n1b, A + ly.a_xn1, A + ly.a_st1, R);
+    if ((rc = linear_forward(A + ly.a_xn1, d, P + ly.o_inw, P + ly.o_inb, A + ly.a_qkv, 3 * d, R, d, 3 * d, LIN_NONE, s)))
       return rc;
     const long long pairs = (long long)p.B * p.H;
     const Drop da = make_drop(p.p, seed, 4 * l + SITE_ATTN);
     if (p.S > TOK_MAX_S) {
       ProfScope ps(PC_ATTN_TILE_FWD, s, 4.0 * pairs * p.S * p.S * TOK_DH, 4.0 * R * (4.0 * d));
-      IGI_LAUNCH(k_attn_tile_fwd, dim3(tok_blocks(pairs, AT_THREADS / 64)), dim3(AT_THREADS), 0, s, A + p.a_qkv, A + p.a_ctx, da,
+      IGI_LAUNCH(k_attn_tile_fwd, dim3(tok_blocks(pairs, AT_THREADS / 64)), dim3(AT_THREADS), 0, s, A + ly.a_qkv, A + ly.a_ctx, da,
                  pairs, p.H, p.S);
     } else {
       rc = attn_dispatch(p.S, [&](auto sc) {
         constexpr int SS = decltype(sc)::value;
-        hipLaunchKernelGGL((k_attn_fwd<SS>), dim3(tok_blocks(pairs, 16)), dim3(256), 0, s, A + p.a_qkv, A + p.a_ctx, da,
+        hipLaunchKernelGGL((k_attn_fwd<SS>), dim3(tok_blocks(pairs, 16)), dim3(256), 0, s, A + ly.a_qkv, A + ly.a_ctx, da,
                            pairs, p.H);
       });
       if (rc) return rc;
     }
     float* t0 = W + p.s_g0;  // sa branch output (not needed by backward)
-    if ((rc = linear_forward(A + p.a_ctx, d, P + p.o_ow, P + p.o_ob, t0, d, R, d, d, LIN_NONE, s))) return rc;
-    hipLaunchKernelGGL(k_resid_ln_fwd, dim3(rb), dim3(256), 0, s, A + p.a_x, t0, make_drop(p.p, seed, 4 * l + SITE_SA),
-                       A + p.a_x1, P + p.o_n2w, P + p.o_n2b, A + p.a_xn2, A + p.a_st2, R);
-    if ((rc = linear_forward(A + p.a_xn2, d, P + p.o_w1, P + p.o_b1, A + p.a_z, ff, R, d, ff, LIN_NONE, s))) return rc;
-    hipLaunchKernelGGL(k_gelu_fwd, dim3(tok_blocks(R * ff, 256)), dim3(256), 0, s, A + p.a_z, A + p.a_h,
+    if ((rc = linear_forward(A + ly.a_ctx, d, P + ly.o_ow, P + ly.o_ob, t0, d, R, d, d, LIN_NONE, s))) return rc;
+    hipLaunchKernelGGL(k_resid_ln_fwd, dim3(rb), dim3(256), 0, s, A + ly.a_x, t0, make_drop(p.p, seed, 4 * l + SITE_SA),
+                       A + ly.a_x1, P + ly.o_n2w, P + ly.o_n2b, A + ly.a_xn2, A + ly.a_st2, R);
+    if ((rc = linear_forward(A + ly.a_xn2, d, P + ly.o_w1, P + ly.o_b1, A + ly.a_z, ff, R, d, ff, LIN_NONE, s))) return rc;
+    hipLaunchKernelGGL(k_gelu_fwd, dim3(tok_blocks(R * ff, 256)), dim3(256), 0, s, A + ly.a_z, A + ly.a_h,
                        make_drop(p.p, seed, 4 * l + SITE_FF_ACT), R * ff);
     float* t1 = W + p.s_g1;
-    if ((rc = linear_forward(A + p.a_h, ff, P + p.o_w2, P + p.o_b2, t1, d, R, ff, d, LIN_NONE, s))) return rc;
-    xin = A + p.a_x1;
+    if ((rc = linear_forward(A + ly.a_h, ff, P + ly.o_w2, P + ly.o_b2, t1, d, R, ff, d, LIN_NONE, s))) return rc;
+    xin = A + ly.a_x1;
     branch = t1;
     pending = make_drop(p.p, seed, 4 * l + SITE_FF);
   }
@@ -923,9 +794,10 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
 // activations are staged once each, every weight gradient is a 32 x 32 MFMA tile over the workgroup's rows (operands
 // read along the row axis of the LDS arrays), bias / LayerNorm parameter gradients are column sums of the passes that
 // produce their operands.  A workgroup writes ONE record of all parameter gradients; k_slab_reduce sums the records
-// in fixed order (bitwise reproducible, no atomics).  Same formulas as the kernels above (k_ln_bwd, k_attn_bwd,
-// k_gelu_bwd, the dropout hash on the same element numbers); sums associate differently (per-workgroup records instead
-// of split-row slabs), so results agree with the launch-per-operation path to rounding, not bitwise.
+// in fixed order (bitwise reproducible, no atomics).  The formulas are the routines k_ln_bwd and k_gelu_bwd call (ln_bwd,
+// gelu_grad, drop_apply on the same element numbers) and, restated in step 7 for its register count, k_attn_bwd's attn_bwd;
+// sums associate differently (per-workgroup records instead of split-row slabs), so results agree with the
+// launch-per-operation path to rounding, not bitwise.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int TB_LDW = 3 * TOK_D + 4;        // 100: row pitch of the transposed in_proj image
 constexpr int TB_RED = 3 * TB_THREADS;
@@ -934,9 +806,8 @@ constexpr int TB_LDS_FLOATS = 2 * TB_ROWS * TF_LDX + 2 * TB_ROWS * TF_LDZ + TF_F
 
 struct TokBwdArgs {
   const float* dy; const float* params; float* dx; float* W; float* part;
-  long long R, per_layer, a_layer, P;
-  long long o_inw, o_inb, o_ow, o_ob, o_w1, o_b1, o_w2, o_b2, o_n1w, o_n1b, o_n2w, o_n2b;
-  long long a_x, a_st1, a_xn1, a_qkv, a_ctx, a_x1, a_st2, a_xn2, a_z, a_h;
+  long long R, P;        // P: floats of a workgroup's gradient record (all layers)
+  TokLayout lay;
   int S, H, L, rows_per_wg;
   float p; unsigned long long seed;
 };
@@ -960,8 +831,9 @@ __global__ __launch_bounds__(TB_THREADS) void k_token_bwd(const TokBwdArgs a) {
   const int mtiles = (nrows + 31) >> 5;
   const int f = tid & 31, hw = tid >> 5;
   float* G0 = a.part + (long long)blockIdx.x * a.P;
+  const TokLayout& ly = a.lay;
 
-  // C[rows][N] = A[rows][K] . Wimg[N][K]^T (the forward's loop, no bias)
+  // C[rows][N] = A[rows][K] . Wimg[N][K]^T (tile32_kdot like the forward's Linears, no bias)
   auto dgrad = [&](const float* A, int lda, int K, const float* Wimg, int ldw, int N, float* C, int ldc) {
     const int ntiles = N >> 5;
     for (int t = wave; t < mtiles * ntiles; t += TB_NW) {
@@ -969,14 +841,7 @@ __global__ __launch_bounds__(TB_THREADS) void k_token_bwd(const TokBwdArgs a) {
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const float* ap = A + (32 * mt + l31) * lda + 4 * h;
-      const float* bp = Wimg + (32 * nt + l31) * ldw + 4 * h;
-      for (int c = 0; c < K; c += 8) {
-        const f32x4 av = *reinterpret_cast<const f32x4*>(ap + c);
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(bp + c);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
-      }
+      tile32_kdot(A + (32 * mt + l31) * lda + 4 * h, Wimg + (32 * nt + l31) * ldw + 4 * h, K, acc);
 #pragma unroll
       for (int r = 0; r < 16; ++r) C[(32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h) * ldc + 32 * nt + l31] = acc[r];
     }
@@ -1027,19 +892,19 @@ __global__ __launch_bounds__(TB_THREADS) void k_token_bwd(const TokBwdArgs a) {
   for (int row = hw; row < nrows; row += TB_HW) bg[row * TF_LDX + f] = a.dy[(r0 + row) * TOK_D + f];
 
   for (int l = a.L - 1; l >= 0; --l) {
-    const float* P = a.params + (long long)l * a.per_layer;
-    const float* A = a.W + (long long)l * a.a_layer;
-    float* G = G0 + (long long)l * a.per_layer;
+    const float* P = a.params + (long long)l * ly.per_layer;
+    const float* A = a.W + (long long)l * ly.a_layer;
+    float* G = G0 + (long long)l * ly.per_layer;
     // ---- the layer's weights, transposed: image[n = input feature][k = output feature]
     for (int u = tid; u < TOK_D * TF_FF; u += TB_THREADS) {
-      w2t[(u & 127) * TF_LDX + (u >> 7)] = P[a.o_w2 + u];            // linear2.weight [32][128]
-      w1t[(u & 31) * TF_LDZ + (u >> 5)] = P[a.o_w1 + u];             // linear1.weight [128][32]
+      w2t[(u & 127) * TF_LDX + (u >> 7)] = P[ly.o_w2 + u];            // linear2.weight [32][128]
+      w1t[(u & 31) * TF_LDZ + (u >> 5)] = P[ly.o_w1 + u];             // linear1.weight [128][32]
     }
-    for (int u = tid; u < TOK_D * TOK_D; u += TB_THREADS) wot[(u & 31) * TF_LDX + (u >> 5)] = P[a.o_ow + u];
-    for (int u = tid; u < 3 * TOK_D * TOK_D; u += TB_THREADS) wit[(u & 31) * TB_LDW + (u >> 5)] = P[a.o_inw + u];
+    for (int u = tid; u < TOK_D * TOK_D; u += TB_THREADS) wot[(u & 31) * TF_LDX + (u >> 5)] = P[ly.o_ow + u];
+    for (int u = tid; u < 3 * TOK_D * TOK_D; u += TB_THREADS) wit[(u & 31) * TB_LDW + (u >> 5)] = P[ly.o_inw + u];
     // ---- 1. dff = mask_ff(dres); db2
     {
-      const Drop dr = make_drop_dev(a.p, a.seed, 4 * l + SITE_FF);
+      const Drop dr = make_drop(a.p, a.seed, 4 * l + SITE_FF);
       float sb = 0.f;
       for (int row = hw; row < nrows; row += TB_HW) {
         const float v = drop_apply(dr, (unsigned int)((r0 + row) * TOK_D + f), bg[row * TF_LDX + f]);
@@ -1048,25 +913,23 @@ __global__ __launch_bounds__(TB_THREADS) void k_token_bwd(const TokBwdArgs a) {
       }
       put32(0, sb);
     }
-    stage(A + a.a_h, TF_FF, ba, TF_LDZ);
+    stage(A + ly.a_h, TF_FF, ba, TF_LDZ);
     __syncthreads();
-    sum32(0, G + a.o_b2);
+    sum32(0, G + ly.o_b2);
     // ---- 2. dW2 = dff^T h; dh = dff W2
-    wgrad(bd, TF_LDX, TOK_D, ba, TF_LDZ, TF_FF, G + a.o_w2);
+    wgrad(bd, TF_LDX, TOK_D, ba, TF_LDZ, TF_FF, G + ly.o_w2);
     dgrad(bd, TF_LDX, TOK_D, w2t, TF_LDX, TF_FF, bw, TF_LDZ);
     __syncthreads();
-    stage(A + a.a_z, TF_FF, ba, TF_LDZ);
+    stage(A + ly.a_z, TF_FF, ba, TF_LDZ);
     __syncthreads();
     // ---- 3. dz = mask_act(dh) gelu'(z); db1
     {
-      const Drop dr = make_drop_dev(a.p, a.seed, 4 * l + SITE_FF_ACT);
+      const Drop dr = make_drop(a.p, a.seed, 4 * l + SITE_FF_ACT);
       const int c = tid & 127;
       float sb = 0.f;
       for (int row = tid >> 7; row < nrows; row += TB_THREADS / 128) {
-        const float x = ba[row * TF_LDZ + c];
-        const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
-        const float pdf = 0.39894228040143268f * __expf(-0.5f * x * x);
-        const float v = drop_apply(dr, (unsigned int)((r0 + row) * TF_FF + c), bw[row * TF_LDZ + c]) * (cdf + x * pdf);
+        const float gd = gelu_grad(ba[row * TF_LDZ + c]);
+        const float v = drop_apply(dr, (unsigned int)((r0 + row) * TF_FF + c), bw[row * TF_LDZ + c]) * gd;
         bw[row * TF_LDZ + c] = v;
         sb += v;
       }
@@ -1077,30 +940,23 @@ __global__ __launch_bounds__(TB_THREADS) void k_token_bwd(const TokBwdArgs a) {
       float t = red[tid];
 #pragma unroll
       for (int q = 1; q < TB_THREADS / 128; ++q) t += red[128 * q + tid];
-      G[a.o_b1 + tid] = t;
+      G[ly.o_b1 + tid] = t;
     }
-    stage(A + a.a_xn2, TOK_D, ba, TF_LDZ);
+    stage(A + ly.a_xn2, TOK_D, ba, TF_LDZ);
     __syncthreads();
     // ---- 4. dW1 = dz^T xn2; dxn2 = dz W1
-    wgrad(bw, TF_LDZ, TF_FF, ba, TF_LDZ, TOK_D, G + a.o_w1);
+    wgrad(bw, TF_LDZ, TF_FF, ba, TF_LDZ, TOK_D, G + ly.o_w1);
     dgrad(bw, TF_LDZ, TF_FF, w1t, TF_LDZ, TOK_D, bd, TF_LDX);
     __syncthreads();
     // ---- 5. LayerNorm 2 backward + residual: dx1; dsa = mask_sa(dx1); d(norm2), d(out_proj.bias)
     {
-      const Drop dr = make_drop_dev(a.p, a.seed, 4 * l + SITE_SA);
-      const float gm = P[a.o_n2w + f];
+      const Drop dr = make_drop(a.p, a.seed, 4 * l + SITE_SA);
+      const float gm = P[ly.o_n2w + f];
       float sg = 0.f, sb = 0.f, so = 0.f;
       for (int row = hw; row < nrows; row += TB_HW) {
         const long long i = (r0 + row) * TOK_D + f;
-        const float mean = A[a.a_st2 + 2 * (r0 + row)], rstd = A[a.a_st2 + 2 * (r0 + row) + 1];
-        const float xhat = (A[a.a_x1 + i] - mean) * rstd;
-        const float d = bd[row * TF_LDX + f];
-        sg += d * xhat;
-        sb += d;
-        const float g = d * gm;
-        const float m1 = half32_sum(g) * (1.0f / TOK_D);
-        const float m2 = half32_sum(g * xhat) * (1.0f / TOK_D);
-        const float v = bg[row * TF_LDX + f] + rstd * (g - m1 - xhat * m2);
+        const float v = ln_bwd(bd[row * TF_LDX + f], A[ly.a_x1 + i], A[ly.a_st2 + 2 * (r0 + row)], A[ly.a_st2 + 2 * (r0 + row) + 1], gm,
+                               bg[row * TF_LDX + f], sg, sb);
         bg[row * TF_LDX + f] = v;
         const float ds = drop_apply(dr, (unsigned int)i, v);
         bd[row * TF_LDX + f] = ds;
@@ -1108,19 +964,20 @@ __global__ __launch_bounds__(TB_THREADS) void k_token_bwd(const TokBwdArgs a) {
       }
       put32(0, sg); put32(1, sb); put32(2, so);
     }
-    stage(A + a.a_ctx, TOK_D, ba, TF_LDZ);
+    stage(A + ly.a_ctx, TOK_D, ba, TF_LDZ);
     __syncthreads();
-    sum32(0, G + a.o_n2w); sum32(1, G + a.o_n2b); sum32(2, G + a.o_ob);
+    sum32(0, G + ly.o_n2w); sum32(1, G + ly.o_n2b); sum32(2, G + ly.o_ob);
     // ---- 6. dWo = dsa^T ctx; dctx = dsa Wo
-    wgrad(bd, TF_LDX, TOK_D, ba, TF_LDZ, TOK_D, G + a.o_ow);
+    wgrad(bd, TF_LDX, TOK_D, ba, TF_LDZ, TOK_D, G + ly.o_ow);
     dgrad(bd, TF_LDX, TOK_D, wot, TF_LDX, TOK_D, bw, TF_LDZ);
     __syncthreads();
-    // ---- 7. attention backward (k_attn_bwd's arithmetic): dqkv -> ba; d(in_proj.bias)
+    // ---- 7. attention backward: dqkv -> ba; d(in_proj.bias).  The one place that restates token_math.h's attn_bwd instead of
+    // calling it: through the routine k_token_bwd<4> allocates 238 VGPRs, written out 236 (its figure before the routines
+    // existed; 256 is the ceiling).  Keep the two in step: tests/test_gpu_token_encoder_bits.py pins both.
     {
-      const Drop dr = make_drop_dev(a.p, a.seed, 4 * l + SITE_ATTN);
+      const Drop dr = make_drop(a.p, a.seed, 4 * l + SITE_ATTN);
       const int dl = tid & 15, slot = tid >> 4;          // slot parity = head (H == 2)
       const int nsamp = nrows / S;
-      const float scale = 0.25f;
       float sq = 0.f, sk = 0.f, sv = 0.f;
       for (int g = slot; g < nsamp * a.H; g += TB_THREADS / 16) {
         const int bl = g / a.H, hh = g - bl * a.H;
@@ -1128,11 +985,13 @@ __global__ __launch_bounds__(TB_THREADS) void k_token_bwd(const TokBwdArgs a) {
         float q[S], k[S], v[S], dc[S], dq[S], dk[S], dv[S];
 #pragma unroll
         for (int s2 = 0; s2 < S; ++s2) {
-          const float* row = A + a.a_qkv + (r0 + bl * S + s2) * (3 * TOK_D) + hh * TOK_DH + dl;
+          const float* row = A + ly.a_qkv + (r0 + bl * S + s2) * (3 * TOK_D) + hh * TOK_DH + dl;
           q[s2] = row[0]; k[s2] = row[TOK_D]; v[s2] = row[2 * TOK_D];
           dc[s2] = bw[(bl * S + s2) * TF_LDZ + hh * TOK_DH + dl];
-          dq[s2] = 0.f; dk[s2] = 0.f; dv[s2] = 0.f;
         }
+        const float scale = 0.25f;
+#pragma unroll
+        for (int s2 = 0; s2 < S; ++s2) { dq[s2] = 0.f; dk[s2] = 0.f; dv[s2] = 0.f; }
 #pragma unroll
         for (int i = 0; i < S; ++i) {
           float pr[S], mx = -INFINITY;
@@ -1173,34 +1032,27 @@ __global__ __launch_bounds__(TB_THREADS) void k_token_bwd(const TokBwdArgs a) {
       float t = 0.f;
 #pragma unroll
       for (int q = 0; q < TB_THREADS / 32; ++q) t += red[TB_THREADS * which + (2 * q + hh) * 16 + dl];   // the slots of head hh, in order
-      G[a.o_inb + tid] = t;
+      G[ly.o_inb + tid] = t;
     }
-    stage(A + a.a_xn1, TOK_D, bw, TF_LDZ);
+    stage(A + ly.a_xn1, TOK_D, bw, TF_LDZ);
     __syncthreads();
     // ---- 8. dWin = dqkv^T xn1; dxn1 = dqkv Win
-    wgrad(ba, TF_LDZ, 3 * TOK_D, bw, TF_LDZ, TOK_D, G + a.o_inw);
+    wgrad(ba, TF_LDZ, 3 * TOK_D, bw, TF_LDZ, TOK_D, G + ly.o_inw);
     dgrad(ba, TF_LDZ, 3 * TOK_D, wit, TB_LDW, TOK_D, bd, TF_LDX);
     __syncthreads();
     // ---- 9. LayerNorm 1 backward + residual: the gradient of this layer's input; d(norm1)
     {
-      const float gm = P[a.o_n1w + f];
+      const float gm = P[ly.o_n1w + f];
       float sg = 0.f, sb = 0.f;
       for (int row = hw; row < nrows; row += TB_HW) {
         const long long i = (r0 + row) * TOK_D + f;
-        const float mean = A[a.a_st1 + 2 * (r0 + row)], rstd = A[a.a_st1 + 2 * (r0 + row) + 1];
-        const float xhat = (A[a.a_x + i] - mean) * rstd;
-        const float d = bd[row * TF_LDX + f];
-        sg += d * xhat;
-        sb += d;
-        const float g = d * gm;
-        const float m1 = half32_sum(g) * (1.0f / TOK_D);
-        const float m2 = half32_sum(g * xhat) * (1.0f / TOK_D);
-        bg[row * TF_LDX + f] += rstd * (g - m1 - xhat * m2);
+        bg[row * TF_LDX + f] = ln_bwd(bd[row * TF_LDX + f], A[ly.a_x + i], A[ly.a_st1 + 2 * (r0 + row)], A[ly.a_st1 + 2 * (r0 + row) + 1],
+                                      gm, bg[row * TF_LDX + f], sg, sb);
       }
       put32(0, sg); put32(1, sb);
     }
     __syncthreads();
-    sum32(0, G + a.o_n1w); sum32(1, G + a.o_n1b);
+    sum32(0, G + ly.o_n1w); sum32(1, G + ly.o_n1b);
     // (the next layer's first pass reads bg rows this thread wrote and writes red slot 0 after its weights loop; the
     //  sums above read red: one more barrier keeps them apart)
     __syncthreads();
@@ -1223,31 +1075,21 @@ static int token_backward(const igi_token_cfg* c, const float* dy, const float* 
   if (!dy || !params || !dx || !grads || !workspace) return IGI_E_BADARG;
   if (workspace_bytes < p.total_bytes) return IGI_E_WORKSPACE;
   float* W = tok_ws(workspace);
+  const TokLayout& ly = p.lay;
   // (S <= TB_FUSED_MAX_S: with five or more tokens per sample the attention pass of k_token_bwd holds more than 256 registers
   //  -- 88 to 940 bytes of scratch per lane in the S = 5 .. 8 instantiations -- so those run the launch-per-operation
   //  backward below, which does not spill; the instantiations are not built)
   if (token_bwd_fused_enabled() && p.S <= TB_FUSED_MAX_S && p.bwd_grid > 0 && p.ff == TF_FF && p.d == TOK_D && p.H == 2 && !bf16_mode() &&
-      ((p.a_layer | p.a_xn1 | p.a_ctx | p.a_xn2 | p.a_h | p.a_z) & 3) == 0) {
+      ((ly.a_layer | ly.a_xn1 | ly.a_ctx | ly.a_xn2 | ly.a_h | ly.a_z) & 3) == 0) {
     TokBwdArgs a;
     a.dy = dy; a.params = params; a.dx = dx; a.W = W; a.part = W + p.s_part;
-    a.R = p.R; a.per_layer = p.per_layer; a.a_layer = p.a_layer; a.P = p.per_layer * p.L;
-    a.o_inw = p.o_inw; a.o_inb = p.o_inb; a.o_ow = p.o_ow; a.o_ob = p.o_ob; a.o_w1 = p.o_w1; a.o_b1 = p.o_b1;
-    a.o_w2 = p.o_w2; a.o_b2 = p.o_b2; a.o_n1w = p.o_n1w; a.o_n1b = p.o_n1b; a.o_n2w = p.o_n2w; a.o_n2b = p.o_n2b;
-    a.a_x = p.a_x; a.a_st1 = p.a_st1; a.a_xn1 = p.a_xn1; a.a_qkv = p.a_qkv; a.a_ctx = p.a_ctx; a.a_x1 = p.a_x1;
-    a.a_st2 = p.a_st2; a.a_xn2 = p.a_xn2; a.a_z = p.a_z; a.a_h = p.a_h;
+    a.R = p.R; a.lay = ly; a.P = ly.per_layer * p.L;
     a.S = p.S; a.H = p.H; a.L = p.L; a.p = p.p; a.seed = seed;
     a.rows_per_wg = p.bwd_samples * p.S;
     rc = attn_dispatch(p.S, [&](auto sc) {
       constexpr int SS = decltype(sc)::value;
-      if constexpr (SS <= TB_FUSED_MAX_S) {
-        static bool attr = false;
-        if (!attr) {
-          (void)hipFuncSetAttribute((const void*)k_token_bwd<SS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(sizeof(float) * TB_LDS_FLOATS));
-          attr = true;
-        }
-        hipLaunchKernelGGL((k_token_bwd<SS>), dim3(p.bwd_grid), dim3(TB_THREADS), sizeof(float) * TB_LDS_FLOATS, s, a);
-      }
+      if constexpr (SS <= TB_FUSED_MAX_S)
+        tok_launch_lds<k_token_bwd<SS>>(p.bwd_grid, TB_THREADS, sizeof(float) * TB_LDS_FLOATS, s, a);
     });
     if (rc) return rc;
     SegTable t;
@@ -1283,57 +1125,57 @@ static int token_backward(const igi_token_cfg* c, const float* dy, const float* 
     dbr = dy;
   }
   for (int l = p.L - 1; l >= 0; --l) {
-    const float* P = params + (long long)l * p.per_layer;
-    float* G = grads + (long long)l * p.per_layer;
-    float* A = W + (long long)l * p.a_layer;
+    const float* P = params + (long long)l * ly.per_layer;
+    float* G = grads + (long long)l * ly.per_layer;
+    float* A = W + (long long)l * ly.a_layer;
     // ---- ff block: f = linear2(h)
-    if ((rc = linear_backward(A + p.a_h, ff, P + p.o_w2, nullptr, 0, dbr, d, w0, ff, G + p.o_w2, G + p.o_b2, R, ff, d,
+    if ((rc = linear_backward(A + ly.a_h, ff, P + ly.o_w2, nullptr, 0, dbr, d, w0, ff, G + ly.o_w2, G + ly.o_b2, R, ff, d,
                               LIN_NONE, lin_ws_next(), p.lin_bytes, s, &sums)))
       return rc;
-    hipLaunchKernelGGL(k_gelu_bwd, dim3(tok_blocks(R * ff, 256)), dim3(256), 0, s, w0, A + p.a_z, w1,
+    hipLaunchKernelGGL(k_gelu_bwd, dim3(tok_blocks(R * ff, 256)), dim3(256), 0, s, w0, A + ly.a_z, w1,
                        make_drop(p.p, seed, 4 * l + SITE_FF_ACT), R * ff);
-    if ((rc = linear_backward(A + p.a_xn2, d, P + p.o_w1, nullptr, 0, w1, ff, g0, d, G + p.o_w1, G + p.o_b1, R, d, ff,
+    if ((rc = linear_backward(A + ly.a_xn2, d, P + ly.o_w1, nullptr, 0, w1, ff, g0, d, G + ly.o_w1, G + ly.o_b1, R, d, ff,
                               LIN_NONE, lin_ws_next(), p.lin_bytes, s, &sums)))
       return rc;
     // ---- LN2 backward + residual: dx1 and its masked copy for the sa branch (g1)
     float* dx1 = rB;
     float* lnpart = lnpart_next();
-    hipLaunchKernelGGL(k_ln_bwd, dim3(p.ln_blocks), dim3(256), 0, s, g0, A + p.a_x1, A + p.a_st2, P + p.o_n2w, dres,
+    hipLaunchKernelGGL(k_ln_bwd, dim3(p.ln_blocks), dim3(256), 0, s, g0, A + ly.a_x1, A + ly.a_st2, P + ly.o_n2w, dres,
                        dx1, make_drop(p.p, seed, 4 * l + SITE_SA), p.p > 0.f ? g1 : (float*)nullptr, lnpart, R);
     // norm2.weight and norm2.bias are adjacent
-    if (!split_sum_defer(sums, G + p.o_n2w, lnpart, 2LL * d, 2LL * d, p.ln_blocks))
-      split_sum(G + p.o_n2w, lnpart, 2LL * d, p.ln_blocks, 2LL * d, s);
+    if (!split_sum_defer(sums, G + ly.o_n2w, lnpart, 2LL * d, 2LL * d, p.ln_blocks))
+      split_sum(G + ly.o_n2w, lnpart, 2LL * d, p.ln_blocks, 2LL * d, s);
     const float* da = p.p > 0.f ? g1 : dx1;
     // ---- sa block: a = out_proj(ctx)
-    if ((rc = linear_backward(A + p.a_ctx, d, P + p.o_ow, nullptr, 0, da, d, g0, d, G + p.o_ow, G + p.o_ob, R, d, d,
+    if ((rc = linear_backward(A + ly.a_ctx, d, P + ly.o_ow, nullptr, 0, da, d, g0, d, G + ly.o_ow, G + ly.o_ob, R, d, d,
                               LIN_NONE, lin_ws_next(), p.lin_bytes, s, &sums)))
       return rc;
     const long long pairs = (long long)p.B * p.H;
     const Drop datt = make_drop(p.p, seed, 4 * l + SITE_ATTN);
     if (p.S > TOK_MAX_S) {
       ProfScope ps(PC_ATTN_TILE_BWD, s, 12.0 * pairs * p.S * p.S * TOK_DH, 4.0 * R * (7.0 * d));
-      IGI_LAUNCH(k_attn_tile_bwd, dim3(tok_blocks(pairs, AT_THREADS / 64)), dim3(AT_THREADS), 0, s, A + p.a_qkv, g0, w1, datt,
+      IGI_LAUNCH(k_attn_tile_bwd, dim3(tok_blocks(pairs, AT_THREADS / 64)), dim3(AT_THREADS), 0, s, A + ly.a_qkv, g0, w1, datt,
                  pairs, p.H, p.S);
     } else {
       rc = attn_dispatch(p.S, [&](auto sc) {
         constexpr int SS = decltype(sc)::value;
-        hipLaunchKernelGGL((k_attn_bwd<SS>), dim3(tok_blocks(pairs, 16)), dim3(256), 0, s, A + p.a_qkv, g0, w1, datt,
+        hipLaunchKernelGGL((k_attn_bwd<SS>), dim3(tok_blocks(pairs, 16)), dim3(256), 0, s, A + ly.a_qkv, g0, w1, datt,
                            pairs, p.H);
       });
       if (rc) return rc;
     }
-    if ((rc = linear_backward(A + p.a_xn1, d, P + p.o_inw, nullptr, 0, w1, 3 * d, g0, d, G + p.o_inw, G + p.o_inb, R, d,
+    if ((rc = linear_backward(A + ly.a_xn1, d, P + ly.o_inw, nullptr, 0, w1, 3 * d, g0, d, G + ly.o_inw, G + ly.o_inb, R, d,
                               3 * d, LIN_NONE, lin_ws_next(), p.lin_bytes, s, &sums)))
       return rc;
     // ---- LN1 backward + residual: gradient of this layer's input; masked copy for the ff branch of l-1
     float* dxl = (l == 0) ? dx : rA;
     const bool mask_below = (l > 0) && p.p > 0.f;
     lnpart = lnpart_next();
-    hipLaunchKernelGGL(k_ln_bwd, dim3(p.ln_blocks), dim3(256), 0, s, g0, A + p.a_x, A + p.a_st1, P + p.o_n1w, dx1, dxl,
+    hipLaunchKernelGGL(k_ln_bwd, dim3(p.ln_blocks), dim3(256), 0, s, g0, A + ly.a_x, A + ly.a_st1, P + ly.o_n1w, dx1, dxl,
                        make_drop(p.p, seed, 4 * (l - 1) + SITE_FF), mask_below ? g1 : (float*)nullptr, lnpart, R);
     // norm1.weight and norm1.bias are adjacent
-    if (!split_sum_defer(sums, G + p.o_n1w, lnpart, 2LL * d, 2LL * d, p.ln_blocks))
-      split_sum(G + p.o_n1w, lnpart, 2LL * d, p.ln_blocks, 2LL * d, s);
+    if (!split_sum_defer(sums, G + ly.o_n1w, lnpart, 2LL * d, 2LL * d, p.ln_blocks))
+      split_sum(G + ly.o_n1w, lnpart, 2LL * d, p.ln_blocks, 2LL * d, s);
     dres = dxl;
     dbr = mask_below ? g1 : dxl;
   }

@@ -1,10 +1,13 @@
 #!/usr/bin/env python
 """One forward + backward of the student's two-layer token encoder at sequence lengths beyond 8 tokens, beside ATen.
 
-    python tools/bench_token_seq.py [--pairs R] [--iters K] [--control-only] [--out profiles/token_seq.json]
+    python tools/bench_token_seq.py [--pairs R] [--iters K] [--control-only] [--shapes BxS,...] [--root TREE]
+                                    [--out profiles/token_seq.json]
 
 Shapes (B, S): (2048, 12), (2048, 32), (8192, 9) -- the tile attention kernels and k_token_fwd_long -- and (2048, 3), the
-register-attention path, as a control that must not move against the parent commit.  Train mode, dropout 0.1, the weights
+register-attention path, as a control that must not move against the parent commit; --shapes picks others (8192x2: the
+one-launch kernels at full workgroups).  --root: the tree whose package and library to time (default: this one), to set
+another commit's build beside this one in the same job.  Train mode, dropout 0.1, the weights
 of tests/test_gpu_token_encoder.py.  ``HipTransformerEncoder`` and ATen's fp32 ``nn.TransformerEncoder`` (the only other
 implementation of these shapes) run on the same device in R alternating pairs of K iterations each (forward, backward of
 a fixed upstream gradient; device synchronise around every round; ms per iteration).  The two draw different dropout
@@ -18,8 +21,6 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
 
 SHAPES = [(2048, 12), (2048, 32), (8192, 9), (2048, 3)]
 
@@ -48,7 +49,10 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "token_seq.json"))
     ap.add_argument("--control-only", action="store_true", help="time the 2048 x 3 control alone (any commit's build takes it)")
+    ap.add_argument("--shapes", default="", help="comma-separated BxS list instead of the default shapes")
+    ap.add_argument("--root", default=ROOT, help="the tree whose package and library to load")
     args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
     import torch
     import torch.nn as nn
     if not torch.cuda.is_available():
@@ -60,7 +64,8 @@ def main():
     nets = {"hip": HipTransformerEncoder(layer, num_layers=2).cuda().train(),
             "aten": nn.TransformerEncoder(layer, num_layers=2, enable_nested_tensor=False).cuda().train()}
     rows = {}
-    for B, S in (SHAPES[-1:] if args.control_only else SHAPES):
+    shapes = [tuple(int(v) for v in t.split("x")) for t in args.shapes.split(",") if t] or (SHAPES[-1:] if args.control_only else SHAPES)
+    for B, S in shapes:
         g = torch.Generator().manual_seed(B + S)
         x = torch.randn(B, S, 32, generator=g).cuda().requires_grad_(True)
         dy = torch.randn(B, S, 32, generator=g).cuda()
