@@ -760,6 +760,29 @@ int igi_image_pair_augment(const float* img, const float* seg, int64_t n, int t,
                            int out_w, int patch, float noise_std, uint64_t seed, float* out_img, float* out_seg,
                            igi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Train-time augmentation of the offline student's tactile images (csrc/tactile_augment.h), ONE launch from the resident
+ * arena to the batch tensor (_Crop + _TrainAugment + GaussianNoise + Masking of algo/models/transformer/utils.py over a
+ * minibatch).  An image is one (sample, t, finger) plane and has its own parameters:
+ *   arena     : fp32 [n][planes][hs][ws], planes = t * fingers, one channel
+ *   rows      : [b] sample numbers; one outside [0, n) reads as frames of zeros (never outside the arena)
+ *   params    : int32 [b*planes][IGI_TACTILE_AUG_WORDS]: top, left of the crop window (any value; a read outside the stored
+ *               frame gives 0), the jitter flag, then the fp32 bit patterns of brightness b, contrast c and the rotation
+ *               angle in radians.  Flag != 0: x = clamp(x b, 0, 1), m = the image's mean (fixed summation order),
+ *               x = clamp((x - m) c + m, 0, 1); flag 0: the window passes bit for bit.  The rotation is the one of
+ *               igi_image_pair_augment (nearest, round half to even, zero fill outside the window; angle 0 copies) and
+ *               acts on the jittered window
+ *   keep      : uint8 [b*planes][out_h / patch][out_w / patch] or NULL; 0 zeroes that patch; rows and columns past the last
+ *               whole patch are untouched
+ *   noise_std : > 0 adds noise_std * z, z the Box-Muller sample of igi_image_pair_augment on plane p = 2 (hash sites 4 and
+ *               5), e = the element's linear index in out.  A pure function: same arguments, same bits
+ *   out       : fp32 [b][planes][out_h][out_w], out_h <= hs, out_w <= ws; out_h * out_w above 8192: IGI_E_UNSUPPORTED
+ * ---------------------------------------------------------------------------------------- */
+#define IGI_TACTILE_AUG_WORDS 6
+int igi_tactile_augment(const float* arena, int64_t n, int planes, int hs, int ws, const int64_t* rows, int64_t b,
+                        const int32_t* params, const uint8_t* keep, int out_h, int out_w, int patch, float noise_std,
+                        uint64_t seed, float* out, igi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

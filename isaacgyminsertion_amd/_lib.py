@@ -243,6 +243,9 @@ _EXPORTS = {
     "igi_image_pair_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "igi_tactile_augment": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_void_p,
+                                      C.c_void_p]),
     "igi_pointnet_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "igi_pointnet_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),

@@ -383,7 +383,8 @@ class ResidentLoader:
     then every epoch is a ``randperm`` + row gathers on the GPU.  Iterates like the reference's
     ``DataLoader(ds, batch_size, shuffle=True)`` (runner.py:524-551): same 8-tuple per batch, last
     partial batch kept; ``len()`` = number of batches.  ``tactile_transform`` (train-time augmentation)
-    is applied per batch on the device.  ``sync_transform`` (utils.SyncTransform / SyncEvalTransform): the camera pair
+    is applied per batch on the device; one with a ``fused`` method (utils.TactileAugment) builds field 0 of a batch in
+    ONE launch from the resident arena, its random numbers drawn from ``generator``.  ``sync_transform`` (utils.SyncTransform / SyncEvalTransform): the camera pair
     (fields 1 and 2) is stored as logged and every batch of it is ONE ``sync_transform.fused`` launch -- gather, crop,
     rotation, noise, patch masking -- instead of two ``index_select``s; its random numbers come from ``generator``."""
 
@@ -437,6 +438,9 @@ class ResidentLoader:
                     continue
                 if pair is not None and j in (1, 2):
                     batch.append(pair[j - 1])
+                    continue
+                if j == 0 and hasattr(self.tactile_transform, 'fused'):
+                    batch.append(self.tactile_transform.fused(f, idx, self.generator))
                     continue
                 x = f.index_select(0, idx)
                 if j == 0 and self.tactile_transform is not None:

@@ -31,8 +31,8 @@ from .... import ops
 from ....optim import FlatAdam
 from .data import DataNormalizer, ResidentLoader, TactileDataset
 from .tact import MultiModalModel
-from .utils import (SyncCenterReshapeTransform, TactileTransform, define_img_transforms, define_tactile_transforms,
-                    log_output)
+from .utils import (SyncCenterReshapeTransform, TactileTransform, define_img_transforms, define_tactile_augment,
+                    define_tactile_transforms, log_output)
 
 
 class _Schedule:
@@ -106,6 +106,21 @@ class Runner:
             self.cfg.get('tactile_masking_prob', 0.0))
         self.process_tactile = TactileTransform(self.tactile_transform)
         self.eval_process_tactile = TactileTransform(self.tactile_eval_transform)
+        # offline_train.tactile_augment (not a reference key): "torch" (and absent) = the two objects above feed the
+        # loaders; "fused" = a TactileAugment pair does, one native launch per batch with per-image windows and the
+        # loader's generator
+        self.tactile_augment_mode = self.cfg.get('tactile_augment', 'torch')
+        if self.tactile_augment_mode not in ('torch', 'fused'):
+            raise ValueError(f"offline_train.tactile_augment: expected 'torch' or 'fused', got {self.tactile_augment_mode!r}")
+        self.tactile_augment = self.tactile_eval_augment = None
+        if self.tactile_augment_mode == 'fused':
+            if self.tactile_channel != 1:
+                raise NotImplementedError(f"offline_train.tactile_augment: 'fused' reads single-channel tactile frames "
+                                          f"(tactile_type 'gray'), got tactile_type {self.cfg.tactile_type!r}")
+            self.tactile_augment, self.tactile_eval_augment = define_tactile_augment(
+                self.tactile_width, self.tactile_height, self.crop_tactile_width, self.crop_tactile_height,
+                self.cfg.get('tactile_patch_size', 16), self.cfg.get('tactile_gaussian_noise', 0.0),
+                self.cfg.get('tactile_masking_prob', 0.0))
         # external camera (runner.py:152-173)
         self.img_channel = 1 if self.cfg.get('img_type', 'depth') == "depth" else 3
         self.img_width, self.img_height = self.cfg.get('img_width', 54), self.cfg.get('img_height', 96)
@@ -288,12 +303,18 @@ class Runner:
                             tactile_transform=None, include_img=self.cfg.model.use_img,
                             include_seg=self.cfg.model.use_seg, include_lin=self.cfg.model.use_lin,
                             include_tactile=self.cfg.model.use_tactile, obs_keys=self.cfg.train.obs_keys)
-        tf = (self.tactile_transform if train else self.tactile_eval_transform) if self.cfg.model.use_tactile else None
+        fused = self.tactile_augment_mode == 'fused'
+        pair = (self.tactile_augment, self.tactile_eval_augment) if fused else \
+            (self.tactile_transform, self.tactile_eval_transform)
+        tf = (pair[0] if train else pair[1]) if self.cfg.model.use_tactile else None
         if tf is not None:
             tf.to(self.device)
         sync = (self.sync_transform if train else self.sync_eval_transform) \
             if (self.cfg.model.use_img or self.cfg.model.use_seg) else None      # the dataset loads the pair for either
-        return ResidentLoader(ds, batch_size, shuffle=True, device=self.device, tactile_transform=tf, sync_transform=sync)
+        dl = ResidentLoader(ds, batch_size, shuffle=True, device=self.device, tactile_transform=tf, sync_transform=sync)
+        if fused and tf is not None and dl.fields is not None and dl.fields[0] is not None:
+            tf.check_arena(dl.fields[0])          # a resize or a multi-channel arena: refused here, not at the first batch
+        return dl
 
     def run_train(self, file_list, save_folder, epochs=100, train_test_split=0.9, train_batch_size=32,
                   val_batch_size=32, learning_rate=1e-4, device='cuda:0', print_every=50, eval_every=250,

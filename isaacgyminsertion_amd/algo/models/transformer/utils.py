@@ -17,6 +17,14 @@ Camera pair (depth frames + segmentation masks; utils.py:12-128, 280-322, 422-45
 ``SyncEvalTransform``, ``SyncCenterReshapeTransform``, ``SyncRandomCrop``, ``SyncCenterCrop``.  Called on tensors they
 are torch ops on any device; ``SyncTransform.fused`` builds a minibatch from the resident arenas in one native launch
 (csrc/augment.h).  DESIGN.md section 4 has the parameter contract and the two evaluation-side deviations.
+
+Tactile images in one launch (``offline_train.tactile_augment: "fused"``): ``define_tactile_augment`` -> (``TactileAugment``,
+its ``train=False`` twin).  The train transform above with its random numbers apart from its arithmetic, image by image:
+``draw`` on the CPU from the loader's generator (a window, a jitter and an angle per image, one noise seed per batch),
+``apply`` in torch ops on any device, ``fused`` = draw + torch.ops.mi355ppo.tactile_augment, which builds the batch from the
+resident arena in one native launch (csrc/tactile_augment.h).  It differs from the ``nn.Sequential`` in three recorded ways
+(DESIGN.md section 4): a window per image instead of one per batch, the loader's generator instead of the device's, and
+no 5-tap blur (sigma <= 0.1 moves no pixel by 1e-21 of the image's range).
 """
 import math
 import os
@@ -438,6 +446,191 @@ class TactileTransform:
         if self.tactile_transform is not None:
             y = self.tactile_transform(y)
         return y.reshape(B, T, Fg, C, *y.shape[2:])
+
+
+# ---------------------------------------------------------------------------------------------
+# tactile images, random numbers apart from the arithmetic: one native launch per batch (csrc/tactile_augment.h)
+# ---------------------------------------------------------------------------------------------
+_M32 = 0xFFFFFFFF
+
+
+def _mul32(x, k):
+    """(x * k) mod 2^32 for an int64 tensor of 32-bit values: two 16-bit halves, so no product leaves int64."""
+    return ((x & 0xFFFF) * k + ((((x >> 16) * k) & 0xFFFF) << 16)) & _M32
+
+
+def _tok_hash(seed, site, idx):
+    """csrc/tok_hash.h on an int64 tensor ``idx`` (taken modulo 2^32) -> int64 values below 2^32."""
+    lo, hi = seed & _M32, (seed >> 32) & _M32
+    x = _mul32(idx & _M32, 0x9E3779B1) ^ lo ^ ((site * 0x85EBCA77) & _M32)
+    x = _mul32(x ^ (x >> 16), 0x7FEB352D)
+    x = _mul32(x ^ (x >> 15), 0x846CA68B)
+    x = ((x ^ (x >> 16)) + hi) & _M32
+    x = _mul32(x ^ (x >> 15), 0x2C1B3C6D)
+    x = _mul32(x ^ (x >> 12), 0x297A2D39)
+    return x ^ (x >> 15)
+
+
+def _hash_gauss(seed, plane, shape, dtype, device):
+    """csrc/aug_gauss.h: the Box-Muller sample of every element of an output tensor of ``shape``, in ``dtype``."""
+    e = torch.arange(math.prod(shape), device=device)
+    k1, k2 = _tok_hash(seed, 2 * plane, e) >> 8, _tok_hash(seed, 2 * plane + 1, e) >> 8
+    low = torch.log((k1.to(dtype) + 0.5) * 2.0 ** -24)
+    high = torch.log1p(-(((0xFFFFFF - k1).to(dtype) + 0.5) * 2.0 ** -24))
+    ln_u1 = torch.where(k1 < (1 << 23), low, high)
+    z = torch.sqrt(-2.0 * ln_u1) * torch.cos((2.0 * math.pi) * (k2.to(dtype) * 2.0 ** -24))
+    return z.reshape(shape)
+
+
+TACTILE_NOISE_PLANE = 2      # the camera pair draws its noise on planes 0 and 1 of the same hash
+
+
+class TactileAugment(nn.Module):
+    """The train transform of ``define_tactile_transforms`` -- crop, brightness / contrast jitter (p 0.3), rotation
+    <= 3 degrees (p 0.5), Gaussian noise, patch masking -- with the random numbers of a call apart from its arithmetic,
+    image by image: an image is one single-channel (sample, t, finger) plane and has its own window, jitter, angle and
+    patch mask.  ``_TrainAugment``'s 5-tap blur (sigma <= 0.1) is left out: it moves no pixel by 1e-21 of the image's
+    range.
+      ``draw(n_images, generator)`` -> (offsets, jitter, angles, keep, seed) on the CPU;
+      ``apply(x, ...)``             -> the transform of (..., C, H, W) images with those draws, in plain torch ops on any
+                                       device and in x's dtype; the noise is the kernel's counter hash of ``seed``;
+      ``fused(arena, rows)``        -> draw + torch.ops.mi355ppo.tactile_augment: the gather from the resident
+                                       (N, T, F, 1, H, W) arena and the whole transform in one launch.
+    ``forward(x)`` is draw + apply from torch's default CPU generator.  In ``eval()`` mode (``train=False``) it is the
+    eval transform: the centre window, nothing random, nothing drawn."""
+
+    JITTER_P, ROTATE_P, JITTER, ROTATE_DEG = 0.3, 0.5, 0.1, 3.0
+
+    def __init__(self, size, crop_size, patch=16, noise_std=0.0, masking_prob=0.0, train=True):
+        super().__init__()
+        self._size, self.crop_size = tuple(size), tuple(crop_size)
+        if self.crop_size[0] > self._size[0] or self.crop_size[1] > self._size[1]:
+            raise ValueError(f"crop size {self.crop_size} larger than the image {self._size}")
+        self.patch, self.noise_std, self.masking_prob = int(patch), float(noise_std), float(masking_prob)
+        self.generator = None
+        self.train(bool(train))
+
+    @property
+    def size(self):
+        """(rows, columns) the crop is taken from."""
+        return self._size
+
+    @property
+    def is_identity(self):
+        return not self.training and self.crop_size == self._size
+
+    def draw(self, n_images, generator=None):
+        """The random numbers of one batch, from ``generator`` (torch's default when None), as CPU tensors, one row per
+        image: ``offsets`` int32 (n, 2) uniform over the valid (top, left); ``jitter`` fp32 (n, 3) = (flag, brightness,
+        contrast), the factors uniform in 1 +- 0.1 where the flag is 1 and 1 elsewhere; ``angles`` fp32 (n,) radians,
+        uniform in +- 3 degrees with probability 0.5 and 0 elsewhere; ``keep`` uint8 (n, gh, gw) or None; ``seed`` one
+        63-bit int per batch (0 without noise).  A stage that is off draws nothing; evaluation draws nothing at all."""
+        n = int(n_images)
+        (h, w), (ch, cw) = self._size, self.crop_size
+        offsets = torch.zeros(n, 2, dtype=torch.int32)
+        jitter = torch.ones(n, 3)
+        jitter[:, 0] = 0
+        angles = torch.zeros(n)
+        if not self.training:
+            top, left = _center_offsets(h, w, ch, cw)
+            offsets[:, 0], offsets[:, 1] = top, left
+            return offsets, jitter, angles, None, 0
+        if h > ch:
+            offsets[:, 0] = torch.randint(0, h - ch + 1, (n,), generator=generator, dtype=torch.int32)
+        if w > cw:
+            offsets[:, 1] = torch.randint(0, w - cw + 1, (n,), generator=generator, dtype=torch.int32)
+        u = torch.rand(3, n, generator=generator)
+        on = u[0] < self.JITTER_P
+        jitter[:, 0] = on.float()
+        jitter[:, 1] = torch.where(on, 1 + (u[1] * 2 - 1) * self.JITTER, jitter[:, 1])
+        jitter[:, 2] = torch.where(on, 1 + (u[2] * 2 - 1) * self.JITTER, jitter[:, 2])
+        u = torch.rand(2, n, generator=generator)
+        angles = torch.where(u[0] < self.ROTATE_P, (u[1] * 2 - 1) * (self.ROTATE_DEG * math.pi / 180), angles)
+        keep = None
+        if self.masking_prob > 0.0:
+            drop = torch.rand(n, ch // self.patch, cw // self.patch, generator=generator) < self.masking_prob
+            keep = (~drop).to(torch.uint8)
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator)) if self.noise_std > 0.0 else 0
+        return offsets, jitter, angles, keep, seed
+
+    @staticmethod
+    def pack(offsets, jitter, angles):
+        """The draws of ``draw`` as the op's ``params``: int32 (n, 6) = top, left, flag, bits of (b, c, angle)."""
+        return torch.cat([offsets.to(torch.int32), (jitter[:, :1] != 0).to(torch.int32),
+                          jitter[:, 1:].float().contiguous().view(torch.int32),
+                          angles.float().reshape(-1, 1).view(torch.int32)], 1)
+
+    def apply(self, x, offsets, jitter, angles, keep=None, noise_std=0.0, seed=0):
+        """(..., C, H, W) images at ``size``, one row of the draws per image -> (..., C, ch, cw): batched torch ops."""
+        lead, (C, H, W) = x.shape[:-3], x.shape[-3:]
+        ch, cw = self.crop_size
+        dev = x.device
+        y = x.reshape(-1, C, H, W)
+        n = y.shape[0]
+        if (H, W) != (ch, cw):
+            off = offsets.to(dev).long()
+            ri = (off[:, :1] + torch.arange(ch, device=dev))[:, :, None]
+            ci = (off[:, 1:] + torch.arange(cw, device=dev))[:, None, :]
+            y = y.permute(0, 2, 3, 1)[torch.arange(n, device=dev)[:, None, None], ri, ci].permute(0, 3, 1, 2)
+        if bool((jitter[:, 0] != 0).any()):               # on the draw's (CPU) tensor: no device read-back
+            j = jitter.to(dev).to(y.dtype)
+            on, b, c = (j[:, k].reshape(n, 1, 1, 1) for k in range(3))
+            z = (y * b).clamp(0, 1)
+            mean = z.mean(dim=(1, 2, 3), keepdim=True)
+            y = torch.where(on != 0, ((z - mean) * c + mean).clamp(0, 1), y)
+        if bool((angles != 0).any()):
+            ang = angles.to(dev)
+            y = torch.where((ang != 0).reshape(n, 1, 1, 1), _rotate(y.contiguous(), ang), y)
+        if noise_std > 0.0:
+            y = y + float(np.float32(noise_std)) * _hash_gauss(int(seed), TACTILE_NOISE_PLANE, tuple(y.shape), y.dtype, dev)
+        if keep is not None:
+            p = self.patch
+            gh, gw = ch // p, cw // p
+            m = keep.to(dev).to(y.dtype).repeat_interleave(p, 1).repeat_interleave(p, 2)
+            y = y.clone()
+            y[:, :, :gh * p, :gw * p] *= m.unsqueeze(1)
+        return y.reshape(*lead, C, ch, cw)
+
+    def forward(self, x):
+        offsets, jitter, angles, keep, seed = self.draw(x.numel() // math.prod(x.shape[-3:]), self.generator)
+        return self.apply(x, offsets, jitter, angles, keep, self.noise_std if self.training else 0.0, seed)
+
+    def check_arena(self, arena):
+        """The fused path reads single-channel frames stored at ``size``; anything else is the torch path's."""
+        if arena.dim() != 6 or arena.shape[3] != 1:
+            raise NotImplementedError(f"offline_train.tactile_augment: 'fused' reads single-channel (gray) tactile frames, "
+                                      f"got an arena of shape {tuple(arena.shape)}; use 'torch'")
+        if tuple(arena.shape[-2:]) != self._size:
+            raise NotImplementedError(f"offline_train.tactile_augment: 'fused' does not resize: the frames are stored at "
+                                      f"{tuple(arena.shape[-2:])}, tactile_width x tactile_height is {self._size}; use 'torch'")
+
+    def fused(self, arena, rows, generator=None):
+        """``arena.index_select(0, rows) -> forward`` as one native launch: ``arena`` the loader's resident
+        (N, T, F, 1, H, W) field, ``rows`` the batch's int64 sample numbers on its device.  Every draw of the batch
+        crosses to the device in ONE copy."""
+        self.check_arena(arena)
+        n = rows.numel() * arena.shape[1] * arena.shape[2]
+        offsets, jitter, angles, keep, seed = self.draw(n, generator if generator is not None else self.generator)
+        noise_std = self.noise_std if self.training else 0.0
+        ch, cw = self.crop_size
+        if ch * cw > ops.TACTILE_AUG_MAX_PIXELS:          # larger than the kernel's window: the same draws in torch ops
+            return self.apply(arena.index_select(0, rows), offsets, jitter, angles, keep, noise_std, seed)
+        words = self.pack(offsets, jitter, angles)
+        if keep is None:
+            params, keep_d = words.to(arena.device), None
+        else:
+            both = torch.cat([words.view(torch.uint8).reshape(-1), keep.reshape(-1)]).to(arena.device)
+            params = both[:words.numel() * 4].view(torch.int32).view(n, ops.TACTILE_AUG_WORDS)
+            keep_d = both[words.numel() * 4:].view(keep.shape)
+        return torch.ops.mi355ppo.tactile_augment(arena, rows, params, keep_d, ch, cw, self.patch, noise_std, seed)
+
+
+def define_tactile_augment(width, height, crop_width, crop_height, img_patch_size=16, img_gaussian_noise=0.0,
+                           img_masking_prob=0.0):
+    """``define_tactile_transforms``' arguments -> (TactileAugment, its ``train=False`` twin)."""
+    args = ((width, height), (crop_width, crop_height), img_patch_size)
+    return (TactileAugment(*args, img_gaussian_noise, img_masking_prob, train=True),
+            TactileAugment(*args, 0.0, 0.0, train=False))
 
 
 def set_seed(seed, torch_deterministic=False, rank=0):

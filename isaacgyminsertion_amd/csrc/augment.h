@@ -19,8 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aug_gauss.h"
 #include "gemm_f32.h"
-#include "tok_hash.h"
 
 namespace igi {
 
@@ -40,19 +40,6 @@ struct ImagePairArgs {
   float noise_std;
   unsigned long long seed;
 };
-
-// ln(u1) of u1 = (k + 1/2) 2^-24, k < 2^24.  k + 1/2 is exact in fp32 below 2^23; above it 2^24 - (k + 1/2) is, and
-// log1pf of the exact distance from 1 keeps z accurate where u1 -> 1 (z -> 0).
-__device__ __forceinline__ float aug_log_u1(unsigned int k) {
-  if (k < (1u << 23)) return logf(((float)k + 0.5f) * 0x1p-24f);
-  return log1pf(-(((float)(0xFFFFFFu - k) + 0.5f) * 0x1p-24f));
-}
-
-__device__ __forceinline__ float aug_gauss(unsigned long long seed, unsigned int plane, unsigned int e) {
-  const unsigned int h1 = tok_hash(seed, 2u * plane, e), h2 = tok_hash(seed, 2u * plane + 1u, e);
-  const float u2 = (float)(h2 >> 8) * 0x1p-24f;
-  return sqrtf(-2.0f * aug_log_u1(h1 >> 8)) * cosf(6.283185307179586f * u2);
-}
 
 // grid (planes = B*T*2, bands): a workgroup owns AUG_BAND groups of four consecutive pixels of one output plane
 __global__ __launch_bounds__(256) void k_image_pair_augment(const ImagePairArgs a) {

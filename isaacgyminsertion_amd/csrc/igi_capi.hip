@@ -19,6 +19,7 @@
 #include "comm.h"
 #include "glue.h"
 #include "augment.h"
+#include "tactile_augment.h"
 #include "peak_probe.h"
 
 namespace {
@@ -699,6 +700,15 @@ int igi_image_pair_augment(const float* img, const float* seg, int64_t n, int t,
                            igi_stream_t stream) {
   return fail(igi::image_pair_augment(img, seg, n, t, hs, ws, rows, b, offsets, angles, keep, out_h, out_w, patch,
                                       noise_std, seed, out_img, out_seg, S(stream)), "igi_image_pair_augment");
+}
+
+static_assert(IGI_TACTILE_AUG_WORDS == igi::TAC_PARAM_WORDS, "igi_ppo.h and tactile_augment.h disagree on the record");
+
+int igi_tactile_augment(const float* arena, int64_t n, int planes, int hs, int ws, const int64_t* rows, int64_t b,
+                        const int32_t* params, const uint8_t* keep, int out_h, int out_w, int patch, float noise_std,
+                        uint64_t seed, float* out, igi_stream_t stream) {
+  return fail(igi::tactile_augment(arena, n, planes, hs, ws, rows, b, params, keep, out_h, out_w, patch, noise_std, seed,
+                                   out, S(stream)), "igi_tactile_augment");
 }
 
 size_t igi_pointnet_workspace_bytes(int64_t batch) { return batch < 1 ? 0 : igi::pointnet_workspace_bytes(batch); }

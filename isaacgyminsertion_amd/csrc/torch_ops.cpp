@@ -364,6 +364,37 @@ Tensor pointnet_max_bwd(const Tensor& x, const Tensor& params, const Tensor& dy,
   return grads;
 }
 
+// ---- loader (utils.py:131-277: the tactile transform chain over a minibatch, one launch from the resident arena)
+Tensor tactile_augment(const Tensor& arena, const Tensor& rows, const Tensor& params, const c10::optional<Tensor>& keep,
+                       int64_t out_h, int64_t out_w, int64_t patch, double noise_std, int64_t seed) {
+  check(arena, "arena"); check(rows, "rows", at::kLong); check(params, "params", at::kInt);
+  TORCH_CHECK(arena.dim() == 6 && arena.size(3) == 1 && arena.numel() > 0, "arena: expected (N, T, F, 1, Hs, Ws) non-empty, got ", arena.sizes());
+  TORCH_CHECK(rows.dim() == 1, "rows: expected 1 dimensions, got shape ", rows.sizes());
+  const int64_t N = arena.size(0), T = arena.size(1), F = arena.size(2), Hs = arena.size(4), Ws = arena.size(5);
+  const int64_t B = rows.numel(), n_img = B * T * F;
+  TORCH_CHECK(params.dim() == 2 && params.size(0) == n_img && params.size(1) == IGI_TACTILE_AUG_WORDS,
+              "params: expected shape (", n_img, ", ", IGI_TACTILE_AUG_WORDS, "), got ", params.sizes());
+  TORCH_CHECK(out_h >= 1 && out_h <= Hs, "out_h: expected 1..", Hs, " (the stored height), got ", out_h);
+  TORCH_CHECK(out_w >= 1 && out_w <= Ws, "out_w: expected 1..", Ws, " (the stored width), got ", out_w);
+  TORCH_CHECK(noise_std >= 0, "noise_std: expected >= 0, got ", noise_std);
+  TORCH_CHECK(rows.device() == arena.device() && params.device() == arena.device(), "rows / params: all arguments must share one device");
+  const bool masked = keep.has_value() && keep->defined();
+  if (masked) {
+    TORCH_CHECK(patch >= 1, "patch: expected >= 1 with a keep mask, got ", patch);
+    check(*keep, "keep", at::kByte);
+    TORCH_CHECK(keep->dim() == 3 && keep->size(0) == n_img && keep->size(1) == out_h / patch && keep->size(2) == out_w / patch,
+                "keep: expected shape (", n_img, ", ", out_h / patch, ", ", out_w / patch, "), got ", keep->sizes());
+    TORCH_CHECK(keep->device() == arena.device(), "keep: all arguments must share one device");
+  }
+  Tensor out = at::empty({B, T, F, 1, out_h, out_w}, arena.options());
+  if (B == 0) return out;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(arena.device());
+  rc(igi_tactile_augment(fp(arena), N, (int)(T * F), (int)Hs, (int)Ws, rows.data_ptr<int64_t>(), B, params.data_ptr<int32_t>(),
+                         masked ? keep->data_ptr<uint8_t>() : nullptr, (int)out_h, (int)out_w, (int)patch, (float)noise_std,
+                         (uint64_t)seed, fp(out), stream_of(arena)), "igi_tactile_augment");
+  return out;
+}
+
 }  // namespace
 
 // Schemas: character for character those of isaacgyminsertion_amd/ops.py (tests/test_torch_library_cpp.py compares them).
@@ -383,6 +414,7 @@ TORCH_LIBRARY(mi355ppo, m) {
   m.def("spatial_softargmax_bwd(Tensor x, Tensor out, Tensor stat, Tensor dout, bool normalize) -> Tensor");
   m.def("pointnet_max_fwd(Tensor x, Tensor params) -> (Tensor, Tensor)");
   m.def("pointnet_max_bwd(Tensor x, Tensor params, Tensor dy, Tensor idx) -> Tensor");
+  m.def("tactile_augment(Tensor arena, Tensor rows, Tensor params, Tensor? keep, int out_h, int out_w, int patch, float noise_std, int seed) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(mi355ppo, CompositeExplicitAutograd, m) {
@@ -401,4 +433,5 @@ TORCH_LIBRARY_IMPL(mi355ppo, CompositeExplicitAutograd, m) {
   m.impl("spatial_softargmax_bwd", spatial_softargmax_bwd);
   m.impl("pointnet_max_fwd", pointnet_max_fwd);
   m.impl("pointnet_max_bwd", pointnet_max_bwd);
+  m.impl("tactile_augment", tactile_augment);
 }

@@ -1675,6 +1675,62 @@ def _(img, seg, rows, offsets, angles, keep, out_h, out_w, patch, noise_std, see
     return img.new_empty(shape), img.new_empty(shape)
 
 
+TACTILE_AUG_WORDS = 6      # IGI_TACTILE_AUG_WORDS: top, left, jitter flag, bits of (brightness, contrast, angle)
+TACTILE_AUG_MAX_PIXELS = 8192
+
+
+@_op("tactile_augment(Tensor arena, Tensor rows, Tensor params, Tensor? keep, int out_h, int out_w, int patch, "
+     "float noise_std, int seed) -> Tensor")
+def tactile_augment(arena: Tensor, rows: Tensor, params: Tensor, keep: Optional[Tensor], out_h: int, out_w: int,
+                    patch: int, noise_std: float, seed: int) -> Tensor:
+    """The tactile images of a minibatch, augmented, in ONE launch from the resident arena (igi_tactile_augment; replaces
+    ``index_select`` + ``_Crop`` / ``_TrainAugment`` / ``GaussianNoise`` / ``Masking``, utils.py:131-277): ``arena`` fp32
+    (N, T, F, 1, Hs, Ws); ``rows`` int64 (B,); ``params`` int32 (B*T*F, 6), per image (top, left, jitter flag, and the
+    fp32 bit patterns of brightness, contrast, angle in radians); ``keep`` uint8 (B*T*F, out_h // patch, out_w // patch)
+    or None (0 zeroes that patch); ``noise_std`` > 0 adds hash-drawn Gaussian noise of ``seed`` -> fp32
+    (B, T, F, 1, out_h, out_w).  A window of more than 8192 pixels is refused.  The inputs are data: no autograd."""
+    _check_layout(arena, "arena", torch.float32, 6)
+    _check_layout(rows, "rows", torch.int64, 1)
+    _check_layout(params, "params", torch.int32, 2)
+    N, T, Fg, ch, Hs, Ws = arena.shape
+    if ch != 1 or arena.numel() == 0:
+        raise RuntimeError(f"arena: expected (N, T, F, 1, Hs, Ws) non-empty, got {tuple(arena.shape)}")
+    B = rows.numel()
+    n_img = B * T * Fg
+    if tuple(params.shape) != (n_img, TACTILE_AUG_WORDS):
+        raise RuntimeError(f"params: expected shape {(n_img, TACTILE_AUG_WORDS)}, got {tuple(params.shape)}")
+    if out_h < 1 or out_h > Hs:
+        raise RuntimeError(f"out_h: expected 1..{Hs} (the stored height), got {out_h}")
+    if out_w < 1 or out_w > Ws:
+        raise RuntimeError(f"out_w: expected 1..{Ws} (the stored width), got {out_w}")
+    if not noise_std >= 0:
+        raise RuntimeError(f"noise_std: expected >= 0, got {noise_std}")
+    if keep is not None:
+        if patch < 1:
+            raise RuntimeError(f"patch: expected >= 1 with a keep mask, got {patch}")
+        _check_layout(keep, "keep", torch.uint8, 3)
+        want = (n_img, out_h // patch, out_w // patch)
+        if tuple(keep.shape) != want:
+            raise RuntimeError(f"keep: expected shape {want}, got {tuple(keep.shape)}")
+    dev = arena.device
+    for t, nm in ((arena, "arena"), (rows, "rows"), (params, "params"), (keep, "keep")):
+        if t is not None:
+            _check(t, nm, dtype=t.dtype, device=dev)
+    out = torch.empty((B, T, Fg, 1, out_h, out_w), dtype=torch.float32, device=dev)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        _rc(_lib.lib().igi_tactile_augment(_p(arena), N, T * Fg, Hs, Ws, _p(rows), B, _p(params), _p(keep), out_h, out_w,
+                                           patch, noise_std, C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), _p(out),
+                                           _stream(arena)), "igi_tactile_augment")
+    return out
+
+
+@_fake("tactile_augment")
+def _(arena, rows, params, keep, out_h, out_w, patch, noise_std, seed):
+    return arena.new_empty((rows.numel(), arena.shape[1], arena.shape[2], 1, out_h, out_w))
+
+
 @_op("cat_cols(Tensor[] parts, Tensor? add) -> Tensor")
 def cat_cols(parts: List[Tensor], add: Optional[Tensor]) -> Tensor:
     """``torch.cat(parts, dim=1) (+ add)`` for 2-D fp32 parts with the same number of rows, ``add`` one row of the
@@ -1751,4 +1807,5 @@ OP_NAMES = ["gae_advnorm", "ppo_minibatch_fwd_bwd", "ppo_clip_adam", "ppo_update
             "rollout_env_store",
             "bc_loss_fwd_bwd", "bc_loss", "bc_loss_value_grad", "gemm_f32", "linear", "linear_bwd", "mlp_fwd", "mlp_bwd", "tactile_cnn_fwd", "tactile_cnn_bwd", "spatial_softargmax_fwd", "spatial_softargmax_bwd",
             "pointnet_max_fwd", "pointnet_max_bwd", "pointnet_max_fwd_multi", "pointnet_max_bwd_multi", "depth_backbone_fwd", "depth_backbone_bwd", "token_encoder_fwd",
-            "token_encoder_bwd", "gather_rows", "cat_cols", "split_cols", "image_pair_augment"]
+            "token_encoder_bwd", "gather_rows", "cat_cols", "split_cols", "image_pair_augment",
+            "tactile_augment"]

@@ -90,6 +90,8 @@ def default_config(num_envs=4096, horizon_length=32, rl_device="cuda:0", multi_g
             # camera augmentation (offline_config.yaml img_*; img_rotation_deg is ours: the reference hard-codes 1 degree)
             "img_patch_size": 16, "img_gaussian_noise": 0.0, "img_masking_prob": 0.0, "img_rotation_deg": 0.0,
             "tactile_patch_size": 16, "tactile_gaussian_noise": 0.001, "tactile_masking_prob": 0.0,
+            # ours: "torch" = the torch-op transform per batch; "fused" = one native launch per batch (utils.TactileAugment)
+            "tactile_augment": "torch",
             "tactile_color_jitter": False, "seed": 0, "data_folder": "", "output_dir": "outputs/offline",
             # supervised learning (offline_config.yaml:28-83)
             "train": {"latent_scale": 1.0, "action_scale": 1.0, "latent_loss": False, "action_regularization": False, "epochs": 100, "train_batch_size": 64,
