@@ -61,10 +61,7 @@ class Masking(nn.Module):
         p = self.img_patch_size
         gh, gw = x.shape[-2] // p, x.shape[-1] // p
         drop = torch.rand((x.shape[0], gh, gw), device=x.device) < self.img_masking_prob
-        keep = (~drop).to(x.dtype).repeat_interleave(p, 1).repeat_interleave(p, 2)
-        out = x.clone()
-        out[:, :, :gh * p, :gw * p] *= keep.unsqueeze(1)
-        return out
+        return _mask_patches(x, ~drop, p)
 
 
 class _Resize(nn.Module):
@@ -166,9 +163,58 @@ def _center_crop(x, size):
     return x[..., top:top + ch, left:left + cw]
 
 
+# The draws and the torch-op steps SyncTransform, SyncEvalTransform and TactileAugment share.  Every draw is on the CPU from
+# ``generator`` (torch's default when None); a stage that is off draws nothing, so a seeded run keeps its random stream.
+def _draw_windows(n, size, crop, generator):
+    """int32 (n, 2): (top, left) uniform over the valid positions; an axis with no room to move draws nothing."""
+    offsets = torch.zeros(n, 2, dtype=torch.int32)
+    for k in range(2):
+        if size[k] > crop[k]:
+            offsets[:, k] = torch.randint(0, size[k] - crop[k] + 1, (n,), generator=generator, dtype=torch.int32)
+    return offsets
+
+
+def _center_windows(n, size, crop):
+    """int32 (n, 2): the centre window, n times."""
+    return torch.tensor([_center_offsets(*size, *crop)], dtype=torch.int32).repeat(n, 1)
+
+
+def _draw_keep(n, crop, patch, prob, generator):
+    """uint8 (n, gh, gw), 0 with probability ``prob``: one grid of whole patches per image; None when ``prob`` is 0."""
+    if not prob > 0.0:
+        return None
+    drop = torch.rand(n, crop[0] // patch, crop[1] // patch, generator=generator) < prob
+    return (~drop).to(torch.uint8)
+
+
+def _draw_seed(noise_std, generator):
+    """One 63-bit noise seed per batch; 0, and nothing drawn, without noise."""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator)) if noise_std > 0.0 else 0
+
+
+def _gather_windows(x, offsets, crop):
+    """(n, ..., H, W), one (top, left) per row of x -> (n, ..., ch, cw): every row's own window, one advanced index."""
+    dev = x.device
+    off = offsets.to(dev).long()
+    ni = torch.arange(x.shape[0], device=dev)[:, None, None]
+    ri = (off[:, :1] + torch.arange(crop[0], device=dev))[:, :, None]
+    ci = (off[:, 1:] + torch.arange(crop[1], device=dev))[:, None, :]
+    return x.movedim((-2, -1), (1, 2))[ni, ri, ci].movedim((1, 2), (-2, -1))
+
+
+def _mask_patches(y, keep, patch):
+    """(n, C, h, w) times ``keep`` (n, gh, gw), every entry a whole patch, the same for every channel; rows / columns past
+    the last whole patch are kept.  A copy: ``y`` is left as it is."""
+    gh, gw = keep.shape[1:]
+    m = keep.to(y.device).to(y.dtype).repeat_interleave(patch, 1).repeat_interleave(patch, 2)
+    y = y.clone()
+    y[:, :, :gh * patch, :gw * patch] *= m.unsqueeze(1)
+    return y
+
+
 def _rotate(x, ang):
     """(n, C, H, W) rotated about the image centre by ``ang`` (n,) radians: nearest resampling, zero fill (torchvision's
-    defaults) -- the arithmetic of ``_TrainAugment`` above, and the one csrc/augment.h restates per pixel."""
+    defaults) -- the arithmetic of ``_TrainAugment`` above, and the one csrc/aug_pixel.h restates per pixel."""
     cos, sin = torch.cos(ang), torch.sin(ang)
     H, W = x.shape[-2:]
     zero = torch.zeros_like(cos)
@@ -291,46 +337,28 @@ class SyncTransform(nn.Module):
         int32 (B, 2) uniform over the valid (top, left); ``angles`` fp32 (B, 2) radians uniform in +-rotation_deg, column
         0 the image's and column 1 the mask's; ``keep`` uint8 (B*T, gh, gw) or None; ``seed`` a 63-bit int (0 without
         noise).  A stage that is off draws nothing."""
-        (h, w), (ch, cw) = self.size, self.crop_size
-        offsets = torch.zeros(B, 2, dtype=torch.int32)
-        if h > ch:
-            offsets[:, 0] = torch.randint(0, h - ch + 1, (B,), generator=generator, dtype=torch.int32)
-        if w > cw:
-            offsets[:, 1] = torch.randint(0, w - cw + 1, (B,), generator=generator, dtype=torch.int32)
+        offsets = _draw_windows(B, self.size, self.crop_size, generator)
         angles = torch.zeros(B, 2)
         if self.rotation_deg > 0.0:
             angles = (torch.rand(B, 2, generator=generator) * 2 - 1) * (self.rotation_deg * math.pi / 180)
-        keep = None
-        if self.masking_prob > 0.0:
-            drop = torch.rand(B * T, ch // self.patch, cw // self.patch, generator=generator) < self.masking_prob
-            keep = (~drop).to(torch.uint8)
-        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator)) if self.noise_std > 0.0 else 0
-        return offsets, angles, keep, seed
+        keep = _draw_keep(B * T, self.crop_size, self.patch, self.masking_prob, generator)
+        return offsets, angles, keep, _draw_seed(self.noise_std, generator)
 
     def apply(self, img, mask, offsets, angles, keep=None, noise_std=0.0):
         """(B, T, C, H, W) pair at the resize target -> cropped, rotated, noised, masked pair: batched torch ops."""
         B, T, C = img.shape[:3]
         ch, cw = self.crop_size
-        dev = img.device
-        off = offsets.to(dev).long()
-        bi = torch.arange(B, device=dev)[:, None, None]
-        ri = (off[:, :1] + torch.arange(ch, device=dev))[:, :, None]
-        ci = (off[:, 1:] + torch.arange(cw, device=dev))[:, None, :]
         turned = (angles != 0).any(0).tolist()            # on the draw's (CPU) tensor: no device read-back
-        ang = angles.to(dev)
+        ang = angles.to(img.device)
         outs = []
         for k, x in enumerate((img, mask)):
-            y = x.permute(0, 3, 4, 1, 2)[bi, ri, ci].permute(0, 3, 4, 1, 2).reshape(B * T, C, ch, cw)
+            y = _gather_windows(x, offsets, self.crop_size).reshape(B * T, C, ch, cw)
             if turned[k]:
                 y = _rotate(y, ang[:, k].repeat_interleave(T))
             if noise_std > 0.0:
                 y = y + torch.randn_like(y) * noise_std
             if k == 0 and keep is not None:
-                p = self.patch
-                gh, gw = ch // p, cw // p
-                m = keep.to(dev).to(y.dtype).repeat_interleave(p, 1).repeat_interleave(p, 2)
-                y = y.clone()
-                y[:, :, :gh * p, :gw * p] *= m.unsqueeze(1)
+                y = _mask_patches(y, keep, self.patch)
             outs.append(y.reshape(B, T, C, ch, cw))
         return outs[0], outs[1]
 
@@ -376,8 +404,7 @@ class SyncEvalTransform(SyncTransform):
         return self.crop_size == tuple(self.size)
 
     def draw(self, B, T, generator=None):
-        top, left = _center_offsets(*self.size, *self.crop_size)
-        return torch.tensor([[top, left]], dtype=torch.int32).repeat(B, 1), torch.zeros(B, 2), None, 0
+        return _center_windows(B, self.size, self.crop_size), torch.zeros(B, 2), None, 0
 
     def forward(self, img, mask):
         lead = img.shape[:-3]
@@ -526,19 +553,12 @@ class TactileAugment(nn.Module):
         uniform in +- 3 degrees with probability 0.5 and 0 elsewhere; ``keep`` uint8 (n, gh, gw) or None; ``seed`` one
         63-bit int per batch (0 without noise).  A stage that is off draws nothing; evaluation draws nothing at all."""
         n = int(n_images)
-        (h, w), (ch, cw) = self._size, self.crop_size
-        offsets = torch.zeros(n, 2, dtype=torch.int32)
         jitter = torch.ones(n, 3)
         jitter[:, 0] = 0
         angles = torch.zeros(n)
         if not self.training:
-            top, left = _center_offsets(h, w, ch, cw)
-            offsets[:, 0], offsets[:, 1] = top, left
-            return offsets, jitter, angles, None, 0
-        if h > ch:
-            offsets[:, 0] = torch.randint(0, h - ch + 1, (n,), generator=generator, dtype=torch.int32)
-        if w > cw:
-            offsets[:, 1] = torch.randint(0, w - cw + 1, (n,), generator=generator, dtype=torch.int32)
+            return _center_windows(n, self._size, self.crop_size), jitter, angles, None, 0
+        offsets = _draw_windows(n, self._size, self.crop_size, generator)
         u = torch.rand(3, n, generator=generator)
         on = u[0] < self.JITTER_P
         jitter[:, 0] = on.float()
@@ -546,12 +566,8 @@ class TactileAugment(nn.Module):
         jitter[:, 2] = torch.where(on, 1 + (u[2] * 2 - 1) * self.JITTER, jitter[:, 2])
         u = torch.rand(2, n, generator=generator)
         angles = torch.where(u[0] < self.ROTATE_P, (u[1] * 2 - 1) * (self.ROTATE_DEG * math.pi / 180), angles)
-        keep = None
-        if self.masking_prob > 0.0:
-            drop = torch.rand(n, ch // self.patch, cw // self.patch, generator=generator) < self.masking_prob
-            keep = (~drop).to(torch.uint8)
-        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator)) if self.noise_std > 0.0 else 0
-        return offsets, jitter, angles, keep, seed
+        keep = _draw_keep(n, self.crop_size, self.patch, self.masking_prob, generator)
+        return offsets, jitter, angles, keep, _draw_seed(self.noise_std, generator)
 
     @staticmethod
     def pack(offsets, jitter, angles):
@@ -568,10 +584,7 @@ class TactileAugment(nn.Module):
         y = x.reshape(-1, C, H, W)
         n = y.shape[0]
         if (H, W) != (ch, cw):
-            off = offsets.to(dev).long()
-            ri = (off[:, :1] + torch.arange(ch, device=dev))[:, :, None]
-            ci = (off[:, 1:] + torch.arange(cw, device=dev))[:, None, :]
-            y = y.permute(0, 2, 3, 1)[torch.arange(n, device=dev)[:, None, None], ri, ci].permute(0, 3, 1, 2)
+            y = _gather_windows(y, offsets, self.crop_size)
         if bool((jitter[:, 0] != 0).any()):               # on the draw's (CPU) tensor: no device read-back
             j = jitter.to(dev).to(y.dtype)
             on, b, c = (j[:, k].reshape(n, 1, 1, 1) for k in range(3))
@@ -584,11 +597,7 @@ class TactileAugment(nn.Module):
         if noise_std > 0.0:
             y = y + float(np.float32(noise_std)) * _hash_gauss(int(seed), TACTILE_NOISE_PLANE, tuple(y.shape), y.dtype, dev)
         if keep is not None:
-            p = self.patch
-            gh, gw = ch // p, cw // p
-            m = keep.to(dev).to(y.dtype).repeat_interleave(p, 1).repeat_interleave(p, 2)
-            y = y.clone()
-            y[:, :, :gh * p, :gw * p] *= m.unsqueeze(1)
+            y = _mask_patches(y, keep, self.patch)
         return y.reshape(*lead, C, ch, cw)
 
     def forward(self, x):

@@ -1,4 +1,4 @@
-// The Gaussian sample of the augmentation kernels (augment.h, tactile_augment.h): Box-Muller over two values of the counter
+// The Gaussian sample of the augmentation kernels (aug_pixel.h): Box-Muller over two values of the counter
 // hash, a pure function of (seed, plane, element).  Planes in use: 0 = camera depth, 1 = camera mask, 2 = tactile.
 // tests/img_augment_ref.py `gauss` restates it in float64.
 #pragma once

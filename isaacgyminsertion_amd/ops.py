@@ -1617,6 +1617,30 @@ def _check_layout(t, name, dtype, dim):
         raise RuntimeError(f"{name}: expected a contiguous tensor, got strides {tuple(t.stride())}")
 
 
+def _check_augment_args(out_h, out_w, Hs, Ws, noise_std, keep, patch, n_img, tensors):
+    """What the two augmentation ops check alike: the output size against the stored one, ``noise_std``, ``patch`` and the
+    ``keep`` grids of ``n_img`` images (``patch`` is not looked at without a ``keep``), then -- last -- that every tensor
+    of ``tensors`` ((tensor or None, name), the first one the arena) is on the arena's device, which is returned."""
+    if out_h < 1 or out_h > Hs:
+        raise RuntimeError(f"out_h: expected 1..{Hs} (the stored height), got {out_h}")
+    if out_w < 1 or out_w > Ws:
+        raise RuntimeError(f"out_w: expected 1..{Ws} (the stored width), got {out_w}")
+    if not noise_std >= 0:
+        raise RuntimeError(f"noise_std: expected >= 0, got {noise_std}")
+    if keep is not None:
+        if patch < 1:
+            raise RuntimeError(f"patch: expected >= 1 with a keep mask, got {patch}")
+        _check_layout(keep, "keep", torch.uint8, 3)
+        want = (n_img, out_h // patch, out_w // patch)
+        if tuple(keep.shape) != want:
+            raise RuntimeError(f"keep: expected shape {want}, got {tuple(keep.shape)}")
+    dev = tensors[0][0].device
+    for t, nm in tensors:
+        if t is not None:
+            _check(t, nm, dtype=t.dtype, device=dev)
+    return dev
+
+
 @_op("image_pair_augment(Tensor img, Tensor seg, Tensor rows, Tensor offsets, Tensor angles, Tensor? keep, int out_h, "
      "int out_w, int patch, float noise_std, int seed) -> (Tensor, Tensor)")
 def image_pair_augment(img: Tensor, seg: Tensor, rows: Tensor, offsets: Tensor, angles: Tensor, keep: Optional[Tensor],
@@ -1640,23 +1664,8 @@ def image_pair_augment(img: Tensor, seg: Tensor, rows: Tensor, offsets: Tensor, 
     for t, nm in ((offsets, "offsets"), (angles, "angles")):
         if tuple(t.shape) != (B, 2):
             raise RuntimeError(f"{nm}: expected shape {(B, 2)}, got {tuple(t.shape)}")
-    if out_h < 1 or out_h > Hs:
-        raise RuntimeError(f"out_h: expected 1..{Hs} (the stored height), got {out_h}")
-    if out_w < 1 or out_w > Ws:
-        raise RuntimeError(f"out_w: expected 1..{Ws} (the stored width), got {out_w}")
-    if not noise_std >= 0:
-        raise RuntimeError(f"noise_std: expected >= 0, got {noise_std}")
-    if keep is not None:
-        if patch < 1:
-            raise RuntimeError(f"patch: expected >= 1 with a keep mask, got {patch}")
-        _check_layout(keep, "keep", torch.uint8, 3)
-        want = (B * T, out_h // patch, out_w // patch)
-        if tuple(keep.shape) != want:
-            raise RuntimeError(f"keep: expected shape {want}, got {tuple(keep.shape)}")
-    dev = img.device
-    for t, nm in ((img, "img"), (seg, "seg"), (rows, "rows"), (offsets, "offsets"), (angles, "angles"), (keep, "keep")):
-        if t is not None:
-            _check(t, nm, dtype=t.dtype, device=dev)
+    dev = _check_augment_args(out_h, out_w, Hs, Ws, noise_std, keep, patch, B * T, (
+        (img, "img"), (seg, "seg"), (rows, "rows"), (offsets, "offsets"), (angles, "angles"), (keep, "keep")))
     outs = (torch.empty((B, T, 1, out_h, out_w), dtype=torch.float32, device=dev),
             torch.empty((B, T, 1, out_h, out_w), dtype=torch.float32, device=dev))
     if B == 0:
@@ -1699,23 +1708,8 @@ def tactile_augment(arena: Tensor, rows: Tensor, params: Tensor, keep: Optional[
     n_img = B * T * Fg
     if tuple(params.shape) != (n_img, TACTILE_AUG_WORDS):
         raise RuntimeError(f"params: expected shape {(n_img, TACTILE_AUG_WORDS)}, got {tuple(params.shape)}")
-    if out_h < 1 or out_h > Hs:
-        raise RuntimeError(f"out_h: expected 1..{Hs} (the stored height), got {out_h}")
-    if out_w < 1 or out_w > Ws:
-        raise RuntimeError(f"out_w: expected 1..{Ws} (the stored width), got {out_w}")
-    if not noise_std >= 0:
-        raise RuntimeError(f"noise_std: expected >= 0, got {noise_std}")
-    if keep is not None:
-        if patch < 1:
-            raise RuntimeError(f"patch: expected >= 1 with a keep mask, got {patch}")
-        _check_layout(keep, "keep", torch.uint8, 3)
-        want = (n_img, out_h // patch, out_w // patch)
-        if tuple(keep.shape) != want:
-            raise RuntimeError(f"keep: expected shape {want}, got {tuple(keep.shape)}")
-    dev = arena.device
-    for t, nm in ((arena, "arena"), (rows, "rows"), (params, "params"), (keep, "keep")):
-        if t is not None:
-            _check(t, nm, dtype=t.dtype, device=dev)
+    dev = _check_augment_args(out_h, out_w, Hs, Ws, noise_std, keep, patch, n_img, (
+        (arena, "arena"), (rows, "rows"), (params, "params"), (keep, "keep")))
     out = torch.empty((B, T, Fg, 1, out_h, out_w), dtype=torch.float32, device=dev)
     if B == 0:
         return out

@@ -29,20 +29,29 @@ def rot_angles():
 
 
 def window(x, rows, offsets, out_h, out_w):
-    """Gather + crop: (N, T, 1, Hs, Ws) -> (B, T, 1, out_h, out_w) float64.  A sample number outside [0, N) and every
-    position outside the stored frame read as 0."""
-    N, T, _, Hs, Ws = x.shape
-    B = rows.numel()
-    out = torch.zeros(B, T, 1, out_h, out_w, dtype=torch.float64)
-    for b in range(B):
-        r, top, left = int(rows[b]), int(offsets[b, 0]), int(offsets[b, 1])
+    """Gather + crop: (N, ..., Hs, Ws), `planes` images per sample -> (B*planes, 1, out_h, out_w) float64, every image
+    with its own (top, left) row of ``offsets`` (B*planes, 2).  A sample number outside [0, N) and every position outside
+    the stored frame read as 0."""
+    N, (Hs, Ws) = x.shape[0], x.shape[-2:]
+    frames = x.reshape(N, -1, Hs, Ws)
+    planes = frames.shape[1]
+    out = torch.zeros(rows.numel() * planes, 1, out_h, out_w, dtype=torch.float64)
+    for i in range(out.shape[0]):
+        b, plane = divmod(i, planes)
+        r, top, left = int(rows[b]), int(offsets[i, 0]), int(offsets[i, 1])
         if not 0 <= r < N:
             continue
         y0, y1 = max(top, 0), min(top + out_h, Hs)
         x0, x1 = max(left, 0), min(left + out_w, Ws)
         if y0 < y1 and x0 < x1:
-            out[b, :, :, y0 - top:y1 - top, x0 - left:x1 - left] = x[r, :, :, y0:y1, x0:x1].double()
+            out[i, 0, y0 - top:y1 - top, x0 - left:x1 - left] = frames[r, plane, y0:y1, x0:x1].double()
     return out
+
+
+def sample_window(x, rows, offsets, out_h, out_w):
+    """The camera's case of ``window``: (N, T, 1, Hs, Ws) and one (top, left) per SAMPLE -> (B, T, 1, out_h, out_w)."""
+    T = x.shape[1]
+    return window(x, rows, offsets.repeat_interleave(T, 0), out_h, out_w).reshape(rows.numel(), T, 1, out_h, out_w)
 
 
 def _theta(ang, H, W):
@@ -98,7 +107,7 @@ def augment(img, seg, rows, offsets, angles, keep, out_h, out_w, patch, noise_st
     outs, bands = [], []
     for k, x in enumerate((img, seg)):
         ang = angles[:, k].repeat_interleave(T)
-        y = window(x, rows, offsets, out_h, out_w).reshape(B * T, 1, out_h, out_w)
+        y = window(x, rows, offsets.repeat_interleave(T, 0), out_h, out_w)
         y = torch.where((ang != 0)[:, None, None, None], rotate(y, ang), y)
         if noise_std > 0:
             y = y + float(np.float32(noise_std)) * gauss(seed, k, y.shape)

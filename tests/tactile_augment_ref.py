@@ -1,36 +1,17 @@
 """Float64 restatement of the tactile augmentation (csrc/tactile_augment.h, utils.TactileAugment) -- TEST INFRASTRUCTURE.
 
-Plain torch on the CPU, image by image where the kernel works image by image: slicing for the gather and the crop, the
-jitter's two clamped lines in float64, and from tests/img_augment_ref.py the float64 rotation, its tie band, the
+Plain torch on the CPU, image by image where the kernel works image by image: the jitter's two clamped lines in float64,
+and from tests/img_augment_ref.py the gather and crop by slicing (``window``), the float64 rotation, its tie band, the
 Box-Muller over ``oracle.token_dropout.tok_hash`` and the repeated ``keep``.  Every function takes the op's arguments (CPU
 tensors; the fp32 parameters are widened exactly) and returns float64.
 """
 import numpy as np
 import torch
 
-from tests.img_augment_ref import TIE_EPS, TIE_SHARE_MAX, gauss, patch_mask, rotate, tie_band  # noqa: F401
+from tests.img_augment_ref import TIE_EPS, TIE_SHARE_MAX, gauss, patch_mask, rotate, tie_band, window  # noqa: F401
 
 NOISE_PLANE = 2          # hash sites 4 and 5; the camera pair holds planes 0 and 1
 U = 2.0 ** -24           # fp32 unit roundoff
-
-
-def window(arena, rows, offsets, out_h, out_w):
-    """Gather + crop: (N, T, F, 1, Hs, Ws) -> (B*T*F, 1, out_h, out_w) float64, every image with its own (top, left).  A
-    sample number outside [0, N) and every position outside the stored frame read as 0."""
-    N, T, Fg, _, Hs, Ws = arena.shape
-    B = rows.numel()
-    out = torch.zeros(B * T * Fg, 1, out_h, out_w, dtype=torch.float64)
-    for i in range(B * T * Fg):
-        b, plane = divmod(i, T * Fg)
-        r, top, left = int(rows[b]), int(offsets[i, 0]), int(offsets[i, 1])
-        if not 0 <= r < N:
-            continue
-        y0, y1 = max(top, 0), min(top + out_h, Hs)
-        x0, x1 = max(left, 0), min(left + out_w, Ws)
-        if y0 < y1 and x0 < x1:
-            frame = arena[r].reshape(T * Fg, Hs, Ws)[plane]
-            out[i, 0, y0 - top:y1 - top, x0 - left:x1 - left] = frame[y0:y1, x0:x1].double()
-    return out
 
 
 def jitter_image(x, b, c):

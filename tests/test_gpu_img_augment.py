@@ -67,7 +67,7 @@ def test_rotation_matches_the_restatement_off_the_tie_band(arena, out, T):
     assert (share <= R.TIE_SHARE_MAX).all()
     assert torch.equal(torch.where(band[0], ra, a.double()), ra)
     assert torch.equal(torch.where(band[1], rb, b.double()), rb)
-    win_a, win_b = R.window(img, ROWS, off, *out), R.window(seg, ROWS, off, *out)
+    win_a, win_b = R.sample_window(img, ROWS, off, *out), R.sample_window(seg, ROWS, off, *out)
     assert torch.equal(a[0].double(), win_a[0]) and torch.equal(b[0].double(), win_b[0])      # angle 0: the window
     assert torch.equal(a[2].double(), win_a[2])                                               # sample 2: mask only
     if out == (54, 96):               # (at 17 x 23 one degree moves no pixel by half a pixel: the rotation is a copy)
@@ -90,7 +90,7 @@ def test_patch_masking_is_exact_and_image_only(arena, out, patch, T):
     a, b = _op(img, seg, ROWS, off, ang, keep, *out, patch)
     ra, rb, _ = R.augment(img, seg, ROWS, off, ang, keep, *out, patch)
     assert torch.equal(a.double(), ra) and torch.equal(b.double(), rb)
-    assert torch.equal(b.double(), R.window(seg, ROWS, off, *out))
+    assert torch.equal(b.double(), R.sample_window(seg, ROWS, off, *out))
     dropped = R.patch_mask(keep, *out, patch).reshape(5, T, 1, *out) == 0
     assert ((a == 0) == dropped).all()
     assert not dropped[..., gh * patch:, :].any() and not dropped[..., :, gw * patch:].any()  # remainder rows / columns

@@ -212,7 +212,7 @@ def test_sync_transform_apply_equals_the_restatement():
     assert a.shape == (5, 2, 1, 17, 23) and a.dtype == torch.float32
     assert band.double().mean() <= R.TIE_SHARE_MAX
     assert torch.equal(torch.where(band[0], ra, a.double()), ra) and torch.equal(torch.where(band[1], rb, b.double()), rb)
-    assert not torch.equal(ra[3], R.window(img, torch.arange(5), off, 17, 23)[3])        # it did rotate
+    assert not torch.equal(ra[3], R.sample_window(img, torch.arange(5), off, 17, 23)[3]) # it did rotate
 
 
 def test_sync_transform_forward_on_an_item_and_a_batch():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """One training batch of the camera pair (depth frames + segmentation masks) through the fused augmentation, beside ATen.
 
-    python tools/bench_img_augment.py [--rounds R] [--iters K] [--out profiles/img_augment.json]
+    python tools/bench_img_augment.py [--rounds R] [--iters K] [--root TREE] [--out profiles/img_augment.json]
 
 The batch of the offline student's default configuration: 64 samples, T = 1, arenas of 60 x 104 frames (2048 resident
 samples), crop to 54 x 96, rotation 1 degree, Gaussian noise 0.01, patch masking 0.3 (patch 16).
@@ -10,7 +10,9 @@ samples), crop to 54 x 96, rotation 1 degree, Gaussian noise 0.01, patch masking
   aten  : two ``index_select``s, then ``SyncTransform.forward`` -- the same CPU draw and the torch-op composition
           (advanced-index crop, affine_grid + grid_sample, randn noise, repeat_interleave mask) on the device.
 Host clock around K iterations ending in a device synchronise, R alternating rounds, medians with min .. max, in ms per
-batch.  The record is stamped with the library's build hash.  No bar: the pair is stated in README as it comes out.
+batch.  The record is stamped with the library's build hash.  --root: the tree whose package and library to time
+(default: this one), to set another commit's build beside this one in the same job. No bar: the pair is stated in README
+as it comes out.
 """
 import argparse
 import json
@@ -34,7 +36,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "img_augment.json"))
+    ap.add_argument("--root", default=ROOT, help="the tree whose package and library to load")
     args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_img_augment: no HIP device (timings are taken on the GPU only)")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """One training batch of tactile images through the fused augmentation, beside today's torch path.
 
-    python tools/bench_tactile_augment.py [--rounds R] [--iters K] [--out profiles/tactile_augment.json]
+    python tools/bench_tactile_augment.py [--rounds R] [--iters K] [--root TREE] [--out profiles/tactile_augment.json]
 
 The batch of the offline student: 64 samples, T = 1, 3 fingers, 32 x 64 frames in [-1, 1] (2048 resident samples), in two
 configurations:
@@ -12,7 +12,9 @@ configurations:
   torch : ``index_select``, then the ``nn.Sequential`` of ``define_tactile_transforms`` (``_Crop`` + ``_TrainAugment`` +
           ``GaussianNoise`` + ``Masking``) on the device, as ``ResidentLoader`` calls it -- code from before the fused path.
 Host clock around K iterations ending in a device synchronise, R alternating rounds, medians with min .. max, in ms per
-batch.  The record is stamped with the library's build hash.  No bar: the pairs are stated in README as they come out.
+batch.  The record is stamped with the library's build hash.  --root: the tree whose package and library to time
+(default: this one), to set another commit's build beside this one in the same job. No bar: the pairs are stated in
+README as they come out.
 """
 import argparse
 import json
@@ -39,7 +41,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tactile_augment.json"))
+    ap.add_argument("--root", default=ROOT, help="the tree whose package and library to load")
     args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_tactile_augment: no HIP device (timings are taken on the GPU only)")
