@@ -783,6 +783,36 @@ int igi_tactile_augment(const float* arena, int64_t n, int planes, int hs, int w
                         const int32_t* params, const uint8_t* keep, int out_h, int out_w, int patch, float noise_std,
                         uint64_t seed, float* out, igi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Train-time augmentation of the online student's segmented point cloud (csrc/pcl_augment.h), ONE launch from the
+ * environment's cloud tensor to a new tensor (PointCloudAugmentations.augment of the reference's environment,
+ * factory_utils.py:83-166, which runs it object by object on a boolean-masked subset of the envs):
+ *   clouds    : fp32 [n][p_total][3], p_total = the sum of points[0 .. nobj), nobj in 1..4 consecutive objects (the layout
+ *               of igi_pointnet_forward_multi); never written.  points[o] in 1..4096 (above: IGI_E_UNSUPPORTED)
+ *   points    : HOST array of nobj counts
+ *   episode   : DEVICE int32 [n], the caller's episode counter of every env; never written
+ *   params    : the stages' parameters.  Env e is augmented iff its hit draw falls below hit_prob (one draw per env); a
+ *               missed env is copied bit for bit.  A hit cloud: (a) x += clamp(sigma z, +-noise_clip) on the points whose
+ *               mask draw falls below noise_prob, then x += clamp(const_noise pn, +-noise_clip); (b) rot_deg > 0: rotation
+ *               about one axis through the origin by an angle uniform in +-rot_deg degrees; (c) int(points[o] *
+ *               outlier_ratio) points replaced by outliers -- with probability contour_prob just outside the cloud's
+ *               bounding box, else outlier_scale z; of two outliers on one point the later one wins; (d) dropout_ratio > 0:
+ *               with probability 1 - no_dropout_prob per cloud, every point is zeroed with probability dropout_ratio.
+ *               pn, the angle and the axis are per-episode: a pure function of (seed_episode, env, episode[env]), shared
+ *               by an env's objects; every other draw is a pure function of (seed_step, element).  The hash sites and
+ *               Gaussian planes are tabled in csrc/pcl_augment.h.  Probabilities outside [0, 1], negative sigma /
+ *               noise_clip / rot_deg / ratios, and n * p_total * 3 >= 2^32: IGI_E_BADARG
+ *   out       : fp32 [n][p_total][3], not the input.  Same arguments, same bits
+ * ---------------------------------------------------------------------------------------- */
+#define IGI_PCL_AUG_MAX_POINTS 4096
+typedef struct igi_pcl_augment_params {
+  double sigma, noise_clip, const_noise, noise_prob, hit_prob, rot_deg, outlier_ratio, contour_prob, outlier_scale,
+      dropout_ratio, no_dropout_prob;
+} igi_pcl_augment_params;
+int igi_pcl_augment(const float* clouds, int64_t n, int nobj, const int32_t* points, const int32_t* episode,
+                    const igi_pcl_augment_params* params, uint64_t seed_episode, uint64_t seed_step, float* out,
+                    igi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,13 @@ class DepthCfg(C.Structure):
     _fields_ = [("batch", C.c_int32), ("latent_dim", C.c_int32)]
 
 
+class PclAugmentParams(C.Structure):
+    """struct igi_pcl_augment_params"""
+    FIELDS = ("sigma", "noise_clip", "const_noise", "noise_prob", "hit_prob", "rot_deg", "outlier_ratio", "contour_prob",
+              "outlier_scale", "dropout_ratio", "no_dropout_prob")
+    _fields_ = [(k, C.c_double) for k in FIELDS]
+
+
 class ProfEntry(C.Structure):
     """struct igi_prof_entry"""
     _fields_ = [("name", C.c_char_p), ("launches", C.c_int64), ("total_ms", C.c_double),
@@ -246,6 +253,8 @@ _EXPORTS = {
     "igi_tactile_augment": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_void_p,
                                       C.c_void_p]),
+    "igi_pcl_augment": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_void_p,
+                                  C.POINTER(PclAugmentParams), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "igi_pointnet_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "igi_pointnet_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),

@@ -22,6 +22,7 @@ from ..models.transformer.runner import Runner as Student
 from ..ppo.experience import StudentBuffer
 from ..ppo.frozen_ppo import _NullWriter, _summary_writer, log_test_result
 from ...bc_loss import bc_loss
+from ...envs.pcl_augment import PclAugment
 from ...optim import FlatAdam
 from ...utils.config import parse_latent_loss
 from ...utils.misc import AverageScalarMeter
@@ -86,6 +87,9 @@ class ExtrinsicAdapt(object):
         self.stud_obs_mean_std.train()
         self.pcl_mean_std = RunningMeanStd((3,)).to(self.device)
         self.pcl_mean_std.train()
+        self.pcl_augment, self.pcl_episode = self._make_pcl_augment(), None
+        if self.pcl_augment is not None:
+            self.pcl_episode = torch.zeros(self.num_actors, dtype=torch.int32, device=self.device)
         self.student = Student(student_cfg)
         self.stats = None
         self.output_dir = output_dir
@@ -157,9 +161,33 @@ class ExtrinsicAdapt(object):
             self.stud_obs_mean_std.train()
             self.pcl_mean_std.train()
 
-    def process_obs(self, obs, obj_id=2, socket_id=3, distinct=True):
+    def _make_pcl_augment(self):
+        """``task.env.pcl_augment``: absent / "off" = None; "fused" = the environment's point-cloud augmentation on the
+        learner's side (the reference runs it inside its IsaacGym task, factory_task_insertion.py:876-881, 951-986).
+        Switched on it is the reference's live ``augment``: noise on ``PclProbNoise`` of the envs; rotation by up to
+        ``randomize.pcl_rot`` degrees, outliers and dropout are further switches (off by default, as in the reference)."""
+        env = self.task_config.env
+        key = env.get('pcl_augment', None)
+        if key is None or (isinstance(key, str) and key == 'off'):
+            return None
+        if not (isinstance(key, str) and key == 'fused'):
+            raise ValueError(f"task.env.pcl_augment: expected 'off' or 'fused', got {key!r}")
+        if not self.pcl_info:
+            raise ValueError("task.env.pcl_augment: 'fused' needs the point cloud (train.ppo.pcl_info: True)")
+        rnd = self.task_config.get('randomize', None) or {}
+        points = [int(env[n]) for flag, n in (('include_plug_pcl', 'num_points'), ('merge_socket_pcl', 'num_points_socket'),
+                                              ('merge_goal_pcl', 'num_points_goal'), ('include_all_pcl', 'num_points_goal'))
+                  if env[flag]]                      # the PointNets' objects, in their order (runner.py: pcl_conf)
+        seed = int(self.full_config.get('seed', 0)) + (self.rank if self.multi_gpu else 0)
+        return PclAugment(points, hit_prob=float(env.get('PclProbNoise', 0.7)),
+                          rot_deg=float(rnd.get('pcl_rot', 30.0)) if rnd.get('pcl_rotate', False) else 0.0,
+                          outlier_ratio=float(rnd.get('pcl_outlier_ratio', 0.0)),
+                          dropout_ratio=float(rnd.get('pcl_dropout_ratio', 0.0)), seed=seed)
+
+    def process_obs(self, obs, obj_id=2, socket_id=3, distinct=True, augment=False):
         """ext_adapt.py:383-435: normalise student_obs and the point cloud (both normalisers are in
-        train mode during rollout: SURVEY Appendix A17); tactile passes through."""
+        train mode during rollout: SURVEY Appendix A17); tactile passes through.  ``augment`` (the rollout's calls only):
+        the cloud goes through ``PclAugment.fused`` before its normaliser when ``task.env.pcl_augment`` is on."""
         student_obs = obs['student_obs'] if self.obs_info else None
         tactile = obs['tactile'] if self.tactile_info else None
         img = obs['img'] if self.img_info else None
@@ -171,6 +199,8 @@ class ExtrinsicAdapt(object):
             if self.img_info:
                 img = img * valid_mask
         if self.pcl_info:
+            if augment and self.pcl_augment is not None:
+                pcl = self.pcl_augment.fused(pcl.contiguous(), self.pcl_episode)
             pcl = self.pcl_mean_std(pcl.reshape(-1, 3)).reshape((obs['pcl'].shape[0], -1, 3))
         if student_obs is not None:
             if self.stats is not None and self.train_config.from_offline:
@@ -278,7 +308,7 @@ class ExtrinsicAdapt(object):
             n_obs = self.running_mean_std(self.obs['obs'])
             n_priv_info = self.priv_mean_std(self.obs['priv_info'])
             res_dict = self.agent.full_act({'obs': n_obs, 'priv_info': n_priv_info})
-            student_dict = self.process_obs(self.obs)
+            student_dict = self.process_obs(self.obs, augment=True)
             latent, _ = self.student.predict(student_dict, requires_grad=False)
             if not self.only_bc:                                   # ext_adapt.py:684-690
                 student_actions, _ = self.agent.act_inference({'obs': n_obs, 'latent': latent})
@@ -312,6 +342,8 @@ class ExtrinsicAdapt(object):
             # (ext_adapt.py:735-760 gathers the finished episodes with nonzero() every step)
             rewards = rewards.to(torch.float32).contiguous()
             dones = self.dones if self.dones.dtype == torch.uint8 else self.dones.to(torch.uint8)
+            if self.pcl_episode is not None:       # a finished env redraws its per-episode parameters (reset_idx does)
+                self.pcl_episode += dones.reshape(-1).to(torch.int32)
             touts = infos.get('time_outs') if self.ppo_config['value_bootstrap'] else None
             if touts is not None:
                 touts = (touts.view(torch.uint8) if touts.dtype == torch.bool else touts.to(torch.uint8)).contiguous()

@@ -20,6 +20,7 @@
 #include "glue.h"
 #include "augment.h"
 #include "tactile_augment.h"
+#include "pcl_augment.h"
 #include "peak_probe.h"
 
 namespace {
@@ -709,6 +710,20 @@ int igi_tactile_augment(const float* arena, int64_t n, int planes, int hs, int w
                         uint64_t seed, float* out, igi_stream_t stream) {
   return fail(igi::tactile_augment(arena, n, planes, hs, ws, rows, b, params, keep, out_h, out_w, patch, noise_std, seed,
                                    out, S(stream)), "igi_tactile_augment");
+}
+
+static_assert(IGI_PCL_AUG_MAX_POINTS == igi::PCL_MAX_POINTS, "igi_ppo.h and pcl_augment.h disagree on the largest cloud");
+static_assert(sizeof(igi_pcl_augment_params) == sizeof(igi::PclAugParams), "igi_ppo.h and pcl_augment.h disagree on the parameters");
+
+int igi_pcl_augment(const float* clouds, int64_t n, int nobj, const int32_t* points, const int32_t* episode,
+                    const igi_pcl_augment_params* params, uint64_t seed_episode, uint64_t seed_step, float* out,
+                    igi_stream_t stream) {
+  if (!params) return fail(IGI_E_BADARG, "igi_pcl_augment");
+  const igi::PclAugParams q{params->sigma, params->noise_clip, params->const_noise, params->noise_prob, params->hit_prob,
+                            params->rot_deg, params->outlier_ratio, params->contour_prob, params->outlier_scale,
+                            params->dropout_ratio, params->no_dropout_prob};
+  return fail(igi::pcl_augment(clouds, n, nobj, points, episode, q, seed_episode, seed_step, out, S(stream)),
+              "igi_pcl_augment");
 }
 
 size_t igi_pointnet_workspace_bytes(int64_t batch) { return batch < 1 ? 0 : igi::pointnet_workspace_bytes(batch); }

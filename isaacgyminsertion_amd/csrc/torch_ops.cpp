@@ -395,6 +395,48 @@ Tensor tactile_augment(const Tensor& arena, const Tensor& rows, const Tensor& pa
   return out;
 }
 
+// ---- rollout (factory_utils.py:83-166: the environment's point-cloud augmentation, one launch on the learner's side)
+Tensor pcl_augment(const Tensor& clouds, at::IntArrayRef points, const Tensor& episode, at::ArrayRef<double> params,
+                   int64_t seed_episode, int64_t seed_step) {
+  static const char* const names[11] = {"sigma", "noise_clip", "const_noise", "noise_prob", "hit_prob", "rot_deg",
+                                        "outlier_ratio", "contour_prob", "outlier_scale", "dropout_ratio", "no_dropout_prob"};
+  TORCH_CHECK(clouds.defined() && clouds.scalar_type() == at::kFloat, "clouds: expected dtype ", at::kFloat);
+  TORCH_CHECK(clouds.dim() == 3, "clouds: expected 3 dimensions, got shape ", clouds.sizes());
+  TORCH_CHECK(clouds.is_contiguous(), "clouds: expected a contiguous tensor");
+  TORCH_CHECK(episode.defined() && episode.scalar_type() == at::kInt, "episode: expected dtype ", at::kInt);
+  TORCH_CHECK(episode.dim() == 1, "episode: expected 1 dimensions, got shape ", episode.sizes());
+  TORCH_CHECK(episode.is_contiguous(), "episode: expected a contiguous tensor");
+  const int64_t nobj = (int64_t)points.size();
+  TORCH_CHECK(nobj >= 1 && nobj <= 4, "points: expected 1..4 objects, got ", nobj);
+  int32_t pts[4];
+  int64_t total = 0;
+  for (int64_t k = 0; k < nobj; ++k) {
+    TORCH_CHECK(points[k] >= 1 && points[k] <= IGI_PCL_AUG_MAX_POINTS, "points[", k, "]: expected 1..", IGI_PCL_AUG_MAX_POINTS,
+                " points, got ", points[k]);
+    pts[k] = (int32_t)points[k];
+    total += points[k];
+  }
+  TORCH_CHECK((clouds.size(1) == 1 && clouds.size(2) == total * 3) || (clouds.size(1) == total && clouds.size(2) == 3),
+              "clouds: expected (N, 1, ", total * 3, ") or (N, ", total, ", 3) for points ", points, ", got ", clouds.sizes());
+  const int64_t N = clouds.size(0);
+  TORCH_CHECK(episode.size(0) == N, "episode: expected shape (", N, ",), got ", episode.sizes());
+  TORCH_CHECK(params.size() == 11, "params: expected 11 values, got ", params.size());
+  for (int k : {3, 4, 6, 7, 9, 10}) TORCH_CHECK(params[k] >= 0 && params[k] <= 1, names[k], ": expected a value in [0, 1], got ", params[k]);
+  for (int k : {0, 1, 5}) TORCH_CHECK(params[k] >= 0, names[k], ": expected >= 0, got ", params[k]);
+  TORCH_CHECK(N * total * 3 < (int64_t(1) << 32), "clouds: expected fewer than 2^32 coordinates (32-bit element numbers), got ",
+              N * total * 3);
+  check(clouds, "clouds"); check(episode, "episode", at::kInt);
+  TORCH_CHECK(episode.device() == clouds.device(), "episode: all arguments must share one device");
+  Tensor out = at::empty_like(clouds);
+  if (N == 0) return out;
+  const igi_pcl_augment_params q{params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7],
+                                 params[8], params[9], params[10]};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(clouds.device());
+  rc(igi_pcl_augment(fp(clouds), N, (int)nobj, pts, episode.data_ptr<int32_t>(), &q, (uint64_t)seed_episode,
+                     (uint64_t)seed_step, fp(out), stream_of(clouds)), "igi_pcl_augment");
+  return out;
+}
+
 }  // namespace
 
 // Schemas: character for character those of isaacgyminsertion_amd/ops.py (tests/test_torch_library_cpp.py compares them).
@@ -415,6 +457,7 @@ TORCH_LIBRARY(mi355ppo, m) {
   m.def("pointnet_max_fwd(Tensor x, Tensor params) -> (Tensor, Tensor)");
   m.def("pointnet_max_bwd(Tensor x, Tensor params, Tensor dy, Tensor idx) -> Tensor");
   m.def("tactile_augment(Tensor arena, Tensor rows, Tensor params, Tensor? keep, int out_h, int out_w, int patch, float noise_std, int seed) -> Tensor");
+  m.def("pcl_augment(Tensor clouds, int[] points, Tensor episode, float[] params, int seed_episode, int seed_step) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(mi355ppo, CompositeExplicitAutograd, m) {
@@ -434,4 +477,5 @@ TORCH_LIBRARY_IMPL(mi355ppo, CompositeExplicitAutograd, m) {
   m.impl("pointnet_max_fwd", pointnet_max_fwd);
   m.impl("pointnet_max_bwd", pointnet_max_bwd);
   m.impl("tactile_augment", tactile_augment);
+  m.impl("pcl_augment", pcl_augment);
 }

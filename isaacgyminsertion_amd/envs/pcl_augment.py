@@ -3,7 +3,13 @@
 names and argument meaning; every method is batched elementwise torch on the device the cloud lives on, so it
 adds a handful of launches per environment step to the rollout, nothing to the update.  ``augment`` applies what
 the reference applies (point-wise + per-env constant noise; rotation / outliers / dropout exist but are commented
-out there, factory_utils.py:156-162)."""
+out there, factory_utils.py:156-162).
+
+``PclAugment`` is the learner-side form of the same augmentation: the whole chain, with the environment's per-step hit and
+per-episode parameters, in one native launch (csrc/pcl_augment.h)."""
+import math
+
+import numpy as np
 import torch
 
 
@@ -69,3 +75,164 @@ class PointCloudAugmentations:
         if not pointcloud_batch.shape[0]:
             return pointcloud_batch
         return self.random_noise(pointcloud_batch, pcl_noise)
+
+
+# ---------------------------------------------------------------------------------------------
+# the same augmentation on the learner's side: one native launch per environment step (csrc/pcl_augment.h)
+# ---------------------------------------------------------------------------------------------
+_M32 = np.uint64(0xFFFFFFFF)
+# csrc/pcl_augment.h: the table of hash sites and Gaussian planes
+PLANE_PN, PLANE_JITTER, PLANE_FREE, PLANE_CONTOUR = 3, 4, 5, 6
+SITE_HIT, SITE_ANGLE, SITE_AXIS, SITE_MASK, SITE_CONTOUR, SITE_SIDE, SITE_INDEX, SITE_EXEMPT, SITE_DROP = range(14, 23)
+
+
+def _hash(lo, hi, site, idx):
+    """csrc/tok_hash.h in numpy uint64 arithmetic masked to 32 bits: ``lo`` / ``hi`` the seed's two words (ints or arrays
+    that broadcast against ``idx``) -> uint64 values below 2^32 of the broadcast shape."""
+    def mul(x, k):
+        return (x * np.uint64(k)) & _M32
+    lo, hi = np.asarray(lo, dtype=np.uint64) & _M32, np.asarray(hi, dtype=np.uint64) & _M32
+    x = mul(np.asarray(idx, dtype=np.uint64) & _M32, 0x9E3779B1) ^ lo ^ np.uint64((site * 0x85EBCA77) & 0xFFFFFFFF)
+    x = mul(x ^ (x >> np.uint64(16)), 0x7FEB352D)
+    x = mul(x ^ (x >> np.uint64(15)), 0x846CA68B)
+    x = ((x ^ (x >> np.uint64(16))) + hi) & _M32
+    x = mul(x ^ (x >> np.uint64(15)), 0x2C1B3C6D)
+    x = mul(x ^ (x >> np.uint64(12)), 0x297A2D39)
+    return x ^ (x >> np.uint64(15))
+
+
+def _gauss(lo, hi, plane, e):
+    """csrc/aug_gauss.h: the Box-Muller sample of (seed, plane, e), float64."""
+    k1, k2 = _hash(lo, hi, 2 * plane, e) >> np.uint64(8), _hash(lo, hi, 2 * plane + 1, e) >> np.uint64(8)
+    u1 = (k1.astype(np.float64) + 0.5) * 2.0 ** -24
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * math.pi * (k2.astype(np.float64) * 2.0 ** -24))
+
+
+def _threshold(p):
+    """An event of probability ``p`` is ``hash < _threshold(p)``: p rounded to float32, times 2^32, truncated (the token
+    encoder's ``make_drop``), kept above 32 bits so that p = 1 is "always"."""
+    return np.uint64(int(float(np.float32(p)) * 2.0 ** 32)) if p > 0 else np.uint64(0)
+
+
+class PclAugment:
+    """``PointCloudAugmentations.augment`` with the reference's environment logic around it (factory_task_insertion.py:
+    299-303, 876-881, 951-986: applied to ``hit_prob`` of the envs per step, with a per-episode offset / angle / axis), for
+    the whole cloud tensor of an environment step -- ``points`` the 1..4 consecutive objects of the PointNets' layout -- and
+    with the random numbers of a call apart from its arithmetic: every draw is the counter hash of csrc/pcl_augment.h.
+      ``draw()``                           -> the step's seed, from this object's private CPU generator;
+      ``apply(clouds, episode, seed_step)`` -> the augmentation in plain torch ops, on any device and in clouds' dtype;
+      ``fused(clouds, episode)``            -> draw + torch.ops.mi355ppo.pcl_augment: one launch.
+    ``episode`` is the caller's int32 (N,) episode counter; the per-episode parameters change when it does.  Stages:
+    noise (always), rotation (``rot_deg`` > 0), outliers (``outlier_ratio`` > 0), dropout (``dropout_ratio`` > 0).  The
+    input is never written."""
+
+    def __init__(self, points, hit_prob=0.7, rot_deg=0.0, outlier_ratio=0.0, dropout_ratio=0.0, sigma=0.001,
+                 noise_clip=0.001, const_noise=0.001, noise_prob=0.3, contour_prob=0.75, outlier_scale=1.5,
+                 no_dropout_prob=0.8, seed=0):
+        self.points = [int(p) for p in points]
+        if not 1 <= len(self.points) <= 4 or min(self.points) < 1:
+            raise ValueError(f"points: expected 1..4 objects of at least one point, got {list(points)}")
+        self.hit_prob, self.rot_deg, self.outlier_ratio = float(hit_prob), float(rot_deg), float(outlier_ratio)
+        self.dropout_ratio, self.sigma, self.noise_clip = float(dropout_ratio), float(sigma), float(noise_clip)
+        self.const_noise, self.noise_prob, self.contour_prob = float(const_noise), float(noise_prob), float(contour_prob)
+        self.outlier_scale, self.no_dropout_prob = float(outlier_scale), float(no_dropout_prob)
+        for nm in ("hit_prob", "outlier_ratio", "dropout_ratio", "noise_prob", "contour_prob", "no_dropout_prob"):
+            if not 0 <= getattr(self, nm) <= 1:
+                raise ValueError(f"{nm}: expected a value in [0, 1], got {getattr(self, nm)}")
+        for nm in ("rot_deg", "sigma", "noise_clip"):
+            if not getattr(self, nm) >= 0:
+                raise ValueError(f"{nm}: expected >= 0, got {getattr(self, nm)}")
+        self.generator = torch.Generator().manual_seed(int(seed))
+        self.seed_episode = self.draw()
+        self.seed_step = None            # the last seed ``fused`` drew
+
+    def params(self):
+        """The op's ``params`` (ops.PCL_AUG_PARAMS)."""
+        return [self.sigma, self.noise_clip, self.const_noise, self.noise_prob, self.hit_prob, self.rot_deg,
+                self.outlier_ratio, self.contour_prob, self.outlier_scale, self.dropout_ratio, self.no_dropout_prob]
+
+    def draw(self):
+        """One 63-bit seed from the private generator; torch's global generators are not touched."""
+        return int(torch.randint(0, 2 ** 63 - 1, (1,), generator=self.generator))
+
+    def apply(self, clouds, episode, seed_step):
+        pts, Pt = self.points, sum(self.points)
+        N = clouds.shape[0]
+        if clouds.numel() != N * Pt * 3:
+            raise ValueError(f"clouds: expected {Pt * 3} coordinates per env for points {pts}, got {tuple(clouds.shape)}")
+        x = clouds.reshape(N, Pt, 3)
+        dt, dev = x.dtype, x.device
+
+        def T(a, dtype=dt):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype)
+
+        f32 = lambda v: float(np.float32(v))   # noqa: E731  (the kernel receives fp32 scalars)
+        st_lo, st_hi = int(seed_step) & 0xFFFFFFFF, (int(seed_step) >> 32) & 0xFFFFFFFF
+        ep = episode.detach().cpu().numpy().astype(np.int64).astype(np.uint64) & _M32
+        ep_lo = self.seed_episode & 0xFFFFFFFF
+        ep_hi = (np.uint64((self.seed_episode >> 32) & 0xFFFFFFFF) + ep) & _M32          # se = seed + (episode << 32)
+        env = np.arange(N, dtype=np.uint64)
+        g = env[:, None] * np.uint64(Pt) + np.arange(Pt, dtype=np.uint64)[None]              # (N, Pt) point numbers
+        e = g[:, :, None] * np.uint64(3) + np.arange(3, dtype=np.uint64)                    # (N, Pt, 3)
+        hit = _hash(st_lo, st_hi, SITE_HIT, env) < _threshold(self.hit_prob)
+        clip = f32(self.noise_clip)
+        # a. noise
+        y = x
+        jit = torch.zeros_like(x)
+        if self.sigma > 0:
+            mask = _hash(st_lo, st_hi, SITE_MASK, g) < _threshold(self.noise_prob)
+            z = _gauss(st_lo, st_hi, PLANE_JITTER, e)
+            jit = (T(z) * f32(self.sigma)).clamp(-clip, clip) * T(mask)[:, :, None]
+        y = y + jit
+        pn = _gauss(ep_lo, ep_hi[:, None], PLANE_PN, env[:, None] * np.uint64(3) + np.arange(3, dtype=np.uint64))
+        y = y + (T(pn) * f32(self.const_noise)).clamp(-clip, clip)[:, None, :]
+        # b. rotation
+        if self.rot_deg > 0:
+            u = (_hash(ep_lo, ep_hi, SITE_ANGLE, env) >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+            axis = T(((_hash(ep_lo, ep_hi, SITE_AXIS, env) >> np.uint64(8)) * np.uint64(3)) >> np.uint64(24), torch.int64)
+            ang = ((2.0 * T(u) - 1.0) * f32(self.rot_deg)) * (f32(math.pi / 180) if dt == torch.float32 else math.pi / 180)
+            cs, sn = torch.cos(ang)[:, None], torch.sin(ang)[:, None]
+            a0, a1, a2 = y[..., 0], y[..., 1], y[..., 2]
+            ax = axis[:, None]
+            r0 = torch.where(ax == 0, a0, torch.where(ax == 1, a0 * cs - a2 * sn, a0 * cs + a1 * sn))
+            r1 = torch.where(ax == 0, a1 * cs + a2 * sn, torch.where(ax == 1, a1, a1 * cs - a0 * sn))
+            r2 = torch.where(ax == 0, a2 * cs - a1 * sn, torch.where(ax == 1, a0 * sn + a2 * cs, a2))
+            y = torch.stack([r0, r1, r2], -1)
+        # c. outliers, d. dropout: object by object
+        drop_all = np.zeros((N, Pt), dtype=bool)
+        parts, off = [], 0
+        for o, P in enumerate(pts):
+            sl = y[:, off:off + P]
+            K = int(P * self.outlier_ratio)
+            if K > 0:
+                lo, hi = sl.min(dim=1, keepdim=True).values, sl.max(dim=1, keepdim=True).values
+                gk, ek = g[:, off:off + K], e[:, off:off + K]
+                contour = _hash(st_lo, st_hi, SITE_CONTOUR, gk) < _threshold(self.contour_prob)
+                idx = ((_hash(st_lo, st_hi, SITE_INDEX, gk) >> np.uint64(8)) * np.uint64(P)) >> np.uint64(24)
+                free = T(_gauss(st_lo, st_hi, PLANE_FREE, ek)) * f32(self.outlier_scale)
+                beyond = T(np.abs(_gauss(st_lo, st_hi, PLANE_CONTOUR, ek)))
+                side = T(_hash(st_lo, st_hi, SITE_SIDE, ek) < _threshold(0.5), torch.bool)
+                new = torch.where(T(contour, torch.bool)[:, :, None], torch.where(side, hi + beyond, lo - beyond), free)
+                win = np.full((N, P), -1, dtype=np.int64)                                    # the highest k wins
+                np.maximum.at(win, (np.repeat(np.arange(N), K), idx.astype(np.int64).reshape(-1)), np.tile(np.arange(K), N))
+                w = T(win, torch.int64)
+                picked = torch.gather(new, 1, w.clamp(min=0)[:, :, None].expand(N, P, 3))
+                sl = torch.where((w >= 0)[:, :, None], picked, sl)
+            if self.dropout_ratio > 0:
+                live = _hash(st_lo, st_hi, SITE_EXEMPT, env * np.uint64(4) + np.uint64(o)) < _threshold(1.0 - self.no_dropout_prob)
+                drop_all[:, off:off + P] = (_hash(st_lo, st_hi, SITE_DROP, g[:, off:off + P]) <
+                                            _threshold(self.dropout_ratio)) & live[:, None]
+            parts.append(sl)
+            off += P
+        y = torch.cat(parts, 1) if len(parts) > 1 else parts[0]
+        if self.dropout_ratio > 0:
+            y = torch.where(T(drop_all, torch.bool)[:, :, None], torch.zeros_like(y), y)
+        return torch.where(T(hit, torch.bool)[:, None, None], y, x).reshape(clouds.shape)
+
+    def fused(self, clouds, episode):
+        """draw + the op; clouds above 4096 points per object take the same draws through ``apply``."""
+        from .. import ops                   # registers torch.ops.mi355ppo (and loads the native library) on first use
+        self.seed_step = self.draw()
+        if max(self.points) > ops.PCL_AUG_MAX_POINTS:
+            return self.apply(clouds, episode, self.seed_step)
+        return torch.ops.mi355ppo.pcl_augment(clouds, self.points, episode, self.params(), self.seed_episode, self.seed_step)

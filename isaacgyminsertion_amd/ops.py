@@ -1725,6 +1725,72 @@ def _(arena, rows, params, keep, out_h, out_w, patch, noise_std, seed):
     return arena.new_empty((rows.numel(), arena.shape[1], arena.shape[2], 1, out_h, out_w))
 
 
+PCL_AUG_MAX_POINTS = 4096     # IGI_PCL_AUG_MAX_POINTS: per object
+PCL_AUG_MAX_OBJECTS = 4
+PCL_AUG_PARAMS = _lib.PclAugmentParams.FIELDS    # the order of ``params``: struct igi_pcl_augment_params, field for field
+_PCL_AUG_PROBS = ("noise_prob", "hit_prob", "outlier_ratio", "contour_prob", "dropout_ratio", "no_dropout_prob")
+_PCL_AUG_NONNEG = ("sigma", "noise_clip", "rot_deg")
+
+
+def _pcl_cloud_shape(clouds, total):
+    """The two layouts of the environment's cloud tensor: (N, 1, P_total * 3) and (N, P_total, 3)."""
+    return tuple(clouds.shape[1:]) in ((1, total * 3), (total, 3))
+
+
+@_op("pcl_augment(Tensor clouds, int[] points, Tensor episode, float[] params, int seed_episode, int seed_step) -> Tensor")
+def pcl_augment(clouds: Tensor, points: List[int], episode: Tensor, params: List[float], seed_episode: int,
+                seed_step: int) -> Tensor:
+    """The environment's segmented point cloud, augmented, in ONE launch (igi_pcl_augment; the reference's environment runs
+    ``PointCloudAugmentations.augment`` object by object on a boolean-masked subset, factory_utils.py:83-166): ``clouds``
+    fp32 (N, 1, P_total * 3) or (N, P_total, 3), P_total = sum(points), 1..4 consecutive objects of 1..4096 points;
+    ``episode`` int32 (N,), the caller's episode counters (the per-episode offset / angle / axis are a function of
+    (seed_episode, env, episode[env])); ``params`` the eleven values of ``PCL_AUG_PARAMS`` in that order -> a new fp32
+    tensor of clouds' shape; neither input is written.  The inputs are data: no autograd."""
+    _check_layout(clouds, "clouds", torch.float32, 3)
+    _check_layout(episode, "episode", torch.int32, 1)
+    nobj = len(points)
+    if nobj < 1 or nobj > PCL_AUG_MAX_OBJECTS:
+        raise RuntimeError(f"points: expected 1..{PCL_AUG_MAX_OBJECTS} objects, got {nobj}")
+    for k, n in enumerate(points):
+        if n < 1 or n > PCL_AUG_MAX_POINTS:
+            raise RuntimeError(f"points[{k}]: expected 1..{PCL_AUG_MAX_POINTS} points, got {n}")
+    total = sum(points)
+    if not _pcl_cloud_shape(clouds, total):
+        raise RuntimeError(f"clouds: expected (N, 1, {total * 3}) or (N, {total}, 3) for points {list(points)}, got "
+                           f"{tuple(clouds.shape)}")
+    N = clouds.shape[0]
+    if tuple(episode.shape) != (N,):
+        raise RuntimeError(f"episode: expected shape {(N,)}, got {tuple(episode.shape)}")
+    if len(params) != len(PCL_AUG_PARAMS):
+        raise RuntimeError(f"params: expected {len(PCL_AUG_PARAMS)} values {PCL_AUG_PARAMS}, got {len(params)}")
+    q = dict(zip(PCL_AUG_PARAMS, params))
+    for nm in _PCL_AUG_PROBS:
+        if not 0 <= q[nm] <= 1:
+            raise RuntimeError(f"{nm}: expected a value in [0, 1], got {q[nm]}")
+    for nm in _PCL_AUG_NONNEG:
+        if not q[nm] >= 0:
+            raise RuntimeError(f"{nm}: expected >= 0, got {q[nm]}")
+    if N * total * 3 >= 2 ** 32:
+        raise RuntimeError(f"clouds: expected fewer than 2^32 coordinates (32-bit element numbers), got {N * total * 3}")
+    _check(clouds, "clouds", dtype=torch.float32)
+    _check(episode, "episode", dtype=torch.int32, device=clouds.device)
+    out = torch.empty_like(clouds)
+    if N == 0:
+        return out
+    with torch.cuda.device(clouds.device):
+        _rc(_lib.lib().igi_pcl_augment(_p(clouds), N, nobj, (C.c_int32 * nobj)(*points), _p(episode),
+                                       C.byref(_lib.PclAugmentParams(*params)),
+                                       C.c_uint64(seed_episode & 0xFFFFFFFFFFFFFFFF),
+                                       C.c_uint64(seed_step & 0xFFFFFFFFFFFFFFFF), _p(out), _stream(clouds)),
+            "igi_pcl_augment")
+    return out
+
+
+@_fake("pcl_augment")
+def _(clouds, points, episode, params, seed_episode, seed_step):
+    return torch.empty_like(clouds)
+
+
 @_op("cat_cols(Tensor[] parts, Tensor? add) -> Tensor")
 def cat_cols(parts: List[Tensor], add: Optional[Tensor]) -> Tensor:
     """``torch.cat(parts, dim=1) (+ add)`` for 2-D fp32 parts with the same number of rows, ``add`` one row of the
@@ -1802,4 +1868,4 @@ OP_NAMES = ["gae_advnorm", "ppo_minibatch_fwd_bwd", "ppo_clip_adam", "ppo_update
             "bc_loss_fwd_bwd", "bc_loss", "bc_loss_value_grad", "gemm_f32", "linear", "linear_bwd", "mlp_fwd", "mlp_bwd", "tactile_cnn_fwd", "tactile_cnn_bwd", "spatial_softargmax_fwd", "spatial_softargmax_bwd",
             "pointnet_max_fwd", "pointnet_max_bwd", "pointnet_max_fwd_multi", "pointnet_max_bwd_multi", "depth_backbone_fwd", "depth_backbone_bwd", "token_encoder_fwd",
             "token_encoder_bwd", "gather_rows", "cat_cols", "split_cols", "image_pair_augment",
-            "tactile_augment"]
+            "tactile_augment", "pcl_augment"]

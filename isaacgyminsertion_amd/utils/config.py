@@ -69,7 +69,12 @@ def default_config(num_envs=4096, horizon_length=32, rl_device="cuda:0", multi_g
                     "record_video_every": 10 ** 9, "num_points": 400, "num_points_socket": 400,
                     "num_points_goal": 400, "include_plug_pcl": True, "merge_socket_pcl": True,
                     "merge_goal_pcl": False, "include_all_pcl": False,
-                    "tactile_history_len": 1, "img_history_len": 1},
+                    "tactile_history_len": 1, "img_history_len": 1,
+                    # ours: "off" = the student distils on the clouds as the environment hands them over; "fused" = one
+                    # native launch per rollout step (envs/pcl_augment.py: PclAugment) on PclProbNoise of the envs
+                    "pcl_augment": "off", "PclProbNoise": 0.7},
+            # pcl_rot is the reference's key (degrees); the stages its ``augment`` has commented out are switches of ours
+            "randomize": {"pcl_rot": 30.0, "pcl_rotate": False, "pcl_outlier_ratio": 0.0, "pcl_dropout_ratio": 0.0},
             "rl": {"max_episode_length": 512},
             "data_logger": {"collect_data": False},
             "tactile": {"encoder": {"width": 64, "height": 64, "num_channels": 1}, "crop_roi": True},
