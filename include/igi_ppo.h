@@ -628,12 +628,16 @@ int igi_depth_backward(const igi_depth_cfg* cfg, const float* x, const float* dy
                        void* workspace, size_t workspace_bytes, igi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Token decoder of the student: `layers` x nn.TransformerEncoderLayer(d_model 32, nhead 2, dim_feedforward ff,
+ * Token decoder of the student: `layers` x nn.TransformerEncoderLayer(d_model, nhead, dim_feedforward ff,
  * activation "gelu", batch_first, norm_first) over `seq` <= 32 tokens per sample
- * (seq <= 8: attention in registers, 16 lanes per (sample, head); 9 .. 32: one 32 x 32 MFMA tile per (sample, head);
- * beyond 32: IGI_E_UNSUPPORTED)
  * (algo/models/transformer/tact.py:137-158: MultiLayerDecoder.sa_decoder), forward and backward.
- * x, y, dy, dx: (batch, seq, 32) fp32.  params / grads: layers x igi_token_param_count()/layers floats, each layer
+ * Supported: d_model in {32, 64, 128}; nhead with d_model / nhead in {16, 32, 64}; seq <= 32; ff a multiple of 4;
+ * layers <= 8; batch * seq <= 2^26.  Anything else: IGI_E_UNSUPPORTED (there is no fallback).
+ *   (32, 2), the reference's stock config: seq <= 8 attention in registers, 16 lanes per (sample, head); 9 .. 32 one
+ *     32 x 32 MFMA tile per (sample, head); one-launch forward / backward kernels where ff = 128 and the shape allows.
+ *   every other (d_model, nhead): one launch per operation, LayerNorm with a wave per row, attention on the MFMA tile
+ *     at every seq (heads of 64 in two column passes).
+ * x, y, dy, dx: (batch, seq, d_model) fp32.  params / grads: layers x igi_token_param_count()/layers floats, each layer
  * in nn.TransformerEncoderLayer's parameter order (in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias,
  * linear1.weight, linear1.bias, linear2.weight, linear2.bias, norm1.weight, norm1.bias, norm2.weight, norm2.bias).
  * training != 0 applies the layer's four dropouts (attention probabilities, both residual branches, after the

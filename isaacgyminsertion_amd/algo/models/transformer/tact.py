@@ -122,6 +122,20 @@ class MultiModalModel(nn.Module):
                 "point clouds with an observation history (context_size > 1) are not built: the reference sizes the decoder "
                 "for context_size point-cloud tokens and its pcl branch supplies one (tact.py:375, 542-583), so it cannot "
                 "run this configuration itself")
+        # the tokens are concatenated along the sequence axis and the decoder is built tactile_encoding_size wide
+        # (tact.py:375): an included modality of another width fails in that concatenation, so say so here
+        sizes = {"tactile_encoding_size": tactile_encoding_size}
+        if include_img:
+            sizes["img_encoding_size"] = img_encoding_size
+        if include_seg:
+            sizes["seg_encoding_size"] = seg_encoding_size
+        if include_lin or include_pcl:            # (the point-cloud token is lin_encoding_size wide)
+            sizes["lin_encoding_size"] = lin_encoding_size
+        odd = {k: v for k, v in sizes.items() if v != tactile_encoding_size}
+        if odd:
+            raise ValueError(
+                f"the decoder is tactile_encoding_size = {tactile_encoding_size} wide and every included modality's token "
+                f"must be as wide: " + ", ".join(f"{k} = {v}" for k, v in odd.items()))
         self.context_size = context_size
         self.num_output_params = num_outputs
         self.tactile_encoding_size = tactile_encoding_size

@@ -1,6 +1,9 @@
-// Token decoder of the student: a stack of nn.TransformerEncoderLayer(d_model=32, nhead=2,
-// dim_feedforward=128, activation="gelu", batch_first=True, norm_first=True) over S <= 32 tokens
-// (algo/models/transformer/tact.py:137-158), forward and backward.
+// Token decoder of the student: a stack of nn.TransformerEncoderLayer(d_model, nhead, dim_feedforward,
+// activation="gelu", batch_first=True, norm_first=True) over S <= 32 tokens
+// (algo/models/transformer/tact.py:137-158), forward and backward.  d_model is 32, 64 or 128 with heads of 16, 32 or 64
+// features; (32, 2, 128) is the reference's stock config and the only one the register attention and the one-launch
+// kernels below are built for (TokenPlan::narrow).  Every other pair runs launch per operation with the LayerNorm
+// kernels' <64> / <128> instantiations and the tile attention kernels at every S.
 //
 //   per layer:  x1 = x  + drop(out_proj(attn(in_proj(LN1(x)))))          (sa block,  norm_first)
 //               x2 = x1 + drop(linear2(drop(gelu(linear1(LN2(x1))))))    (ff block)
@@ -8,15 +11,17 @@
 // Rows are tokens, sample-major (row = b * S + s); every Linear is a row-wise product and runs on the
 // MFMA GEMMs (linear.h: igi_linear_forward / backward with deterministic split sums for the weight
 // gradients); everything else is a handful of small fused kernels around the routines of token_math.h:
-//   k_resid_ln_fwd : residual add (+ dropout of the branch) fused with the NEXT LayerNorm (ln_fwd); a 32-lane
-//                    half wave owns a row (lane = feature), statistics by DPP row sums
+//   k_resid_ln_fwd<D> : residual add (+ dropout of the branch) fused with the NEXT LayerNorm (ln_fwd); a 32-lane
+//                    half wave owns a row of 32 features (lane = feature), a wave a row of 64 / 128 (D / 64 features per
+//                    lane), statistics by DPP row sums and cross-row exchanges
 //   k_attn_fwd/bwd : softmax(q k^T / sqrt(16)) v for an S x S block per (sample, head) (attn_ctx_row / attn_bwd);
 //                    16 lanes own a (sample, head) pair, lane = head dimension; backward recomputes the
-//                    probabilities (nothing S x S is ever stored); S <= 8
-//   k_attn_tile_fwd/bwd : the same for 9 <= S <= 32: a wave owns a (sample, head) pair, the S x S block is one padded
-//                    32 x 32 tile of v_mfma_f32_32x32x2_f32, S a runtime argument
+//                    probabilities (nothing S x S is ever stored); S <= 8, (32, 2) only
+//   k_attn_tile_fwd/bwd<DH, DM> : the same with heads of DH features in a DM-wide model: a wave owns a (sample, head) pair,
+//                    the S x S block is one padded 32 x 32 tile of v_mfma_f32_32x32x2_f32, S a runtime argument;
+//                    <16, 32> at 9 <= S <= 32, the others at every S
 //   k_gelu_fwd/bwd : exact (erf) GELU + dropout (gelu / gelu_grad)
-//   k_ln_bwd       : LayerNorm backward + residual gradient add (ln_bwd) + (optionally) the dropout mask of the
+//   k_ln_bwd<D>    : LayerNorm backward + residual gradient add (ln_bwd) + (optionally) the dropout mask of the
 //                    branch below it; per-block partial sums for the LayerNorm weight / bias gradients,
 //                    reduced in fixed order
 // The one-launch kernels further down (k_token_fwd<S>, k_token_fwd_long, k_token_bwd<S>) carry whole samples through
@@ -48,6 +53,8 @@ struct TokLayout {
 };
 struct TokenPlan {
   int B, S, d, H, ff, L;
+  int dh;                // head width d / H
+  bool narrow;           // (d, H) = (32, 2): the configuration of the register attention and the one-launch kernels
   long long R;           // token rows
   float p;               // dropout probability (0 when not training)
   TokLayout lay;
@@ -61,12 +68,21 @@ constexpr int TB_ROWS = 64;                     // token rows per workgroup of t
 
 static inline long long ru4ll(long long x) { return (x + 3) & ~3LL; }
 
+// d_model 32, 64 or 128 with heads of 16, 32 or 64
+static inline bool token_width_supported(int d, int nhead) {
+  if ((d != 32 && d != 64 && d != 128) || nhead < 1 || d % nhead) return false;
+  const int dh = d / nhead;
+  return dh == 16 || dh == 32 || dh == 64;
+}
+
 static int make_token_plan(const igi_token_cfg* c, TokenPlan* p) {
   if (!c || c->batch < 1 || c->seq < 1 || c->layers < 1 || c->ff < 4 || c->dropout < 0.f || c->dropout >= 1.f)
     return IGI_E_BADARG;
-  if (c->d_model != TOK_D || c->nhead * TOK_DH != TOK_D || c->seq > TOK_MAX_SEQ || (c->ff & 3) || c->layers > 8)
+  if (!token_width_supported(c->d_model, c->nhead) || c->seq > TOK_MAX_SEQ || (c->ff & 3) || c->layers > 8)
     return IGI_E_UNSUPPORTED;
   p->B = c->batch; p->S = c->seq; p->d = c->d_model; p->H = c->nhead; p->ff = c->ff; p->L = c->layers;
+  p->dh = p->d / p->H;
+  p->narrow = p->d == TOK_D && p->dh == TOK_DH;
   p->R = (long long)c->batch * c->seq;
   if (p->R > (1LL << 26)) return IGI_E_UNSUPPORTED;
   p->p = c->training ? c->dropout : 0.f;
@@ -105,7 +121,7 @@ static int make_token_plan(const igi_token_cfg* c, TokenPlan* p) {
   p->bwd_grid = (int)((p->B + p->bwd_samples - 1) / p->bwd_samples);
   // one 100 KB gradient record per workgroup: beyond 1024 of them (>= 21 K samples of three tokens) the backward runs
   // launch by launch on split-row slabs instead, and no record space is reserved
-  if (p->bwd_grid > 1024 || p->S > TOK_MAX_S) p->bwd_grid = 0;   // (S > 8: no one-launch backward either)
+  if (p->bwd_grid > 1024 || p->S > TOK_MAX_S || !p->narrow) p->bwd_grid = 0;   // (S > 8, or not (32, 2): no one-launch backward either)
   p->s_part = stake((long long)p->bwd_grid * ly.per_layer * p->L);   // one gradient record per workgroup
   p->s_lin = stake(0);
   size_t lb = linear_workspace_bytes(R, d, 3 * d);
@@ -120,22 +136,33 @@ static int make_token_plan(const igi_token_cfg* c, TokenPlan* p) {
 }
 
 // x_out = x_prev + drop(delta)  (delta may be null: x_out = x_prev), then xn = LN(x_out) (gamma may be
-// null: residual only).  Half wave per row.
+// null: residual only).  A row belongs to LnShape<D>::LANES lanes (a half wave at D = 32, a wave at 64 / 128), each with
+// the features f + LANES * u.
+template <int D>
 __global__ __launch_bounds__(256) void k_resid_ln_fwd(const float* __restrict__ xprev, const float* __restrict__ delta,
                                                       Drop dr, float* __restrict__ xout,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       float* __restrict__ xn, float* __restrict__ stats, long long R) {
-  const int f = threadIdx.x & 31;
-  const long long hw = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-  const long long nhw = ((long long)gridDim.x * blockDim.x) >> 5;
+  constexpr int LANES = LnShape<D>::LANES, NV = LnShape<D>::NV;
+  const int f = threadIdx.x & (LANES - 1);
+  const long long hw = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / LANES;
+  const long long nhw = ((long long)gridDim.x * blockDim.x) / LANES;
   for (long long r = hw; r < R; r += nhw) {
-    const long long i = r * TOK_D + f;
-    float v = xprev[i];
-    if (delta) v += drop_apply(dr, (unsigned int)i, delta[i]);
-    if (xout) xout[i] = v;
+    const long long i = r * D + f;
+    float v[NV];
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      v[u] = xprev[i + LANES * u];
+      if (delta) v[u] += drop_apply(dr, (unsigned int)(i + LANES * u), delta[i + LANES * u]);
+      if (xout) xout[i + LANES * u] = v[u];
+    }
     if (gamma) {
-      float mean, rstd;
-      xn[i] = ln_fwd(v, gamma[f], beta[f], mean, rstd);
+      float gm[NV], bt[NV], o[NV], mean, rstd;
+#pragma unroll
+      for (int u = 0; u < NV; ++u) { gm[u] = gamma[f + LANES * u]; bt[u] = beta[f + LANES * u]; }
+      ln_fwd<D>(v, gm, bt, o, mean, rstd);
+#pragma unroll
+      for (int u = 0; u < NV; ++u) xn[i + LANES * u] = o[u];
       if (f == 0) { stats[2 * r] = mean; stats[2 * r + 1] = rstd; }
     }
   }
@@ -143,32 +170,55 @@ __global__ __launch_bounds__(256) void k_resid_ln_fwd(const float* __restrict__ 
 
 // LayerNorm backward + residual:  dx = dres + rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dxn * gamma.
 // Optionally also writes dmask = drop_mask(dx) for the branch feeding the residual BELOW this norm.
-// Per-block partial sums of (dxn * xhat, dxn) per feature go to part[block][2][32].
+// Per-block partial sums of (dxn * xhat, dxn) per feature go to part[block][2][D], the block's row owners added in order.
+template <int D>
 __global__ __launch_bounds__(256) void k_ln_bwd(const float* __restrict__ dxn, const float* __restrict__ x,
                                                 const float* __restrict__ stats, const float* __restrict__ gamma,
                                                 const float* __restrict__ dres, float* __restrict__ dx, Drop dr,
                                                 float* __restrict__ dmask, float* __restrict__ part, long long R) {
-  __shared__ float red[2][8][TOK_D];
-  const int f = threadIdx.x & 31, hwl = threadIdx.x >> 5;
-  const long long hw = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-  const long long nhw = ((long long)gridDim.x * blockDim.x) >> 5;
-  const float gm = gamma[f];
-  float sg = 0.f, sb = 0.f;
+  constexpr int LANES = LnShape<D>::LANES, NV = LnShape<D>::NV, OWNERS = 256 / LANES;
+  __shared__ float red[2][OWNERS][D];
+  const int f = threadIdx.x & (LANES - 1), hwl = threadIdx.x / LANES;
+  const long long hw = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / LANES;
+  const long long nhw = ((long long)gridDim.x * blockDim.x) / LANES;
+  float gm[NV], sg[NV], sb[NV];
+#pragma unroll
+  for (int u = 0; u < NV; ++u) { gm[u] = gamma[f + LANES * u]; sg[u] = 0.f; sb[u] = 0.f; }
   for (long long r = hw; r < R; r += nhw) {
-    const long long i = r * TOK_D + f;
-    const float v = ln_bwd(dxn[i], x[i], stats[2 * r], stats[2 * r + 1], gm, dres[i], sg, sb);
-    dx[i] = v;
-    if (dmask) dmask[i] = drop_apply(dr, (unsigned int)i, v);
+    const long long i = r * D + f;
+    float dn[NV], xx[NV], ds[NV], v[NV];
+#pragma unroll
+    for (int u = 0; u < NV; ++u) { dn[u] = dxn[i + LANES * u]; xx[u] = x[i + LANES * u]; ds[u] = dres[i + LANES * u]; }
+    ln_bwd<D>(dn, xx, stats[2 * r], stats[2 * r + 1], gm, ds, v, sg, sb);
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      dx[i + LANES * u] = v[u];
+      if (dmask) dmask[i + LANES * u] = drop_apply(dr, (unsigned int)(i + LANES * u), v[u]);
+    }
   }
-  red[0][hwl][f] = sg;
-  red[1][hwl][f] = sb;
+#pragma unroll
+  for (int u = 0; u < NV; ++u) {
+    red[0][hwl][f + LANES * u] = sg[u];
+    red[1][hwl][f + LANES * u] = sb[u];
+  }
   __syncthreads();
-  if (threadIdx.x < 2 * TOK_D) {
-    const int w = threadIdx.x / TOK_D, ff = threadIdx.x % TOK_D;
+  if (threadIdx.x < 2 * D) {
+    const int w = threadIdx.x / D, ff = threadIdx.x % D;
     float a = 0.f;
-    for (int q = 0; q < 8; ++q) a += red[w][q][ff];
-    part[((long long)blockIdx.x * 2 + w) * TOK_D + ff] = a;
+    for (int q = 0; q < OWNERS; ++q) a += red[w][q][ff];
+    part[((long long)blockIdx.x * 2 + w) * D + ff] = a;
   }
+}
+
+// the LayerNorm kernels' instantiation of a supported width
+template <typename F>
+static int width_dispatch(int d, F&& f) {
+  switch (d) {
+    case 32: f(std::integral_constant<int, 32>()); return 0;
+    case 64: f(std::integral_constant<int, 64>()); return 0;
+    case 128: f(std::integral_constant<int, 128>()); return 0;
+  }
+  return IGI_E_UNSUPPORTED;
 }
 
 // masked copy: dst = drop_mask(src)
@@ -244,28 +294,50 @@ __device__ __forceinline__ int tile_row(int r, int half) { return (r & 3) + 8 * 
 __device__ __forceinline__ int tok_opaque(int x) { asm volatile("" : "+s"(x)); return x; }
 __device__ __forceinline__ int tok_opaque_lane(int x) { asm volatile("" : "+v"(x)); return x; }
 
-// probabilities of the pair: pr[r] = softmax_j(q_i . k_j / 4) at lane (i = lane & 31, half), j = tile_row(r, half)
-// (0 for j >= S).  q: the pair's first query row (this head's 16 columns), k 32 floats further on, pitch ld.
-__device__ __forceinline__ void attn_tile_probs(const float* q, int ld, int S, int lane, f32x16& pr) {
-  const int l31 = lane & 31, half = lane >> 5;
-  const float* row = q + min(l31, S - 1) * ld + 4 * half;
-  f32x4 kv[2], qv[2];
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    kv[c] = *reinterpret_cast<const f32x4*>(row + TOK_D + 8 * c);
-    qv[c] = *reinterpret_cast<const f32x4*>(row + 8 * c);
-  }
-  f32x16 acc;
+// The tile routines are templated on the head width DH (16, 32 or 64); dm is the model width (the k / v / context column
+// offsets and the context pitch), a constant wherever the caller's is.
+template <int DH> struct TileShape {
+  static_assert(DH == 16 || DH == 32 || DH == 64, "head widths of 16, 32 or 64");
+  static constexpr int NC = DH / 8;                 // 8-wide chunks of the contraction over the head dimension
+  static constexpr int CW = DH < 32 ? DH : 32;      // output columns of one pass of the 32 x 32 tile
+  static constexpr int NP = DH / CW;                // column passes
+  static constexpr float SCALE = DH == 16 ? 0.25f : DH == 32 ? 0.17677669529663687f : 0.125f;   // 1 / sqrt(DH)
+};
+
+// acc[r] (lane (n = lane & 31, half), row tile_row(r, half)) = sum_k a[row][k] b[n][k] over the DH columns at a / b (this
+// lane's row + 4 * half): two chunks' operands at a time, so DH = 64 holds 16 operand registers like DH = 16, not 64
+template <int DH>
+__device__ __forceinline__ void attn_tile_headdot(const float* a, const float* b, f32x16& acc) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
-  for (int c = 0; c < 2; ++c)
+  for (int c0 = 0; c0 < TileShape<DH>::NC; c0 += 2) {
+    f32x4 av[2], bv[2];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[c][j], qv[c][j], acc, 0, 0, 0);
+    for (int c = 0; c < 2; ++c) {
+      av[c] = *reinterpret_cast<const f32x4*>(a + 8 * (c0 + c));
+      bv[c] = *reinterpret_cast<const f32x4*>(b + 8 * (c0 + c));
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c][j], bv[c][j], acc, 0, 0, 0);
+    if (TileShape<DH>::NC > 2) __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// probabilities of the pair: pr[r] = softmax_j(q_i . k_j / sqrt(DH)) at lane (i = lane & 31, half), j = tile_row(r, half)
+// (0 for j >= S).  q: the pair's first query row (this head's DH columns), k dm floats further on, pitch ld.
+template <int DH>
+__device__ __forceinline__ void attn_tile_probs(const float* q, int ld, int dm, int S, int lane, f32x16& pr) {
+  const int l31 = lane & 31, half = lane >> 5;
+  const float* row = q + min(l31, S - 1) * ld + 4 * half;
+  f32x16 acc;
+  attn_tile_headdot<DH>(row + dm, row, acc);
   float mx = -INFINITY;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    acc[r] = tile_row(r, half) < S ? acc[r] * 0.25f : -INFINITY;  // 1 / sqrt(16); padded keys
+    acc[r] = tile_row(r, half) < S ? acc[r] * TileShape<DH>::SCALE : -INFINITY;  // 1 / sqrt(DH); padded keys
     mx = fmaxf(mx, acc[r]);
   }
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));   // finite: key 0 is valid
@@ -284,14 +356,15 @@ __device__ __forceinline__ void attn_tile_probs(const float* q, int ld, int S, i
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// C[32][16] = sum_j a[r] (row i = lane & 31, column j = tile_row(r, half)) . X[j][0..15]; a is zero in the columns j >= S.
-// Result at lane (d = lane & 15, half): o[r] = C[tile_row(r, half)][d] (lanes 16 .. 31 of a half wave repeat 0 .. 15).
+// C[32][CW] = sum_j a[r] (row i = lane & 31, column j = tile_row(r, half)) . X[j][0..CW-1]; a is zero in the columns j >= S.
+// Result at lane (d = lane & (CW - 1), half): o[r] = C[tile_row(r, half)][d] (CW = 16: lanes 16 .. 31 of a half wave repeat
+// 0 .. 15).  One call is one column pass: a head of 64 takes two, X 32 columns further on.
 // DROP: a[r] first passes the dropout of element e0 + j (the forward's P . V).
-template <bool DROP>
+template <bool DROP, int CW>
 __device__ __forceinline__ void attn_tile_rowmix(const f32x16& a, const float* X, int ld, int S, int lane, f32x16& o,
                                                  const Drop& dr, unsigned int e0) {
   const int half = lane >> 5;
-  X += lane & 15;
+  X += lane & (CW - 1);
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = 0.f;
 #pragma unroll
@@ -310,23 +383,32 @@ __device__ __forceinline__ void attn_tile_rowmix(const f32x16& a, const float* X
 }
 
 // forward of one pair by one wave.  g: the global (sample, head) index (dropout element numbers); cl (may be null):
-// context rows in LDS, pitch ldc; cg: context rows in global memory, pitch TOK_D (both at this head's columns).
-__device__ __forceinline__ void attn_tile_fwd(const float* q, int ld, int S, long long g, const Drop& dr, float* cl, int ldc,
-                                              float* cg) {
+// context rows in LDS, pitch ldc; cg: context rows in global memory, pitch dm (both at this head's columns).
+template <int DH>
+__device__ __forceinline__ void attn_tile_fwd(const float* q, int ld, int dm, int S, long long g, const Drop& dr, float* cl,
+                                              int ldc, float* cg) {
+  constexpr int CW = TileShape<DH>::CW, NP = TileShape<DH>::NP;
   S = tok_opaque(S);
   const int lane = tok_opaque_lane(threadIdx.x & 63), l31 = lane & 31, half = lane >> 5;
   f32x16 pr, o;
-  attn_tile_probs(q, ld, S, lane, pr);
+  attn_tile_probs<DH>(q, ld, dm, S, lane, pr);
   const unsigned int e0 = (unsigned int)((g * S + l31) * S);
-  attn_tile_rowmix<true>(pr, q + 2 * TOK_D, ld, S, lane, o, dr, e0);
-  if (l31 < TOK_DH) {
-    const int Sw = tok_opaque(S);
+  if constexpr (NP > 1) {                     // the dropout factors once per pair, not once per column pass
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int i = tile_row(r, half);
-      if (i < Sw) {
-        if (cl) cl[i * ldc + l31] = o[r];
-        cg[i * TOK_D + l31] = o[r];
+    for (int r = 0; r < 16; ++r) pr[r] = drop_apply(dr, e0 + (unsigned int)tile_row(r, half), pr[r]);
+  }
+#pragma unroll
+  for (int cp = 0; cp < NP; ++cp) {
+    attn_tile_rowmix<NP == 1, CW>(pr, q + 2 * dm + 32 * cp, ld, S, lane, o, dr, e0);
+    if (l31 < CW) {
+      const int Sw = tok_opaque(S);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = tile_row(r, half);
+        if (i < Sw) {
+          if (cl) cl[i * ldc + 32 * cp + l31] = o[r];
+          cg[i * dm + 32 * cp + l31] = o[r];
+        }
       }
     }
   }
@@ -335,11 +417,12 @@ __device__ __forceinline__ void attn_tile_fwd(const float* q, int ld, int S, lon
 constexpr int AT_LDT = 33;                      // pitch of the 32 x 32 transposition tiles of the backward
 constexpr int AT_TILE = 32 * AT_LDT;
 
-// C[32][16] = sum_i T[j][i] X[i][0..15] for the tile T (row = key j, column = query i; zero in the columns i >= S):
-// A = the tile's row (key = lane & 31), k-step t takes query 2 t + half.  Result as attn_tile_rowmix's.
+// C[32][CW] = sum_i T[j][i] X[i][0..CW-1] for the tile T (row = key j, column = query i; zero in the columns i >= S):
+// A = the tile's row (key = lane & 31), k-step t takes query 2 t + half.  Result as attn_tile_rowmix's, one column pass.
+template <int CW>
 __device__ __forceinline__ void attn_tile_colmix(const float* T, const float* X, int ldx, int S, int lane, f32x16& o) {
   const int l31 = lane & 31, half = lane >> 5;
-  X += lane & 15;
+  X += lane & (CW - 1);
   T += l31 * AT_LDT + half;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = 0.f;
@@ -357,32 +440,24 @@ __device__ __forceinline__ void attn_tile_colmix(const float* T, const float* X,
   }
 }
 
-// backward of one pair by one wave: dV = (P m)^T dC, dP = (dC V^T) m, dS = P (dP - rowsum(dP P)) / 4, dQ = dS K,
+// backward of one pair by one wave: dV = (P m)^T dC, dP = (dC V^T) m, dS = P (dP - rowsum(dP P)) / sqrt(DH), dQ = dS K,
 // dK = dS^T Q (m: the dropout factors).  dP is formed transposed like the scores (A = V rows, B = dC rows), so it meets
 // P register for register; dQ contracts over the keys, which the registers run over; dV and dK contract over the
 // queries, which the lanes run over: P m and dS go through two 32 x 32 LDS tiles (T, this wave's own; the columns of the
-// queries >= S written as zeros) to be read back as A operands with the query as the k index.
-// q / dc / dq: first rows of the pair at this head's columns (dq: pitch ld like q).
-__device__ __forceinline__ void attn_tile_bwd(const float* q, int ld, const float* dc, float* dq, int S, long long g,
+// queries >= S written as zeros) to be read back as A operands with the query as the k index.  P, m and dS are formed
+// once per pair; the three products run TileShape<DH>::NP column passes each off the same registers and tiles.
+// q / dc / dq: first rows of the pair at this head's columns (dq: pitch ld like q; dc: pitch dm).
+template <int DH>
+__device__ __forceinline__ void attn_tile_bwd(const float* q, int ld, int dm, const float* dc, float* dq, int S, long long g,
                                               const Drop& dr, float* T) {
+  constexpr int CW = TileShape<DH>::CW, NP = TileShape<DH>::NP;
   S = tok_opaque(S);
   const int lane = tok_opaque_lane(threadIdx.x & 63), l31 = lane & 31, half = lane >> 5;
   f32x16 pr, dp, o;
-  attn_tile_probs(q, ld, S, lane, pr);
+  attn_tile_probs<DH>(q, ld, dm, S, lane, pr);
   {
     const int rowi = min(l31, S - 1);
-    f32x4 vv[2], cv[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      vv[c] = *reinterpret_cast<const f32x4*>(q + rowi * ld + 2 * TOK_D + 8 * c + 4 * half);
-      cv[c] = *reinterpret_cast<const f32x4*>(dc + rowi * TOK_D + 8 * c + 4 * half);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dp[r] = 0.f;
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv[c][j], cv[c][j], dp, 0, 0, 0);
+    attn_tile_headdot<DH>(q + rowi * ld + 2 * dm + 4 * half, dc + rowi * dm + 4 * half, dp);
   }
   const unsigned int e0 = (unsigned int)((g * S + l31) * S);
   const bool query = l31 < S;
@@ -400,29 +475,35 @@ __device__ __forceinline__ void attn_tile_bwd(const float* q, int ld, const floa
   dot += __shfl_xor(dot, 32, 64);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    dp[r] = pr[r] * (dp[r] - dot) * 0.25f;    // dS: d(loss)/d(score_ij) incl. the 1/sqrt(dh); zero at the padded keys
+    dp[r] = pr[r] * (dp[r] - dot) * TileShape<DH>::SCALE;   // dS: d(loss)/d(score_ij) incl. the 1/sqrt(dh); zero at the padded keys
     T[AT_TILE + tile_row(r, half) * AT_LDT + l31] = query ? dp[r] : 0.f;
   }
   const int Sw = tok_opaque(S);
-  attn_tile_rowmix<false>(dp, q + TOK_D, ld, S, lane, o, dr, 0u);  // dQ = dS K
-  if (l31 < TOK_DH) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int i = tile_row(r, half);
-      if (i < Sw) dq[i * ld + l31] = o[r];
+  for (int cp = 0; cp < NP; ++cp) {
+    attn_tile_rowmix<false, CW>(dp, q + dm + 32 * cp, ld, S, lane, o, dr, 0u);  // dQ = dS K
+    if (l31 < CW) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = tile_row(r, half);
+        if (i < Sw) dq[i * ld + 32 * cp + l31] = o[r];
+      }
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-  for (int w = 0; w < 2; ++w) {               // dV = (P m)^T dC (dC: pitch TOK_D), then dK = dS^T Q
-    attn_tile_colmix(T + w * AT_TILE, w == 0 ? dc : q, w == 0 ? TOK_D : ld, S, lane, o);
-    if (l31 < TOK_DH) {
+  for (int w = 0; w < 2; ++w) {               // dV = (P m)^T dC (dC: pitch dm), then dK = dS^T Q
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int j = tile_row(r, half);
-        if (j < Sw) dq[j * ld + (w == 0 ? 2 * TOK_D : TOK_D) + l31] = o[r];
+    for (int cp = 0; cp < NP; ++cp) {
+      attn_tile_colmix<CW>(T + w * AT_TILE, (w == 0 ? dc : q) + 32 * cp, w == 0 ? dm : ld, S, lane, o);
+      if (l31 < CW) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int j = tile_row(r, half);
+          if (j < Sw) dq[j * ld + (w == 0 ? 2 * dm : dm) + 32 * cp + l31] = o[r];
+        }
       }
     }
   }
@@ -430,7 +511,10 @@ __device__ __forceinline__ void attn_tile_bwd(const float* q, int ld, const floa
   __builtin_amdgcn_wave_barrier();             // the wave's next pair rewrites the tiles
 }
 
+// The tile kernels: DH the head width, DM the model width (H = DM / DH heads).  <16, 32> is the 32-wide model's kernel for
+// 9 .. 32 tokens; every other instantiation is a wide configuration's attention at any S from 1 to 32.
 constexpr int AT_THREADS = 256;                 // four waves, a (sample, head) pair each per step
+template <int DH, int DM>
 __global__ __launch_bounds__(AT_THREADS) void k_attn_tile_fwd(const float* __restrict__ qkv, float* __restrict__ ctx, Drop dr,
                                                               long long pairs, int H, int S) {
   const long long w0 = ((long long)blockIdx.x * AT_THREADS + threadIdx.x) >> 6;
@@ -438,10 +522,11 @@ __global__ __launch_bounds__(AT_THREADS) void k_attn_tile_fwd(const float* __res
   for (long long g = w0; g < pairs; g += nw) {
     const long long b = g / H;
     const int h = (int)(g - b * H);
-    attn_tile_fwd(qkv + b * S * (3 * TOK_D) + h * TOK_DH, 3 * TOK_D, S, g, dr, nullptr, 0, ctx + b * S * TOK_D + h * TOK_DH);
+    attn_tile_fwd<DH>(qkv + b * S * (3 * DM) + h * DH, 3 * DM, DM, S, g, dr, nullptr, 0, ctx + b * S * DM + h * DH);
   }
 }
 
+template <int DH, int DM>
 __global__ __launch_bounds__(AT_THREADS) void k_attn_tile_bwd(const float* __restrict__ qkv, const float* __restrict__ dctx,
                                                               float* __restrict__ dqkv, Drop dr, long long pairs, int H, int S) {
   __shared__ float tiles[AT_THREADS / 64][2 * AT_TILE];
@@ -450,9 +535,21 @@ __global__ __launch_bounds__(AT_THREADS) void k_attn_tile_bwd(const float* __res
   for (long long g = w0; g < pairs; g += nw) {
     const long long b = g / H;
     const int h = (int)(g - b * H);
-    attn_tile_bwd(qkv + b * S * (3 * TOK_D) + h * TOK_DH, 3 * TOK_D, dctx + b * S * TOK_D + h * TOK_DH,
-                  dqkv + b * S * (3 * TOK_D) + h * TOK_DH, S, g, dr, tiles[threadIdx.x >> 6]);
+    attn_tile_bwd<DH>(qkv + b * S * (3 * DM) + h * DH, 3 * DM, DM, dctx + b * S * DM + h * DH, dqkv + b * S * (3 * DM) + h * DH, S,
+                      g, dr, tiles[threadIdx.x >> 6]);
   }
+}
+
+// the tile kernels' instantiation of a supported (head width, model width) pair
+template <typename F>
+static int tile_dispatch(int dh, int dm, F&& f) {
+#define IGI_TILE_CASE(DH_, DM_) \
+  if (dh == DH_ && dm == DM_) { f(std::integral_constant<int, DH_>(), std::integral_constant<int, DM_>()); return 0; }
+  IGI_TILE_CASE(16, 32) IGI_TILE_CASE(32, 32)
+  IGI_TILE_CASE(16, 64) IGI_TILE_CASE(32, 64) IGI_TILE_CASE(64, 64)
+  IGI_TILE_CASE(16, 128) IGI_TILE_CASE(32, 128) IGI_TILE_CASE(64, 128)
+#undef IGI_TILE_CASE
+  return IGI_E_UNSUPPORTED;
 }
 
 // h = drop(gelu(z)), exact erf form (nn.GELU default / activation="gelu")
@@ -620,8 +717,8 @@ __device__ __forceinline__ void token_fwd_body(const TokFwdArgs& a) {
       const int nsamp = nrows / a.S;
       for (int g = wave; g < nsamp * a.H; g += TF_NW) {
         const int bl = g / a.H, hh = g - bl * a.H;
-        attn_tile_fwd(bz + bl * a.S * TF_LDZ + hh * TOK_DH, TF_LDZ, a.S, (r0 / a.S + bl) * a.H + hh, da,
-                      bn + bl * a.S * TF_LDX + hh * TOK_DH, TF_LDX, A + ly.a_ctx + (r0 + bl * a.S) * TOK_D + hh * TOK_DH);
+        attn_tile_fwd<TOK_DH>(bz + bl * a.S * TF_LDZ + hh * TOK_DH, TF_LDZ, TOK_D, a.S, (r0 / a.S + bl) * a.H + hh, da,
+                              bn + bl * a.S * TF_LDX + hh * TOK_DH, TF_LDX, A + ly.a_ctx + (r0 + bl * a.S) * TOK_D + hh * TOK_DH);
       }
     } else {
       // ---- attention: 16 lanes per (sample, head), attn_ctx_row on the LDS rows; context -> bn
@@ -710,7 +807,8 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
   float* W = tok_ws(workspace);
   const TokLayout& ly = p.lay;
   // (the alignment terms are linear_forward's conditions for the LDS-DMA kernel, whose k order the fused kernel reproduces)
-  if (token_fused_enabled() && p.ff == TF_FF && p.d == TOK_D && p.R >= 4 && aligned16(params) && !bf16_mode() &&
+  // (the one-launch kernels are (32, 2) only: a layer's weights at 64 wide are 196 KB, above LDS)
+  if (token_fused_enabled() && p.ff == TF_FF && p.narrow && p.R >= 4 && aligned16(params) && !bf16_mode() &&
       ((ly.per_layer | ly.o_inw | ly.o_ow | ly.o_w1 | ly.o_w2 | ly.a_layer | ly.a_xn1 | ly.a_ctx | ly.a_xn2 | ly.a_h) & 3) == 0) {
     TokFwdArgs a;
     a.x = x; a.params = params; a.y = y; a.W = W;
@@ -723,8 +821,8 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
     a.rows_per_wg = samples * p.S;
     const int grid = (int)((p.B + samples - 1) / samples);
     // algorithmic work of the stack: the four Linears of a row, the two S x S products of a (sample, head) pair
-    const double tok_flops = (double)p.L * (2.0 * p.R * (4.0 * TOK_D * TOK_D + 2.0 * TOK_D * TF_FF) + 4.0 * p.B * p.H * p.S * p.S * TOK_DH);
-    const double tok_bytes = 4.0 * ((double)p.L * ly.a_layer + 2.0 * p.R * TOK_D + (double)p.L * ly.per_layer);
+    const double tok_flops = (double)p.L * (2.0 * p.R * (4.0 * p.d * p.d + 2.0 * p.d * p.ff) + 4.0 * p.B * p.H * p.S * p.S * p.dh);
+    const double tok_bytes = 4.0 * ((double)p.L * ly.a_layer + 2.0 * p.R * p.d + (double)p.L * ly.per_layer);
     if (p.S > TOK_MAX_S) {
       ProfScope ps(PC_TOKEN_FWD_LONG, s, tok_flops, tok_bytes);
       tok_launch_lds<k_token_fwd_long>(grid, TF_THREADS, sizeof(float) * TF_LDS_FLOATS, s, a);
@@ -739,7 +837,15 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
   }
   const long long R = p.R;
   const int d = p.d, ff = p.ff;
-  const int rb = tok_blocks(R, 8);  // 8 half-wave rows per 256-thread block
+  const int rb = tok_blocks(R, p.d == TOK_D ? 8 : 4);  // rows per 256-thread block: 8 half waves, or 4 waves beyond 32 features
+  const bool tile = p.S > TOK_MAX_S || !p.narrow;     // the register attention kernels: 16-wide heads of a 32-wide model
+  auto resid_ln = [&](const float* xprev, const float* delta, const Drop& dr, float* xout, const float* gamma, const float* beta,
+                      float* xn, float* stats) {
+    return width_dispatch(d, [&](auto dc) {
+      hipLaunchKernelGGL(k_resid_ln_fwd<decltype(dc)::value>, dim3(rb), dim3(256), 0, s, xprev, delta, dr, xout, gamma, beta, xn,
+                         stats, R);
+    });
+  };
   // layer 0 input + LN1
   const float* xin = x;
   const float* branch = nullptr;  // pending residual branch (ff output of the previous layer)
@@ -748,16 +854,18 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
     const float* P = params + (long long)l * ly.per_layer;
     float* A = W + (long long)l * ly.a_layer;
     // x_l = x_{l-1} + drop(ff branch of l-1)  (l == 0: copy of the input), xn1 = LN1(x_l)
-    hipLaunchKernelGGL(k_resid_ln_fwd, dim3(rb), dim3(256), 0, s, xin, branch, pending, A + ly.a_x, P + ly.o_n1w,
-                       P + ly.o_n1b, A + ly.a_xn1, A + ly.a_st1, R);
+    if ((rc = resid_ln(xin, branch, pending, A + ly.a_x, P + ly.o_n1w, P + ly.o_n1b, A + ly.a_xn1, A + ly.a_st1))) return rc;
     if ((rc = linear_forward(A + ly.a_xn1, d, P + ly.o_inw, P + ly.o_inb, A + ly.a_qkv, 3 * d, R, d, 3 * d, LIN_NONE, s)))
       return rc;
     const long long pairs = (long long)p.B * p.H;
     const Drop da = make_drop(p.p, seed, 4 * l + SITE_ATTN);
-    if (p.S > TOK_MAX_S) {
-      ProfScope ps(PC_ATTN_TILE_FWD, s, 4.0 * pairs * p.S * p.S * TOK_DH, 4.0 * R * (4.0 * d));
-      IGI_LAUNCH(k_attn_tile_fwd, dim3(tok_blocks(pairs, AT_THREADS / 64)), dim3(AT_THREADS), 0, s, A + ly.a_qkv, A + ly.a_ctx, da,
-                 pairs, p.H, p.S);
+    if (tile) {
+      ProfScope ps(PC_ATTN_TILE_FWD, s, 4.0 * pairs * p.S * p.S * p.dh, 4.0 * R * (4.0 * d));
+      rc = tile_dispatch(p.dh, d, [&](auto hc, auto mc) {
+        IGI_LAUNCH((k_attn_tile_fwd<decltype(hc)::value, decltype(mc)::value>), dim3(tok_blocks(pairs, AT_THREADS / 64)),
+                   dim3(AT_THREADS), 0, s, A + ly.a_qkv, A + ly.a_ctx, da, pairs, p.H, p.S);
+      });
+      if (rc) return rc;
     } else {
       rc = attn_dispatch(p.S, [&](auto sc) {
         constexpr int SS = decltype(sc)::value;
@@ -768,8 +876,9 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
     }
     float* t0 = W + p.s_g0;  // sa branch output (not needed by backward)
     if ((rc = linear_forward(A + ly.a_ctx, d, P + ly.o_ow, P + ly.o_ob, t0, d, R, d, d, LIN_NONE, s))) return rc;
-    hipLaunchKernelGGL(k_resid_ln_fwd, dim3(rb), dim3(256), 0, s, A + ly.a_x, t0, make_drop(p.p, seed, 4 * l + SITE_SA),
-                       A + ly.a_x1, P + ly.o_n2w, P + ly.o_n2b, A + ly.a_xn2, A + ly.a_st2, R);
+    if ((rc = resid_ln(A + ly.a_x, t0, make_drop(p.p, seed, 4 * l + SITE_SA), A + ly.a_x1, P + ly.o_n2w, P + ly.o_n2b,
+                       A + ly.a_xn2, A + ly.a_st2)))
+      return rc;
     if ((rc = linear_forward(A + ly.a_xn2, d, P + ly.o_w1, P + ly.o_b1, A + ly.a_z, ff, R, d, ff, LIN_NONE, s))) return rc;
     hipLaunchKernelGGL(k_gelu_fwd, dim3(tok_blocks(R * ff, 256)), dim3(256), 0, s, A + ly.a_z, A + ly.a_h,
                        make_drop(p.p, seed, 4 * l + SITE_FF_ACT), R * ff);
@@ -780,8 +889,7 @@ static int token_forward(const igi_token_cfg* c, const float* x, const float* pa
     pending = make_drop(p.p, seed, 4 * l + SITE_FF);
   }
   // y = x1_{L-1} + drop(ff branch)
-  hipLaunchKernelGGL(k_resid_ln_fwd, dim3(rb), dim3(256), 0, s, xin, branch, pending, y, (const float*)nullptr,
-                     (const float*)nullptr, (float*)nullptr, (float*)nullptr, R);
+  if ((rc = resid_ln(xin, branch, pending, y, nullptr, nullptr, nullptr, nullptr))) return rc;
   return (int)hipGetLastError();
 }
 
@@ -1079,7 +1187,7 @@ static int token_backward(const igi_token_cfg* c, const float* dy, const float* 
   // (S <= TB_FUSED_MAX_S: with five or more tokens per sample the attention pass of k_token_bwd holds more than 256 registers
   //  -- 88 to 940 bytes of scratch per lane in the S = 5 .. 8 instantiations -- so those run the launch-per-operation
   //  backward below, which does not spill; the instantiations are not built)
-  if (token_bwd_fused_enabled() && p.S <= TB_FUSED_MAX_S && p.bwd_grid > 0 && p.ff == TF_FF && p.d == TOK_D && p.H == 2 && !bf16_mode() &&
+  if (token_bwd_fused_enabled() && p.S <= TB_FUSED_MAX_S && p.bwd_grid > 0 && p.ff == TF_FF && p.narrow && !bf16_mode() &&
       ((ly.a_layer | ly.a_xn1 | ly.a_ctx | ly.a_xn2 | ly.a_h | ly.a_z) & 3) == 0) {
     TokBwdArgs a;
     a.dy = dy; a.params = params; a.dx = dx; a.W = W; a.part = W + p.s_part;
@@ -1108,6 +1216,14 @@ static int token_backward(const igi_token_cfg* c, const float* dy, const float* 
   float* rB = W + p.s_rB;   // residual-stream gradient between the two blocks of a layer
   float* w0 = W + p.s_wide0;
   float* w1 = W + p.s_wide1;
+  const bool tile = p.S > TOK_MAX_S || !p.narrow;
+  auto ln_bwd_launch = [&](const float* dxn, const float* x, const float* stats, const float* gamma, const float* dres_, float* dx_,
+                           const Drop& dr, float* dmask, float* part) {
+    return width_dispatch(d, [&](auto dc) {
+      hipLaunchKernelGGL(k_ln_bwd<decltype(dc)::value>, dim3(p.ln_blocks), dim3(256), 0, s, dxn, x, stats, gamma, dres_, dx_, dr,
+                         dmask, part, R);
+    });
+  };
   // the sums of every split-row partial of this pass (eight Linears x (weight, bias), four layer norms) are queued and
   // run as ONE launch at the end: each producer therefore keeps its own partial buffer
   SplitSumTable sums;
@@ -1140,8 +1256,9 @@ static int token_backward(const igi_token_cfg* c, const float* dy, const float* 
     // ---- LN2 backward + residual: dx1 and its masked copy for the sa branch (g1)
     float* dx1 = rB;
     float* lnpart = lnpart_next();
-    hipLaunchKernelGGL(k_ln_bwd, dim3(p.ln_blocks), dim3(256), 0, s, g0, A + ly.a_x1, A + ly.a_st2, P + ly.o_n2w, dres,
-                       dx1, make_drop(p.p, seed, 4 * l + SITE_SA), p.p > 0.f ? g1 : (float*)nullptr, lnpart, R);
+    if ((rc = ln_bwd_launch(g0, A + ly.a_x1, A + ly.a_st2, P + ly.o_n2w, dres, dx1, make_drop(p.p, seed, 4 * l + SITE_SA),
+                            p.p > 0.f ? g1 : (float*)nullptr, lnpart)))
+      return rc;
     // norm2.weight and norm2.bias are adjacent
     if (!split_sum_defer(sums, G + ly.o_n2w, lnpart, 2LL * d, 2LL * d, p.ln_blocks))
       split_sum(G + ly.o_n2w, lnpart, 2LL * d, p.ln_blocks, 2LL * d, s);
@@ -1152,10 +1269,13 @@ static int token_backward(const igi_token_cfg* c, const float* dy, const float* 
       return rc;
     const long long pairs = (long long)p.B * p.H;
     const Drop datt = make_drop(p.p, seed, 4 * l + SITE_ATTN);
-    if (p.S > TOK_MAX_S) {
-      ProfScope ps(PC_ATTN_TILE_BWD, s, 12.0 * pairs * p.S * p.S * TOK_DH, 4.0 * R * (7.0 * d));
-      IGI_LAUNCH(k_attn_tile_bwd, dim3(tok_blocks(pairs, AT_THREADS / 64)), dim3(AT_THREADS), 0, s, A + ly.a_qkv, g0, w1, datt,
-                 pairs, p.H, p.S);
+    if (tile) {
+      ProfScope ps(PC_ATTN_TILE_BWD, s, 12.0 * pairs * p.S * p.S * p.dh, 4.0 * R * (7.0 * d));
+      rc = tile_dispatch(p.dh, d, [&](auto hc, auto mc) {
+        IGI_LAUNCH((k_attn_tile_bwd<decltype(hc)::value, decltype(mc)::value>), dim3(tok_blocks(pairs, AT_THREADS / 64)),
+                   dim3(AT_THREADS), 0, s, A + ly.a_qkv, g0, w1, datt, pairs, p.H, p.S);
+      });
+      if (rc) return rc;
     } else {
       rc = attn_dispatch(p.S, [&](auto sc) {
         constexpr int SS = decltype(sc)::value;
@@ -1171,8 +1291,9 @@ static int token_backward(const igi_token_cfg* c, const float* dy, const float* 
     float* dxl = (l == 0) ? dx : rA;
     const bool mask_below = (l > 0) && p.p > 0.f;
     lnpart = lnpart_next();
-    hipLaunchKernelGGL(k_ln_bwd, dim3(p.ln_blocks), dim3(256), 0, s, g0, A + ly.a_x, A + ly.a_st1, P + ly.o_n1w, dx1, dxl,
-                       make_drop(p.p, seed, 4 * (l - 1) + SITE_FF), mask_below ? g1 : (float*)nullptr, lnpart, R);
+    if ((rc = ln_bwd_launch(g0, A + ly.a_x, A + ly.a_st1, P + ly.o_n1w, dx1, dxl, make_drop(p.p, seed, 4 * (l - 1) + SITE_FF),
+                            mask_below ? g1 : (float*)nullptr, lnpart)))
+      return rc;
     // norm1.weight and norm1.bias are adjacent
     if (!split_sum_defer(sums, G + ly.o_n1w, lnpart, 2LL * d, 2LL * d, p.ln_blocks))
       split_sum(G + ly.o_n1w, lnpart, 2LL * d, p.ln_blocks, 2LL * d, s);

@@ -1,6 +1,6 @@
-// The token encoder's arithmetic, each formula once: dropout, LayerNorm forward / backward of a row element, erf GELU and
-// its derivative, the register attention of one (sample, head) pair (S <= 8) and the 32 x 32 k-contiguous MFMA tile
-// product.  The routines compute on registers only: the launch-per-operation kernels and the one-launch kernels of
+// The token encoder's arithmetic, each formula once: dropout, LayerNorm forward / backward of a row's elements (rows of
+// 32, 64 or 128 features), erf GELU and its derivative, the register attention of one (sample, head) pair (S <= 8, heads
+// of 16) and the 32 x 32 k-contiguous MFMA tile product.  The routines compute on registers only: the launch-per-operation kernels and the one-launch kernels of
 // token_encoder.h load the operands from global memory or LDS, call them, and store the results, so the two paths cannot
 // drift apart (the library builds with -ffp-contract=off: one expression, one rounding, wherever it is inlined).
 #pragma once
@@ -11,7 +11,7 @@
 
 namespace igi {
 
-constexpr int TOK_D = 32, TOK_DH = 16;
+constexpr int TOK_D = 32, TOK_DH = 16;   // the width and head width of the one-launch and register attention kernels
 constexpr float TOK_LN_EPS = 1e-5f;
 
 // ---- dropout: keep iff tok_hash(seed, site, index) >= p * 2^32 (tok_hash.h); kept values are scaled by 1/(1-p)
@@ -44,26 +44,78 @@ __device__ __forceinline__ float half32_sum(float v) {  // sum over 32 consecuti
   return v + __shfl_xor(v, 16, 64);
 }
 
-// ---- LayerNorm over a row of TOK_D features held by a half wave (lane = feature).  Forward: the normalised element of
-// v with this feature's gamma / beta; mean and rstd of the row come back in every lane.
-__device__ __forceinline__ float ln_fwd(float v, float gamma, float beta, float& mean, float& rstd) {
-  mean = half32_sum(v) * (1.0f / TOK_D);
-  const float c = v - mean;
-  const float var = half32_sum(c * c) * (1.0f / TOK_D);
-  rstd = 1.0f / sqrtf(var + TOK_LN_EPS);
-  return c * rstd * gamma + beta;
+// ---- LayerNorm over a row of D features (32, 64 or 128).  D = 32: a half wave owns the row, lane = feature.  D = 64 / 128:
+// a whole wave owns the row and a lane holds the D / 64 features lane, lane + 64 (loads stay coalesced).  A row sum is
+// the lane's own features in order, the DPP row sum, then the exchanges across the 16-lane rows: one fixed order.
+template <int D> struct LnShape {
+  static_assert(D == 32 || D == 64 || D == 128, "LayerNorm rows of 32, 64 or 128 features");
+  static constexpr int LANES = D == 32 ? 32 : 64;   // lanes that own a row
+  static constexpr int NV = D / LANES;              // features per lane: f = lane + LANES * u
+};
+template <int D>
+__device__ __forceinline__ float ln_row_sum(float v) {   // sum over the lanes that own a row, in every one of them
+  v = half32_sum(v);
+  if constexpr (D > 32) v += __shfl_xor(v, 32, 64);
+  return v;
 }
-// Backward + residual: dx = dres + rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dxn * gamma; the feature's terms of
+// Forward: the normalised elements of v with their features' gamma / beta; mean and rstd of the row come back in every lane.
+template <int D>
+__device__ __forceinline__ void ln_fwd(const float (&v)[LnShape<D>::NV], const float (&gamma)[LnShape<D>::NV],
+                                       const float (&beta)[LnShape<D>::NV], float (&o)[LnShape<D>::NV], float& mean,
+                                       float& rstd) {
+  constexpr int NV = LnShape<D>::NV;
+  float s = v[0];
+#pragma unroll
+  for (int u = 1; u < NV; ++u) s += v[u];
+  mean = ln_row_sum<D>(s) * (1.0f / D);
+  float c[NV];
+  c[0] = v[0] - mean;
+  float q = c[0] * c[0];
+#pragma unroll
+  for (int u = 1; u < NV; ++u) { c[u] = v[u] - mean; q += c[u] * c[u]; }
+  const float var = ln_row_sum<D>(q) * (1.0f / D);
+  rstd = 1.0f / sqrtf(var + TOK_LN_EPS);
+#pragma unroll
+  for (int u = 0; u < NV; ++u) o[u] = c[u] * rstd * gamma[u] + beta[u];
+}
+// Backward + residual: dx = dres + rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dxn * gamma; the features' terms of
 // the LayerNorm weight / bias gradients (dxn * xhat, dxn) are added to sg / sb.
+template <int D>
+__device__ __forceinline__ void ln_bwd(const float (&dxn)[LnShape<D>::NV], const float (&x)[LnShape<D>::NV], float mean,
+                                       float rstd, const float (&gamma)[LnShape<D>::NV],
+                                       const float (&dres)[LnShape<D>::NV], float (&dx)[LnShape<D>::NV],
+                                       float (&sg)[LnShape<D>::NV], float (&sb)[LnShape<D>::NV]) {
+  constexpr int NV = LnShape<D>::NV;
+  float xhat[NV], g[NV];
+#pragma unroll
+  for (int u = 0; u < NV; ++u) {
+    xhat[u] = (x[u] - mean) * rstd;
+    sg[u] += dxn[u] * xhat[u];
+    sb[u] += dxn[u];
+    g[u] = dxn[u] * gamma[u];
+  }
+  float s1 = g[0], s2 = g[0] * xhat[0];
+#pragma unroll
+  for (int u = 1; u < NV; ++u) { s1 += g[u]; s2 += g[u] * xhat[u]; }
+  const float m1 = ln_row_sum<D>(s1) * (1.0f / D);
+  const float m2 = ln_row_sum<D>(s2) * (1.0f / D);
+#pragma unroll
+  for (int u = 0; u < NV; ++u) dx[u] = dres[u] + rstd * (g[u] - m1 - xhat[u] * m2);
+}
+// the 32-wide row of the one-launch kernels, one feature per lane: the same routines on one-element arrays
+__device__ __forceinline__ float ln_fwd(float v, float gamma, float beta, float& mean, float& rstd) {
+  const float vv[1] = {v}, gm[1] = {gamma}, bt[1] = {beta};
+  float o[1];
+  ln_fwd<TOK_D>(vv, gm, bt, o, mean, rstd);
+  return o[0];
+}
 __device__ __forceinline__ float ln_bwd(float dxn, float x, float mean, float rstd, float gamma, float dres, float& sg,
                                         float& sb) {
-  const float xhat = (x - mean) * rstd;
-  sg += dxn * xhat;
-  sb += dxn;
-  const float g = dxn * gamma;
-  const float m1 = half32_sum(g) * (1.0f / TOK_D);
-  const float m2 = half32_sum(g * xhat) * (1.0f / TOK_D);
-  return dres + rstd * (g - m1 - xhat * m2);
+  const float dn[1] = {dxn}, xx[1] = {x}, gm[1] = {gamma}, dr[1] = {dres};
+  float o[1], g1[1] = {sg}, b1[1] = {sb};
+  ln_bwd<TOK_D>(dn, xx, mean, rstd, gm, dr, o, g1, b1);
+  sg = g1[0]; sb = b1[0];
+  return o[0];
 }
 
 // ---- exact (erf) GELU (nn.GELU default / activation="gelu") and its derivative

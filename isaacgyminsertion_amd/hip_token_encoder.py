@@ -1,5 +1,5 @@
-"""Stack of ``nn.TransformerEncoderLayer(d_model=32, nhead=2, dim_feedforward=128, activation="gelu",
-batch_first=True, norm_first=True)`` whose forward / backward run in libigi_hip.so
+"""Stack of ``nn.TransformerEncoderLayer(d_model, nhead, dim_feedforward, activation="gelu", batch_first=True,
+norm_first=True)`` (32 / 2 / 128 in the reference's stock config; d_model 32, 64 or 128 with heads of 16, 32 or 64) whose forward / backward run in libigi_hip.so
 (igi_token_forward / igi_token_backward: MFMA GEMMs for the eight Linears, fused LayerNorm / attention /
 GELU / residual-dropout kernels around them) -- the ``sa_decoder`` of the reference's MultiLayerDecoder
 (algo/models/transformer/tact.py:137-158).
@@ -26,7 +26,10 @@ from .flat_params import flat_parameters
 class HipTransformerEncoder(nn.Module):
     """Drop-in for ``nn.TransformerEncoder(encoder_layer, num_layers, enable_nested_tensor=False)``
     (no final norm, no masks: the reference passes neither) over up to 32 tokens per sample (= sequence_length x
-    modalities of the student; more raises, there is no fallback)."""
+    modalities of the student) of ``d_model`` 32, 64 or 128 features with heads of 16, 32 or 64 (``d_model / nhead``:
+    the student's ``*_encoding_size`` and ``num_heads``).  More tokens, another width or another head width raise:
+    there is no fallback.  ``d_model=32, nhead=2`` (the reference's stock config) also has one-launch kernels; the
+    other configurations run one launch per operation."""
 
     def __init__(self, encoder_layer, num_layers):
         super().__init__()

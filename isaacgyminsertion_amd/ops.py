@@ -1497,19 +1497,30 @@ register_autograd(f"{NS}::depth_backbone_fwd", _dep_backward, setup_context=_dep
 TOKEN_MAX_SEQ = 32    # csrc/token_encoder.h: TOK_MAX_SEQ, one 32 x 32 matrix-pipe tile per (sample, head)
 
 
+TOKEN_WIDTHS = (32, 64, 128)        # csrc/token_encoder.h: token_width_supported
+TOKEN_HEAD_WIDTHS = (16, 32, 64)
+
+
 def _token_cfg(x, nhead, ff, layers, dropout, training):
     B, S, d = x.shape
     if S > TOKEN_MAX_SEQ:
         raise RuntimeError(f"token encoder: {S} tokens per sample, the native kernels take at most {TOKEN_MAX_SEQ} "
                            f"(tokens = sequence_length x modalities; there is no fallback)")
+    if d not in TOKEN_WIDTHS or nhead < 1 or d % nhead or d // nhead not in TOKEN_HEAD_WIDTHS:
+        raise RuntimeError(f"token encoder: d_model {d} with {nhead} heads, the native kernels take d_model in "
+                           f"{list(TOKEN_WIDTHS)} with heads of d_model / nhead in {list(TOKEN_HEAD_WIDTHS)} features "
+                           f"(d_model = the *_encoding_size of the student, nhead = num_heads; there is no fallback)")
     return _lib.TokenCfg(B, S, d, nhead, ff, layers, float(dropout), 1 if training else 0)
 
 
 @_op("token_encoder_fwd(Tensor x, Tensor params, int nhead, int ff, int layers, float dropout, bool training, int seed) -> (Tensor, Tensor)")
 def token_encoder_fwd(x: Tensor, params: Tensor, nhead: int, ff: int, layers: int, dropout: float, training: bool,
                       seed: int) -> Tuple[Tensor, Tensor]:
-    """``layers`` x TransformerEncoderLayer(d, nhead, ff, gelu, batch_first, norm_first) over (B, S <= 32, d)
-    (tact.py:143-148; S <= 8: register attention kernels, 9 <= S <= 32: the matrix-pipe tile kernels); dropout masks from a counter hash of ``seed`` -> igi_token_forward."""
+    """``layers`` x TransformerEncoderLayer(d, nhead, ff, gelu, batch_first, norm_first) over (B, S <= 32, d), d in
+    {32, 64, 128} with heads of d / nhead in {16, 32, 64} features (tact.py:143-148).  (32, 2): register attention
+    kernels at S <= 8, the matrix-pipe tile kernels at 9 <= S <= 32, one-launch kernels where they apply; every other
+    (d, nhead) runs launch per operation with the tile attention kernels at every S.  Anything else raises (no
+    fallback).  Dropout masks from a counter hash of ``seed`` -> igi_token_forward."""
     _check(x, "x", dim=3)
     cfg = _token_cfg(x, nhead, ff, layers, dropout, training)
     L = _lib.lib()
