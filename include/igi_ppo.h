@@ -788,6 +788,25 @@ int igi_tactile_augment(const float* arena, int64_t n, int planes, int hs, int w
                         uint64_t seed, float* out, igi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same chain for the ONLINE student's distillation step (csrc/tactile_augment_seeded.h), ONE launch from the rollout
+ * storage's time-major arena to the minibatch tensor, with nothing drawn on the host but `seed`:
+ *   arena     : fp32 [n][planes][hs][ws], n = horizon * envs flat rows, planes = history * fingers; never written
+ *   rows      : [b] flat rows (the ones igi_gather_rows takes); one outside [0, n) reads as frames of zeros
+ *   the window is the top-left out_h x out_w of the stored frame.  Per image (image = row-in-batch * planes + plane): the
+ *   jitter flag (probability 0.3), brightness and contrast in 1 +- 0.1, the rotate flag (0.5), the angle in +- 3 degrees and,
+ *   with masking_prob > 0, the keep value of every out_h / patch x out_w / patch patch (kept with probability
+ *   1 - masking_prob) are the counter hash of (seed, site, element) at the sites tabled in csrc/tactile_augment_seeded.h,
+ *   every event an integer comparison.  An image with both flags off passes bit for bit
+ *   noise_std : as igi_tactile_augment, from the same seed
+ *   out       : fp32 [b][planes][out_h][out_w], not the arena; out_h * out_w above 8192: IGI_E_UNSUPPORTED
+ *   draws     : int32 [b*planes][IGI_TACTILE_AUG_WORDS] or NULL: 0, 0, the jitter flag, the fp32 bit patterns of b, c, angle
+ *               the kernel used.  masking_prob outside [0, 1], or > 0 with patch < 1: IGI_E_BADARG.  Same arguments, same bits
+ * ---------------------------------------------------------------------------------------- */
+int igi_tactile_augment_seeded(const float* arena, int64_t n, int planes, int hs, int ws, const int64_t* rows, int64_t b,
+                               int out_h, int out_w, int patch, float noise_std, double masking_prob, uint64_t seed,
+                               float* out, int32_t* draws, igi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Train-time augmentation of the online student's segmented point cloud (csrc/pcl_augment.h), ONE launch from the
  * environment's cloud tensor to a new tensor (PointCloudAugmentations.augment of the reference's environment,
  * factory_utils.py:83-166, which runs it object by object on a boolean-masked subset of the envs):

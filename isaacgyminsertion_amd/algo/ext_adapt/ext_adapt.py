@@ -19,6 +19,7 @@ import torch.distributed as dist
 from ..models.models_split import ActorCriticSplit as ActorCritic
 from ..models.running_mean_std import RunningMeanStd
 from ..models.transformer.runner import Runner as Student
+from ..models.transformer.utils import TactileAugment
 from ..ppo.experience import StudentBuffer
 from ..ppo.frozen_ppo import _NullWriter, _summary_writer, log_test_result
 from ...bc_loss import bc_loss
@@ -90,6 +91,7 @@ class ExtrinsicAdapt(object):
         self.pcl_augment, self.pcl_episode = self._make_pcl_augment(), None
         if self.pcl_augment is not None:
             self.pcl_episode = torch.zeros(self.num_actors, dtype=torch.int32, device=self.device)
+        self.tactile_augment, self.tactile_seed = self._make_tactile_augment(), None
         self.student = Student(student_cfg)
         self.stats = None
         self.output_dir = output_dir
@@ -183,6 +185,42 @@ class ExtrinsicAdapt(object):
                           rot_deg=float(rnd.get('pcl_rot', 30.0)) if rnd.get('pcl_rotate', False) else 0.0,
                           outlier_ratio=float(rnd.get('pcl_outlier_ratio', 0.0)),
                           dropout_ratio=float(rnd.get('pcl_dropout_ratio', 0.0)), seed=seed)
+
+    def _make_tactile_augment(self):
+        """``offline_train.tactile_augment_online``: absent / "off" = None; "fused" = the train transform of the tactile
+        images (the call the reference comments out, runner.py:402) on the minibatch of every optimizer step, in one native
+        launch straight from the rollout storage (``TactileAugment.fused_seeded``).  Strengths are the reference's keys
+        ``tactile_gaussian_noise`` / ``tactile_masking_prob`` / ``tactile_patch_size``.  The rollout, evaluation and
+        deployment read the frames as they are."""
+        cfg, name = self.train_config, "offline_train.tactile_augment_online"
+        key = cfg.get('tactile_augment_online', None)
+        if key is None or (isinstance(key, str) and key == 'off'):
+            return None
+        if not (isinstance(key, str) and key == 'fused'):
+            raise ValueError(f"{name}: expected 'off' or 'fused', got {key!r}")
+        if not self.tactile_info:
+            raise ValueError(f"{name}: 'fused' needs the tactile images (train.ppo.tactile_info: True)")
+        if cfg.tactile_type != 'gray':
+            raise NotImplementedError(f"{name}: 'fused' reads single-channel tactile frames (tactile_type 'gray'), got "
+                                      f"tactile_type {cfg.tactile_type!r}")
+        crop = (cfg.get('tactile_crop_w', 0), cfg.get('tactile_crop_h', 0))
+        if crop != (0, 0):
+            raise NotImplementedError(f"{name}: 'fused' does not crop (the rollout's predict has no centre crop of stored "
+                                      f"frames): tactile_crop_w / tactile_crop_h must be 0, got {crop}")
+        size = (int(cfg.tactile_width), int(cfg.tactile_height))
+        aug = TactileAugment(size, size, cfg.get('tactile_patch_size', 16), cfg.get('tactile_gaussian_noise', 0.0),
+                             cfg.get('tactile_masking_prob', 0.0), train=True)
+        # one seed per optimizer step from a private CPU generator: torch's global generators are not touched
+        aug.generator = torch.Generator().manual_seed(int(self.full_config.get('seed', 0)) + (self.rank if self.multi_gpu else 0))
+        return aug
+
+    def _augmented_tactile(self, b):
+        """The tactile input of minibatch ``b`` under ``tactile_augment_online: "fused"``: one seed, one launch, read from
+        the time-major arena in place -> (B, history, fingers, 1, W, H)."""
+        aug = self.tactile_augment
+        self.tactile_seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=aug.generator))
+        arena = self.storage.storage_dict['n_tactile']
+        return aug.fused_seeded(arena.reshape(arena.shape[0] * arena.shape[1], -1), b.rows, self.tactile_seed)[0]
 
     def process_obs(self, obs, obj_id=2, socket_id=3, distinct=True, augment=False):
         """ext_adapt.py:383-435: normalise student_obs and the point cloud (both normalisers are in
@@ -363,11 +401,13 @@ class ExtrinsicAdapt(object):
         """Forward + loss + backward of minibatch ``i`` (ext_adapt.py:785-828): the raw local gradient is left in
         ``self.optim.flat_grad``.  Returns (action loss, latent loss)."""
         b = self.storage[i]
+        fused_tactile = self.tactile_augment is not None     # then the augmentation's launch gathers n_tactile itself
         if hasattr(b, 'prefetch'):           # the keys this step reads, gathered by one launch
-            b.prefetch(('n_student_obs', 'n_tactile', 'n_img', 'n_seg', 'n_pcl', 'teacher_actions') +
-                       (() if self.only_bc else ('n_obs', 'latent_gt')))
+            b.prefetch(('n_student_obs',) + (() if fused_tactile else ('n_tactile',)) +
+                       ('n_img', 'n_seg', 'n_pcl', 'teacher_actions') + (() if self.only_bc else ('n_obs', 'latent_gt')))
         student_dict = {
-            'student_obs': b.get('n_student_obs'), 'tactile': b.get('n_tactile'), 'img': b.get('n_img'),
+            'student_obs': b.get('n_student_obs'),
+            'tactile': self._augmented_tactile(b) if fused_tactile else b.get('n_tactile'), 'img': b.get('n_img'),
             'seg': b.get('n_seg'),
             'pcl': b['n_pcl'].reshape(b['n_pcl'].shape[0], -1, 3) if 'n_pcl' in b else None,
         }

@@ -510,6 +510,14 @@ def _hash_gauss(seed, plane, shape, dtype, device):
 
 
 TACTILE_NOISE_PLANE = 2      # the camera pair draws its noise on planes 0 and 1 of the same hash
+# csrc/tactile_augment_seeded.h: the hash sites of the seeded draws (0..13 are the Gaussian planes', 14..22 the point cloud's)
+TACTILE_SITES = dict(JITTER=23, BRIGHT=24, CONTRAST=25, ROTATE=26, ANGLE=27, KEEP=28)
+
+
+def _hash_threshold(p):
+    """An event of probability ``p`` is ``hash < _hash_threshold(p)``: the point-cloud path's helper, as a Python int."""
+    from ....envs.pcl_augment import _threshold
+    return int(_threshold(p))
 
 
 class TactileAugment(nn.Module):
@@ -522,7 +530,11 @@ class TactileAugment(nn.Module):
       ``apply(x, ...)``             -> the transform of (..., C, H, W) images with those draws, in plain torch ops on any
                                        device and in x's dtype; the noise is the kernel's counter hash of ``seed``;
       ``fused(arena, rows)``        -> draw + torch.ops.mi355ppo.tactile_augment: the gather from the resident
-                                       (N, T, F, 1, H, W) arena and the whole transform in one launch.
+                                       (N, T, F, 1, H, W) arena and the whole transform in one launch;
+      ``draw_seeded(n_images, seed)`` / ``fused_seeded(arena2d, rows, seed)`` -> the online student's form: no crop, and
+                                       every draw the counter hash of one seed, evaluated by the kernel itself
+                                       (torch.ops.mi355ppo.tactile_augment_seeded); ``draw_seeded`` + ``apply`` is the same
+                                       function in torch ops.
     ``forward(x)`` is draw + apply from torch's default CPU generator.  In ``eval()`` mode (``train=False``) it is the
     eval transform: the centre window, nothing random, nothing drawn."""
 
@@ -569,6 +581,34 @@ class TactileAugment(nn.Module):
         keep = _draw_keep(n, self.crop_size, self.patch, self.masking_prob, generator)
         return offsets, jitter, angles, keep, _draw_seed(self.noise_std, generator)
 
+    def draw_seeded(self, n_images, seed):
+        """The tuple ``draw`` returns, as k_tactile_augment_seeded draws it from ``seed`` alone (the table of
+        csrc/tactile_augment_seeded.h, restated on the CPU through ``_tok_hash``): ``offsets`` 0 (no crop online); image
+        i's flags are the integer comparisons of its hashes; its factors and angle are float64 arithmetic on exact operands
+        rounded once to fp32 -- the kernel's bits; ``keep`` cell by cell at element ``i * gh * gw + cell``; the returned
+        seed is ``seed``, which the noise hashes too.  Evaluation draws nothing."""
+        n, seed = int(n_images), int(seed)
+        if not self.training:
+            return self.draw(n)
+        S = TACTILE_SITES
+        img = torch.arange(n)
+
+        def unit(site):                                   # 2u - 1, u = (h >> 8) 2^-24: exact in fp32 and in float64
+            return (_tok_hash(seed, site, img) >> 8).double() * 2.0 ** -23 - 1.0
+        on = _tok_hash(seed, S["JITTER"], img) < _hash_threshold(self.JITTER_P)
+        turn = _tok_hash(seed, S["ROTATE"], img) < _hash_threshold(self.ROTATE_P)
+        amp, rad = float(np.float32(self.JITTER)), float(np.float32(self.ROTATE_DEG * math.pi / 180))
+        one = torch.ones(n)
+        jitter = torch.stack([on.float(), torch.where(on, (unit(S["BRIGHT"]) * amp + 1.0).float(), one),
+                              torch.where(on, (unit(S["CONTRAST"]) * amp + 1.0).float(), one)], 1)
+        angles = torch.where(turn, (unit(S["ANGLE"]) * rad).float(), torch.zeros(n))
+        gh, gw = self.crop_size[0] // self.patch, self.crop_size[1] // self.patch
+        keep = None
+        if self.masking_prob > 0.0 and gh * gw > 0:
+            cell = torch.arange(n * gh * gw)
+            keep = (_tok_hash(seed, S["KEEP"], cell) >= _hash_threshold(self.masking_prob)).to(torch.uint8).reshape(n, gh, gw)
+        return torch.zeros(n, 2, dtype=torch.int32), jitter, angles, keep, seed
+
     @staticmethod
     def pack(offsets, jitter, angles):
         """The draws of ``draw`` as the op's ``params``: int32 (n, 6) = top, left, flag, bits of (b, c, angle)."""
@@ -612,6 +652,28 @@ class TactileAugment(nn.Module):
         if tuple(arena.shape[-2:]) != self._size:
             raise NotImplementedError(f"offline_train.tactile_augment: 'fused' does not resize: the frames are stored at "
                                       f"{tuple(arena.shape[-2:])}, tactile_width x tactile_height is {self._size}; use 'torch'")
+
+    def fused_seeded(self, arena2d, rows, seed, want_draws=False, fingers=3):
+        """The online student's minibatch in one native launch, every draw hashed from ``seed``: ``arena2d`` the rollout
+        storage's time-major tactile arena as the gather sees it, (horizon * envs, history * fingers * H * W) single-channel
+        frames at ``size``, read in place; ``rows`` the minibatch's int64 flat rows on its device -> (out, draws): fp32
+        (B, history, fingers, 1, H, W) and, with ``want_draws``, the kernel's own draws as ``pack`` lays them out (else None).
+        There is no crop online.  Above the kernel's window the same draws go through ``apply``."""
+        H, W = self._size
+        if self.crop_size != self._size:
+            raise NotImplementedError(f"TactileAugment.fused_seeded does not crop: crop size {self.crop_size}, stored {self._size}")
+        if arena2d.dim() != 2 or arena2d.shape[1] % (fingers * H * W) != 0 or arena2d.shape[1] == 0:
+            raise ValueError(f"arena2d: expected (rows, history * {fingers} * {H} * {W}), got {tuple(arena2d.shape)}")
+        arena = arena2d.reshape(arena2d.shape[0], -1, fingers, 1, H, W)
+        if not self.training:
+            return arena.index_select(0, rows), None
+        if H * W > ops.TACTILE_AUG_MAX_PIXELS:            # larger than the kernel's window: the same draws in torch ops
+            n = rows.numel() * arena.shape[1] * fingers
+            offsets, jitter, angles, keep, seed = self.draw_seeded(n, seed)
+            out = self.apply(arena.index_select(0, rows), offsets, jitter, angles, keep, self.noise_std, seed)
+            return out, (self.pack(offsets, jitter, angles).to(arena.device) if want_draws else None)
+        return torch.ops.mi355ppo.tactile_augment_seeded(arena, rows, H, W, self.patch, self.noise_std, self.masking_prob,
+                                                         int(seed), bool(want_draws))
 
     def fused(self, arena, rows, generator=None):
         """``arena.index_select(0, rows) -> forward`` as one native launch: ``arena`` the loader's resident

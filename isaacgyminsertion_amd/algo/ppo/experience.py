@@ -144,6 +144,11 @@ class _LazyMinibatch:
     def __init__(self, storage, flat_rows, rows_total):
         self._s, self._flat, self._rt, self._c = storage, flat_rows, rows_total, {}
 
+    @property
+    def rows(self):
+        """The minibatch's int64 flat rows of the time-major arena (what every gather here is given)."""
+        return self._flat
+
     def __getitem__(self, k):
         if k not in self._c:
             v = self._s[k]

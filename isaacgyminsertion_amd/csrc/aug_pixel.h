@@ -1,5 +1,6 @@
-// What every output pixel of the augmentation kernels goes through (augment.h: the camera pair; tactile_augment.h: the
-// tactile images), written once.  An output plane is out_h x out_w pixels cut from a stored frame of Hs x Ws; per pixel:
+// What every output pixel of the augmentation kernels goes through (augment.h: the camera pair; tactile_augment.h and
+// tactile_augment_seeded.h: the tactile images), written once.  An output plane is out_h x out_w pixels cut from a stored
+// frame of Hs x Ws; per pixel:
 //   crop     window [top, top+out_h) x [left, left+out_w) of the frame; a read outside the frame, and every read of a
 //            sample that is not live (number outside [0, N)), gives 0                                  -- aug_frame_read
 //   rotate   about the window's centre; the source coordinate is that of F.affine_grid / F.grid_sample(nearest, zeros,
@@ -15,8 +16,10 @@
 //   store    groups of four consecutive pixels of a row: one 16-byte store where out_w % 4 == 0 and the output is 16-byte
 //            aligned, scalar stores (the last group of a row may be partial) elsewhere
 // aug_rows is that chain from noise on, over a range of groups; where the window's value comes from -- the stored frame
-// through the window, LDS, the stored frame unrotated -- is its `fetch` argument.  AugShape and aug_shape hold what the two
-// launches check and derive alike.  tests/img_augment_ref.py restates every step in float64.
+// through the window, LDS, the stored frame unrotated -- is its `fetch` argument, and where a patch's keep value comes from
+// -- the caller's grids in global memory, a grid the workgroup built in LDS -- is the `keep_of` argument of aug_rows_keep
+// (aug_rows is that function over AugShape's own grids).  AugShape and aug_shape hold what the launches check and derive
+// alike.  tests/img_augment_ref.py restates every step in float64.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,15 +87,14 @@ __device__ __forceinline__ float aug_frame_read(const float* __restrict__ src, c
   return in ? src[sy * c.Ws + sx] : 0.f;
 }
 
-// Groups q = q0, q0 + 256, ... < q1 of output plane number `image` (its tensor's base `out`, its keep grid or none):
-// fetch(x, y), noise of `noise_plane`, keep, store.
-template <class Fetch>
-__device__ __forceinline__ void aug_rows(const AugShape& c, float* __restrict__ out, long long image, bool masked,
-                                         unsigned int noise_plane, int q0, int q1, Fetch fetch) {
+// Groups q = q0, q0 + 256, ... < q1 of output plane number `image` (its tensor's base `out`): fetch(x, y), noise of
+// `noise_plane`, times keep_of(cell) inside the c.gh x c.gw whole patches where `masked`, store.
+template <class Fetch, class Keep>
+__device__ __forceinline__ void aug_rows_keep(const AugShape& c, float* __restrict__ out, long long image, bool masked,
+                                              unsigned int noise_plane, int q0, int q1, Fetch fetch, Keep keep_of) {
   const int W = c.out_w;
   const long long e0 = image * ((long long)c.out_h * W);
   float* __restrict__ dst = out + e0;
-  const unsigned char* __restrict__ keep = (masked && c.keep) ? c.keep + image * ((long long)c.gh * c.gw) : nullptr;
   const int mh = c.gh * c.patch, mw = c.gw * c.patch;  // the masked region (whole patches)
   for (int q = q0; q < q1; q += 256) {
     const int y = q / c.qpr, x0 = (q - y * c.qpr) * 4;
@@ -105,7 +107,7 @@ __device__ __forceinline__ void aug_rows(const AugShape& c, float* __restrict__ 
       float p = fetch(x, y);
       if (c.noise_std > 0.f)
         p = p + c.noise_std * aug_gauss(c.seed, noise_plane, (unsigned int)(e0 + (long long)y * W + x));
-      if (keep && y < mh && x < mw) p = p * (float)keep[(y / c.patch) * c.gw + x / c.patch];
+      if (masked && y < mh && x < mw) p = p * keep_of((y / c.patch) * c.gw + x / c.patch);
       v[j] = p;
     }
     float* o = dst + (long long)y * W + x0;
@@ -117,6 +119,14 @@ __device__ __forceinline__ void aug_rows(const AugShape& c, float* __restrict__ 
         if (x0 + j < W) o[j] = v[j];
     }
   }
+}
+
+// The same with the plane's keep grid of AugShape (or none).
+template <class Fetch>
+__device__ __forceinline__ void aug_rows(const AugShape& c, float* __restrict__ out, long long image, bool masked,
+                                         unsigned int noise_plane, int q0, int q1, Fetch fetch) {
+  const unsigned char* __restrict__ keep = (masked && c.keep) ? c.keep + image * ((long long)c.gh * c.gw) : nullptr;
+  aug_rows_keep(c, out, image, keep != nullptr, noise_plane, q0, q1, fetch, [&](int cell) { return (float)keep[cell]; });
 }
 
 }  // namespace igi

@@ -21,6 +21,7 @@
 #include "augment.h"
 #include "tactile_augment.h"
 #include "pcl_augment.h"
+#include "tactile_augment_seeded.h"
 #include "peak_probe.h"
 
 namespace {
@@ -710,6 +711,13 @@ int igi_tactile_augment(const float* arena, int64_t n, int planes, int hs, int w
                         uint64_t seed, float* out, igi_stream_t stream) {
   return fail(igi::tactile_augment(arena, n, planes, hs, ws, rows, b, params, keep, out_h, out_w, patch, noise_std, seed,
                                    out, S(stream)), "igi_tactile_augment");
+}
+
+int igi_tactile_augment_seeded(const float* arena, int64_t n, int planes, int hs, int ws, const int64_t* rows, int64_t b,
+                               int out_h, int out_w, int patch, float noise_std, double masking_prob, uint64_t seed,
+                               float* out, int32_t* draws, igi_stream_t stream) {
+  return fail(igi::tactile_augment_seeded(arena, n, planes, hs, ws, rows, b, out_h, out_w, patch, noise_std, masking_prob,
+                                          seed, out, draws, S(stream)), "igi_tactile_augment_seeded");
 }
 
 static_assert(IGI_PCL_AUG_MAX_POINTS == igi::PCL_MAX_POINTS, "igi_ppo.h and pcl_augment.h disagree on the largest cloud");

@@ -44,6 +44,7 @@
 //   site 20        step   g              replaced index
 //   site 21        step   env * 4 + o    cloud exempt from dropout (h >= thr(1 - no_dropout_prob))
 //   site 22        step   g              drop
+//   (sites 23..28: tactile_augment_seeded.h)
 // tests/pcl_augment_ref.py restates all of it in float64.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -13,7 +13,9 @@
 // (thread i owns pixels i, i + 256, ...), the mean is summed in a FIXED order -- each thread its own pixels in rising
 // order, a butterfly over the wave's 64 lanes, then the four waves' sums left to right -- the thread rewrites its own
 // pixels, and after one barrier the rotated gather reads LDS.  No atomics, no workspace: the output is a pure function of
-// the arguments.  An image with neither reads global memory directly.
+// the arguments.  An image with neither reads global memory directly.  That per-image body is tac_image, which
+// k_tactile_augment_seeded runs too (tactile_augment_seeded.h: the online student's step, every parameter hashed from one
+// seed).
 #pragma once
 #include "aug_pixel.h"
 
@@ -31,30 +33,22 @@ struct TactileAugArgs {
   int planes;
 };
 
-// grid (images = B * planes)
-__global__ __launch_bounds__(256) void k_tactile_augment(const TactileAugArgs a) {
-  __shared__ float win[TAC_MAX_PIXELS];
-  __shared__ float wave_sum[4];
-  const AugShape& c = a.c;
-  const long long image = blockIdx.x;                  // b * planes + plane
-  const long long b = image / a.planes;
-  const int plane = (int)(image - b * a.planes);
+// One image by the whole workgroup: the window at (top, left) of the stored plane `src` -> jitter -> rotation -> noise ->
+// keep_of (where `masked`) -> output plane number `image`.  `win` is the workgroup's LDS window of TAC_MAX_PIXELS floats,
+// `wave_sum` its four floats.  Every argument but the thread's number is uniform over the workgroup.
+template <class Keep>
+__device__ __forceinline__ void tac_image(const AugShape& c, const float* __restrict__ src, bool live, float* __restrict__ dst,
+                                          long long image, long long top, long long left, bool jit, float jb, float jc,
+                                          float ang, bool masked, float* __restrict__ win, float* __restrict__ wave_sum,
+                                          Keep keep_of) {
   const int W = c.out_w, H = c.out_h, P = H * W;
   const int tid = (int)threadIdx.x;
-  // per-image parameters: uniform over the workgroup
-  const int* __restrict__ prm = a.params + image * TAC_PARAM_WORDS;
-  const long long top = prm[0], left = prm[1];
-  const bool jit = prm[2] != 0;
-  const float jb = __int_as_float(prm[3]), jc = __int_as_float(prm[4]);
-  const AugRot r = aug_rot(__int_as_float(prm[5]), W, H);
-  const long long row = c.rows[b];
-  const bool live = row >= 0 && row < c.N;
-  const float* __restrict__ src = a.src + (live ? row * a.planes + plane : 0) * ((long long)c.Hs * c.Ws);
+  const AugRot r = aug_rot(ang, W, H);
   const int nq = H * c.qpr;
 
   if (!jit && !r.on) {                                 // the window of the stored frame, as it is
-    aug_rows(c, a.dst, image, true, TAC_NOISE_PLANE, tid, nq,
-             [&](int x, int y) { return aug_frame_read(src, c, live, y + top, x + left); });
+    aug_rows_keep(c, dst, image, masked, TAC_NOISE_PLANE, tid, nq,
+                  [&](int x, int y) { return aug_frame_read(src, c, live, y + top, x + left); }, keep_of);
     return;
   }
   float part = 0.f;
@@ -76,10 +70,28 @@ __global__ __launch_bounds__(256) void k_tactile_augment(const TactileAugArgs a)
     for (int p = tid; p < P; p += 256) win[p] = fminf(fmaxf((win[p] - m) * jc + m, 0.f), 1.f);   // the thread's own pixels
   }
   __syncthreads();
-  aug_rows(c, a.dst, image, true, TAC_NOISE_PLANE, tid, nq, [&](int x, int y) {
+  aug_rows_keep(c, dst, image, masked, TAC_NOISE_PLANE, tid, nq, [&](int x, int y) {
     int wx, wy;
     return aug_window_pos(r, W, H, x, y, wx, wy) ? win[wy * W + wx] : 0.f;
-  });
+  }, keep_of);
+}
+
+// grid (images = B * planes)
+__global__ __launch_bounds__(256) void k_tactile_augment(const TactileAugArgs a) {
+  __shared__ float win[TAC_MAX_PIXELS];
+  __shared__ float wave_sum[4];
+  const AugShape& c = a.c;
+  const long long image = blockIdx.x;                  // b * planes + plane
+  const long long b = image / a.planes;
+  const int plane = (int)(image - b * a.planes);
+  // per-image parameters: uniform over the workgroup
+  const int* __restrict__ prm = a.params + image * TAC_PARAM_WORDS;
+  const long long row = c.rows[b];
+  const bool live = row >= 0 && row < c.N;
+  const float* __restrict__ src = a.src + (live ? row * a.planes + plane : 0) * ((long long)c.Hs * c.Ws);
+  const unsigned char* __restrict__ keep = c.keep ? c.keep + image * ((long long)c.gh * c.gw) : nullptr;
+  tac_image(c, src, live, a.dst, image, prm[0], prm[1], prm[2] != 0, __int_as_float(prm[3]), __int_as_float(prm[4]),
+            __int_as_float(prm[5]), keep != nullptr, win, wave_sum, [&](int cell) { return (float)keep[cell]; });
 }
 
 static int tactile_augment(const float* arena, int64_t n, int planes, int hs, int ws, const int64_t* rows, int64_t b,

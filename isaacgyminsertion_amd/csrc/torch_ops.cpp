@@ -395,6 +395,32 @@ Tensor tactile_augment(const Tensor& arena, const Tensor& rows, const Tensor& pa
   return out;
 }
 
+// ---- online distillation step (the same chain from the rollout storage's arena, every draw hashed from one seed)
+std::tuple<Tensor, c10::optional<Tensor>> tactile_augment_seeded(const Tensor& arena, const Tensor& rows, int64_t out_h,
+                                                                 int64_t out_w, int64_t patch, double noise_std,
+                                                                 double masking_prob, int64_t seed, bool want_draws) {
+  check(arena, "arena"); check(rows, "rows", at::kLong);
+  TORCH_CHECK(arena.dim() == 6 && arena.size(3) == 1 && arena.numel() > 0, "arena: expected (R, T, F, 1, Hs, Ws) non-empty, got ", arena.sizes());
+  TORCH_CHECK(rows.dim() == 1, "rows: expected 1 dimensions, got shape ", rows.sizes());
+  const int64_t R = arena.size(0), T = arena.size(1), F = arena.size(2), Hs = arena.size(4), Ws = arena.size(5);
+  const int64_t B = rows.numel(), n_img = B * T * F;
+  TORCH_CHECK(masking_prob >= 0 && masking_prob <= 1, "masking_prob: expected a value in [0, 1], got ", masking_prob);
+  TORCH_CHECK(!(masking_prob > 0) || patch >= 1, "patch: expected >= 1 with a masking_prob, got ", patch);
+  TORCH_CHECK(out_h >= 1 && out_h <= Hs, "out_h: expected 1..", Hs, " (the stored height), got ", out_h);
+  TORCH_CHECK(out_w >= 1 && out_w <= Ws, "out_w: expected 1..", Ws, " (the stored width), got ", out_w);
+  TORCH_CHECK(noise_std >= 0, "noise_std: expected >= 0, got ", noise_std);
+  TORCH_CHECK(rows.device() == arena.device(), "rows: all arguments must share one device");
+  Tensor out = at::empty({B, T, F, 1, out_h, out_w}, arena.options());
+  c10::optional<Tensor> draws;
+  if (want_draws) draws = at::empty({n_img, IGI_TACTILE_AUG_WORDS}, arena.options().dtype(at::kInt));
+  if (B == 0) return {out, draws};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(arena.device());
+  rc(igi_tactile_augment_seeded(fp(arena), R, (int)(T * F), (int)Hs, (int)Ws, rows.data_ptr<int64_t>(), B, (int)out_h, (int)out_w,
+                                (int)patch, (float)noise_std, masking_prob, (uint64_t)seed, fp(out),
+                                want_draws ? draws->data_ptr<int32_t>() : nullptr, stream_of(arena)), "igi_tactile_augment_seeded");
+  return {out, draws};
+}
+
 // ---- rollout (factory_utils.py:83-166: the environment's point-cloud augmentation, one launch on the learner's side)
 Tensor pcl_augment(const Tensor& clouds, at::IntArrayRef points, const Tensor& episode, at::ArrayRef<double> params,
                    int64_t seed_episode, int64_t seed_step) {
@@ -457,6 +483,7 @@ TORCH_LIBRARY(mi355ppo, m) {
   m.def("pointnet_max_fwd(Tensor x, Tensor params) -> (Tensor, Tensor)");
   m.def("pointnet_max_bwd(Tensor x, Tensor params, Tensor dy, Tensor idx) -> Tensor");
   m.def("tactile_augment(Tensor arena, Tensor rows, Tensor params, Tensor? keep, int out_h, int out_w, int patch, float noise_std, int seed) -> Tensor");
+  m.def("tactile_augment_seeded(Tensor arena, Tensor rows, int out_h, int out_w, int patch, float noise_std, float masking_prob, int seed, bool want_draws) -> (Tensor, Tensor?)");
   m.def("pcl_augment(Tensor clouds, int[] points, Tensor episode, float[] params, int seed_episode, int seed_step) -> Tensor");
 }
 
@@ -477,5 +504,6 @@ TORCH_LIBRARY_IMPL(mi355ppo, CompositeExplicitAutograd, m) {
   m.impl("pointnet_max_fwd", pointnet_max_fwd);
   m.impl("pointnet_max_bwd", pointnet_max_bwd);
   m.impl("tactile_augment", tactile_augment);
+  m.impl("tactile_augment_seeded", tactile_augment_seeded);
   m.impl("pcl_augment", pcl_augment);
 }

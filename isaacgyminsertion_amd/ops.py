@@ -1736,6 +1736,46 @@ def _(arena, rows, params, keep, out_h, out_w, patch, noise_std, seed):
     return arena.new_empty((rows.numel(), arena.shape[1], arena.shape[2], 1, out_h, out_w))
 
 
+@_op("tactile_augment_seeded(Tensor arena, Tensor rows, int out_h, int out_w, int patch, float noise_std, "
+     "float masking_prob, int seed, bool want_draws) -> (Tensor, Tensor?)")
+def tactile_augment_seeded(arena: Tensor, rows: Tensor, out_h: int, out_w: int, patch: int, noise_std: float,
+                           masking_prob: float, seed: int, want_draws: bool) -> Tuple[Tensor, Optional[Tensor]]:
+    """The tactile images of an online minibatch, augmented, in ONE launch from the rollout storage's arena with nothing drawn
+    on the host but ``seed`` (igi_tactile_augment_seeded; the chain of ``tactile_augment`` with the window at (0, 0)):
+    ``arena`` fp32 (R, T, F, 1, Hs, Ws), R = horizon * envs flat rows; ``rows`` int64 (B,) flat rows.  Every image's jitter,
+    angle and -- with ``masking_prob`` > 0 -- keep grid of ``patch`` x ``patch`` cells is the counter hash of ``seed`` at the
+    sites of csrc/tactile_augment_seeded.h; ``noise_std`` > 0 adds the hash-drawn Gaussian noise of the same seed -> fp32
+    (B, T, F, 1, out_h, out_w) and, with ``want_draws``, int32 (B*T*F, 6) in the layout of ``tactile_augment``'s ``params``
+    (else None).  A window of more than 8192 pixels is refused.  The inputs are data: no autograd."""
+    _check_layout(arena, "arena", torch.float32, 6)
+    _check_layout(rows, "rows", torch.int64, 1)
+    R, T, Fg, ch, Hs, Ws = arena.shape
+    if ch != 1 or arena.numel() == 0:
+        raise RuntimeError(f"arena: expected (R, T, F, 1, Hs, Ws) non-empty, got {tuple(arena.shape)}")
+    if not 0 <= masking_prob <= 1:
+        raise RuntimeError(f"masking_prob: expected a value in [0, 1], got {masking_prob}")
+    if masking_prob > 0 and patch < 1:
+        raise RuntimeError(f"patch: expected >= 1 with a masking_prob, got {patch}")
+    B = rows.numel()
+    dev = _check_augment_args(out_h, out_w, Hs, Ws, noise_std, None, patch, B * T * Fg, ((arena, "arena"), (rows, "rows")))
+    out = torch.empty((B, T, Fg, 1, out_h, out_w), dtype=torch.float32, device=dev)
+    draws = torch.empty((B * T * Fg, TACTILE_AUG_WORDS), dtype=torch.int32, device=dev) if want_draws else None
+    if B == 0:
+        return out, draws
+    with torch.cuda.device(dev):
+        _rc(_lib.lib().igi_tactile_augment_seeded(_p(arena), R, T * Fg, Hs, Ws, _p(rows), B, out_h, out_w, patch, noise_std,
+                                                  masking_prob, C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), _p(out), _p(draws),
+                                                  _stream(arena)), "igi_tactile_augment_seeded")
+    return out, draws
+
+
+@_fake("tactile_augment_seeded")
+def _(arena, rows, out_h, out_w, patch, noise_std, masking_prob, seed, want_draws):
+    n = rows.numel()
+    return (arena.new_empty((n, arena.shape[1], arena.shape[2], 1, out_h, out_w)),
+            arena.new_empty((n * arena.shape[1] * arena.shape[2], TACTILE_AUG_WORDS), dtype=torch.int32) if want_draws else None)
+
+
 PCL_AUG_MAX_POINTS = 4096     # IGI_PCL_AUG_MAX_POINTS: per object
 PCL_AUG_MAX_OBJECTS = 4
 PCL_AUG_PARAMS = _lib.PclAugmentParams.FIELDS    # the order of ``params``: struct igi_pcl_augment_params, field for field
@@ -1879,4 +1919,4 @@ OP_NAMES = ["gae_advnorm", "ppo_minibatch_fwd_bwd", "ppo_clip_adam", "ppo_update
             "bc_loss_fwd_bwd", "bc_loss", "bc_loss_value_grad", "gemm_f32", "linear", "linear_bwd", "mlp_fwd", "mlp_bwd", "tactile_cnn_fwd", "tactile_cnn_bwd", "spatial_softargmax_fwd", "spatial_softargmax_bwd",
             "pointnet_max_fwd", "pointnet_max_bwd", "pointnet_max_fwd_multi", "pointnet_max_bwd_multi", "depth_backbone_fwd", "depth_backbone_bwd", "token_encoder_fwd",
             "token_encoder_bwd", "gather_rows", "cat_cols", "split_cols", "image_pair_augment",
-            "tactile_augment", "pcl_augment"]
+            "tactile_augment", "tactile_augment_seeded", "pcl_augment"]

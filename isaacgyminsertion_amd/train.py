@@ -9,6 +9,7 @@
     python -m isaacgyminsertion_amd.train train.ppo.kl_early_stop=True train.ppo.kl_threshold=0.008
     python -m isaacgyminsertion_amd.train train.algo=ExtrinsicAdapt offline_train.only_bc=False \\
         offline_train.train.latent_loss=True offline_train.train.latent_scale=0.5
+    python -m isaacgyminsertion_amd.train train.algo=ExtrinsicAdapt offline_train.tactile_augment_online=fused
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m isaacgyminsertion_amd.train train.ppo.multi_gpu=True
 
 rank / device / seed selection, ``offline_training`` -> ``Runner.run()``, environment construction, the
