@@ -301,6 +301,15 @@ int igi_teacher_apply_ks(const igi_teacher_cfg* cfg, const igi_teacher_state* st
 int igi_teacher_update_ks(const igi_teacher_cfg* cfg, const igi_rollout* ro, const igi_teacher_state* st,
                           const igi_kl_stop* ks, int64_t adam_t0, igi_stream_t stream);
 
+/* The packed configuration of the mi355ppo ops, (int[] icfg, float[] fcfg) (the layout is written once, in
+ * csrc/teacher_cfg.h), decoded and validated: fills *cfg; with ks != NULL also ks->kl_early_stop / kl_threshold from the
+ * early-stopping tail (zeroed when the lists carry none; stop_state stays NULL, the caller owns that tensor), with
+ * ks == NULL a list carrying the tail is refused for its length.  Host only, no GPU work.  Returns the number of optimizer
+ * steps the stop record covers (the argument of IGI_STOP_STATE_WORDS; 0 without a tail), or IGI_E_BADARG with the
+ * specific reason in igi_last_error(). */
+int64_t igi_teacher_cfg_unpack(const int64_t* icfg, int n_int, const double* fcfg, int n_float, igi_teacher_cfg* cfg,
+                               igi_kl_stop* ks);
+
 /* Latent-gradient fusion of the teacher backward (default ON; IGI_LATZ_FUSE=0 in the environment starts it off;
  * profiles/r06_latz_ab.log): the backward of env_mlp's last (8-wide) layer -- d(latent) from the first trunk layer's row dots,
  * its rank-8 weight / bias gradient and dZ of the 128-wide layer below (autograd of models_split.py:185-232 as called from
@@ -481,6 +490,8 @@ int igi_distill_loss(const float* mu, const float* teacher_actions, const float*
  * writes dlatent (rows, latent_dim) = d/d latent of a loss with gradient dmu (rows, act).  No weight gradient.
  * ---------------------------------------------------------------------------------------- */
 int igi_actor_latent_saved_width(const igi_teacher_cfg* cfg);
+/* latent_dim above: the width of the latent igi_teacher_infer[_contacts] writes and of dlatent; 0 for a cfg the library refuses */
+int igi_teacher_latent_width(const igi_teacher_cfg* cfg);
 int igi_actor_latent_forward(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* obs_n,
                              const float* latent, int latent_dim, int64_t rows, float* mu, float* hsave,
                              igi_stream_t stream);

@@ -133,6 +133,9 @@ _EXPORTS = {
     "igi_distill_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "igi_actor_latent_saved_width": (C.c_int, [C.POINTER(TeacherCfg)]),
+    "igi_teacher_latent_width": (C.c_int, [C.POINTER(TeacherCfg)]),
+    "igi_teacher_cfg_unpack": (C.c_int64, [C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_double), C.c_int,
+                                           C.POINTER(TeacherCfg), C.POINTER(KlStop)]),
     "igi_actor_latent_forward": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(TeacherState), C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "igi_actor_latent_backward": (C.c_int, [C.POINTER(TeacherCfg), C.POINTER(TeacherState), C.c_void_p, C.c_void_p,

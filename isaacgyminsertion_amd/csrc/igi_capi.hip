@@ -11,6 +11,7 @@
 #include "pointnet.h"
 #include "tactile.h"
 #include "teacher.h"
+#include "teacher_cfg.h"
 #include "linear.h"
 #include "mlp_chain.h"
 #include "mlp_fwd.h"
@@ -215,6 +216,17 @@ int igi_actor_latent_saved_width(const igi_teacher_cfg* cfg) {
   igi::TeacherPlan p;
   if (igi::make_plan(cfg, &p)) return 0;
   return igi::actor_latent_saved_width(p);
+}
+
+int igi_teacher_latent_width(const igi_teacher_cfg* cfg) {
+  igi::TeacherPlan p;
+  if (igi::make_plan(cfg, &p)) return 0;
+  return p.xw - p.obs;
+}
+
+int64_t igi_teacher_cfg_unpack(const int64_t* icfg, int n_int, const double* fcfg, int n_float, igi_teacher_cfg* cfg,
+                               igi_kl_stop* ks) {
+  return igi_teacher_cfg_decode(icfg, n_int, fcfg, n_float, cfg, ks, g_err, sizeof(g_err));
 }
 
 int igi_actor_latent_forward(const igi_teacher_cfg* cfg, const igi_teacher_state* st, const float* obs_n,

@@ -13,7 +13,6 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/library.h>
 
-#include <cstring>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -50,39 +49,23 @@ float* fp(const Tensor& t) { return t.data_ptr<float>(); }
 float* fpo(const c10::optional<Tensor>& t) { return t.has_value() && t->defined() ? t->data_ptr<float>() : nullptr; }
 
 // ---- teacher marshalling: (int[] icfg, float[] fcfg) <-> struct igi_teacher_cfg, tensor lists <-> the structs
-igi_teacher_cfg unpack_cfg(at::IntArrayRef ic, at::ArrayRef<double> fc) {
-  constexpr int M = IGI_MAX_LAYERS;
-  // the adaptive learning-rate schedule appends ONE int (lr_schedule) and three floats (kl_threshold, lr_min, lr_max)
-  const bool sched = fc.size() == 15;
-  const int ni = (int)ic.size() - (sched ? 1 : 0);
-  TORCH_CHECK((ni == 8 + 2 * M || ni == 10 + 2 * M || ni == 11 + 2 * M) && (fc.size() == 12 || sched), "teacher cfg: expected ",
-              8 + 2 * M, " (", 10 + 2 * M, " with a shared trunk, ", 11 + 2 * M, " with contacts) ints and 12 floats (one more int and 15 floats with the adaptive "
-              "learning-rate schedule), got ", ic.size(), " and ", fc.size());
+// The lists are decoded by the library (igi_teacher_cfg_unpack: the layout and every check live in csrc/teacher_cfg.h).
+// With `ks`, KL early stopping may ride behind everything else in the three lists of ppo_minibatch_fwd_bwd, ppo_clip_adam
+// and ppo_update (ops.py pack_stop): one trailing int, one trailing float, one trailing state tensor (stop_state, int32).
+// Its tensor is checked here and taken off `st`; ks->kl_early_stop tells whether it was there.
+igi_teacher_cfg unpack_cfg(at::IntArrayRef ic, at::ArrayRef<double> fc, at::TensorList* st = nullptr, igi_kl_stop* ks = nullptr) {
   igi_teacher_cfg c;
-  std::memset(&c, 0, sizeof(c));
-  if (sched) {
-    c.lr_schedule = (int32_t)ic[ni]; c.kl_threshold = fc[12]; c.lr_min = fc[13]; c.lr_max = fc[14];
-    TORCH_CHECK(c.lr_schedule == 1 && c.kl_threshold > 0 && c.lr_min > 0 && c.lr_max >= c.lr_min,
-                "teacher cfg: the schedule fields need lr_schedule == 1, kl_threshold > 0 and 0 < lr_min <= lr_max");
-  }
-  c.obs_dim = (int32_t)ic[0]; c.priv_dim = (int32_t)ic[1]; c.act_dim = (int32_t)ic[2]; c.n_priv_layers = (int32_t)ic[3];
-  for (int i = 0; i < M; ++i) { c.priv_units[i] = (int32_t)ic[4 + i]; c.units[i] = (int32_t)ic[5 + M + i]; }
-  c.n_layers = (int32_t)ic[4 + M];
-  c.num_envs = (int32_t)ic[5 + 2 * M]; c.horizon = (int32_t)ic[6 + 2 * M]; c.mini_epochs = (int32_t)ic[7 + 2 * M];
-  if (ni == 11 + 2 * M) {   // contact mode (ops.py pack_cfg)
-    c.contact_points = (int32_t)ic[8 + 2 * M]; c.contact_emb = (int32_t)ic[9 + 2 * M]; c.only_contact = (int32_t)ic[10 + 2 * M];
-    TORCH_CHECK(c.contact_points >= 1, "teacher cfg: the contact fields need contact_points >= 1");
-  }
-  if (ni == 10 + 2 * M) {   // shared actor-critic trunk (ops.py pack_cfg): two trailing ints, always (1, 0)
-    c.shared_parameters = (int32_t)ic[8 + 2 * M];
-    TORCH_CHECK(c.shared_parameters == 1 && ic[9 + 2 * M] == 0, "teacher cfg: the shared-trunk fields must be (1, 0)");
-  }
-  c.gamma = fc[0]; c.tau = fc[1]; c.lr = fc[2]; c.beta1 = fc[3]; c.beta2 = fc[4]; c.adam_eps = fc[5];
-  c.e_clip = (float)fc[6]; c.critic_coef = (float)fc[7]; c.entropy_coef = (float)fc[8]; c.bounds_loss_coef = (float)fc[9];
-  c.grad_norm = (float)fc[10]; c.rms_eps = (float)fc[11];
-  TORCH_CHECK(c.obs_dim >= 1 && c.priv_dim >= 1 && c.act_dim >= 1 && c.num_envs >= 1 && c.horizon >= 1 && c.mini_epochs >= 1 &&
-                  c.n_layers >= 1 && c.n_layers <= M && c.n_priv_layers >= 1 && c.n_priv_layers <= M,
-              "teacher cfg: non-positive dimension or unsupported layer count");
+  const int64_t steps = igi_teacher_cfg_unpack(ic.data(), (int)ic.size(), fc.data(), (int)fc.size(), &c, ks);
+  TORCH_CHECK(steps >= 0, igi_last_error());
+  if (!ks || !ks->kl_early_stop) return c;
+  TORCH_CHECK(st->size() >= 2, "teacher cfg: too short for the early-stopping tail");
+  const Tensor& stop = st->back();
+  *st = st->slice(0, st->size() - 1);
+  check(stop, "state.stop_state", at::kInt);
+  TORCH_CHECK(stop.device() == (*st)[0].device(), "state.stop_state: all arguments must share one device");
+  TORCH_CHECK(stop.numel() == IGI_STOP_STATE_WORDS(steps), "state.stop_state: expected ", IGI_STOP_STATE_WORDS(steps),
+              " int32 words, got ", stop.numel());
+  ks->stop_state = stop.data_ptr<int32_t>();
   return c;
 }
 
@@ -125,32 +108,6 @@ igi_teacher_state state_struct(at::TensorList st, const igi_teacher_cfg& c) {
   return s;
 }
 
-// KL early stopping rides behind everything else in the three lists of ppo_minibatch_fwd_bwd, ppo_clip_adam and
-// ppo_update (ops.py pack_stop): one trailing int (kl_early_stop = 1), one trailing float (kl_threshold), one trailing
-// state tensor (stop_state, int32).  13 or 16 floats carry it; lists of today's lengths mean "off".  Takes the tail off
-// the three lists and returns whether it was there.
-bool split_stop(at::TensorList& st, at::IntArrayRef& ic, at::ArrayRef<double>& fc, igi_kl_stop* ks) {
-  std::memset(ks, 0, sizeof(*ks));
-  if (fc.size() != 13 && fc.size() != 16) return false;
-  TORCH_CHECK(ic.size() >= 1 && st.size() >= 1 && ic.back() == 1 && fc.back() > 0,
-              "teacher cfg: the early-stopping tail needs kl_early_stop == 1, kl_threshold > 0 and the stop_state tensor "
-              "behind the state list");
-  constexpr int M = IGI_MAX_LAYERS;
-  ks->kl_early_stop = 1; ks->kl_threshold = fc.back();
-  const Tensor& stop = st.back();
-  st = st.slice(0, st.size() - 1); ic = ic.slice(0, ic.size() - 1); fc = fc.slice(0, fc.size() - 1);
-  TORCH_CHECK((int)ic.size() >= 8 + 2 * M && st.size() >= 1, "teacher cfg: too short for the early-stopping tail");
-  const int64_t n_env = ic[5 + 2 * M], hor = ic[6 + 2 * M], E = ic[7 + 2 * M];
-  TORCH_CHECK(n_env >= 1 && hor >= 1 && E >= 1 && n_env * hor >= E, "teacher cfg: non-positive dimension or unsupported layer count");
-  const int64_t B = n_env * hor, steps = E * (B / (B / E));
-  check(stop, "state.stop_state", at::kInt);
-  TORCH_CHECK(stop.device() == st[0].device(), "state.stop_state: all arguments must share one device");
-  TORCH_CHECK(stop.numel() == IGI_STOP_STATE_WORDS(steps), "state.stop_state: expected ", IGI_STOP_STATE_WORDS(steps),
-              " int32 words, got ", stop.numel());
-  ks->stop_state = stop.data_ptr<int32_t>();
-  return true;
-}
-
 igi_rollout rollout_struct(at::TensorList ro, const igi_teacher_cfg& c, const at::Device& dev) {
   static const char* names[10] = {"obses", "priv_info", "rewards", "values", "neglogpacs", "dones", "actions", "mus",
                                   "sigmas", "last_values"};
@@ -189,8 +146,8 @@ void gae_advnorm(at::TensorList rollout, at::TensorList state, at::IntArrayRef i
 void ppo_minibatch_fwd_bwd(at::TensorList rollout, at::TensorList state, at::IntArrayRef icfg, at::ArrayRef<double> fcfg,
                            int64_t mb_index, int64_t step_slot, int64_t phase) {
   igi_kl_stop ks;
-  const bool stopping = split_stop(state, icfg, fcfg, &ks);
-  const igi_teacher_cfg c = unpack_cfg(icfg, fcfg);
+  const igi_teacher_cfg c = unpack_cfg(icfg, fcfg, &state, &ks);
+  const bool stopping = ks.kl_early_stop != 0;
   const igi_teacher_state s = state_struct(state, c);
   const igi_rollout r = rollout_struct(rollout, c, state[0].device());
   TORCH_CHECK(phase >= -1 && phase <= 1, "phase: expected -1, 0 or 1, got ", phase);
@@ -204,8 +161,8 @@ void ppo_minibatch_fwd_bwd(at::TensorList rollout, at::TensorList state, at::Int
 void ppo_clip_adam(at::TensorList state, at::IntArrayRef icfg, at::ArrayRef<double> fcfg, int64_t step_slot, int64_t adam_t,
                    double grad_scale) {
   igi_kl_stop ks;
-  const bool stopping = split_stop(state, icfg, fcfg, &ks);
-  const igi_teacher_cfg c = unpack_cfg(icfg, fcfg);
+  const igi_teacher_cfg c = unpack_cfg(icfg, fcfg, &state, &ks);
+  const bool stopping = ks.kl_early_stop != 0;
   const igi_teacher_state s = state_struct(state, c);
   c10::hip::HIPGuardMasqueradingAsCUDA g(state[0].device());
   if (stopping) rc(igi_teacher_apply_ks(&c, &s, &ks, (int)step_slot, adam_t, (float)grad_scale, stream_of(state[0])), "igi_teacher_apply_ks");
@@ -213,8 +170,8 @@ void ppo_clip_adam(at::TensorList state, at::IntArrayRef icfg, at::ArrayRef<doub
 }
 void ppo_update(at::TensorList rollout, at::TensorList state, at::IntArrayRef icfg, at::ArrayRef<double> fcfg, int64_t adam_t0) {
   igi_kl_stop ks;
-  const bool stopping = split_stop(state, icfg, fcfg, &ks);
-  const igi_teacher_cfg c = unpack_cfg(icfg, fcfg);
+  const igi_teacher_cfg c = unpack_cfg(icfg, fcfg, &state, &ks);
+  const bool stopping = ks.kl_early_stop != 0;
   const igi_teacher_state s = state_struct(state, c);
   const igi_rollout r = rollout_struct(rollout, c, state[0].device());
   c10::hip::HIPGuardMasqueradingAsCUDA g(state[0].device());

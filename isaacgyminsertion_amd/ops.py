@@ -15,6 +15,7 @@ workspace) is passed as tensor lists in the field order of ``struct igi_rollout`
 declared mutated in the schema.
 """
 import ctypes as C
+import functools
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -143,41 +144,20 @@ def pack_cfg(cfg):
     return [int(x) for x in icfg], [float(x) for x in fcfg]
 
 
-def _unpack_cfg(icfg, fcfg):
-    M = _lib.IGI_MAX_LAYERS
-    sched = len(fcfg) == 15      # + lr_schedule | kl_threshold, lr_min, lr_max
-    if sched:
-        icfg, fcfg, tail = icfg[:-1], fcfg[:12], (icfg[-1], *fcfg[12:])
-    if len(icfg) not in (8 + 2 * M, 10 + 2 * M, 11 + 2 * M) or len(fcfg) != 12:
-        raise RuntimeError(f"teacher cfg: expected {8 + 2 * M} ({10 + 2 * M} with a shared trunk, {11 + 2 * M} with contacts) ints and 12 floats (one "
-                           f"more int and 15 floats with the adaptive learning-rate schedule), "
-                           f"got {len(icfg) + sched} and {len(fcfg) + 3 * sched}")
+def _decode(icfg, fcfg, ks=None):
+    """The two lists -> struct igi_teacher_cfg through the library's decoder (csrc/teacher_cfg.h holds the layout and every
+    check); with ``ks`` the early-stopping tail is allowed and fills it.  -> (cfg, optimizer steps of the stop record)"""
     c = _lib.TeacherCfg()
-    if sched:
-        c.lr_schedule, c.kl_threshold, c.lr_min, c.lr_max = tail
-        if c.lr_schedule != 1 or not c.kl_threshold > 0 or not 0 < c.lr_min <= c.lr_max:
-            raise RuntimeError("teacher cfg: the schedule fields need lr_schedule == 1, kl_threshold > 0 and "
-                               "0 < lr_min <= lr_max")
-    c.obs_dim, c.priv_dim, c.act_dim, c.n_priv_layers = icfg[0:4]
-    for i in range(M):
-        c.priv_units[i] = icfg[4 + i]
-        c.units[i] = icfg[5 + M + i]
-    c.n_layers = icfg[4 + M]
-    c.num_envs, c.horizon, c.mini_epochs = icfg[5 + 2 * M:8 + 2 * M]
-    if len(icfg) == 11 + 2 * M:
-        c.contact_points, c.contact_emb, c.only_contact = icfg[8 + 2 * M:11 + 2 * M]
-        if c.contact_points < 1:
-            raise RuntimeError("teacher cfg: the contact fields need contact_points >= 1")
-    if len(icfg) == 10 + 2 * M:
-        c.shared_parameters = icfg[8 + 2 * M]
-        if c.shared_parameters != 1 or icfg[9 + 2 * M] != 0:
-            raise RuntimeError("teacher cfg: the shared-trunk fields must be (1, 0)")
-    (c.gamma, c.tau, c.lr, c.beta1, c.beta2, c.adam_eps, c.e_clip, c.critic_coef, c.entropy_coef,
-     c.bounds_loss_coef, c.grad_norm, c.rms_eps) = fcfg
-    if min(c.obs_dim, c.priv_dim, c.act_dim, c.num_envs, c.horizon, c.mini_epochs) < 1 or \
-            not (1 <= c.n_layers <= M) or not (1 <= c.n_priv_layers <= M):
-        raise RuntimeError("teacher cfg: non-positive dimension or unsupported layer count")
-    return c
+    L = _lib.lib()
+    steps = L.igi_teacher_cfg_unpack((C.c_int64 * len(icfg))(*icfg), len(icfg), (C.c_double * len(fcfg))(*fcfg),
+                                     len(fcfg), C.byref(c), None if ks is None else C.byref(ks))
+    if steps < 0:
+        raise RuntimeError(L.igi_last_error().decode())
+    return c, steps
+
+
+def _unpack_cfg(icfg, fcfg):
+    return _decode(icfg, fcfg)[0]
 
 
 def pack_stop(icfg, fcfg, state, kl_threshold, stop_state):
@@ -188,50 +168,54 @@ def pack_stop(icfg, fcfg, state, kl_threshold, stop_state):
 
 
 def _split_stop(state, icfg, fcfg):
-    """(state, icfg, fcfg, struct igi_kl_stop or None): takes the early-stopping tail off the three lists (13 or 16
-    floats carry it; 12 or 15 do not) and validates it."""
-    if len(fcfg) not in (13, 16):
-        return state, icfg, fcfg, None
-    if len(icfg) < 1 or len(state) < 1 or icfg[-1] != 1 or not fcfg[-1] > 0:
-        raise RuntimeError("teacher cfg: the early-stopping tail needs kl_early_stop == 1, kl_threshold > 0 and the "
-                           "stop_state tensor behind the state list")
+    """(state, icfg, fcfg, struct igi_kl_stop or None): takes the early-stopping tail off the three lists, where the
+    decoder finds one, and checks its tensor."""
     ks = _lib.KlStop()
-    ks.kl_early_stop, ks.kl_threshold = 1, float(fcfg[-1])
-    stop, state, icfg, fcfg = state[-1], state[:-1], icfg[:-1], fcfg[:-1]
-    M = _lib.IGI_MAX_LAYERS
-    if len(icfg) < 8 + 2 * M or len(state) < 1:
+    _, steps = _decode(icfg, fcfg, ks)
+    if not ks.kl_early_stop:
+        return state, icfg, fcfg, None
+    if len(state) < 2:
         raise RuntimeError("teacher cfg: too short for the early-stopping tail")
-    n_env, hor, E = (int(x) for x in icfg[5 + 2 * M:8 + 2 * M])
-    if min(n_env, hor, E) < 1 or n_env * hor < E:
-        raise RuntimeError("teacher cfg: non-positive dimension or unsupported layer count")
-    B = n_env * hor
-    steps = E * (B // (B // E))
+    stop = state[-1]
+    state, icfg, fcfg = (x[:-1] for x in (state, icfg, fcfg))
     _check(stop, "state.stop_state", dtype=torch.int32, shape=(_lib.stop_state_words(steps),), device=state[0].device)
     ks.stop_state = stop.data_ptr()
-    if len(fcfg) == 15 and float(fcfg[12]) != ks.kl_threshold:      # one threshold: the scheduler's is the stop's
-        raise RuntimeError(f"teacher cfg: the early-stopping tail's kl_threshold {ks.kl_threshold} differs from the "
-                           f"adaptive schedule's {fcfg[12]}")
     return state, icfg, fcfg, ks
 
 
 _STATE_CACHE = {}
 
 
-def _teacher_args(state, icfg, fcfg):
-    """(cfg struct, state struct, device) for a teacher op call.  The full validation of the sixteen state tensors and
-    the two library queries (parameter count, workspace size) run once per distinct (configuration, tensor set); a
-    call with the same configuration values and the same tensors (address, size, dtype) reuses the result -- the
-    policy-inference op runs once per environment step."""
+@functools.lru_cache(maxsize=64)
+def _cfg_widths(icfg, fcfg):
+    """(cfg struct, latent width, row width of ``actor_latent_fwd``'s saved activations) of the two lists, given as
+    tuples; the widths are those of the library's plan.  Host only, plain Python ints: the fake kernels come here too."""
+    cfg = _unpack_cfg(icfg, fcfg)
+    L = _lib.lib()
+    if L.igi_teacher_param_count(C.byref(cfg)) <= 0:
+        raise RuntimeError("teacher cfg rejected by the library: " + L.igi_last_error().decode())
+    return cfg, L.igi_teacher_latent_width(C.byref(cfg)), L.igi_actor_latent_saved_width(C.byref(cfg))
+
+
+def _teacher_args_w(state, icfg, fcfg):
+    """(cfg struct, state struct, device, latent width, saved width) for a teacher op call.  The decoding, the full
+    validation of the sixteen state tensors and the library queries (parameter count, workspace size, widths) run once
+    per distinct (configuration, tensor set); a call with the same configuration values and the same tensors (address,
+    size, dtype) reuses the result -- the policy-inference op runs once per environment step."""
     key = (tuple(icfg), tuple(fcfg), tuple((t.data_ptr(), t.numel(), t.dtype) for t in state))
     hit = _STATE_CACHE.get(key)
     if hit is not None:
         return hit
-    cfg = _unpack_cfg(icfg, fcfg)
+    cfg, lat_w, saved_w = _cfg_widths(key[0], key[1])
     st, dev = _state_struct(state, cfg)
     if len(_STATE_CACHE) > 64:
         _STATE_CACHE.clear()
-    _STATE_CACHE[key] = (cfg, st, dev)
-    return cfg, st, dev
+    hit = _STATE_CACHE[key] = (cfg, st, dev, lat_w, saved_w)
+    return hit
+
+
+def _teacher_args(state, icfg, fcfg):
+    return _teacher_args_w(state, icfg, fcfg)[:3]
 
 
 def _state_struct(state, cfg, need=()):
@@ -462,18 +446,10 @@ def actor_critic_infer(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Seque
 
 @_fake("actor_critic_infer")
 def _(state, icfg, fcfg, obs, priv, normalize, want_latent):
-    M = _lib.IGI_MAX_LAYERS
-    act, lat = icfg[2], icfg[4 + icfg[3] - 1]
+    cfg = _cfg_widths(tuple(icfg), tuple(fcfg))[0]
     rows = obs.shape[0]
-    return (obs.new_empty(rows, act), obs.new_empty(rows, 1), obs.new_empty(rows if want_latent else 0, lat))
-
-
-def _latent_gt_width(icfg):
-    M = _lib.IGI_MAX_LAYERS
-    lat = icfg[4 + icfg[3] - 1]
-    if len(icfg) == 11 + 2 * M:
-        return icfg[9 + 2 * M] + (0 if icfg[10 + 2 * M] else lat)
-    return lat
+    return (obs.new_empty(rows, cfg.act_dim), obs.new_empty(rows, 1),
+            obs.new_empty(rows if want_latent else 0, cfg.priv_units[cfg.n_priv_layers - 1]))
 
 
 @_op("actor_critic_infer_contacts(Tensor(a!)[] state, int[] icfg, float[] fcfg, Tensor obs, Tensor priv, Tensor contacts, bool normalize, bool want_latent) -> (Tensor, Tensor, Tensor)")
@@ -483,7 +459,7 @@ def actor_critic_infer_contacts(state: Sequence[Tensor], icfg: Sequence[int], fc
     """actor_critic_infer for a teacher with ground-truth contacts (models_split.py:172-177): contacts (rows, P) raw;
     latent = latent_gt (rows, priv latent + contact embedding), or (rows, embedding) with only_contact
     -> igi_teacher_infer_contacts."""
-    cfg, st, dev = _teacher_args(state, icfg, fcfg)
+    cfg, st, dev, lat_w, _ = _teacher_args_w(state, icfg, fcfg)
     if cfg.contact_points < 1:
         raise RuntimeError("actor_critic_infer_contacts: the cfg has no contacts (use actor_critic_infer)")
     _check(obs, "obs", shape=(None, cfg.obs_dim), device=dev)
@@ -492,7 +468,7 @@ def actor_critic_infer_contacts(state: Sequence[Tensor], icfg: Sequence[int], fc
     _check(contacts, "contacts", shape=(rows, cfg.contact_points), device=dev)
     mu = torch.empty(rows, cfg.act_dim, dtype=torch.float32, device=dev)
     val = torch.empty(rows, 1, dtype=torch.float32, device=dev)
-    lat = torch.empty(rows if want_latent else 0, _latent_gt_width(icfg), dtype=torch.float32, device=dev)
+    lat = torch.empty(rows if want_latent else 0, lat_w, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _rc(_lib.lib().igi_teacher_infer_contacts(C.byref(cfg), C.byref(st), _p(obs), _p(priv), _p(contacts), rows,
                                                   1 if normalize else 0, _p(mu), _p(val),
@@ -503,15 +479,9 @@ def actor_critic_infer_contacts(state: Sequence[Tensor], icfg: Sequence[int], fc
 
 @_fake("actor_critic_infer_contacts")
 def _(state, icfg, fcfg, obs, priv, contacts, normalize, want_latent):
+    cfg, lat_w, _ = _cfg_widths(tuple(icfg), tuple(fcfg))
     rows = obs.shape[0]
-    return (obs.new_empty(rows, icfg[2]), obs.new_empty(rows, 1),
-            obs.new_empty(rows if want_latent else 0, _latent_gt_width(icfg)))
-
-
-def _actor_saved_width(icfg):
-    """ru4(u_0) + ... of the actor's layers: the row width of ``actor_latent_fwd``'s saved activations."""
-    M = _lib.IGI_MAX_LAYERS
-    return sum((int(icfg[5 + M + i]) + 3) & ~3 for i in range(int(icfg[4 + M])))
+    return (obs.new_empty(rows, cfg.act_dim), obs.new_empty(rows, 1), obs.new_empty(rows if want_latent else 0, lat_w))
 
 
 @_op("actor_latent_fwd(Tensor(a!)[] state, int[] icfg, float[] fcfg, Tensor obs, Tensor latent, bool save) -> (Tensor, Tensor)")
@@ -522,13 +492,13 @@ def actor_latent_fwd(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequenc
     normalised; latent (rows, W) with W the teacher's own extrinsic width.  ``save``: also the post-tanh activations of
     the actor's layers, (rows, sum of the layer widths rounded up to 4) -- the caller's tensor, for ``actor_latent_bwd``
     (empty otherwise).  Uses state.workspace as scratch -> igi_actor_latent_forward."""
-    cfg, st, dev = _teacher_args(state, icfg, fcfg)
+    cfg, st, dev, _, saved_w = _teacher_args_w(state, icfg, fcfg)
     rows = _check(obs, "obs", shape=(None, cfg.obs_dim), device=dev).shape[0]
     _check(latent, "latent", shape=(rows, None), device=dev)
     if rows < 1:
         raise RuntimeError("actor_latent_fwd: no rows")
     mu = torch.empty(rows, cfg.act_dim, dtype=torch.float32, device=dev)
-    saved = torch.empty(rows if save else 0, _actor_saved_width(icfg), dtype=torch.float32, device=dev)
+    saved = torch.empty(rows if save else 0, saved_w, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _rc(_lib.lib().igi_actor_latent_forward(C.byref(cfg), C.byref(st), _p(obs), _p(latent), int(latent.shape[1]), rows,
                                                 _p(mu), _p(saved) if save else None, _stream(obs)),
@@ -538,8 +508,9 @@ def actor_latent_fwd(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequenc
 
 @_fake("actor_latent_fwd")
 def _(state, icfg, fcfg, obs, latent, save):
+    cfg, _, saved_w = _cfg_widths(tuple(icfg), tuple(fcfg))
     rows = obs.shape[0]
-    return obs.new_empty(rows, icfg[2]), obs.new_empty(rows if save else 0, _actor_saved_width(icfg))
+    return obs.new_empty(rows, cfg.act_dim), obs.new_empty(rows if save else 0, saved_w)
 
 
 @_op("actor_latent_bwd(Tensor(a!)[] state, int[] icfg, float[] fcfg, Tensor saved, Tensor dmu) -> Tensor")
@@ -548,12 +519,12 @@ def actor_latent_bwd(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequenc
     """d/d latent of a loss whose gradient with respect to ``actor_latent_fwd``'s mu is ``dmu`` (rows, act), from that
     call's saved activations: the data-gradient chain through the frozen actor, no weight gradient
     -> igi_actor_latent_backward."""
-    cfg, st, dev = _teacher_args(state, icfg, fcfg)
+    cfg, st, dev, lat_w, saved_w = _teacher_args_w(state, icfg, fcfg)
     rows = _check(dmu, "dmu", shape=(None, cfg.act_dim), device=dev).shape[0]
-    _check(saved, "saved", shape=(rows, _actor_saved_width(icfg)), device=dev)
+    _check(saved, "saved", shape=(rows, saved_w), device=dev)
     if rows < 1:
         raise RuntimeError("actor_latent_bwd: no rows")
-    dlatent = torch.empty(rows, _latent_gt_width(icfg), dtype=torch.float32, device=dev)
+    dlatent = torch.empty(rows, lat_w, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _rc(_lib.lib().igi_actor_latent_backward(C.byref(cfg), C.byref(st), _p(saved), _p(dmu), rows, _p(dlatent),
                                                  _stream(dmu)), "igi_actor_latent_backward")
@@ -562,7 +533,7 @@ def actor_latent_bwd(state: Sequence[Tensor], icfg: Sequence[int], fcfg: Sequenc
 
 @_fake("actor_latent_bwd")
 def _(state, icfg, fcfg, saved, dmu):
-    return dmu.new_empty(dmu.shape[0], _latent_gt_width(icfg))
+    return dmu.new_empty(dmu.shape[0], _cfg_widths(tuple(icfg), tuple(fcfg))[1])
 
 
 @_op("rollout_policy_step_contacts(Tensor(a!)[] state, int[] icfg, float[] fcfg, Tensor obs, Tensor priv, Tensor contacts, bool normalize, Tensor noise, Tensor? rms_value, Tensor(b!)? obses_t, Tensor(c!)? priv_t, Tensor(k!)? contacts_t, Tensor(d!) actions_t, Tensor(e!) neglogp_t, Tensor(f!) values_t, Tensor(g!) mus_t, Tensor(h!) sigmas_t, Tensor(i!) actions_clamped, Tensor(j!) values_out) -> ()")

@@ -31,6 +31,8 @@ SHAPES = {
     "units48_40_24_L12": dict(DEFAULT, rows=37, units=(48, 40, 24), L=12),
 }
 GATED = [k for k, v in SHAPES.items() if v["units"] == (512, 256, 128)]
+# a shared trunk under the adaptive learning-rate schedule: one more int behind the shared pair in the packed cfg
+SHARED_ADAPTIVE = dict(DEFAULT, rows=33, shared=True, mb=128, lr_schedule="adaptive")
 _CACHE = {}
 
 
@@ -40,7 +42,7 @@ def _case(name):
         return _CACHE[name]
     from isaacgyminsertion_amd.algo.models.models_split import ActorCriticSplit
     from isaacgyminsertion_amd.teacher_native import TeacherEngine
-    s = SHAPES[name]
+    s = SHARED_ADAPTIVE if name == "shared_adaptive" else SHAPES[name]
     g = torch.Generator().manual_seed(sum(ord(c) for c in name))
     # the initialisation draws from the GLOBAL generator: seeded too, or every process tests another network (the fused
     # against chain comparison then moved between 2.9e-6 and 3.8e-6 at 300 rows from run to run, around its bound)
@@ -56,7 +58,8 @@ def _case(name):
     net = net.to(DEV)
     if s["mb"]:
         eng = TeacherEngine(s["mb"], 1, 1, units=list(s["units"]), priv_units=[256, 128, s["L"]], obs_dim=s["obs"],
-                            priv_dim=64, act_dim=s["act"], device=DEV, **net.engine_kwargs())
+                            priv_dim=64, act_dim=s["act"], device=DEV, lr_schedule=s.get("lr_schedule", "fixed"),
+                            **net.engine_kwargs())
         net.bind_flat_to(eng)
         net.attach_engine(eng)
     obs = torch.randn(s["rows"], s["obs"], generator=g)
@@ -166,6 +169,23 @@ def test_saved_activations_and_backward_match_float64(name):
     assert not net.act_with_grad({'obs': obs, 'latent': lat})[0].requires_grad
     with torch.no_grad():
         assert not net.act_with_grad({'obs': obs, 'latent': lat_g})[0].requires_grad
+
+
+def test_shared_trunk_under_the_adaptive_schedule_matches_float64():
+    """forward with saved activations, then the backward, at 33 rows: the bounds of the test above, and d/d latent as
+    wide as the teacher's extrinsic"""
+    net, obs, lat, dmu, ref = _case("shared_adaptive")
+    eng = net._infer_engine(torch.device(DEV))
+    assert eng.cfg.lr_schedule == 1 and eng.cfg.shared_parameters == 1
+    mu, saved = eng.actor_latent(obs, lat, True)
+    assert saved.shape == (33, 512 + 256 + 128)
+    np.testing.assert_allclose(mu.cpu().numpy(), ref["mu"].numpy(), atol=2e-6, rtol=1e-4)
+    for l, (h, h64) in enumerate(zip(_split_saved(saved, DEFAULT["units"]), ref["hs"])):
+        np.testing.assert_allclose(h.cpu().numpy(), h64.numpy(), atol=2e-6, rtol=1e-4, err_msg=f"h{l + 1}")
+    dlat = eng.actor_latent_backward(saved, dmu)
+    assert dlat.shape == (33, DEFAULT["L"])
+    r = ref["dlatent"].numpy()
+    np.testing.assert_allclose(dlat.cpu().numpy(), r, atol=1e-4 * np.abs(r).max(), rtol=1e-3)
 
 
 def test_launches():

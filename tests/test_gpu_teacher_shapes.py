@@ -64,10 +64,10 @@ def _problem(N, T, units, priv_units, obs_dim=15, P=0, E=0, only_contact=False, 
     return init, ro, perm
 
 
-def _engine(N, T, Ep, units, priv_units, init, perm, obs_dim=15, P=0, E=0, only_contact=False):
+def _engine(N, T, Ep, units, priv_units, init, perm, obs_dim=15, P=0, E=0, only_contact=False, **kw):
     from isaacgyminsertion_amd.teacher_native import TeacherEngine
     eng = TeacherEngine(N, T, Ep, units=units, priv_units=priv_units, perm=perm, obs_dim=obs_dim, contact_points=P,
-                        contact_emb=E, only_contact=only_contact)
+                        contact_emb=E, only_contact=only_contact, **kw)
     eng.load_params(init)
     return eng
 
@@ -256,23 +256,23 @@ INFER_CASES = {
 ROWS = 2 * 256 + 77      # larger than mb = 256 (the chunk loop), neither a multiple of 32 nor of mb
 
 
-def _infer_setup(case):
+def _infer_setup(case, rows=ROWS, **engine_kw):
     units, priv_units, obs_dim, P, E, oc = INFER_CASES[case]
     N, T, Ep = 64, 8, 2
     init, ro, perm = _problem(N, T, units, priv_units, obs_dim, P, E, oc, seed=77)
     g = torch.Generator().manual_seed(1000 + len(case))
     init["sigma"] = 0.3 * torch.randn(ACT, generator=g)
-    eng = _engine(N, T, Ep, units, priv_units, init, perm, obs_dim, P, E, oc)
+    eng = _engine(N, T, Ep, units, priv_units, init, perm, obs_dim, P, E, oc, **engine_kw)
     assert ROWS > eng.mb and ROWS % eng.mb and ROWS % 32
     # running statistics away from their initial (0, 1, 1)
     mean_o, var_o = 0.3 * torch.randn(obs_dim, generator=g).double(), (0.5 + torch.rand(obs_dim, generator=g)).double()
     mean_p, var_p = 0.3 * torch.randn(PRIV, generator=g).double(), (0.5 + torch.rand(PRIV, generator=g)).double()
     eng.rms_obs[:obs_dim], eng.rms_obs[obs_dim:2 * obs_dim] = mean_o.cuda(), var_o.cuda()
     eng.rms_priv[:PRIV], eng.rms_priv[PRIV:2 * PRIV] = mean_p.cuda(), var_p.cuda()
-    obs = 1.5 * torch.randn(ROWS, obs_dim, generator=g) + 0.2
-    priv = torch.randn(ROWS, PRIV, generator=g)
-    contacts = (torch.rand(ROWS, P, generator=g) < 0.2).float() if P else None
-    noise = torch.randn(ROWS, ACT, generator=g)
+    obs = 1.5 * torch.randn(rows, obs_dim, generator=g) + 0.2
+    priv = torch.randn(rows, PRIV, generator=g)
+    contacts = (torch.rand(rows, P, generator=g) < 0.2).float() if P else None
+    noise = torch.randn(rows, ACT, generator=g)
     p64 = {k: v.double() for k, v in init.items()}
 
     def norm64(x, mean, var):     # running_mean_std.py:91-92
@@ -300,6 +300,20 @@ def test_infer_off_the_default_widths_matches_float64(case, normalize):
     torch.cuda.synchronize()
     m, _, v, e = ref(normalize)
     assert lat.shape == (ROWS, E if oc else priv_units[-1] + E)
+    np.testing.assert_allclose(mu.cpu().numpy(), m.numpy(), atol=2e-6, rtol=1e-4)
+    np.testing.assert_allclose(val.cpu().numpy(), v.numpy(), atol=2e-5, rtol=1e-4)
+    np.testing.assert_allclose(lat.cpu().numpy(), e.numpy(), atol=2e-6, rtol=1e-4)
+
+
+def test_infer_contacts_under_the_adaptive_schedule_matches_float64():
+    """The schedule's extra int behind the contact fields must not change what the latent is: the same engine as
+    contacts_E16 built with lr_schedule="adaptive", 33 rows (one full 32-row block and a ragged row), the bounds above."""
+    eng, obs, priv, contacts, _, ref, (_, P, E, oc, priv_units) = _infer_setup("contacts_E16", rows=33, lr_schedule="adaptive")
+    assert eng.cfg.lr_schedule == 1 and P and not oc
+    mu, val, lat = eng.infer_contacts(obs, priv, contacts, want_latent=True, normalize=True)
+    torch.cuda.synchronize()
+    m, _, v, e = ref(True)
+    assert lat.shape == (33, priv_units[-1] + E)
     np.testing.assert_allclose(mu.cpu().numpy(), m.numpy(), atol=2e-6, rtol=1e-4)
     np.testing.assert_allclose(val.cpu().numpy(), v.numpy(), atol=2e-5, rtol=1e-4)
     np.testing.assert_allclose(lat.cpu().numpy(), e.numpy(), atol=2e-6, rtol=1e-4)

@@ -222,8 +222,8 @@ def test_shared_refusals():
 def test_cpp_registration_decodes_a_shared_cfg():
     """The C++ registration (csrc/torch_ops.cpp) in a child process (one process holds one registration of the namespace):
     its decoder takes the shared cfg, alone and under the schedule tail, as far as the CPU-tensor refusal behind it, and
-    refuses the malformed ones by name.  (The early-stopping tail's own tensor check runs ahead of the decoder: that
-    combination is decoded on the GPU, tests/test_gpu_shared_critic.py.)"""
+    refuses the malformed ones by name.  (Under the early-stopping tail the op is tests/test_gpu_shared_critic.py's; the
+    decoder itself takes that combination in tests/test_teacher_cfg_cpu.py.)"""
     lib = os.path.join(ROOT, "isaacgyminsertion_amd", "libigi_torch_ops.so")
     if not os.path.exists(lib):
         pytest.skip("libigi_torch_ops.so not built on this host (python -c 'import __graft_entry__ as g; g.build()')")
