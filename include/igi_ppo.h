@@ -818,6 +818,27 @@ int igi_tactile_augment_seeded(const float* arena, int64_t n, int planes, int hs
                                float* out, int32_t* draws, igi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The camera pair for the ONLINE student's distillation step (csrc/augment_seeded.h), ONE launch from the rollout storage's
+ * two time-major arenas to the two minibatch tensors, with nothing drawn on the host but `seed`:
+ *   img, seg  : fp32 [n][t][hs][ws] depth / mask arenas, n = horizon * envs flat rows; either may be NULL (absent: its planes
+ *               are not launched and its output is not looked at), not both; never written
+ *   rows      : [b] flat rows (the ones igi_gather_rows takes); one outside [0, n) reads as frames of zeros
+ *   the output is at the stored size (no crop).  Per (sample, tensor) one angle in +- max_rad radians shared by its t frames
+ *   (max_rad == 0: no rotation, no hash) and, with masking_prob > 0, per depth frame the keep value of every hs / patch x
+ *   ws / patch patch (kept with probability 1 - masking_prob) are the counter hash of (seed, site, element) at the sites
+ *   tabled in csrc/augment_seeded.h, every event an integer comparison.  Only the depth frames are masked
+ *   noise_std : as igi_image_pair_augment, from the same seed, on both tensors
+ *   out_img, out_seg : fp32 [b][t][hs][ws], no arena; hs * ws above 2^24: IGI_E_BADARG; more than 8192 patches per frame:
+ *               IGI_E_UNSUPPORTED
+ *   draws     : int32 [b][2] or NULL: the fp32 bit patterns of the depth and the mask angle of every sample (both, whichever
+ *               arena is present).  masking_prob outside [0, 1], or > 0 with patch < 1; max_rad negative or NaN: IGI_E_BADARG.
+ *               Same arguments, same bits
+ * ---------------------------------------------------------------------------------------- */
+int igi_image_pair_augment_seeded(const float* img, const float* seg, int64_t n, int t, int hs, int ws, const int64_t* rows,
+                                  int64_t b, int patch, float noise_std, double masking_prob, float max_rad, uint64_t seed,
+                                  float* out_img, float* out_seg, int32_t* draws, igi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Train-time augmentation of the online student's segmented point cloud (csrc/pcl_augment.h), ONE launch from the
  * environment's cloud tensor to a new tensor (PointCloudAugmentations.augment of the reference's environment,
  * factory_utils.py:83-166, which runs it object by object on a boolean-masked subset of the envs):

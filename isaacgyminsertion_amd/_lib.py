@@ -259,6 +259,9 @@ _EXPORTS = {
     "igi_tactile_augment_seeded": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                              C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_uint64, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    "igi_image_pair_augment_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_int64, C.c_int, C.c_float, C.c_double, C.c_float, C.c_uint64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "igi_pcl_augment": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_void_p,
                                   C.POINTER(PclAugmentParams), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "igi_pointnet_workspace_bytes": (C.c_size_t, [C.c_int64]),

@@ -19,7 +19,7 @@ import torch.distributed as dist
 from ..models.models_split import ActorCriticSplit as ActorCritic
 from ..models.running_mean_std import RunningMeanStd
 from ..models.transformer.runner import Runner as Student
-from ..models.transformer.utils import TactileAugment
+from ..models.transformer.utils import SyncTransform, TactileAugment, define_img_transforms  # noqa: F401
 from ..ppo.experience import StudentBuffer
 from ..ppo.frozen_ppo import _NullWriter, _summary_writer, log_test_result
 from ...bc_loss import bc_loss
@@ -92,6 +92,7 @@ class ExtrinsicAdapt(object):
         if self.pcl_augment is not None:
             self.pcl_episode = torch.zeros(self.num_actors, dtype=torch.int32, device=self.device)
         self.tactile_augment, self.tactile_seed = self._make_tactile_augment(), None
+        self.img_augment, self.img_seed = self._make_img_augment(), None
         self.student = Student(student_cfg)
         self.stats = None
         self.output_dir = output_dir
@@ -221,6 +222,50 @@ class ExtrinsicAdapt(object):
         self.tactile_seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=aug.generator))
         arena = self.storage.storage_dict['n_tactile']
         return aug.fused_seeded(arena.reshape(arena.shape[0] * arena.shape[1], -1), b.rows, self.tactile_seed)[0]
+
+    def _make_img_augment(self):
+        """``offline_train.img_augment_online``: absent / "off" = None; "fused" = the train transform of the camera pair (the
+        call the reference comments out, runner.py:421-422) on the minibatch of every optimizer step, in one native launch
+        straight from the rollout storage (``SyncTransform.fused_seeded``).  Strengths are the offline student's keys
+        ``img_gaussian_noise`` / ``img_masking_prob`` / ``img_patch_size`` / ``img_rotation_deg``.  The frames are augmented
+        as stored, i.e. after ``process_obs``'s valid-mask product.  The rollout, evaluation and deployment read the frames
+        as they are."""
+        cfg, name = self.train_config, "offline_train.img_augment_online"
+        key = cfg.get('img_augment_online', None)
+        if key is None or (isinstance(key, str) and key == 'off'):
+            return None
+        if not (isinstance(key, str) and key == 'fused'):
+            raise ValueError(f"{name}: expected 'off' or 'fused', got {key!r}")
+        if not (self.img_info or self.seg_info):
+            raise ValueError(f"{name}: 'fused' needs the camera frames (train.ppo.img_info or train.ppo.seg_info: True)")
+        if cfg.get('img_type', 'depth') != 'depth':
+            raise NotImplementedError(f"{name}: 'fused' reads single-channel camera frames (img_type 'depth'), got "
+                                      f"img_type {cfg.get('img_type')!r}")
+        crop = (cfg.get('img_crop_w', 0), cfg.get('img_crop_h', 0))
+        if crop != (0, 0):
+            raise NotImplementedError(f"{name}: 'fused' does not crop (frames arrive from the environment at the backbone's "
+                                      f"size): img_crop_w / img_crop_h must be 0, got {crop}")
+        size = (int(cfg.get('img_width', 54)), int(cfg.get('img_height', 96)))
+        for queue, info in ((getattr(self.env, 'img_queue', None), self.img_info),
+                            (getattr(self.env, 'seg_queue', None), self.seg_info)):
+            if info and (queue is None or queue.shape[-1] != size[0] * size[1]):
+                raise ValueError(f"{name}: 'fused' needs stored frames of img_width * img_height = {size[0]} * {size[1]} = "
+                                 f"{size[0] * size[1]} pixels, got {None if queue is None else tuple(queue.shape[1:])}")
+        aug = define_img_transforms(*size, *size, cfg.get('img_patch_size', 16), cfg.get('img_gaussian_noise', 0.0),
+                                    cfg.get('img_masking_prob', 0.0), cfg.get('img_rotation_deg', 0.0))[3]
+        # one seed per optimizer step from a private CPU generator (apart from the tactile one; the hash sites differ, so
+        # equal seeds are harmless): torch's global generators are not touched
+        aug.generator = torch.Generator().manual_seed(int(self.full_config.get('seed', 0)) + (self.rank if self.multi_gpu else 0))
+        return aug
+
+    def _augmented_images(self, b):
+        """The camera input of minibatch ``b`` under ``img_augment_online: "fused"``: one seed, one launch, read from the
+        time-major arenas in place -> (img, seg), each (B, history, 1, W, H) or None where the storage has no such field."""
+        aug = self.img_augment
+        self.img_seed = int(torch.randint(0, 2 ** 63 - 1, (1,), generator=aug.generator))
+        flat = [None if a is None else a.reshape(a.shape[0] * a.shape[1], -1)
+                for a in (self.storage.storage_dict.get('n_img'), self.storage.storage_dict.get('n_seg'))]
+        return aug.fused_seeded(flat[0], flat[1], b.rows, self.img_seed)[:2]
 
     def process_obs(self, obs, obj_id=2, socket_id=3, distinct=True, augment=False):
         """ext_adapt.py:383-435: normalise student_obs and the point cloud (both normalisers are in
@@ -402,13 +447,16 @@ class ExtrinsicAdapt(object):
         ``self.optim.flat_grad``.  Returns (action loss, latent loss)."""
         b = self.storage[i]
         fused_tactile = self.tactile_augment is not None     # then the augmentation's launch gathers n_tactile itself
+        fused_img = self.img_augment is not None             # likewise n_img / n_seg
         if hasattr(b, 'prefetch'):           # the keys this step reads, gathered by one launch
             b.prefetch(('n_student_obs',) + (() if fused_tactile else ('n_tactile',)) +
-                       ('n_img', 'n_seg', 'n_pcl', 'teacher_actions') + (() if self.only_bc else ('n_obs', 'latent_gt')))
+                       (() if fused_img else ('n_img', 'n_seg')) + ('n_pcl', 'teacher_actions') +
+                       (() if self.only_bc else ('n_obs', 'latent_gt')))
+        img, seg = self._augmented_images(b) if fused_img else (b.get('n_img'), b.get('n_seg'))
         student_dict = {
             'student_obs': b.get('n_student_obs'),
-            'tactile': self._augmented_tactile(b) if fused_tactile else b.get('n_tactile'), 'img': b.get('n_img'),
-            'seg': b.get('n_seg'),
+            'tactile': self._augmented_tactile(b) if fused_tactile else b.get('n_tactile'), 'img': img,
+            'seg': seg,
             'pcl': b['n_pcl'].reshape(b['n_pcl'].shape[0], -1, 3) if 'n_pcl' in b else None,
         }
         latent, _ = self.student.predict(student_dict, requires_grad=True)

@@ -304,7 +304,12 @@ class SyncTransform(nn.Module):
                                     device (the noise is ``torch.randn``);
       ``fused(arena, arena, rows)`` -> draw + torch.ops.mi355ppo.image_pair_augment: the gather from the resident arenas
                                     and the whole transform in one launch (the noise is the kernel's counter hash of
-                                    ``seed``).
+                                    ``seed``);
+      ``draw_seeded(B, T, seed)`` / ``apply_seeded`` / ``fused_seeded(arena2d, arena2d, rows, seed)`` -> the online
+                                    student's form: no crop, either tensor may be absent, and every draw the counter hash
+                                    of one seed, evaluated by the kernel itself
+                                    (torch.ops.mi355ppo.image_pair_augment_seeded, csrc/augment_seeded.h);
+                                    ``draw_seeded`` + ``apply_seeded`` is the same function in torch ops.
     ``forward(img, mask)`` is draw + apply from torch's default generator, on one item (T, C, H, W) as the dataset calls
     it, or on a batch."""
 
@@ -346,21 +351,88 @@ class SyncTransform(nn.Module):
 
     def apply(self, img, mask, offsets, angles, keep=None, noise_std=0.0):
         """(B, T, C, H, W) pair at the resize target -> cropped, rotated, noised, masked pair: batched torch ops."""
-        B, T, C = img.shape[:3]
+        return self._apply(img, mask, offsets, angles, keep, noise_std, lambda k, y: torch.randn_like(y) * noise_std)
+
+    def _apply(self, img, mask, offsets, angles, keep, noise_std, noise_of):
+        """``apply`` with the noise term of tensor ``k`` (0 = image, 1 = mask) from ``noise_of(k, y)``; a tensor that is None
+        stays None."""
         ch, cw = self.crop_size
         turned = (angles != 0).any(0).tolist()            # on the draw's (CPU) tensor: no device read-back
-        ang = angles.to(img.device)
         outs = []
         for k, x in enumerate((img, mask)):
+            if x is None:
+                outs.append(None)
+                continue
+            B, T, C = x.shape[:3]
             y = _gather_windows(x, offsets, self.crop_size).reshape(B * T, C, ch, cw)
             if turned[k]:
-                y = _rotate(y, ang[:, k].repeat_interleave(T))
+                y = _rotate(y, angles[:, k].to(x.device).repeat_interleave(T))
             if noise_std > 0.0:
-                y = y + torch.randn_like(y) * noise_std
+                y = y + noise_of(k, y)
             if k == 0 and keep is not None:
                 y = _mask_patches(y, keep, self.patch)
             outs.append(y.reshape(B, T, C, ch, cw))
         return outs[0], outs[1]
+
+    @property
+    def max_rad(self):
+        """``rotation_deg`` in radians, formed in double and rounded once to fp32: the value the seeded kernel is handed."""
+        return float(np.float32(self.rotation_deg * math.pi / 180))
+
+    def draw_seeded(self, B, T, seed):
+        """The tuple ``draw`` returns, as k_image_pair_augment_seeded draws it from ``seed`` alone (the table of
+        csrc/augment_seeded.h, restated on the CPU through ``_tok_hash``): ``offsets`` 0 (no crop online); the angle of
+        (sample b, tensor which) is the hash of element ``2 b + which`` -- float64 arithmetic on exact operands rounded once
+        to fp32, the kernel's bits; ``keep`` cell by cell at element ``(b T + t) gh gw + cell``; the returned seed is
+        ``seed``, which the noise hashes too.  No generator is asked for anything; a stage that is off evaluates no hash."""
+        B, T, seed = int(B), int(T), int(seed)
+        angles = torch.zeros(B, 2)
+        if self.rotation_deg > 0.0:
+            unit = (_tok_hash(seed, IMG_SITES["ANGLE"], torch.arange(2 * B)) >> 8).double() * 2.0 ** -23 - 1.0   # exact
+            angles = (unit * self.max_rad).float().reshape(B, 2)
+        gh, gw = self.crop_size[0] // self.patch, self.crop_size[1] // self.patch
+        keep = None
+        if self.masking_prob > 0.0 and gh * gw > 0:
+            cell = torch.arange(B * T * gh * gw)
+            keep = (_tok_hash(seed, IMG_SITES["KEEP"], cell) >= _hash_threshold(self.masking_prob)).to(torch.uint8)
+            keep = keep.reshape(B * T, gh, gw)
+        return torch.zeros(B, 2, dtype=torch.int32), angles, keep, seed
+
+    def apply_seeded(self, img, mask, offsets, angles, keep=None, noise_std=0.0, seed=0):
+        """``apply`` with the noise the kernels add: ``_hash_gauss`` of ``seed`` on plane 0 (image) and plane 1 (mask), at
+        every element's linear index in its output, times ``noise_std`` rounded to fp32 (the kernel is handed a float).  Any
+        device and float dtype; either tensor may be None."""
+        std = float(np.float32(noise_std))
+        return self._apply(img, mask, offsets, angles, keep, noise_std,
+                           lambda k, y: std * _hash_gauss(int(seed), k, tuple(y.shape), y.dtype, y.device))
+
+    def fused_seeded(self, img_arena2d, seg_arena2d, rows, seed, want_draws=False):
+        """The online student's minibatch in one native launch, every draw hashed from ``seed``: the arenas are the rollout
+        storage's time-major camera fields as the gather sees them, (horizon * envs, T * H * W) single-channel frames at
+        ``size``, read in place (either may be None); ``rows`` the minibatch's int64 flat rows on their device ->
+        (img, seg, draws): fp32 (B, T, 1, H, W) where the arena is there and, with ``want_draws``, int32 (B, 2), the bits of
+        the kernel's own angles (else None).  There is no crop online.  Above the kernel's limits the same draws go through
+        ``apply_seeded``."""
+        H, W = (int(v) for v in self.size)
+        if self.crop_size != (H, W):
+            raise NotImplementedError(f"SyncTransform.fused_seeded does not crop: crop size {self.crop_size}, stored {(H, W)}")
+        arenas = [a for a in (img_arena2d, seg_arena2d) if a is not None]
+        if not arenas:
+            raise ValueError("img_arena2d / seg_arena2d: expected at least one arena, got None for both")
+        for a in arenas:
+            if a.dim() != 2 or a.shape[1] % (H * W) != 0 or a.shape[1] == 0 or a.shape != arenas[0].shape:
+                raise ValueError(f"arena2d: expected (rows, T * {H} * {W}), the same for both, got {tuple(a.shape)}")
+        T, B = arenas[0].shape[1] // (H * W), rows.numel()
+        gather = lambda a: None if a is None else a.index_select(0, rows).reshape(B, T, 1, H, W)   # noqa: E731
+        if not self.training:
+            return gather(img_arena2d), gather(seg_arena2d), None
+        cells = (H // self.patch) * (W // self.patch) if self.masking_prob > 0.0 else 0
+        if cells > ops.IMG_AUG_MAX_CELLS or H * W > 1 << 24:   # beyond the kernel: the same draws in torch ops
+            offsets, angles, keep, seed = self.draw_seeded(B, T, seed)
+            img, seg = self.apply_seeded(gather(img_arena2d), gather(seg_arena2d), offsets, angles, keep, self.noise_std, seed)
+            return img, seg, (angles.view(torch.int32).to(rows.device) if want_draws else None)
+        return torch.ops.mi355ppo.image_pair_augment_seeded(img_arena2d, seg_arena2d, rows, T, H, W, self.patch, self.noise_std,
+                                                            self.masking_prob, self.max_rad, int(seed), bool(want_draws))
 
     def forward(self, img, mask):
         item = img.dim() == 4
@@ -512,6 +584,8 @@ def _hash_gauss(seed, plane, shape, dtype, device):
 TACTILE_NOISE_PLANE = 2      # the camera pair draws its noise on planes 0 and 1 of the same hash
 # csrc/tactile_augment_seeded.h: the hash sites of the seeded draws (0..13 are the Gaussian planes', 14..22 the point cloud's)
 TACTILE_SITES = dict(JITTER=23, BRIGHT=24, CONTRAST=25, ROTATE=26, ANGLE=27, KEEP=28)
+# csrc/augment_seeded.h: the camera pair's seeded draws (its noise is on planes 0 and 1, sites 0..3)
+IMG_SITES = {"ANGLE": 29, "KEEP": 30}
 
 
 def _hash_threshold(p):

@@ -23,6 +23,7 @@
 #include "tactile_augment.h"
 #include "pcl_augment.h"
 #include "tactile_augment_seeded.h"
+#include "augment_seeded.h"
 #include "peak_probe.h"
 
 namespace {
@@ -730,6 +731,13 @@ int igi_tactile_augment_seeded(const float* arena, int64_t n, int planes, int hs
                                float* out, int32_t* draws, igi_stream_t stream) {
   return fail(igi::tactile_augment_seeded(arena, n, planes, hs, ws, rows, b, out_h, out_w, patch, noise_std, masking_prob,
                                           seed, out, draws, S(stream)), "igi_tactile_augment_seeded");
+}
+
+int igi_image_pair_augment_seeded(const float* img, const float* seg, int64_t n, int t, int hs, int ws, const int64_t* rows,
+                                  int64_t b, int patch, float noise_std, double masking_prob, float max_rad, uint64_t seed,
+                                  float* out_img, float* out_seg, int32_t* draws, igi_stream_t stream) {
+  return fail(igi::image_pair_augment_seeded(img, seg, n, t, hs, ws, rows, b, patch, noise_std, masking_prob, max_rad, seed,
+                                             out_img, out_seg, draws, S(stream)), "igi_image_pair_augment_seeded");
 }
 
 static_assert(IGI_PCL_AUG_MAX_POINTS == igi::PCL_MAX_POINTS, "igi_ppo.h and pcl_augment.h disagree on the largest cloud");

@@ -378,6 +378,45 @@ std::tuple<Tensor, c10::optional<Tensor>> tactile_augment_seeded(const Tensor& a
   return {out, draws};
 }
 
+// ---- online distillation step (the camera pair from the rollout storage's two arenas, every draw hashed from one seed)
+std::tuple<c10::optional<Tensor>, c10::optional<Tensor>, c10::optional<Tensor>> image_pair_augment_seeded(
+    const c10::optional<Tensor>& img_arena, const c10::optional<Tensor>& seg_arena, const Tensor& rows, int64_t T, int64_t h,
+    int64_t w, int64_t patch, double noise_std, double masking_prob, double max_rad, int64_t seed, bool want_draws) {
+  const bool has_img = img_arena.has_value() && img_arena->defined(), has_seg = seg_arena.has_value() && seg_arena->defined();
+  TORCH_CHECK(has_img || has_seg, "img_arena / seg_arena: expected at least one arena, got None for both");
+  if (has_img) check(*img_arena, "img_arena");
+  if (has_seg) check(*seg_arena, "seg_arena");
+  check(rows, "rows", at::kLong);
+  TORCH_CHECK(rows.dim() == 1, "rows: expected 1 dimensions, got shape ", rows.sizes());
+  TORCH_CHECK(T >= 1 && h >= 1 && w >= 1, "T / h / w: expected >= 1, got (", T, ", ", h, ", ", w, ")");
+  const Tensor& first = has_img ? *img_arena : *seg_arena;
+  auto arena_ok = [&](const Tensor& a, const char* nm) {
+    TORCH_CHECK(a.dim() == 2 && a.size(1) == T * h * w && a.size(0) > 0, nm, ": expected (R, T*h*w = ", T * h * w,
+                ") non-empty, got ", a.sizes());
+    TORCH_CHECK(a.device() == rows.device(), nm, ": all arguments must share one device");
+  };
+  if (has_img) arena_ok(*img_arena, "img_arena");
+  if (has_seg) arena_ok(*seg_arena, "seg_arena");
+  TORCH_CHECK(!(has_img && has_seg) || img_arena->sizes() == seg_arena->sizes(), "seg_arena: expected img_arena's shape ",
+              first.sizes(), ", got ", has_seg ? seg_arena->sizes() : first.sizes());
+  TORCH_CHECK(masking_prob >= 0 && masking_prob <= 1, "masking_prob: expected a value in [0, 1], got ", masking_prob);
+  TORCH_CHECK(!(masking_prob > 0) || patch >= 1, "patch: expected >= 1 with a masking_prob, got ", patch);
+  TORCH_CHECK(max_rad >= 0, "max_rad: expected >= 0, got ", max_rad);
+  TORCH_CHECK(noise_std >= 0, "noise_std: expected >= 0, got ", noise_std);
+  const int64_t B = rows.numel(), R = first.size(0);
+  c10::optional<Tensor> out_img, out_seg, draws;
+  if (has_img) out_img = at::empty({B, T, 1, h, w}, first.options());
+  if (has_seg) out_seg = at::empty({B, T, 1, h, w}, first.options());
+  if (want_draws) draws = at::empty({B, 2}, first.options().dtype(at::kInt));
+  if (B == 0) return {out_img, out_seg, draws};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(first.device());
+  rc(igi_image_pair_augment_seeded(fpo(img_arena), fpo(seg_arena), R, (int)T, (int)h, (int)w, rows.data_ptr<int64_t>(), B,
+                                   (int)patch, (float)noise_std, masking_prob, (float)max_rad, (uint64_t)seed, fpo(out_img),
+                                   fpo(out_seg), want_draws ? draws->data_ptr<int32_t>() : nullptr, stream_of(first)),
+     "igi_image_pair_augment_seeded");
+  return {out_img, out_seg, draws};
+}
+
 // ---- rollout (factory_utils.py:83-166: the environment's point-cloud augmentation, one launch on the learner's side)
 Tensor pcl_augment(const Tensor& clouds, at::IntArrayRef points, const Tensor& episode, at::ArrayRef<double> params,
                    int64_t seed_episode, int64_t seed_step) {
@@ -441,6 +480,7 @@ TORCH_LIBRARY(mi355ppo, m) {
   m.def("pointnet_max_bwd(Tensor x, Tensor params, Tensor dy, Tensor idx) -> Tensor");
   m.def("tactile_augment(Tensor arena, Tensor rows, Tensor params, Tensor? keep, int out_h, int out_w, int patch, float noise_std, int seed) -> Tensor");
   m.def("tactile_augment_seeded(Tensor arena, Tensor rows, int out_h, int out_w, int patch, float noise_std, float masking_prob, int seed, bool want_draws) -> (Tensor, Tensor?)");
+  m.def("image_pair_augment_seeded(Tensor? img_arena, Tensor? seg_arena, Tensor rows, int T, int h, int w, int patch, float noise_std, float masking_prob, float max_rad, int seed, bool want_draws) -> (Tensor?, Tensor?, Tensor?)");
   m.def("pcl_augment(Tensor clouds, int[] points, Tensor episode, float[] params, int seed_episode, int seed_step) -> Tensor");
 }
 
@@ -462,5 +502,6 @@ TORCH_LIBRARY_IMPL(mi355ppo, CompositeExplicitAutograd, m) {
   m.impl("pointnet_max_bwd", pointnet_max_bwd);
   m.impl("tactile_augment", tactile_augment);
   m.impl("tactile_augment_seeded", tactile_augment_seeded);
+  m.impl("image_pair_augment_seeded", image_pair_augment_seeded);
   m.impl("pcl_augment", pcl_augment);
 }

@@ -1747,6 +1747,65 @@ def _(arena, rows, out_h, out_w, patch, noise_std, masking_prob, seed, want_draw
             arena.new_empty((n * arena.shape[1] * arena.shape[2], TACTILE_AUG_WORDS), dtype=torch.int32) if want_draws else None)
 
 
+IMG_AUG_MAX_CELLS = 8192      # IMG_MAX_CELLS of csrc/augment_seeded.h: keep cells per frame
+
+
+@_op("image_pair_augment_seeded(Tensor? img_arena, Tensor? seg_arena, Tensor rows, int T, int h, int w, int patch, "
+     "float noise_std, float masking_prob, float max_rad, int seed, bool want_draws) -> (Tensor?, Tensor?, Tensor?)")
+def image_pair_augment_seeded(img_arena: Optional[Tensor], seg_arena: Optional[Tensor], rows: Tensor, T: int, h: int, w: int,
+                              patch: int, noise_std: float, masking_prob: float, max_rad: float, seed: int,
+                              want_draws: bool) -> Tuple[Optional[Tensor], Optional[Tensor], Optional[Tensor]]:
+    """The camera pair of an online minibatch, augmented, in ONE launch from the rollout storage's arenas with nothing drawn on
+    the host but ``seed`` (igi_image_pair_augment_seeded; the chain of ``image_pair_augment`` with the window at (0, 0) and
+    the output at the stored size): ``img_arena`` / ``seg_arena`` fp32 (R, T*h*w), R = horizon * envs flat rows of ``T``
+    single-channel frames, either may be None, not both; ``rows`` int64 (B,) flat rows.  Every (sample, tensor) angle in
+    +-``max_rad`` radians and -- with ``masking_prob`` > 0 -- every depth frame's keep grid of ``patch`` x ``patch`` cells
+    is the counter hash of ``seed`` at the sites of csrc/augment_seeded.h; ``noise_std`` > 0 adds the hash-drawn Gaussian
+    noise of the same seed to both -> (img, seg, draws): fp32 (B, T, 1, h, w) where the arena is present (else None) and,
+    with ``want_draws``, int32 (B, 2), the bits of the (depth, mask) angles (else None).  More than 8192 cells per frame are
+    refused.  The inputs are data: no autograd."""
+    if img_arena is None and seg_arena is None:
+        raise RuntimeError("img_arena / seg_arena: expected at least one arena, got None for both")
+    present = [(a, nm) for a, nm in ((img_arena, "img_arena"), (seg_arena, "seg_arena")) if a is not None]
+    for a, nm in present:
+        _check_layout(a, nm, torch.float32, 2)
+    _check_layout(rows, "rows", torch.int64, 1)
+    if T < 1 or h < 1 or w < 1:
+        raise RuntimeError(f"T / h / w: expected >= 1, got {(T, h, w)}")
+    for a, nm in present:
+        if a.shape[1] != T * h * w or a.shape[0] == 0:
+            raise RuntimeError(f"{nm}: expected (R, T*h*w = {T * h * w}) non-empty, got {tuple(a.shape)}")
+    if len(present) == 2 and img_arena.shape != seg_arena.shape:
+        raise RuntimeError(f"seg_arena: expected img_arena's shape {tuple(img_arena.shape)}, got {tuple(seg_arena.shape)}")
+    if not 0 <= masking_prob <= 1:
+        raise RuntimeError(f"masking_prob: expected a value in [0, 1], got {masking_prob}")
+    if masking_prob > 0 and patch < 1:
+        raise RuntimeError(f"patch: expected >= 1 with a masking_prob, got {patch}")
+    if not max_rad >= 0:
+        raise RuntimeError(f"max_rad: expected >= 0, got {max_rad}")
+    B, R = rows.numel(), present[0][0].shape[0]
+    dev = _check_augment_args(h, w, h, w, noise_std, None, patch, B * T, tuple(present) + ((rows, "rows"),))
+    outs = [torch.empty((B, T, 1, h, w), dtype=torch.float32, device=dev) if a is not None else None
+            for a in (img_arena, seg_arena)]
+    draws = torch.empty((B, 2), dtype=torch.int32, device=dev) if want_draws else None
+    if B == 0:
+        return outs[0], outs[1], draws
+    with torch.cuda.device(dev):
+        _rc(_lib.lib().igi_image_pair_augment_seeded(_p(img_arena), _p(seg_arena), R, T, h, w, _p(rows), B, patch, noise_std,
+                                                     masking_prob, max_rad, C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF),
+                                                     _p(outs[0]), _p(outs[1]), _p(draws), _stream(rows)),
+            "igi_image_pair_augment_seeded")
+    return outs[0], outs[1], draws
+
+
+@_fake("image_pair_augment_seeded")
+def _(img_arena, seg_arena, rows, T, h, w, patch, noise_std, masking_prob, max_rad, seed, want_draws):
+    shape = (rows.numel(), T, 1, h, w)
+    return (rows.new_empty(shape, dtype=torch.float32) if img_arena is not None else None,
+            rows.new_empty(shape, dtype=torch.float32) if seg_arena is not None else None,
+            rows.new_empty((rows.numel(), 2), dtype=torch.int32) if want_draws else None)
+
+
 PCL_AUG_MAX_POINTS = 4096     # IGI_PCL_AUG_MAX_POINTS: per object
 PCL_AUG_MAX_OBJECTS = 4
 PCL_AUG_PARAMS = _lib.PclAugmentParams.FIELDS    # the order of ``params``: struct igi_pcl_augment_params, field for field
@@ -1889,5 +1948,5 @@ OP_NAMES = ["gae_advnorm", "ppo_minibatch_fwd_bwd", "ppo_clip_adam", "ppo_update
             "rollout_env_store",
             "bc_loss_fwd_bwd", "bc_loss", "bc_loss_value_grad", "gemm_f32", "linear", "linear_bwd", "mlp_fwd", "mlp_bwd", "tactile_cnn_fwd", "tactile_cnn_bwd", "spatial_softargmax_fwd", "spatial_softargmax_bwd",
             "pointnet_max_fwd", "pointnet_max_bwd", "pointnet_max_fwd_multi", "pointnet_max_bwd_multi", "depth_backbone_fwd", "depth_backbone_bwd", "token_encoder_fwd",
-            "token_encoder_bwd", "gather_rows", "cat_cols", "split_cols", "image_pair_augment",
+            "token_encoder_bwd", "gather_rows", "cat_cols", "split_cols", "image_pair_augment", "image_pair_augment_seeded",
             "tactile_augment", "tactile_augment_seeded", "pcl_augment"]

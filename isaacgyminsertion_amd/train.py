@@ -10,6 +10,8 @@
     python -m isaacgyminsertion_amd.train train.algo=ExtrinsicAdapt offline_train.only_bc=False \\
         offline_train.train.latent_loss=True offline_train.train.latent_scale=0.5
     python -m isaacgyminsertion_amd.train train.algo=ExtrinsicAdapt offline_train.tactile_augment_online=fused
+    python -m isaacgyminsertion_amd.train train.algo=ExtrinsicAdapt train.ppo.img_info=True train.ppo.seg_info=True \\
+        offline_train.img_augment_online=fused offline_train.img_gaussian_noise=0.01
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m isaacgyminsertion_amd.train train.ppo.multi_gpu=True
 
 rank / device / seed selection, ``offline_training`` -> ``Runner.run()``, environment construction, the

@@ -100,6 +100,9 @@ def default_config(num_envs=4096, horizon_length=32, rl_device="cuda:0", multi_g
             # ours: the ONLINE student's tactile frames in its distillation step (the call runner.py:402 comments out):
             # "off" = as stored; "fused" = one native launch per optimizer step, every draw hashed from one seed
             "tactile_augment_online": "off",
+            # ours: the ONLINE student's camera pair in its distillation step (the call runner.py:421-422 comments out):
+            # "off" = as stored; "fused" = one native launch per optimizer step, every draw hashed from one seed
+            "img_augment_online": "off",
             "tactile_color_jitter": False, "seed": 0, "data_folder": "", "output_dir": "outputs/offline",
             # supervised learning (offline_config.yaml:28-83)
             "train": {"latent_scale": 1.0, "action_scale": 1.0, "latent_loss": False, "action_regularization": False, "epochs": 100, "train_batch_size": 64,
