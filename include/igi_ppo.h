@@ -99,6 +99,18 @@ int igi_gemm_set_bf16_inputs(int on);
  * when IT is called: a forward / backward pair must run under ONE setting (the Python op's autograd formula records the
  * forward's setting and re-establishes it around the backward).  on < 0 only queries.  Returns the previous setting. */
 int igi_conv_set_bf16_inputs(int on);
+/* The same opt-in mode for the six large products of the depth backbone (igi_depth_forward / igi_depth_backward): conv2
+ * (3 x 3, 32 -> 64) forward, data gradient and weight gradient, and the 64768 -> 128 Linear forward (split-K), data
+ * gradient (with its ELU' epilogue) and weight gradient.  Each product term is float(bf16(a)) * float(bf16(b)), round to
+ * nearest even, exact in fp32, accumulated in fp32 on v_mfma_f32_32x32x16_bf16; operands stay fp32 in memory and are
+ * rounded where the MFMA operands are formed; the tiles are the fp32 path's.  Unchanged fp32: conv1 + max-pool + ELU with
+ * its arg-max bytes (the mode changes no pool decision) and conv1's weight gradient, the 128 -> latent Linear, biases,
+ * bias-gradient sums, ELU and ELU', the split-K reductions, the weight pack / permute kernels.  Deterministic.  Off by
+ * default; IGI_DEPTH_BF16=1 in the environment starts it on.  Independent of igi_gemm_set_bf16_inputs and
+ * igi_conv_set_bf16_inputs: neither reaches these six products' choice here, and this switch reaches nothing outside the
+ * depth backbone.  igi_depth_backward must run under the setting its igi_depth_forward ran under (the autograd formula of
+ * ops.depth_backbone_fwd records it and re-establishes it).  on < 0 only queries.  Returns the previous setting. */
+int igi_depth_set_bf16_inputs(int on);
 /* EXPERIMENT, off by default (IGI_GEMM_X3 = 6 | 9 in the environment starts it on): fp32 products on the bf16 matrix pipe by
  * an exact three-plane split of every operand element (x = hi + mid + lo in bf16: each plane product is exact in fp32, the
  * MFMA accumulates in fp32) for the large k-contiguous forward products (K >= 256).  products = 9: all nine cross products,
@@ -637,6 +649,12 @@ int igi_depth_forward(const igi_depth_cfg* cfg, const float* x, const float* par
                       size_t workspace_bytes, igi_stream_t stream);
 int igi_depth_backward(const igi_depth_cfg* cfg, const float* x, const float* dy, const float* params, float* grads,
                        void* workspace, size_t workspace_bytes, igi_stream_t stream);
+/* Where igi_depth_forward leaves its activations in the workspace (diagnostics / parity tests): byte offsets[3] and rows[3]
+ * of a1 = ELU(max-pool(conv1)) (batch * 25 * 46 rows of 32, channels-last), a2 = ELU(conv2) (batch * 23 * 44 rows of 64,
+ * channels-last: a row of the big Linear's input is an image's 1012 rows) and h3 = ELU(Linear 64768 -> 128) (batch rows of
+ * 128), all fp32.  The pool's arg-max bytes (uint8, one per element of a1: 2 * dy + dx inside the 2 x 2 window) start
+ * right behind a1, at offsets[0] + 4 * 32 * rows[0].  Returns 0, or an error for a configuration the backbone rejects. */
+int igi_depth_activation_layout(const igi_depth_cfg* cfg, int64_t offsets[3], int64_t rows[3]);
 
 /* ------------------------------------------------------------------------------------------
  * Token decoder of the student: `layers` x nn.TransformerEncoderLayer(d_model, nhead, dim_feedforward ff,

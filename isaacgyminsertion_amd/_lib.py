@@ -109,6 +109,7 @@ _EXPORTS = {
     "igi_build_info": (C.c_char_p, []),
     "igi_gemm_set_bf16_inputs": (C.c_int, [C.c_int]),
     "igi_conv_set_bf16_inputs": (C.c_int, [C.c_int]),
+    "igi_depth_set_bf16_inputs": (C.c_int, [C.c_int]),
     "igi_gemm_set_bf16x3": (C.c_int, [C.c_int]),
     "igi_teacher_set_latz_fuse": (C.c_int, [C.c_int]),
     "igi_prof_enable": (C.c_int, [C.c_int]),
@@ -226,6 +227,7 @@ _EXPORTS = {
     "igi_depth_workspace_bytes": (C.c_size_t, [C.POINTER(DepthCfg)]),
     "igi_depth_forward": (C.c_int, [C.POINTER(DepthCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.c_void_p]),
+    "igi_depth_activation_layout": (C.c_int, [C.POINTER(DepthCfg), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "igi_depth_backward": (C.c_int, [C.POINTER(DepthCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_size_t, C.c_void_p]),
     "igi_token_param_count": (C.c_int64, [C.POINTER(TokenCfg)]),

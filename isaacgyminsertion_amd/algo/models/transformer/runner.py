@@ -85,6 +85,11 @@ class Runner:
         # forward's setting by itself: ops.tactile_cnn_fwd).  None = key absent: the process switch is left alone.
         self.conv_bf16_inputs = bool(self.cfg.model.get('conv_bf16_inputs', False)) \
             if 'conv_bf16_inputs' in self.cfg.model else None
+        # offline_train.model.depth_bf16_inputs (not a reference key either): the same for the depth backbone's conv2 and
+        # 64768 -> 128 Linear (ops.depth_bf16_inputs; the camera and segmentation encoders), a switch of its own --
+        # conv_bf16_inputs keeps meaning "tactile convolutions only".  None = key absent: left alone.
+        self.depth_bf16_inputs = bool(self.cfg.model.get('depth_bf16_inputs', False)) \
+            if 'depth_bf16_inputs' in self.cfg.model else None
         gpu = self.cfg.gpu_ids[0] if 'gpu_ids' in self.cfg else 0
         self.device = cfg.get('rl_device', f'cuda:{gpu}') if hasattr(cfg, 'get') else f'cuda:{gpu}'
         self._init_transforms()
@@ -166,9 +171,13 @@ class Runner:
         return self.model
 
     def _conv_mode(self):
-        if self.conv_bf16_inputs is None:
-            return contextlib.nullcontext()
-        return ops.conv_bf16_inputs(self.conv_bf16_inputs)
+        """the two bf16-input switches this Runner's config names, around one forward of its model"""
+        stack = contextlib.ExitStack()
+        if self.conv_bf16_inputs is not None:
+            stack.enter_context(ops.conv_bf16_inputs(self.conv_bf16_inputs))
+        if getattr(self, 'depth_bf16_inputs', None) is not None:
+            stack.enter_context(ops.depth_bf16_inputs(self.depth_bf16_inputs))
+        return stack
 
     def predict(self, obs_dict, requires_grad=False, display=False):
         """runner.py:374-381"""

@@ -18,6 +18,11 @@
 //     permuted back.
 //   * conv1's weight gradient (the input needs none) routes each pooled gradient to its arg-max position
 //     and accumulates 25 taps per (pooled pixel, channel) on the VALU against the LDS-resident image.
+//   * opt-in, depth_bf16_mode() (igi_depth_set_bf16_inputs): the six large products -- conv2 and the 64768 -> 128 Linear,
+//     forward / data gradient / weight gradient -- run the bf16-input twins of the SAME tiles (operands stay fp32 in
+//     memory and LDS and are rounded to bf16, nearest even, where the v_mfma_f32_32x32x16_bf16 operands are formed; fp32
+//     accumulation).  conv1 (the raw depth frame, the pool's decisions), the 128 -> latent Linear, biases, bias-gradient
+//     sums, ELU / ELU', the split-K reductions and the pack / permute kernels stay fp32.
 // Parameter vector in state_dict order: image_compression.{0,3,6,8}.{weight,bias}.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -250,6 +255,7 @@ static int depth_forward(const igi_depth_cfg* c, const float* x, const float* pa
   float* wfp = twsp<float>(ws, p.w_wfp);
   float* slab = twsp<float>(ws, p.w_fcslab);
   float* h3 = twsp<float>(ws, p.w_h3);
+  const int bf = depth_bf16_mode();   // the setting in force at this call: conv2 and fc1 with bf16-rounded operands
   IGI_HIP_TRY(hipMemsetAsync(zero, 0, 256, s));
   {
     ConvWJobs jw;
@@ -262,7 +268,7 @@ static int depth_forward(const igi_depth_cfg* c, const float* x, const float* pa
                      params + p.o_c1b, a1, twsp<unsigned char>(ws, p.w_idx1), p.B);
   {  // conv2 + bias + ELU: (B,25,46,32) -> (B,23,44,64)
     GemmArgs g;
-    g.A = a1; g.gather = 1; g.conv = conv_desc(zero, DP_H2, DP_W2, DP_PH, DP_PW, DP_C1, 1, 0, 3, 3);
+    g.A = a1; g.gather = 1; g.conv_bf16 = bf; g.conv = conv_desc(zero, DP_H2, DP_W2, DP_PH, DP_PW, DP_C1, 1, 0, 3, 3);
     g.B = w2r; g.ldb = 288;
     g.M = p.B * DP_P2; g.N = DP_C2; g.K = 288; g.lda = 288;
     g.C = a2; g.ldc = DP_C2; g.bias = params + p.o_c2b; g.epilogue = EPI_BIAS_ELU;
@@ -270,7 +276,7 @@ static int depth_forward(const igi_depth_cfg* c, const float* x, const float* pa
   }
   {  // Linear(64768 -> 128), split over k
     GemmArgs g;
-    g.A = a2; g.lda = DP_FLAT;
+    g.A = a2; g.lda = DP_FLAT; g.bf16_inputs = bf;
     g.B = wfp; g.ldb = DP_FLAT;
     g.M = p.B; g.N = DP_FC; g.K = DP_FLAT;
     g.C = slab; g.ldc = DP_FC;
@@ -304,6 +310,7 @@ static int depth_backward(const igi_depth_cfg* c, const float* x, const float* d
   float* c2red = twsp<float>(ws, p.w_c2red);
   float* c1part = twsp<float>(ws, p.w_c1part);
   float* dwfp = twsp<float>(ws, p.w_dwfp);
+  const int bf = depth_bf16_mode();   // must be the forward's setting: the saved a2 / h3 were computed under it
   // Linear(128 -> latent)
   if ((rc = linear_backward(h3, DP_FC, params + p.o_f2w, nullptr, 0, dy, p.L, dh3, DP_FC, grads + p.o_f2w,
                             grads + p.o_f2b, p.B, DP_FC, p.L, LIN_NONE, twsp<void>(ws, p.w_lin), p.lin_bytes + 64, s)))
@@ -312,7 +319,7 @@ static int depth_backward(const igi_depth_cfg* c, const float* x, const float* d
   hipLaunchKernelGGL(k_depth_elu_grad, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s, dh3, h3, dz3, n3);
   {  // fc1 weight gradient (channels-last column order) + bias: dW[128][64768] = dz3^T a2
     GemmArgs g;
-    g.A = dz3; g.lda = DP_FC;
+    g.A = dz3; g.lda = DP_FC; g.bf16_inputs = bf;
     g.B = a2; g.ldb = DP_FLAT;
     g.M = DP_FC; g.N = DP_FLAT; g.K = p.B;
     g.C = dwfp; g.ldc = DP_FLAT; g.Cbias = grads + p.o_f1b;
@@ -321,7 +328,7 @@ static int depth_backward(const igi_depth_cfg* c, const float* x, const float* d
   }
   {  // d(conv2 pre-activation) = (dz3 . Wp) * elu'(a2)
     GemmArgs g;
-    g.A = dz3; g.lda = DP_FC;
+    g.A = dz3; g.lda = DP_FC; g.bf16_inputs = bf;
     g.B = wfp; g.ldb = DP_FLAT;
     g.M = p.B; g.N = DP_FLAT; g.K = DP_FC;
     g.C = dz2; g.ldc = DP_FLAT; g.aux = a2; g.ldaux = DP_FLAT; g.epilogue = EPI_ELUGRAD;
@@ -329,7 +336,7 @@ static int depth_backward(const igi_depth_cfg* c, const float* x, const float* d
   }
   {  // conv2 weight gradient, transposed (taps on M), split over the output pixels
     GemmArgs g;
-    g.A = a1; g.gather = 3; g.conv = conv_desc(zero, DP_H2, DP_W2, DP_PH, DP_PW, DP_C1, 1, 0, 3, 3); g.lda = 288;
+    g.A = a1; g.gather = 3; g.conv_bf16 = bf; g.conv = conv_desc(zero, DP_H2, DP_W2, DP_PH, DP_PW, DP_C1, 1, 0, 3, 3); g.lda = 288;
     g.B = dz2; g.ldb = DP_C2;
     g.M = 288; g.N = DP_C2; g.K = p.B * DP_P2;
     g.C = c2slab; g.ldc = DP_C2; g.Cbias = c2slab + (long long)p.sk_c2 * 288 * DP_C2; g.bias_from_b = 1;
@@ -344,7 +351,7 @@ static int depth_backward(const igi_depth_cfg* c, const float* x, const float* d
   }
   {  // conv2 data gradient -> g1 = d(pooled pre-ELU map) = (dz2 (*) flipped W2) * elu'(a1)
     GemmArgs g;
-    g.A = dz2; g.gather = 1; g.conv = conv_desc(zero, DP_PH, DP_PW, DP_H2, DP_W2, DP_C2, 1, 2, 3, 3); g.lda = 576;
+    g.A = dz2; g.gather = 1; g.conv_bf16 = bf; g.conv = conv_desc(zero, DP_PH, DP_PW, DP_H2, DP_W2, DP_C2, 1, 2, 3, 3); g.lda = 576;
     g.B = w2d; g.ldb = 576;
     g.M = p.B * DP_P1; g.N = DP_C1; g.K = 576;
     g.C = g1; g.ldc = DP_C1; g.aux = a1; g.ldaux = DP_C1; g.epilogue = EPI_ELUGRAD;

@@ -40,6 +40,16 @@ static inline int& conv_bf16_mode_ref() {
 }
 static inline int conv_bf16_mode() { return conv_bf16_mode_ref(); }
 
+// opt-in bf16-input mode of the depth backbone's six large products (conv2 and the 64768 -> 128 Linear: forward, data
+// gradient, weight gradient; depth.h): IGI_DEPTH_BF16=1 in the environment, or igi_depth_set_bf16_inputs().  Independent
+// of the two switches above: nothing but depth.h reads it, and depth.h reads neither of them.
+static inline int& depth_bf16_mode_ref() {
+  static int m = -1;
+  if (m < 0) { const char* e = getenv("IGI_DEPTH_BF16"); m = e ? (atoi(e) != 0) : 0; }
+  return m;
+}
+static inline int depth_bf16_mode() { return depth_bf16_mode_ref(); }
+
 // EXPERIMENT (off by default): fp32 products on the bf16 matrix pipe by an EXACT three-plane split -- every operand element
 // x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (each difference is exact, 3 x 8
 // significant bits = fp32's 24), every cross product of two planes is exact in fp32, the MFMA accumulates in fp32.

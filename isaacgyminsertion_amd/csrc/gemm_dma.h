@@ -1082,6 +1082,9 @@ __global__ __launch_bounds__(DMA_THREADS) void gemm_dma_conv_bf16_kernel(const G
   gemm_dma_body<BN, A_KC, B_KC, GATHER, NS, BM, false, false, 1>(g, n_tiles, m_tiles, xcd_remap(blockIdx.x, gridDim.x));
 }
 
+// the 128 x 128 two-stage tile of the plain products with bf16-rounded operands: <true, *> under bf16_mode() or for one call
+// (GemmArgs::bf16_inputs), <false, false> (a weight gradient in a launch of its own: both operands reduction-major, bias
+// sums of the un-rounded A image) for one call only -- under bf16_mode() the weight gradients take the grouped kernel
 template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(DMA_THREADS) void gemm_dma_bf16_kernel(const GemmArgs g, int n_tiles, int m_tiles) {
   gemm_dma_body<128, A_KC, B_KC, 0, 2, DMA_BM, false, false, 1>(g, n_tiles, m_tiles, xcd_remap(blockIdx.x, gridDim.x));
@@ -1489,11 +1492,26 @@ static hipError_t launch_conv_tile(const GemmArgs& g, bool akc, bool bkc, hipStr
   return g.conv_bf16 ? launch_dma_cfg<BN, NS, BM, true>(g, akc, bkc, s) : launch_dma_cfg<BN, NS, BM>(g, akc, bkc, s);
 }
 
+// A plain product on the 128 x 128 two-stage tile with the bf16-input inner loop (gemm_dma_bf16_kernel): same tiles,
+// loaders, split-k and epilogues as gemm_dma_kernel<128, akc, bkc, 0, 2>.  The caller checked dma_eligible().
+static hipError_t launch_dma_bf16_128(const GemmArgs& g, bool akc, bool bkc, hipStream_t s) {
+  const int n_tiles = (g.N + 127) / 128, m_tiles = (g.M + DMA_BM - 1) / DMA_BM;
+  GemmArgs gg = g;
+  gg.wide_epi = dma_wide_epi_ok(g);
+  constexpr size_t shm = DMA_SHM_128X2;
+  const dim3 grid(n_tiles * m_tiles * g.nbatch * g.splitk);
+  if (akc && bkc) IGI_DMA_LAUNCH_SHM((gemm_dma_bf16_kernel<true, true>), grid, shm, shm, s, gg, n_tiles, m_tiles);
+  else if (akc) IGI_DMA_LAUNCH_SHM((gemm_dma_bf16_kernel<true, false>), grid, shm, shm, s, gg, n_tiles, m_tiles);
+  else if (!bkc) IGI_DMA_LAUNCH_SHM((gemm_dma_bf16_kernel<false, false>), grid, shm, shm, s, gg, n_tiles, m_tiles);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
 // Front door used by the C ABI and the teacher/student orchestration.
 static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   if (g.M <= 0 || g.N <= 0) return hipSuccess;
   dma_norm_splitk(g);
-  if (!dma_eligible(g, akc, bkc)) return g.gather ? hipErrorInvalidValue : launch_gemm(g, akc, bkc, s);
+  if (!dma_eligible(g, akc, bkc)) return (g.gather || g.bf16_inputs) ? hipErrorInvalidValue : launch_gemm(g, akc, bkc, s);
   const double fl = 2.0 * g.M * g.N * (double)g.K * g.nbatch * g.flop_credit;
   const double by = 4.0 * g.nbatch * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N * g.splitk);
   // Tile width (measured on the teacher update, 4096 x 32): 128-wide tiles with a 2-stage ring = 64-72 KB of LDS, so TWO
@@ -1512,6 +1530,14 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   // error, not fp32.
   const bool cbf = g.conv_bf16 != 0;
   if (cbf && !(g.N <= 64 && ((g.gather == 1 && akc && bkc) || (g.gather == 3 && !akc && !bkc)))) return hipErrorInvalidValue;
+  // bf16_inputs (the depth backbone's big Linear under depth_bf16_mode()): this call on the 128 x 128 two-stage tile with
+  // the bf16-input inner loop -- the tile the fp32 path gives these products, except a one-k-tile weight gradient (32
+  // images), which stays on it too -- booked under a class of its own.  A product that tile cannot take is an error.
+  if (g.bf16_inputs) {
+    if (g.gather || g.N <= 64 || (!akc && bkc)) return hipErrorInvalidValue;
+    ProfScope ps(PC_DMAB_128_TT + (akc ? (bkc ? 0 : 1) : 2), s, fl, by);
+    return launch_dma_bf16_128(g, akc, bkc, s);
+  }
   if (tall_fwd) {
     const bool pmj = conv_pmajor_ok(g, bkc);
     if (g.N <= 32)   // conv1 forward, conv2 data gradient: a 32-wide tile, no padded MFMA columns
@@ -1558,8 +1584,7 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
     const dim3 grid(n_tiles * m_tiles * g.nbatch * g.splitk);
     if (x3 && x3_mode() == 9) IGI_DMA_LAUNCH_SHM((gemm_dma_x3_kernel<9>), grid, shm, shm, s, gg, n_tiles, m_tiles);
     else if (x3) IGI_DMA_LAUNCH_SHM((gemm_dma_x3_kernel<6>), grid, shm, shm, s, gg, n_tiles, m_tiles);
-    else if (bkc) IGI_DMA_LAUNCH_SHM((gemm_dma_bf16_kernel<true, true>), grid, shm, shm, s, gg, n_tiles, m_tiles);
-    else IGI_DMA_LAUNCH_SHM((gemm_dma_bf16_kernel<true, false>), grid, shm, shm, s, gg, n_tiles, m_tiles);
+    else return launch_dma_bf16_128(g, true, bkc, s);
     return hipGetLastError();
   }
   if (bn == 128) return launch_dma_cfg<128, 2>(g, akc, bkc, s);

@@ -128,7 +128,10 @@ struct GemmArgs {
   int gather = 0;          // 0 none | 1 A = im2col gather (k-contiguous) | 2 B = im2col (reduction-major)
                            // | 3 A = im2col (reduction-major): conv weight gradient with taps on the M side
   int bias_from_b = 0;     // Cbias = column sums of B over k (instead of A), indexed by n
-  int conv_bf16 = 0;       // im2col products only (set by the tactile encoder from conv_bf16_mode()): bf16-input tiles
+  int conv_bf16 = 0;       // im2col products only (set by the tactile encoder from conv_bf16_mode() and by the depth
+                           // backbone from depth_bf16_mode()): bf16-input tiles
+  int bf16_inputs = 0;     // plain (not gathered) products: THIS call runs the 128 x 128 tile's bf16-input inner loop, whatever
+                           // bf16_mode() says (the depth backbone's big Linear under depth_bf16_mode()); gemm_dma.h, gemm()
   double flop_credit = 1.0;  // profiler only: algorithmic / executed flops (zero-padded operands, e.g. K 23 run as 32)
   // LDS-DMA kernels: divisors of the workgroup's tile decomposition (n_tiles, m_tiles, splitk), set by the launchers
   // (dma_set_divs).  A division by a run-time value is expanded through the vector unit's float reciprocal (~15

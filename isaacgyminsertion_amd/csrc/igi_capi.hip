@@ -171,6 +171,12 @@ int igi_conv_set_bf16_inputs(int on) {
   return prev;
 }
 
+int igi_depth_set_bf16_inputs(int on) {
+  const int prev = igi::depth_bf16_mode();
+  if (on >= 0) igi::depth_bf16_mode_ref() = on != 0;
+  return prev;
+}
+
 int igi_mfma_peak_probe(int shape, int blocks, int iters, uint64_t* clocks_dev, float* sink_dev, igi_stream_t stream) {
   return fail(igi::mfma_peak_probe(shape, blocks, iters, (unsigned long long*)clocks_dev, sink_dev, S(stream)), "igi_mfma_peak_probe");
 }
@@ -618,6 +624,15 @@ size_t igi_depth_workspace_bytes(const igi_depth_cfg* cfg) {
 int igi_depth_forward(const igi_depth_cfg* cfg, const float* x, const float* params, float* y, void* workspace,
                       size_t workspace_bytes, igi_stream_t stream) {
   return fail(igi::depth_forward(cfg, x, params, y, workspace, workspace_bytes, S(stream)), "igi_depth_forward");
+}
+
+int igi_depth_activation_layout(const igi_depth_cfg* cfg, int64_t offsets[3], int64_t rows[3]) {
+  igi::DepthPlan p;
+  int rc = igi::make_depth_plan(cfg, &p);
+  if (rc || !offsets || !rows) return fail(rc ? rc : IGI_E_BADARG, "igi_depth_activation_layout");
+  offsets[0] = (int64_t)p.w_a1; offsets[1] = (int64_t)p.w_a2; offsets[2] = (int64_t)p.w_h3;
+  rows[0] = (int64_t)p.B * igi::DP_P1; rows[1] = (int64_t)p.B * igi::DP_P2; rows[2] = p.B;
+  return 0;
 }
 
 int igi_depth_backward(const igi_depth_cfg* cfg, const float* x, const float* dy, const float* params, float* grads,

@@ -28,6 +28,10 @@ enum ProfClass {
   // gradient; weight gradient), which the fp32 path books under gemm_dma_kernel<64,...>
   PC_CONVB_TALL64_TT, PC_CONVB_TALL32_TT, PC_CONVB_TALL64_SSA, PC_CONVB_WG_TALL32, PC_CONVB_WG_TALL64,
   PC_CONVB_PM64, PC_CONVB_PM32, PC_CONVB_PW32, PC_CONVB_PW64, PC_CONVB_PW64_192, PC_CONVB_ROW64, PC_CONVB_WG64, PC_CONVB_PW64_128,
+  // the 128 x 128 two-stage tile with the bf16-input inner loop asked for by ONE call (GemmArgs::bf16_inputs: the depth
+  // backbone's big Linear under depth_bf16_mode()), by operand layout as PC_DMA_128_*; under the process-wide bf16_mode()
+  // the same kernels stay booked as PC_DMA_128_*
+  PC_DMAB_128_TT, PC_DMAB_128_TF, PC_DMAB_128_FF,
   PC_POINTNET_FWD, PC_POINTNET_BWD, PC_SOFTARGMAX_FWD, PC_SOFTARGMAX_BWD,
   PC_DMA_HEAD, PC_TRUNK_LOSS, PC_RB_TRUNK, PC_RB_ENV, PC_MLP_FWD, PC_POLICY_FWD, PC_ACTOR_LATENT, PC_FWD12, PC_ENV_FWD, PC_GEMM_GENERIC, PC_GATHER_NORMALIZE, PC_RMS_FINAL, PC_NORMALIZE,
   PC_LOSS, PC_LATENT_BWD, PC_SLAB_REDUCE, PC_SUMSQ, PC_ADAM, PC_ADAM_GATHER, PC_LR_SCHEDULE, PC_PREPARE,
@@ -62,6 +66,7 @@ static const char* const kProfNames[PC_COUNT] = {
     "gemm_dma_conv_bf16_kernel<64,false,false,5,2,192>",
     "gemm_dma_conv_bf16_kernel<64,true,true,1,3,128>", "gemm_dma_conv_bf16_kernel<64,false,false,3,3,128>",
     "gemm_dma_conv_bf16_kernel<64,false,false,5,3,128>",
+    "gemm_dma_bf16_kernel<true,true>", "gemm_dma_bf16_kernel<true,false>", "gemm_dma_bf16_kernel<false,false>",
     "k_pointnet_fwd", "k_pointnet_bwd", "k_softargmax_fwd", "k_softargmax_bwd",
     "gemm_dma_head_kernel<true>", "k_trunk_loss",
     "k_rb_level#trunk3: dW 256->128 x2 + dgrad 128->256 x2", "k_rb_level#env2: dW env 256->128 + env dgrad 128->256 (+ dW env 64->256 from its tiles)",

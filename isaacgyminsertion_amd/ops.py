@@ -1405,6 +1405,35 @@ def _pnm_backward(ctx, dy, didx):
 register_autograd(f"{NS}::pointnet_max_fwd_multi", _pnm_backward, setup_context=_pnm_setup)
 
 
+class depth_bf16_inputs:
+    """Opt-in bf16-input, fp32-accumulate arithmetic of the depth backbone's six large products -- conv2 and the
+    64768 -> 128 Linear: forward, data gradient, weight gradient (igi_depth_set_bf16_inputs; off by default,
+    ``IGI_DEPTH_BF16=1`` starts it on).  conv1 with its pooling, the 128 -> latent Linear and every bias / ELU stay fp32.
+    ``depth_bf16_inputs(True)`` sets the process-wide switch at once and remembers the previous value in ``.previous``;
+    used as a context manager it restores that value on exit, as ``conv_bf16_inputs`` does::
+
+        ops.depth_bf16_inputs(True)                # on from here
+        with ops.depth_bf16_inputs(True): ...      # on inside the block only
+
+    ``depth_backbone_fwd`` records the setting its forward ran under and its autograd formula re-establishes it around
+    the backward op.  Nothing but the depth backbone reads this switch, and the backbone reads no other."""
+
+    def __init__(self, on):
+        self.previous = bool(_lib.lib().igi_depth_set_bf16_inputs(1 if on else 0))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().igi_depth_set_bf16_inputs(1 if self.previous else 0)
+        return False
+
+
+def depth_bf16_inputs_enabled():
+    """the current setting of the switch (igi_depth_set_bf16_inputs(-1): a query)"""
+    return bool(_lib.lib().igi_depth_set_bf16_inputs(-1))
+
+
 @_op("depth_backbone_fwd(Tensor x, Tensor params, int latent_dim) -> (Tensor, Tensor)")
 def depth_backbone_fwd(x: Tensor, params: Tensor, latent_dim: int) -> Tuple[Tensor, Tensor]:
     """DepthOnlyFCBackbone54x96 forward (tact.py:81-113) on (32k, 1, 54, 96) -> igi_depth_forward."""
@@ -1452,6 +1481,7 @@ def _(x, dy, params, ws):
 def _dep_setup(ctx, inputs, output):
     x, params, latent_dim = inputs
     ctx.save_for_backward(x, params, output[1])
+    ctx.depth_bf16 = depth_bf16_inputs_enabled()   # setup_context runs right behind the forward op: still its setting
     ctx.set_materialize_grads(False)
 
 
@@ -1459,7 +1489,8 @@ def _dep_backward(ctx, dy, dws):
     x, params, ws = ctx.saved_tensors
     if dy is None:
         return None, None, None
-    return None, torch.ops.mi355ppo.depth_backbone_bwd(x, dy.contiguous(), params, ws), None
+    with depth_bf16_inputs(ctx.depth_bf16):        # the arithmetic the saved activations were computed in
+        return None, torch.ops.mi355ppo.depth_backbone_bwd(x, dy.contiguous(), params, ws), None
 
 
 register_autograd(f"{NS}::depth_backbone_fwd", _dep_backward, setup_context=_dep_setup)
