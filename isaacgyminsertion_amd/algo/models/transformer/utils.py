@@ -35,7 +35,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .... import ops  # noqa: F401  (registers torch.ops.mi355ppo)
+from .... import draws, ops  # noqa: F401  (ops registers torch.ops.mi355ppo)
 
 
 class GaussianNoise(nn.Module):
@@ -381,30 +381,28 @@ class SyncTransform(nn.Module):
 
     def draw_seeded(self, B, T, seed):
         """The tuple ``draw`` returns, as k_image_pair_augment_seeded draws it from ``seed`` alone (the table of
-        csrc/augment_seeded.h, restated on the CPU through ``_tok_hash``): ``offsets`` 0 (no crop online); the angle of
+        csrc/augment_seeded.h, restated on the CPU through ``draws``): ``offsets`` 0 (no crop online); the angle of
         (sample b, tensor which) is the hash of element ``2 b + which`` -- float64 arithmetic on exact operands rounded once
         to fp32, the kernel's bits; ``keep`` cell by cell at element ``(b T + t) gh gw + cell``; the returned seed is
         ``seed``, which the noise hashes too.  No generator is asked for anything; a stage that is off evaluates no hash."""
         B, T, seed = int(B), int(T), int(seed)
         angles = torch.zeros(B, 2)
         if self.rotation_deg > 0.0:
-            unit = (_tok_hash(seed, IMG_SITES["ANGLE"], torch.arange(2 * B)) >> 8).double() * 2.0 ** -23 - 1.0   # exact
+            unit = draws.unit(draws.tok_hash(seed, draws.SITES["IMG_SITE_ANGLE"], torch.arange(2 * B)))
             angles = (unit * self.max_rad).float().reshape(B, 2)
         gh, gw = self.crop_size[0] // self.patch, self.crop_size[1] // self.patch
         keep = None
         if self.masking_prob > 0.0 and gh * gw > 0:
-            cell = torch.arange(B * T * gh * gw)
-            keep = (_tok_hash(seed, IMG_SITES["KEEP"], cell) >= _hash_threshold(self.masking_prob)).to(torch.uint8)
-            keep = keep.reshape(B * T, gh, gw)
+            keep = draws.keep_grid(seed, draws.SITES["IMG_SITE_KEEP"], self.masking_prob, (B * T, gh, gw))
         return torch.zeros(B, 2, dtype=torch.int32), angles, keep, seed
 
     def apply_seeded(self, img, mask, offsets, angles, keep=None, noise_std=0.0, seed=0):
-        """``apply`` with the noise the kernels add: ``_hash_gauss`` of ``seed`` on plane 0 (image) and plane 1 (mask), at
+        """``apply`` with the noise the kernels add: ``draws.gauss`` of ``seed`` on plane 0 (image) and plane 1 (mask), at
         every element's linear index in its output, times ``noise_std`` rounded to fp32 (the kernel is handed a float).  Any
         device and float dtype; either tensor may be None."""
         std = float(np.float32(noise_std))
         return self._apply(img, mask, offsets, angles, keep, noise_std,
-                           lambda k, y: std * _hash_gauss(int(seed), k, tuple(y.shape), y.dtype, y.device))
+                           lambda k, y: std * draws.gauss(int(seed), k, draws.elements(y.shape, y.device), y.dtype))
 
     def fused_seeded(self, img_arena2d, seg_arena2d, rows, seed, want_draws=False):
         """The online student's minibatch in one native launch, every draw hashed from ``seed``: the arenas are the rollout
@@ -550,50 +548,6 @@ class TactileTransform:
 # ---------------------------------------------------------------------------------------------
 # tactile images, random numbers apart from the arithmetic: one native launch per batch (csrc/tactile_augment.h)
 # ---------------------------------------------------------------------------------------------
-_M32 = 0xFFFFFFFF
-
-
-def _mul32(x, k):
-    """(x * k) mod 2^32 for an int64 tensor of 32-bit values: two 16-bit halves, so no product leaves int64."""
-    return ((x & 0xFFFF) * k + ((((x >> 16) * k) & 0xFFFF) << 16)) & _M32
-
-
-def _tok_hash(seed, site, idx):
-    """csrc/tok_hash.h on an int64 tensor ``idx`` (taken modulo 2^32) -> int64 values below 2^32."""
-    lo, hi = seed & _M32, (seed >> 32) & _M32
-    x = _mul32(idx & _M32, 0x9E3779B1) ^ lo ^ ((site * 0x85EBCA77) & _M32)
-    x = _mul32(x ^ (x >> 16), 0x7FEB352D)
-    x = _mul32(x ^ (x >> 15), 0x846CA68B)
-    x = ((x ^ (x >> 16)) + hi) & _M32
-    x = _mul32(x ^ (x >> 15), 0x2C1B3C6D)
-    x = _mul32(x ^ (x >> 12), 0x297A2D39)
-    return x ^ (x >> 15)
-
-
-def _hash_gauss(seed, plane, shape, dtype, device):
-    """csrc/aug_gauss.h: the Box-Muller sample of every element of an output tensor of ``shape``, in ``dtype``."""
-    e = torch.arange(math.prod(shape), device=device)
-    k1, k2 = _tok_hash(seed, 2 * plane, e) >> 8, _tok_hash(seed, 2 * plane + 1, e) >> 8
-    low = torch.log((k1.to(dtype) + 0.5) * 2.0 ** -24)
-    high = torch.log1p(-(((0xFFFFFF - k1).to(dtype) + 0.5) * 2.0 ** -24))
-    ln_u1 = torch.where(k1 < (1 << 23), low, high)
-    z = torch.sqrt(-2.0 * ln_u1) * torch.cos((2.0 * math.pi) * (k2.to(dtype) * 2.0 ** -24))
-    return z.reshape(shape)
-
-
-TACTILE_NOISE_PLANE = 2      # the camera pair draws its noise on planes 0 and 1 of the same hash
-# csrc/tactile_augment_seeded.h: the hash sites of the seeded draws (0..13 are the Gaussian planes', 14..22 the point cloud's)
-TACTILE_SITES = dict(JITTER=23, BRIGHT=24, CONTRAST=25, ROTATE=26, ANGLE=27, KEEP=28)
-# csrc/augment_seeded.h: the camera pair's seeded draws (its noise is on planes 0 and 1, sites 0..3)
-IMG_SITES = {"ANGLE": 29, "KEEP": 30}
-
-
-def _hash_threshold(p):
-    """An event of probability ``p`` is ``hash < _hash_threshold(p)``: the point-cloud path's helper, as a Python int."""
-    from ....envs.pcl_augment import _threshold
-    return int(_threshold(p))
-
-
 class TactileAugment(nn.Module):
     """The train transform of ``define_tactile_transforms`` -- crop, brightness / contrast jitter (p 0.3), rotation
     <= 3 degrees (p 0.5), Gaussian noise, patch masking -- with the random numbers of a call apart from its arithmetic,
@@ -657,30 +611,26 @@ class TactileAugment(nn.Module):
 
     def draw_seeded(self, n_images, seed):
         """The tuple ``draw`` returns, as k_tactile_augment_seeded draws it from ``seed`` alone (the table of
-        csrc/tactile_augment_seeded.h, restated on the CPU through ``_tok_hash``): ``offsets`` 0 (no crop online); image
+        csrc/tactile_augment_seeded.h, restated on the CPU through ``draws``): ``offsets`` 0 (no crop online); image
         i's flags are the integer comparisons of its hashes; its factors and angle are float64 arithmetic on exact operands
         rounded once to fp32 -- the kernel's bits; ``keep`` cell by cell at element ``i * gh * gw + cell``; the returned
         seed is ``seed``, which the noise hashes too.  Evaluation draws nothing."""
         n, seed = int(n_images), int(seed)
         if not self.training:
             return self.draw(n)
-        S = TACTILE_SITES
         img = torch.arange(n)
-
-        def unit(site):                                   # 2u - 1, u = (h >> 8) 2^-24: exact in fp32 and in float64
-            return (_tok_hash(seed, site, img) >> 8).double() * 2.0 ** -23 - 1.0
-        on = _tok_hash(seed, S["JITTER"], img) < _hash_threshold(self.JITTER_P)
-        turn = _tok_hash(seed, S["ROTATE"], img) < _hash_threshold(self.ROTATE_P)
+        h = {k: draws.tok_hash(seed, draws.SITES["TAC_SITE_" + k], img)
+             for k in ("JITTER", "BRIGHT", "CONTRAST", "ROTATE", "ANGLE")}
+        on, turn = h["JITTER"] < draws.threshold(self.JITTER_P), h["ROTATE"] < draws.threshold(self.ROTATE_P)
         amp, rad = float(np.float32(self.JITTER)), float(np.float32(self.ROTATE_DEG * math.pi / 180))
         one = torch.ones(n)
-        jitter = torch.stack([on.float(), torch.where(on, (unit(S["BRIGHT"]) * amp + 1.0).float(), one),
-                              torch.where(on, (unit(S["CONTRAST"]) * amp + 1.0).float(), one)], 1)
-        angles = torch.where(turn, (unit(S["ANGLE"]) * rad).float(), torch.zeros(n))
+        jitter = torch.stack([on.float(), torch.where(on, (draws.unit(h["BRIGHT"]) * amp + 1.0).float(), one),
+                              torch.where(on, (draws.unit(h["CONTRAST"]) * amp + 1.0).float(), one)], 1)
+        angles = torch.where(turn, (draws.unit(h["ANGLE"]) * rad).float(), torch.zeros(n))
         gh, gw = self.crop_size[0] // self.patch, self.crop_size[1] // self.patch
         keep = None
         if self.masking_prob > 0.0 and gh * gw > 0:
-            cell = torch.arange(n * gh * gw)
-            keep = (_tok_hash(seed, S["KEEP"], cell) >= _hash_threshold(self.masking_prob)).to(torch.uint8).reshape(n, gh, gw)
+            keep = draws.keep_grid(seed, draws.SITES["TAC_SITE_KEEP"], self.masking_prob, (n, gh, gw))
         return torch.zeros(n, 2, dtype=torch.int32), jitter, angles, keep, seed
 
     @staticmethod
@@ -709,7 +659,8 @@ class TactileAugment(nn.Module):
             ang = angles.to(dev)
             y = torch.where((ang != 0).reshape(n, 1, 1, 1), _rotate(y.contiguous(), ang), y)
         if noise_std > 0.0:
-            y = y + float(np.float32(noise_std)) * _hash_gauss(int(seed), TACTILE_NOISE_PLANE, tuple(y.shape), y.dtype, dev)
+            z = draws.gauss(int(seed), draws.PLANES["TAC_NOISE_PLANE"], draws.elements(y.shape, dev), y.dtype)
+            y = y + float(np.float32(noise_std)) * z
         if keep is not None:
             y = _mask_patches(y, keep, self.patch)
         return y.reshape(*lead, C, ch, cw)

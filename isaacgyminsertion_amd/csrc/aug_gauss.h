@@ -1,10 +1,10 @@
 // The Gaussian sample of the augmentation kernels (aug_pixel.h): Box-Muller over two values of the counter
-// hash, a pure function of (seed, plane, element).  Planes in use: 0 = camera depth, 1 = camera mask, 2 = tactile.
-// tests/img_augment_ref.py `gauss` restates it in float64.
+// hash, a pure function of (seed, plane, element): plane p uses sites 2p and 2p + 1.  The planes in use are tabled in
+// draws.h.  tests/img_augment_ref.py `gauss` restates it in float64.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "tok_hash.h"
+#include "draws.h"
 
 namespace igi {
 
@@ -17,8 +17,7 @@ __device__ __forceinline__ float aug_log_u1(unsigned int k) {
 
 __device__ __forceinline__ float aug_gauss(unsigned long long seed, unsigned int plane, unsigned int e) {
   const unsigned int h1 = tok_hash(seed, 2u * plane, e), h2 = tok_hash(seed, 2u * plane + 1u, e);
-  const float u2 = (float)(h2 >> 8) * 0x1p-24f;
-  return sqrtf(-2.0f * aug_log_u1(h1 >> 8)) * cosf(6.283185307179586f * u2);
+  return sqrtf(-2.0f * aug_log_u1(h1 >> 8)) * cosf(6.283185307179586f * draw_u(h2));
 }
 
 }  // namespace igi

@@ -11,16 +11,15 @@
 // tok_hash.h evaluated by the workgroup itself (uniform over it), and the keep cells its band covers are hashed into LDS
 // behind one barrier before the chain reads them -- a pure function of (seed, frame, cell), whichever band asks.
 //
-// Draws.  b = the position in the minibatch (not the arena row), u(h) = (h >> 8) 2^-24, thr(p) = pcl_threshold(p) of
-// pcl_augment.h, computed on the host once; every event is an integer comparison.  2u - 1 is exact in fp32 (tac_unit) and the
-// angle is ONE fp32 multiply of exact operands: a float64 product rounded once to fp32 gives the same bits.  max_rad is
-// rotation_deg * pi / 180 formed in double on the host and rounded once to fp32; max_rad == 0 evaluates no hash and takes the
-// angle-0 copy path of aug_window_pos.
+// Draws (the numbers of the planes and the sites, and u / 2u - 1 / thr: draws.h).  b = the position in the minibatch (not the
+// arena row), u(h) = (h >> 8) 2^-24, thr(p) = draw_threshold(p), computed on the host once; every event is an integer
+// comparison.  2u - 1 is exact in fp32 (draw_unit) and the angle is ONE fp32 multiply of exact operands: a float64 product
+// rounded once to fp32 gives the same bits.  max_rad is rotation_deg * pi / 180 formed in double on the host and rounded
+// once to fp32; max_rad == 0 evaluates no hash and takes the angle-0 copy path of aug_window_pos.
 //
 //   site / plane    element (mod 2^32)          draw
-//   plane 0 (0,1)   depth output's linear index noise z                                       (planes 0..2: aug_gauss.h)
+//   plane 0 (0,1)   depth output's linear index noise z
 //   plane 1 (2,3)   mask output's linear index  noise z
-//   (planes 3..6, sites 14..22: pcl_augment.h; sites 23..28: tactile_augment_seeded.h)
 //   site 29         2*b + which                 angle = (2u - 1) * max_rad radians: one per (sample, tensor), shared by its T frames
 //   site 30         (b*T + t) * gh*gw + cell    depth patch kept iff h >= thr(masking_prob)
 // Only the depth frames are patch-masked; both tensors are rotated and noised (the chains of define_img_transforms).  With
@@ -29,11 +28,11 @@
 // No atomics, no workspace: the outputs are a pure function of the arguments.  tests/img_online_ref.py restates the draws.
 #pragma once
 #include "augment.h"
-#include "tactile_augment_seeded.h"
+#include "draws.h"
 
 namespace igi {
 
-constexpr unsigned int IMG_SITE_ANGLE = 29, IMG_SITE_KEEP = 30;
+static_assert(IMG_PLANE_DEPTH == 0 && IMG_PLANE_MASK == 1, "the noise plane of a tensor is its `which`");
 constexpr int IMG_MAX_CELLS = 8192;   // keep cells per frame: one byte of LDS each
 
 struct ImagePairSeededArgs {
@@ -49,7 +48,7 @@ struct ImagePairSeededArgs {
 
 __device__ __forceinline__ float img_angle(const ImagePairSeededArgs& a, long long b, int which) {
   if (a.max_rad == 0.f) return 0.f;
-  return tac_unit(tok_hash(a.c.seed, IMG_SITE_ANGLE, (unsigned int)(2 * b + which))) * a.max_rad;
+  return draw_unit(tok_hash(a.c.seed, IMG_SITE_ANGLE, (unsigned int)(2 * b + which))) * a.max_rad;
 }
 
 // grid (planes = B*T*count, bands): a workgroup owns AUG_BAND groups of four consecutive pixels of one output plane
@@ -105,7 +104,7 @@ static int image_pair_augment_seeded(const float* img, const float* seg, int64_t
   if ((!img && !seg) || (img && !out_img) || (seg && !out_seg)) return IGI_E_BADARG;
   if ((out_img && (out_img == img || out_img == seg || out_img == out_seg)) || (out_seg && (out_seg == img || out_seg == seg)))
     return IGI_E_BADARG;                                                                // an arena is never written
-  if (!pcl_prob(masking_prob) || (masking_prob > 0 && patch < 1) || !(max_rad >= 0.f)) return IGI_E_BADARG;
+  if (!draw_is_prob(masking_prob) || (masking_prob > 0 && patch < 1) || !(max_rad >= 0.f)) return IGI_E_BADARG;
   if ((long long)hs * ws > (1ll << 24)) return IGI_E_BADARG;                            // grid.y and int pixel numbers
   ImagePairSeededArgs a;
   if (int rc = aug_shape(a.c, n, t, hs, ws, rows, b, nullptr, hs, ws, 1, noise_std, seed,
@@ -118,7 +117,7 @@ static int image_pair_augment_seeded(const float* img, const float* seg, int64_t
   a.src[0] = img; a.src[1] = seg; a.dst[0] = out_img; a.dst[1] = out_seg;
   a.draws = draws; a.T = t;
   a.first = img ? 0 : 1; a.count = (img && seg) ? 2 : 1;
-  a.max_rad = max_rad; a.thr_keep = pcl_threshold(masking_prob);
+  a.max_rad = max_rad; a.thr_keep = draw_threshold(masking_prob);
   if (b * t * a.count > (1ll << 30)) return IGI_E_BADARG;
   const long long nq = (long long)hs * a.c.qpr;
   hipLaunchKernelGGL(k_image_pair_augment_seeded,

@@ -23,15 +23,15 @@
 // rotates it in place and takes the bounding box (wave butterfly, then the four waves' values: min / max do not depend on
 // order), and the store pass is element by element again: two barriers.
 //
-// Draws.  Every Bernoulli event is the integer comparison  tok_hash(...) < thr(p),  thr(p) = (u64)((double)(float)p * 2^32)
-// (oracle/token_dropout.py `threshold`, kept in 64 bits so that p = 1 is "always"): fp32 and float64 restatements agree on
-// every event.  Per-step draws hash `seed_step`; per-episode draws hash  se = seed_episode + (episode[env] << 32)  (the
+// Draws (the numbers of the planes and sites, and thr / u / the index draw: draws.h).  Every Bernoulli event is the integer
+// comparison  tok_hash(...) < thr(p),  thr(p) = draw_threshold(p): fp32 and float64 restatements agree on every event.
+// Per-step draws hash `seed_step`; per-episode draws hash  se = seed_episode + (episode[env] << 32)  (the
 // episode number enters the hash's high word), so they are a pure function of (seed_episode, env, episode[env]).
 // g = env * P_total + p is a point's number (p counted over the env's objects), g * 3 + c a coordinate's; outlier k of
 // object o uses the numbers of point off[o] + k.  Refused: N * P_total * 3 >= 2^32.
 //
 //   site / plane   seed   element        draw
-//   plane 3 (6,7)  se     env * 3 + c    pn[c], the per-episode offset            (planes 0..2: aug_gauss.h)
+//   plane 3 (6,7)  se     env * 3 + c    pn[c], the per-episode offset
 //   plane 4 (8,9)  step   g * 3 + c      jitter z
 //   plane 5 (10,11) step  g * 3 + c      free outlier z
 //   plane 6 (12,13) step  g * 3 + c      contour outlier |z|
@@ -44,7 +44,6 @@
 //   site 20        step   g              replaced index
 //   site 21        step   env * 4 + o    cloud exempt from dropout (h >= thr(1 - no_dropout_prob))
 //   site 22        step   g              drop
-//   (sites 23..28: tactile_augment_seeded.h)
 // tests/pcl_augment_ref.py restates all of it in float64.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -57,10 +56,6 @@ namespace igi {
 
 constexpr int PCL_MAX_POINTS = 4096;   // per object: the LDS cloud is 48 KB, the index list 8 KB
 constexpr int PCL_MAX_OBJECTS = 4;
-constexpr unsigned int PCL_PLANE_PN = 3, PCL_PLANE_JITTER = 4, PCL_PLANE_FREE = 5, PCL_PLANE_CONTOUR = 6;
-constexpr unsigned int PCL_SITE_HIT = 14, PCL_SITE_ANGLE = 15, PCL_SITE_AXIS = 16, PCL_SITE_MASK = 17,
-                       PCL_SITE_CONTOUR = 18, PCL_SITE_SIDE = 19, PCL_SITE_INDEX = 20, PCL_SITE_EXEMPT = 21,
-                       PCL_SITE_DROP = 22;
 constexpr int PCL_RED_FLOATS = 32;     // 4 waves x (lo[3], hi[3]), padded
 
 struct PclAugArgs {
@@ -132,19 +127,16 @@ __global__ __launch_bounds__(256) void k_pcl_augment(const PclAugArgs a) {
       const int p = i / 3, c = i - 3 * p;
       pts[i] = pcl_noise(a, src[i], g0 + (unsigned int)p, c, c == 0 ? offc[0] : c == 1 ? offc[1] : offc[2]);
     }
-    for (int k = tid; k < K; k += 256) {
-      const unsigned long long h = tok_hash(a.seed_step, PCL_SITE_INDEX, g0 + (unsigned int)k) >> 8;
-      idx[k] = (unsigned short)((h * (unsigned long long)P) >> 24);
-    }
+    for (int k = tid; k < K; k += 256)
+      idx[k] = (unsigned short)draw_index(tok_hash(a.seed_step, PCL_SITE_INDEX, g0 + (unsigned int)k), (unsigned long long)P);
     __syncthreads();
     // one thread per point: rotate in place, take the bounding box
     float sn = 0.f, cs = 1.f;
     int axis = 0;
     if (a.rot_on) {
-      const float u = (float)(tok_hash(se, PCL_SITE_ANGLE, env) >> 8) * 0x1p-24f;
-      const float deg = (2.0f * u - 1.0f) * a.rot_deg;
+      const float deg = draw_unit(tok_hash(se, PCL_SITE_ANGLE, env)) * a.rot_deg;
       sincosf(deg * 0.017453292519943295f, &sn, &cs);
-      axis = (int)(((unsigned long long)(tok_hash(se, PCL_SITE_AXIS, env) >> 8) * 3ull) >> 24);
+      axis = (int)draw_index(tok_hash(se, PCL_SITE_AXIS, env), 3);
     }
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int p = tid; p < P; p += 256) {
@@ -203,20 +195,13 @@ struct PclAugParams {            // igi_pcl_augment_params, field for field
       dropout_ratio, no_dropout_prob;
 };
 
-// oracle/token_dropout.py `threshold`, in 64 bits: p = 1 -> 2^32, above every hash
-static unsigned long long pcl_threshold(double p) {
-  return p > 0 ? (unsigned long long)((double)(float)p * 4294967296.0) : 0ull;
-}
-
-static bool pcl_prob(double p) { return p >= 0 && p <= 1; }
-
 static int pcl_augment(const float* clouds, int64_t n, int nobj, const int32_t* points, const int32_t* episode,
                        const PclAugParams& q, uint64_t seed_episode, uint64_t seed_step, float* out, hipStream_t s) {
   if (!clouds || !points || !episode || !out || n < 1 || nobj < 1 || nobj > PCL_MAX_OBJECTS || clouds == out)
     return IGI_E_BADARG;
-  if (!pcl_prob(q.noise_prob) || !pcl_prob(q.hit_prob) || !pcl_prob(q.contour_prob) || !pcl_prob(q.no_dropout_prob) ||
-      !pcl_prob(q.outlier_ratio) || !pcl_prob(q.dropout_ratio) || !(q.sigma >= 0) || !(q.noise_clip >= 0) ||
-      !(q.rot_deg >= 0))
+  if (!draw_is_prob(q.noise_prob) || !draw_is_prob(q.hit_prob) || !draw_is_prob(q.contour_prob) ||
+      !draw_is_prob(q.no_dropout_prob) || !draw_is_prob(q.outlier_ratio) || !draw_is_prob(q.dropout_ratio) ||
+      !(q.sigma >= 0) || !(q.noise_clip >= 0) || !(q.rot_deg >= 0))
     return IGI_E_BADARG;
   PclAugArgs a{};
   long long total = 0;
@@ -235,9 +220,9 @@ static int pcl_augment(const float* clouds, int64_t n, int nobj, const int32_t* 
   a.sigma = (float)q.sigma; a.clip = (float)q.noise_clip; a.const_noise = (float)q.const_noise;
   a.rot_deg = (float)q.rot_deg; a.outlier_scale = (float)q.outlier_scale;
   a.rot_on = q.rot_deg > 0; a.drop_on = q.dropout_ratio > 0;
-  a.thr_hit = pcl_threshold(q.hit_prob); a.thr_mask = pcl_threshold(q.noise_prob);
-  a.thr_contour = pcl_threshold(q.contour_prob); a.thr_side = pcl_threshold(0.5);
-  a.thr_drop = pcl_threshold(q.dropout_ratio); a.thr_exempt = pcl_threshold(1.0 - q.no_dropout_prob);
+  a.thr_hit = draw_threshold(q.hit_prob); a.thr_mask = draw_threshold(q.noise_prob);
+  a.thr_contour = draw_threshold(q.contour_prob); a.thr_side = draw_threshold(0.5);
+  a.thr_drop = draw_threshold(q.dropout_ratio); a.thr_exempt = draw_threshold(1.0 - q.no_dropout_prob);
   a.seed_episode = seed_episode; a.seed_step = seed_step;
   const dim3 grid((unsigned)(n * nobj));
   if (!a.rot_on && max_k == 0) {

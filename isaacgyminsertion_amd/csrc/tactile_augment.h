@@ -23,7 +23,6 @@ namespace igi {
 
 constexpr int TAC_MAX_PIXELS = 8192;   // the LDS window: 32 KB
 constexpr int TAC_PARAM_WORDS = 6;     // per image: top, left, jitter flag, bits of b, c, angle (radians)
-constexpr unsigned int TAC_NOISE_PLANE = 2;   // the camera pair holds planes 0 and 1
 
 struct TactileAugArgs {
   AugShape c;                    // keep: [B*planes][gh][gw]

@@ -9,14 +9,13 @@
 // per-image parameter is the counter hash of tok_hash.h evaluated by the workgroup itself (uniform over it), and the
 // image's keep grid is built in LDS by the workgroup before the chain reads it.
 //
-// Draws.  image = b * planes + plane (mod 2^32), u(h) = (h >> 8) 2^-24, thr(p) = pcl_threshold(p) of pcl_augment.h, computed
-// on the host once; every event is an integer comparison, so fp32 and a float64 restatement agree on all of them.  2u - 1 is
-// exact in fp32, and each factor below is ONE rounding of exact operands (the fmaf is explicit): float64 arithmetic rounded
-// once to fp32 gives the same bits.
+// Draws (the numbers of the plane and the sites, and u / 2u - 1 / thr: draws.h).  image = b * planes + plane (mod 2^32),
+// u(h) = (h >> 8) 2^-24, thr(p) = draw_threshold(p), computed on the host once; every event is an integer comparison, so
+// fp32 and a float64 restatement agree on all of them.  2u - 1 is exact in fp32, and each factor below is ONE rounding of
+// exact operands (the fmaf is explicit): float64 arithmetic rounded once to fp32 gives the same bits.
 //
 //   site / plane    element                  draw
-//   plane 2 (4,5)   out's linear index       noise z                                       (planes 0..2: aug_gauss.h)
-//   (planes 3..6, sites 14..22: pcl_augment.h)
+//   plane 2 (4,5)   out's linear index       noise z
 //   site 23         image                    jitter flag: h < thr(0.3)
 //   site 24         image                    brightness b = fmaf(2u - 1, 0.1f, 1.0f); 1 where the flag is off
 //   site 25         image                    contrast c, likewise
@@ -27,13 +26,11 @@
 // workgroup writes the image's record in the layout of TAC_PARAM_WORDS -- 0, 0, flag, bits of b, c, angle.
 // No atomics, no workspace: the output is a pure function of the arguments.  tests/tactile_online_ref.py restates the draws.
 #pragma once
-#include "pcl_augment.h"
+#include "draws.h"
 #include "tactile_augment.h"
 
 namespace igi {
 
-constexpr unsigned int TAC_SITE_JITTER = 23, TAC_SITE_BRIGHT = 24, TAC_SITE_CONTRAST = 25, TAC_SITE_ROTATE = 26,
-                       TAC_SITE_ANGLE = 27, TAC_SITE_KEEP = 28;
 constexpr float TAC_JITTER = 0.1f;                       // TactileAugment.JITTER
 constexpr float TAC_ROTATE_RAD = (float)(3.0 * 3.141592653589793 / 180.0);   // TactileAugment.ROTATE_DEG, in radians
 
@@ -45,8 +42,6 @@ struct TactileSeededArgs {
   int planes, masked;
   unsigned long long thr_jitter, thr_rotate, thr_keep;
 };
-
-__device__ __forceinline__ float tac_unit(unsigned int h) { return 2.0f * ((float)(h >> 8) * 0x1p-24f) - 1.0f; }   // exact
 
 // grid (images = B * planes)
 __global__ __launch_bounds__(256) void k_tactile_augment_seeded(const TactileSeededArgs a) {
@@ -62,9 +57,9 @@ __global__ __launch_bounds__(256) void k_tactile_augment_seeded(const TactileSee
   // per-image parameters: uniform over the workgroup
   const bool jit = tok_hash(c.seed, TAC_SITE_JITTER, im) < a.thr_jitter;
   const bool rot = tok_hash(c.seed, TAC_SITE_ROTATE, im) < a.thr_rotate;
-  const float jb = jit ? __fmaf_rn(tac_unit(tok_hash(c.seed, TAC_SITE_BRIGHT, im)), TAC_JITTER, 1.0f) : 1.0f;
-  const float jc = jit ? __fmaf_rn(tac_unit(tok_hash(c.seed, TAC_SITE_CONTRAST, im)), TAC_JITTER, 1.0f) : 1.0f;
-  const float ang = rot ? tac_unit(tok_hash(c.seed, TAC_SITE_ANGLE, im)) * TAC_ROTATE_RAD : 0.0f;
+  const float jb = jit ? __fmaf_rn(draw_unit(tok_hash(c.seed, TAC_SITE_BRIGHT, im)), TAC_JITTER, 1.0f) : 1.0f;
+  const float jc = jit ? __fmaf_rn(draw_unit(tok_hash(c.seed, TAC_SITE_CONTRAST, im)), TAC_JITTER, 1.0f) : 1.0f;
+  const float ang = rot ? draw_unit(tok_hash(c.seed, TAC_SITE_ANGLE, im)) * TAC_ROTATE_RAD : 0.0f;
   if (a.draws && tid == 0) {
     int* __restrict__ d = a.draws + image * TAC_PARAM_WORDS;
     d[0] = 0; d[1] = 0; d[2] = jit ? 1 : 0;
@@ -87,7 +82,7 @@ static int tactile_augment_seeded(const float* arena, int64_t n, int planes, int
                                   int out_h, int out_w, int patch, float noise_std, double masking_prob, uint64_t seed,
                                   float* out, int32_t* draws, hipStream_t s) {
   if (!arena || !out || arena == out) return IGI_E_BADARG;
-  if (!pcl_prob(masking_prob) || (masking_prob > 0 && patch < 1)) return IGI_E_BADARG;
+  if (!draw_is_prob(masking_prob) || (masking_prob > 0 && patch < 1)) return IGI_E_BADARG;
   TactileSeededArgs a;
   if (int rc = aug_shape(a.c, n, planes, hs, ws, rows, b, nullptr, out_h, out_w, 1, noise_std, seed, aligned16(out)))
     return rc;
@@ -95,7 +90,7 @@ static int tactile_augment_seeded(const float* arena, int64_t n, int planes, int
   a.masked = masking_prob > 0 && out_h / patch > 0 && out_w / patch > 0;
   if (a.masked) { a.c.patch = patch; a.c.gh = out_h / patch; a.c.gw = out_w / patch; }
   a.src = arena; a.dst = out; a.draws = draws; a.planes = planes;
-  a.thr_jitter = pcl_threshold(0.3); a.thr_rotate = pcl_threshold(0.5); a.thr_keep = pcl_threshold(masking_prob);
+  a.thr_jitter = draw_threshold(0.3); a.thr_rotate = draw_threshold(0.5); a.thr_keep = draw_threshold(masking_prob);
   hipLaunchKernelGGL(k_tactile_augment_seeded, dim3((unsigned)(b * planes)), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }

@@ -12,6 +12,8 @@ import math
 import numpy as np
 import torch
 
+from .. import draws
+
 
 class PointCloudAugmentations:
     def __init__(self, num_points=400, sigma=0.001, noise_clip=0.001, rotate_range=(-10, 10), scale_range=(0.8, 1.2),
@@ -80,45 +82,11 @@ class PointCloudAugmentations:
 # ---------------------------------------------------------------------------------------------
 # the same augmentation on the learner's side: one native launch per environment step (csrc/pcl_augment.h)
 # ---------------------------------------------------------------------------------------------
-_M32 = np.uint64(0xFFFFFFFF)
-# csrc/pcl_augment.h: the table of hash sites and Gaussian planes
-PLANE_PN, PLANE_JITTER, PLANE_FREE, PLANE_CONTOUR = 3, 4, 5, 6
-SITE_HIT, SITE_ANGLE, SITE_AXIS, SITE_MASK, SITE_CONTOUR, SITE_SIDE, SITE_INDEX, SITE_EXEMPT, SITE_DROP = range(14, 23)
-
-
-def _hash(lo, hi, site, idx):
-    """csrc/tok_hash.h in numpy uint64 arithmetic masked to 32 bits: ``lo`` / ``hi`` the seed's two words (ints or arrays
-    that broadcast against ``idx``) -> uint64 values below 2^32 of the broadcast shape."""
-    def mul(x, k):
-        return (x * np.uint64(k)) & _M32
-    lo, hi = np.asarray(lo, dtype=np.uint64) & _M32, np.asarray(hi, dtype=np.uint64) & _M32
-    x = mul(np.asarray(idx, dtype=np.uint64) & _M32, 0x9E3779B1) ^ lo ^ np.uint64((site * 0x85EBCA77) & 0xFFFFFFFF)
-    x = mul(x ^ (x >> np.uint64(16)), 0x7FEB352D)
-    x = mul(x ^ (x >> np.uint64(15)), 0x846CA68B)
-    x = ((x ^ (x >> np.uint64(16))) + hi) & _M32
-    x = mul(x ^ (x >> np.uint64(15)), 0x2C1B3C6D)
-    x = mul(x ^ (x >> np.uint64(12)), 0x297A2D39)
-    return x ^ (x >> np.uint64(15))
-
-
-def _gauss(lo, hi, plane, e):
-    """csrc/aug_gauss.h: the Box-Muller sample of (seed, plane, e), float64."""
-    k1, k2 = _hash(lo, hi, 2 * plane, e) >> np.uint64(8), _hash(lo, hi, 2 * plane + 1, e) >> np.uint64(8)
-    u1 = (k1.astype(np.float64) + 0.5) * 2.0 ** -24
-    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * math.pi * (k2.astype(np.float64) * 2.0 ** -24))
-
-
-def _threshold(p):
-    """An event of probability ``p`` is ``hash < _threshold(p)``: p rounded to float32, times 2^32, truncated (the token
-    encoder's ``make_drop``), kept above 32 bits so that p = 1 is "always"."""
-    return np.uint64(int(float(np.float32(p)) * 2.0 ** 32)) if p > 0 else np.uint64(0)
-
-
 class PclAugment:
     """``PointCloudAugmentations.augment`` with the reference's environment logic around it (factory_task_insertion.py:
     299-303, 876-881, 951-986: applied to ``hit_prob`` of the envs per step, with a per-episode offset / angle / axis), for
     the whole cloud tensor of an environment step -- ``points`` the 1..4 consecutive objects of the PointNets' layout -- and
-    with the random numbers of a call apart from its arithmetic: every draw is the counter hash of csrc/pcl_augment.h.
+    with the random numbers of a call apart from its arithmetic: every draw is the counter hash of csrc/pcl_augment.h (``draws``).
       ``draw()``                           -> the step's seed, from this object's private CPU generator;
       ``apply(clouds, episode, seed_step)`` -> the augmentation in plain torch ops, on any device and in clouds' dtype;
       ``fused(clouds, episode)``            -> draw + torch.ops.mi355ppo.pcl_augment: one launch.
@@ -163,34 +131,35 @@ class PclAugment:
         x = clouds.reshape(N, Pt, 3)
         dt, dev = x.dtype, x.device
 
-        def T(a, dtype=dt):
-            return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype)
+        def H(site, idx, seed=int(seed_step)):
+            return draws.tok_hash(seed, draws.SITES["PCL_SITE_" + site], idx)
 
+        def Z(plane, idx, seed=int(seed_step)):              # float64, then rounded once to the cloud's dtype
+            return draws.gauss(seed, draws.PLANES["PCL_PLANE_" + plane], idx, torch.float64).to(dt)
+
+        thr = draws.threshold
         f32 = lambda v: float(np.float32(v))   # noqa: E731  (the kernel receives fp32 scalars)
-        st_lo, st_hi = int(seed_step) & 0xFFFFFFFF, (int(seed_step) >> 32) & 0xFFFFFFFF
-        ep = episode.detach().cpu().numpy().astype(np.int64).astype(np.uint64) & _M32
-        ep_lo = self.seed_episode & 0xFFFFFFFF
-        ep_hi = (np.uint64((self.seed_episode >> 32) & 0xFFFFFFFF) + ep) & _M32          # se = seed + (episode << 32)
-        env = np.arange(N, dtype=np.uint64)
-        g = env[:, None] * np.uint64(Pt) + np.arange(Pt, dtype=np.uint64)[None]              # (N, Pt) point numbers
-        e = g[:, :, None] * np.uint64(3) + np.arange(3, dtype=np.uint64)                    # (N, Pt, 3)
-        hit = _hash(st_lo, st_hi, SITE_HIT, env) < _threshold(self.hit_prob)
+        ep = episode.detach().to(device=dev, dtype=torch.int64)
+        se = (self.seed_episode, (self.seed_episode >> 32) + ep)                            # se = seed + (episode << 32)
+        env = torch.arange(N, device=dev)
+        g = env[:, None] * Pt + torch.arange(Pt, device=dev)[None]                          # (N, Pt) point numbers
+        e = g[:, :, None] * 3 + torch.arange(3, device=dev)                                 # (N, Pt, 3)
+        hit = H("HIT", env) < thr(self.hit_prob)
         clip = f32(self.noise_clip)
         # a. noise
         y = x
         jit = torch.zeros_like(x)
         if self.sigma > 0:
-            mask = _hash(st_lo, st_hi, SITE_MASK, g) < _threshold(self.noise_prob)
-            z = _gauss(st_lo, st_hi, PLANE_JITTER, e)
-            jit = (T(z) * f32(self.sigma)).clamp(-clip, clip) * T(mask)[:, :, None]
+            mask = H("MASK", g) < thr(self.noise_prob)
+            jit = (Z("JITTER", e) * f32(self.sigma)).clamp(-clip, clip) * mask.to(dt)[:, :, None]
         y = y + jit
-        pn = _gauss(ep_lo, ep_hi[:, None], PLANE_PN, env[:, None] * np.uint64(3) + np.arange(3, dtype=np.uint64))
-        y = y + (T(pn) * f32(self.const_noise)).clamp(-clip, clip)[:, None, :]
+        pn = Z("PN", env[:, None] * 3 + torch.arange(3, device=dev), (se[0], se[1][:, None]))
+        y = y + (pn * f32(self.const_noise)).clamp(-clip, clip)[:, None, :]
         # b. rotation
         if self.rot_deg > 0:
-            u = (_hash(ep_lo, ep_hi, SITE_ANGLE, env) >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
-            axis = T(((_hash(ep_lo, ep_hi, SITE_AXIS, env) >> np.uint64(8)) * np.uint64(3)) >> np.uint64(24), torch.int64)
-            ang = ((2.0 * T(u) - 1.0) * f32(self.rot_deg)) * (f32(math.pi / 180) if dt == torch.float32 else math.pi / 180)
+            axis = draws.index(H("AXIS", env, se), 3)
+            unit = draws.unit(H("ANGLE", env, se)).to(dt)                                   # 2u - 1: exact
+            ang = (unit * f32(self.rot_deg)) * (f32(math.pi / 180) if dt == torch.float32 else math.pi / 180)
             cs, sn = torch.cos(ang)[:, None], torch.sin(ang)[:, None]
             a0, a1, a2 = y[..., 0], y[..., 1], y[..., 2]
             ax = axis[:, None]
@@ -199,7 +168,7 @@ class PclAugment:
             r2 = torch.where(ax == 0, a2 * cs - a1 * sn, torch.where(ax == 1, a0 * sn + a2 * cs, a2))
             y = torch.stack([r0, r1, r2], -1)
         # c. outliers, d. dropout: object by object
-        drop_all = np.zeros((N, Pt), dtype=bool)
+        drop_all = torch.zeros(N, Pt, dtype=torch.bool, device=dev)
         parts, off = [], 0
         for o, P in enumerate(pts):
             sl = y[:, off:off + P]
@@ -207,27 +176,25 @@ class PclAugment:
             if K > 0:
                 lo, hi = sl.min(dim=1, keepdim=True).values, sl.max(dim=1, keepdim=True).values
                 gk, ek = g[:, off:off + K], e[:, off:off + K]
-                contour = _hash(st_lo, st_hi, SITE_CONTOUR, gk) < _threshold(self.contour_prob)
-                idx = ((_hash(st_lo, st_hi, SITE_INDEX, gk) >> np.uint64(8)) * np.uint64(P)) >> np.uint64(24)
-                free = T(_gauss(st_lo, st_hi, PLANE_FREE, ek)) * f32(self.outlier_scale)
-                beyond = T(np.abs(_gauss(st_lo, st_hi, PLANE_CONTOUR, ek)))
-                side = T(_hash(st_lo, st_hi, SITE_SIDE, ek) < _threshold(0.5), torch.bool)
-                new = torch.where(T(contour, torch.bool)[:, :, None], torch.where(side, hi + beyond, lo - beyond), free)
-                win = np.full((N, P), -1, dtype=np.int64)                                    # the highest k wins
-                np.maximum.at(win, (np.repeat(np.arange(N), K), idx.astype(np.int64).reshape(-1)), np.tile(np.arange(K), N))
-                w = T(win, torch.int64)
+                contour = H("CONTOUR", gk) < thr(self.contour_prob)
+                idx = draws.index(H("INDEX", gk), P)
+                free = Z("FREE", ek) * f32(self.outlier_scale)
+                beyond = Z("CONTOUR", ek).abs()
+                side = H("SIDE", ek) < thr(0.5)
+                new = torch.where(contour[:, :, None], torch.where(side, hi + beyond, lo - beyond), free)
+                w = torch.full((N, P), -1, device=dev)                                       # the highest k wins
+                w.scatter_reduce_(1, idx, torch.arange(K, device=dev).expand(N, K), "amax")
                 picked = torch.gather(new, 1, w.clamp(min=0)[:, :, None].expand(N, P, 3))
                 sl = torch.where((w >= 0)[:, :, None], picked, sl)
             if self.dropout_ratio > 0:
-                live = _hash(st_lo, st_hi, SITE_EXEMPT, env * np.uint64(4) + np.uint64(o)) < _threshold(1.0 - self.no_dropout_prob)
-                drop_all[:, off:off + P] = (_hash(st_lo, st_hi, SITE_DROP, g[:, off:off + P]) <
-                                            _threshold(self.dropout_ratio)) & live[:, None]
+                live = H("EXEMPT", env * 4 + o) < thr(1.0 - self.no_dropout_prob)
+                drop_all[:, off:off + P] = (H("DROP", g[:, off:off + P]) < thr(self.dropout_ratio)) & live[:, None]
             parts.append(sl)
             off += P
         y = torch.cat(parts, 1) if len(parts) > 1 else parts[0]
         if self.dropout_ratio > 0:
-            y = torch.where(T(drop_all, torch.bool)[:, :, None], torch.zeros_like(y), y)
-        return torch.where(T(hit, torch.bool)[:, None, None], y, x).reshape(clouds.shape)
+            y = torch.where(drop_all[:, :, None], torch.zeros_like(y), y)
+        return torch.where(hit[:, None, None], y, x).reshape(clouds.shape)
 
     def fused(self, clouds, episode):
         """draw + the op; clouds above 4096 points per object take the same draws through ``apply``."""

@@ -93,6 +93,21 @@ def gauss(seed, plane, shape):
     return torch.from_numpy(z).reshape(shape)
 
 
+def threshold(p):
+    """csrc/draws.h ``draw_threshold``: p rounded to fp32, times 2^32, truncated, kept in 64 bits (p = 1: always)."""
+    return int(float(np.float32(p)) * 2.0 ** 32) if p > 0 else 0
+
+
+def _hash(seed, site, n):
+    """The hashes of elements 0 .. n - 1 of ``site``, int64."""
+    return tok_hash(int(seed), site, np.arange(n, dtype=np.uint64)).astype(np.int64)
+
+
+def _unit(seed, site, n):
+    """2u - 1, u = (h >> 8) 2^-24, of the same elements: float64, exact."""
+    return (_hash(seed, site, n) >> 8).astype(np.float64) * 2.0 ** -23 - 1.0
+
+
 def patch_mask(keep, out_h, out_w, patch):
     """uint8 (n, gh, gw) -> float64 (n, 1, out_h, out_w): the multiplier of every pixel (1 past the last whole patch)."""
     n, gh, gw = keep.shape

@@ -17,8 +17,8 @@ import math
 import numpy as np
 import torch
 
-from oracle.token_dropout import tok_hash
 from tests import img_augment_ref as A
+from tests.img_augment_ref import _hash, _unit, threshold  # noqa: F401  (the tests reach them through this module)
 
 SITES = {"ANGLE": 29, "KEEP": 30}
 TIE_SHARE_MAX = 0.001
@@ -35,15 +35,6 @@ ENGINE = dict(envs=8, horizon=4, mini_epochs=4, seed=42, hw=(54, 96), rotation_d
               patch=16)
 
 
-def threshold(p):
-    """csrc/pcl_augment.h ``pcl_threshold``: p rounded to fp32, times 2^32, truncated, kept in 64 bits (p = 1: always)."""
-    return int(float(np.float32(p)) * 2.0 ** 32) if p > 0 else 0
-
-
-def _hash(seed, site, n):
-    return tok_hash(int(seed), site, np.arange(n, dtype=np.uint64)).astype(np.int64)
-
-
 def max_rad(rotation_deg):
     """The fp32 the kernel is handed, as a Python float: the product in double, rounded once."""
     return float(np.float32(rotation_deg * math.pi / 180))
@@ -54,8 +45,7 @@ def draws(B, T, seed, H, W, patch, masking_prob, rotation_deg):
     B, T = int(B), int(T)
     ang = np.zeros(2 * B, dtype=np.float32)
     if rotation_deg > 0:
-        unit = (_hash(seed, SITES["ANGLE"], 2 * B) >> 8).astype(np.float64) * 2.0 ** -23 - 1.0
-        ang = (unit * max_rad(rotation_deg)).astype(np.float32)
+        ang = (_unit(seed, SITES["ANGLE"], 2 * B) * max_rad(rotation_deg)).astype(np.float32)
     gh, gw = H // patch, W // patch
     keep = None
     if masking_prob > 0 and gh * gw > 0:

@@ -1,6 +1,6 @@
 """Float64 restatement of the point-cloud augmentation (csrc/pcl_augment.h) -- TEST INFRASTRUCTURE, independent of
 ``PclAugment.apply``: plain loops over envs and objects, numpy over the points, every draw from
-``oracle.token_dropout.tok_hash`` / ``threshold`` and the ``gauss`` of tests/img_augment_ref.py.
+``oracle.token_dropout.tok_hash`` and the ``gauss`` / ``threshold`` of tests/img_augment_ref.py.
 
 Sites and planes are those tabled in the header.  ``g = env * P_total + p`` numbers a point (p over the env's objects),
 ``g * 3 + c`` a coordinate; outlier k of object o uses the numbers of point ``off[o] + k``.  Per-episode draws hash
@@ -10,8 +10,8 @@ import math
 import numpy as np
 import torch
 
-from oracle.token_dropout import threshold, tok_hash
-from tests.img_augment_ref import gauss
+from oracle.token_dropout import tok_hash
+from tests.img_augment_ref import gauss, threshold
 
 PLANE_PN, PLANE_JITTER, PLANE_FREE, PLANE_CONTOUR = 3, 4, 5, 6
 SITE_HIT, SITE_ANGLE, SITE_AXIS, SITE_MASK, SITE_CONTOUR, SITE_SIDE, SITE_INDEX, SITE_EXEMPT, SITE_DROP = range(14, 23)
@@ -33,11 +33,8 @@ def f32(v):
 
 
 def event(h, p):
-    """hash < threshold(p), with p = 1 "always" (``threshold`` itself is 32 bits wide and defined below 1)."""
-    h = np.asarray(h)
-    if float(np.float32(p)) >= 1.0:
-        return np.ones(h.shape, dtype=bool)
-    return h < threshold(p)
+    """hash < threshold(p), the 64-bit threshold: p = 1 is "always"."""
+    return np.asarray(h).astype(np.int64) < threshold(p)
 
 
 def episode_seed(seed_episode, ep):

@@ -16,8 +16,8 @@ import math
 import numpy as np
 import torch
 
-from oracle.token_dropout import tok_hash
 from tests import tactile_augment_ref as R
+from tests.img_augment_ref import _hash, _unit, threshold  # noqa: F401  (the tests reach them through this module)
 
 SITES = dict(JITTER=23, BRIGHT=24, CONTRAST=25, ROTATE=26, ANGLE=27, KEEP=28)
 JITTER_P, ROTATE_P, JITTER, ROTATE_DEG = 0.3, 0.5, 0.1, 3.0
@@ -33,19 +33,6 @@ EDGE_SEED = 11                                           # the one image of 64 x
 # the trainer cases: 8 envs x 4 steps in 4 minibatches of 8 rows x 3 fingers, 4 mini-epochs = 16 optimizer steps per epoch;
 # the step seeds are the stream of a private generator seeded cfg.seed (42)
 ENGINE = dict(envs=8, horizon=4, mini_epochs=4, seed=42)
-
-
-def threshold(p):
-    """csrc/pcl_augment.h ``pcl_threshold``: p rounded to fp32, times 2^32, truncated, kept in 64 bits (p = 1: always)."""
-    return int(float(np.float32(p)) * 2.0 ** 32) if p > 0 else 0
-
-
-def _hash(seed, site, n):
-    return tok_hash(int(seed), site, np.arange(n, dtype=np.uint64)).astype(np.int64)
-
-
-def _unit(seed, site, n):
-    return (_hash(seed, site, n) >> 8).astype(np.float64) * 2.0 ** -23 - 1.0
 
 
 def draws(n_images, seed, out_h, out_w, patch, masking_prob):

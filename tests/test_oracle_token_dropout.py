@@ -20,9 +20,10 @@ PINNED = [
 
 
 def test_tok_hash_reproduces_the_header():
-    """The literal values were generated once by a scratch C++ program holding a copy of tok_hash's text from
-    csrc/token_encoder.h, compiled for the host (the program is not part of the repository).  Seeds with a zero and a
-    non-zero high word (the ``seed >> 32`` add), sites of both layers, elements above 2^16 and the last uint32."""
+    """The literal values are ``hash`` lines of tools/draws_check.cpp, a host program that includes csrc/tok_hash.h itself
+    (``g++ -std=c++17 tools/draws_check.cpp -o draws_check && ./draws_check`` regenerates them; tests/test_draws_cpu.py
+    compares the list with its output).  Seeds with a zero and a non-zero high word (the ``seed >> 32`` add), sites of both
+    layers, elements above 2^16 and the last uint32."""
     from oracle import token_dropout as td
     for seed, site, idx, want in PINNED:
         assert int(td.tok_hash(seed, site, np.array([idx]))[0]) == want, (seed, site, idx)

@@ -53,20 +53,20 @@ def test_names_through_both_import_paths():
 
 
 def test_header_table_and_python_tables_agree():
-    P = _P()
-    hdr = open(os.path.join(ROOT, "isaacgyminsertion_amd", "csrc", "pcl_augment.h")).read()
+    from isaacgyminsertion_amd import draws
+    hdr = open(os.path.join(ROOT, "isaacgyminsertion_amd", "csrc", "draws.h")).read()
     for name in ("PN", "JITTER", "FREE", "CONTOUR"):
         v = int(re.search(rf"PCL_PLANE_{name} = (\d+)", hdr).group(1))
-        assert v == getattr(P, f"PLANE_{name}") == getattr(R, f"PLANE_{name}") and v > 2      # planes 0..2 are taken
+        assert v == draws.PLANES[f"PCL_PLANE_{name}"] == getattr(R, f"PLANE_{name}") and v > 2      # planes 0..2 are taken
     for name in ("HIT", "ANGLE", "AXIS", "MASK", "CONTOUR", "SIDE", "INDEX", "EXEMPT", "DROP"):
         v = int(re.search(rf"PCL_SITE_{name} = (\d+)", hdr).group(1))
-        assert v == getattr(P, f"SITE_{name}") == getattr(R, f"SITE_{name}") and v > 13       # sites 0..13 are the planes'
+        assert v == draws.SITES[f"PCL_SITE_{name}"] == getattr(R, f"SITE_{name}") and v > 13        # sites 0..13 are the planes'
     idx = np.arange(1000)
     for seed in (0, 12345678901234567, 2 ** 64 - 1):
-        assert np.array_equal(P._hash(seed & 0xFFFFFFFF, seed >> 32, 17, idx), tok_hash(seed, 17, idx).astype(np.uint64))
+        assert np.array_equal(draws.tok_hash(seed, 17, torch.from_numpy(idx)).numpy(), tok_hash(seed, 17, idx).astype(np.int64))
     for p in (0.0, 0.1, 0.3, 0.5, 0.75):
-        assert int(P._threshold(p)) == int(threshold(p))
-    assert int(P._threshold(1.0)) == 2 ** 32                        # above every hash: always
+        assert draws.threshold(p) == int(threshold(p))
+    assert draws.threshold(1.0) == 2 ** 32                          # above every hash: always
 
 
 # ---- the restatement against the reference's arithmetic ------------------------------------------------------------------
@@ -233,8 +233,8 @@ def test_event_frequencies():
     exempt = ~R.event(tok_hash(seed, R.SITE_EXEMPT, np.arange(n)), R.f32(1.0 - 0.8))
     assert within(int(exempt.sum()), n, 0.8)
     axes = np.array([R.episode_params(a.seed_episode, env, 0, 10.0)[1] for env in range(n // 8)])   # 3000 envs ...
-    h = P._hash(a.seed_episode & 0xFFFFFFFF, a.seed_episode >> 32, R.SITE_AXIS, np.arange(n))       # ... and n through the hash
-    ax = ((h >> np.uint64(8)) * np.uint64(3)) >> np.uint64(24)
+    from isaacgyminsertion_amd import draws
+    ax = draws.index(draws.tok_hash(a.seed_episode, R.SITE_AXIS, torch.arange(n)), 3).numpy()       # ... and n through the hash
     assert np.array_equal(ax[:n // 8].astype(int), axes) and set(ax.tolist()) == {0, 1, 2}
     for k in range(3):
         assert within(int((ax == k).sum()), n, 1 / 3)

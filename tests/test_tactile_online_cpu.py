@@ -34,7 +34,7 @@ def test_names_through_both_import_paths():
     from isaacgyminsertion_amd.algo.ext_adapt import ext_adapt
     from isaacgyminsertion_amd.algo.ppo.experience import _LazyMinibatch
     assert shim_u.TactileAugment is U.TactileAugment is ext_adapt.TactileAugment is shim_e.TactileAugment
-    assert shim_u.TACTILE_SITES is U.TACTILE_SITES
+    assert shim_u.define_tactile_transforms is U.define_tactile_transforms
     for name in ("draw_seeded", "fused_seeded"):
         assert callable(getattr(U.TactileAugment, name))
     assert hasattr(ext_adapt.ExtrinsicAdapt, "_make_tactile_augment")
@@ -48,28 +48,31 @@ def test_names_through_both_import_paths():
 
 def test_site_table_of_the_header_and_the_python_tables_agree_and_share_no_site():
     U = _U()
+    from isaacgyminsertion_amd import draws
     hdr = open(os.path.join(CSRC, "tactile_augment_seeded.h")).read()
-    pcl = open(os.path.join(CSRC, "pcl_augment.h")).read()
+    tbl = open(os.path.join(CSRC, "draws.h")).read()
     names = dict(JITTER="JITTER", BRIGHT="BRIGHT", CONTRAST="CONTRAST", ROTATE="ROTATE", ANGLE="ANGLE", KEEP="KEEP")
-    ours = {k: int(re.search(rf"TAC_SITE_{v} = (\d+)", hdr).group(1)) for k, v in names.items()}
-    assert ours == U.TACTILE_SITES == O.SITES == dict(JITTER=23, BRIGHT=24, CONTRAST=25, ROTATE=26, ANGLE=27, KEEP=28)
+    ours = {k: int(re.search(rf"TAC_SITE_{v} = (\d+)", tbl).group(1)) for k, v in names.items()}
+    assert ours == {k: draws.SITES["TAC_SITE_" + k] for k in ours} == O.SITES
+    assert ours == dict(JITTER=23, BRIGHT=24, CONTRAST=25, ROTATE=26, ANGLE=27, KEEP=28)
     for k, v in ours.items():                                 # the comment table says the same
         assert re.search(rf"//\s+site {v}\b", hdr), k
-    pcl_sites = {int(v) for v in re.findall(r"PCL_SITE_\w+ = (\d+)", pcl)}
-    pcl_planes = {int(v) for v in re.findall(r"PCL_PLANE_\w+ = (\d+)", pcl)}
+    pcl_sites = {int(v) for v in re.findall(r"PCL_SITE_\w+ = (\d+)", tbl)}
+    pcl_planes = {int(v) for v in re.findall(r"PCL_PLANE_\w+ = (\d+)", tbl)}
     assert pcl_sites == set(range(14, 23)) and pcl_planes == {3, 4, 5, 6}
     gauss_sites = {2 * p + k for p in {0, 1, 2} | pcl_planes for k in (0, 1)}          # aug_gauss.h: sites 2p, 2p + 1
     assert gauss_sites == set(range(14))
-    assert "2u * plane" in open(os.path.join(CSRC, "aug_gauss.h")).read() and R.NOISE_PLANE == U.TACTILE_NOISE_PLANE == 2
+    assert int(re.search(r"TAC_NOISE_PLANE = (\d+)", tbl).group(1)) == 2
+    assert "2u * plane" in open(os.path.join(CSRC, "aug_gauss.h")).read()
+    assert R.NOISE_PLANE == draws.PLANES["TAC_NOISE_PLANE"] == 2
     assert len(set(ours.values())) == 6 and not set(ours.values()) & (pcl_sites | gauss_sites)
     # the probabilities and amplitudes of the class are the restatement's and the header's
     T = U.TactileAugment
     assert (T.JITTER_P, T.ROTATE_P, T.JITTER, T.ROTATE_DEG) == (O.JITTER_P, O.ROTATE_P, O.JITTER, O.ROTATE_DEG)
-    assert "pcl_threshold(0.3)" in hdr and "pcl_threshold(0.5)" in hdr and "TAC_JITTER = 0.1f" in hdr
+    assert "draw_threshold(0.3)" in hdr and "draw_threshold(0.5)" in hdr and "TAC_JITTER = 0.1f" in hdr
     assert "3.0 * 3.141592653589793 / 180.0" in hdr and "__fmaf_rn" in hdr
-    from isaacgyminsertion_amd.envs.pcl_augment import _threshold
     for p in (0.0, 0.3, 0.5, 0.75, 1.0):
-        assert U._hash_threshold(p) == int(_threshold(p)) == O.threshold(p)
+        assert draws.threshold(p) == O.threshold(p)
     assert O.threshold(1.0) == 2 ** 32
 
 
