@@ -99,6 +99,20 @@ int igi_gemm_set_bf16_inputs(int on);
  * when IT is called: a forward / backward pair must run under ONE setting (the Python op's autograd formula records the
  * forward's setting and re-establishes it around the backward).  on < 0 only queries.  Returns the previous setting. */
 int igi_conv_set_bf16_inputs(int on);
+/* Opt-in split-bf16 mode of the same three convolutions (forward, data gradient and weight gradient of every layer, on
+ * every tile the encoder launches): fp32-grade results from the bf16 matrix pipe.  Every operand element is split where
+ * the MFMA operands are formed into three bf16 planes, x = hi + mid + lo (hi = bf16(x), mid = bf16(x - hi),
+ * lo = bf16(x - hi - mid): three nearest-even conversions, two exact fp32 differences; exact for 2^-103 <= |x| <= the
+ * largest bf16, and for 0), and every product term is the sum of the six plane products mid*mid, lo*hi, hi*lo, mid*hi,
+ * hi*mid, hi*hi -- issued in that order inside each 16-k step, each exact in fp32, accumulated in fp32 on
+ * v_mfma_f32_32x32x16_bf16; mid*lo, lo*mid and lo*lo, below 2^-24 of the leading product, are dropped.  Operands stay fp32
+ * in memory; tiles, launch count, loaders, epilogues, the soft-argmax kernels, the 128 -> latent Linear and the split-K
+ * reductions are the fp32 path's; two runs are bit-identical.  Off by default; IGI_CONV_BF16X3=1 in the environment
+ * starts it on.  A switch of its own: igi_conv_set_bf16_inputs, igi_gemm_set_bf16_inputs, igi_gemm_set_bf16x3 and
+ * igi_depth_set_bf16_inputs neither set it nor are set by it, and it reaches nothing but the tactile convolutions.  With
+ * this switch and igi_conv_set_bf16_inputs BOTH on, igi_tactile_forward and igi_tactile_backward return IGI_E_BADARG.
+ * A forward / backward pair must run under ONE setting, as above.  on < 0 only queries.  Returns the previous setting. */
+int igi_conv_set_bf16x3(int on);
 /* The same opt-in mode for the six large products of the depth backbone (igi_depth_forward / igi_depth_backward): conv2
  * (3 x 3, 32 -> 64) forward, data gradient and weight gradient, and the 64768 -> 128 Linear forward (split-K), data
  * gradient (with its ELU' epilogue) and weight gradient.  Each product term is float(bf16(a)) * float(bf16(b)), round to

@@ -109,6 +109,7 @@ _EXPORTS = {
     "igi_build_info": (C.c_char_p, []),
     "igi_gemm_set_bf16_inputs": (C.c_int, [C.c_int]),
     "igi_conv_set_bf16_inputs": (C.c_int, [C.c_int]),
+    "igi_conv_set_bf16x3": (C.c_int, [C.c_int]),
     "igi_depth_set_bf16_inputs": (C.c_int, [C.c_int]),
     "igi_gemm_set_bf16x3": (C.c_int, [C.c_int]),
     "igi_teacher_set_latz_fuse": (C.c_int, [C.c_int]),

@@ -85,6 +85,13 @@ class Runner:
         # forward's setting by itself: ops.tactile_cnn_fwd).  None = key absent: the process switch is left alone.
         self.conv_bf16_inputs = bool(self.cfg.model.get('conv_bf16_inputs', False)) \
             if 'conv_bf16_inputs' in self.cfg.model else None
+        # offline_train.model.conv_bf16x3 (not a reference key either): the same three convolutions in split-bf16
+        # arithmetic (ops.conv_bf16x3: three exact bf16 planes per operand, fp32-grade results).  None = key absent: the
+        # process switch is left alone.  The two arithmetics exclude each other.
+        self.conv_bf16x3 = bool(self.cfg.model.get('conv_bf16x3', False)) if 'conv_bf16x3' in self.cfg.model else None
+        if self.conv_bf16_inputs and self.conv_bf16x3:
+            raise ValueError("offline_train.model: conv_bf16_inputs and conv_bf16x3 are both True; "
+                             "the tactile convolutions run in one arithmetic")
         # offline_train.model.depth_bf16_inputs (not a reference key either): the same for the depth backbone's conv2 and
         # 64768 -> 128 Linear (ops.depth_bf16_inputs; the camera and segmentation encoders), a switch of its own --
         # conv_bf16_inputs keeps meaning "tactile convolutions only".  None = key absent: left alone.
@@ -171,10 +178,12 @@ class Runner:
         return self.model
 
     def _conv_mode(self):
-        """the two bf16-input switches this Runner's config names, around one forward of its model"""
+        """the arithmetic switches this Runner's config names, around one forward of its model"""
         stack = contextlib.ExitStack()
         if self.conv_bf16_inputs is not None:
             stack.enter_context(ops.conv_bf16_inputs(self.conv_bf16_inputs))
+        if getattr(self, 'conv_bf16x3', None) is not None:
+            stack.enter_context(ops.conv_bf16x3(self.conv_bf16x3))
         if getattr(self, 'depth_bf16_inputs', None) is not None:
             stack.enter_context(ops.depth_bf16_inputs(self.depth_bf16_inputs))
         return stack

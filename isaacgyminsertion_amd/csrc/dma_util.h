@@ -40,6 +40,18 @@ static inline int& conv_bf16_mode_ref() {
 }
 static inline int conv_bf16_mode() { return conv_bf16_mode_ref(); }
 
+// opt-in split-bf16 mode of the same three convolutions: fp32 operands split exactly into three bf16 planes where the MFMA
+// operands are formed, six plane products per term on v_mfma_f32_32x32x16_bf16, fp32 accumulation -- fp32-grade results
+// (gemm_dma.h, gemm_dma_conv_x3_kernel).  IGI_CONV_BF16X3=1 in the environment, or igi_conv_set_bf16x3().  A switch of
+// its own: neither conv_bf16_mode() nor x3_mode() (the plain products' experiment) sets or reads it, and the tactile
+// encoder refuses to run with this one and conv_bf16_mode() both on.
+static inline int& conv_x3_mode_ref() {
+  static int m = -1;
+  if (m < 0) { const char* e = getenv("IGI_CONV_BF16X3"); m = e ? (atoi(e) != 0) : 0; }
+  return m;
+}
+static inline int conv_x3_mode() { return conv_x3_mode_ref(); }
+
 // opt-in bf16-input mode of the depth backbone's six large products (conv2 and the 64768 -> 128 Linear: forward, data
 // gradient, weight gradient; depth.h): IGI_DEPTH_BF16=1 in the environment, or igi_depth_set_bf16_inputs().  Independent
 // of the two switches above: nothing but depth.h reads it, and depth.h reads neither of them.

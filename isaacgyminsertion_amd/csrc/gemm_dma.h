@@ -534,7 +534,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, int n_tiles, in
   constexpr int NW = DMA_WAVES / KG;
   constexpr int WGM = KG == 2 ? 2 : ((BN == 32) ? 8 : ((BN == 64) ? 4 : 2)), WGN = NW / WGM;
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
-  static_assert(KG == 1 || (BN == 64 && (BF16IN == 0 || BF16IN == 1) && STORE_ONLY_OK<STORE_ONLY, HEAD, false, TANHGRAD_ONLY, Hook>::value),
+  static_assert(KG == 1 || (BN == 64 && (BF16IN == 0 || BF16IN == 1 || BF16IN == 6) && STORE_ONLY_OK<STORE_ONLY, HEAD, false, TANHGRAD_ONLY, Hook>::value),
                 "the 192-row tile is built for the plain-store weight-gradient products");
   static_assert(BN != 32 || NS == 2, "waves issue unequal DMA counts on a 32-wide tile: no counted vmcnt waits");
   constexpr int TM = WTM / 32, TN = WTN / 32;
@@ -666,11 +666,14 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g, int n_tiles, in
     const float* as = smem + S * STAGE;
     const float* bs = as + A_FLOATS;
     if constexpr (BF16IN == 6 || BF16IN == 9) {
-      // fp32 on the bf16 pipe, exact three-plane split (experiment, x3_mode): the lane splits the eight k it feeds into
-      // hi / mid / lo planes and issues the cross products smallest first -- nothing is rounded before the accumulator
+      // fp32 on the bf16 pipe, exact three-plane split (x3_mode: experiment; conv_x3_mode: the tactile convolutions' opt-in
+      // mode): the lane splits the eight k it feeds into hi / mid / lo planes and issues the cross products smallest first --
+      // nothing is rounded before the accumulator
+      // (KG == 2: one 16-k half per wave group, the partial accumulators meet in the epilogue as on the fp32 path)
       if (kt + NS - 1 < nk) issue(kt + NS - 1, std::integral_constant<int, (S + NS - 1) % NS>{});
 #pragma unroll
-      for (int gk = 0; gk < 2; ++gk) {
+      for (int g2 = 0; g2 < 2 / KG; ++g2) {
+        const int gk = KG == 2 ? kg : g2;
         bf16x8 ah[TM], am[TM], al[TM], bh[TN], bm[TN], bl[TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -1090,6 +1093,28 @@ __global__ __launch_bounds__(DMA_THREADS) void gemm_dma_bf16_kernel(const GemmAr
   gemm_dma_body<128, A_KC, B_KC, 0, 2, DMA_BM, false, false, 1>(g, n_tiles, m_tiles, xcd_remap(blockIdx.x, gridDim.x));
 }
 
+// the im2col tiles of the tactile convolutions in split-bf16 arithmetic (conv_x3_mode(), opt-in): same loaders, LDS images
+// and epilogues as gemm_dma_kernel<BN, A_KC, B_KC, GATHER, NS, BM>, the six-product inner loop (BF16IN == 6).
+//   * split: every operand element x = hi + mid + lo by split3_bf16 -- three round-to-nearest-even conversions and two
+//     exact fp32 differences, formed per lane where the MFMA operands are formed; operands stay fp32 in memory and in the
+//     LDS images, nothing is stored rounded.  The split is exact for every normal fp32 x whose lo plane does not underflow:
+//     the remainders are multiples of ulp(x) = 2^(e-23), |x - hi| <= 2^(e-8) and |x - hi - mid| <= 2^(e-17), so the 24
+//     significant bits fall into 8 + 8 + 7.  Guaranteed range 2^-103 <= |x| <= 0x1.FEp127 (the largest bf16): every
+//     non-zero remainder and plane is then a NORMAL number (>= 2^-126), whatever the denormal mode.  With gradual underflow
+//     (the host restatement, tests/conv_x3_ref.py) the split stays exact down to |x| >= 2^-110 (bf16 subnormals are
+//     multiples of 2^-133); below that lo rounds.  Zero splits to zero planes (hi keeps the sign, mid = lo = +0); values
+//     above the largest bf16, infinities and NaN are outside the contract.
+//   * products: a * w = sum over the six plane pairs {mid*mid, lo*hi, hi*lo, mid*hi, hi*mid, hi*hi}, issued in that order
+//     (smallest first) inside each 16-k step; mid*lo, lo*mid and lo*lo (below 2^-24 of the leading product) are dropped.
+//     Every plane product is exact in fp32 (8 x 8 significant bits); accumulation is fp32, on v_mfma_f32_32x32x16_bf16.
+//   * everything behind the accumulators (bias + ReLU, ReLU', bias-gradient sums of the un-split fp32 image, soft-argmax
+//     partials, split-k slabs) is the fp32 path's code; tile choice and launch count are the fp32 path's.
+template <int BN, bool A_KC, bool B_KC, int GATHER, int NS, int BM>
+__global__ __launch_bounds__(DMA_THREADS) void gemm_dma_conv_x3_kernel(const GemmArgs g, int n_tiles, int m_tiles) {
+  static_assert(GATHER != 0 && GATHER != 2, "im2col products of the tactile encoder only");
+  gemm_dma_body<BN, A_KC, B_KC, GATHER, NS, BM, false, false, 6>(g, n_tiles, m_tiles, xcd_remap(blockIdx.x, gridDim.x));
+}
+
 // EXPERIMENT (x3_mode): the k-contiguous forward product with every operand split into three exact bf16 planes in the loop
 template <int PRODUCTS>
 __global__ __launch_bounds__(DMA_THREADS) void gemm_dma_x3_kernel(const GemmArgs g, int n_tiles, int m_tiles) {
@@ -1358,7 +1383,7 @@ constexpr size_t DMA_SHM_128X2 = sizeof(float) * 2 * (DMA_BM + 128) * DMA_BK > s
     IGI_LAUNCH((KERNEL), GRID, dim3(DMA_THREADS), SHM, STREAM, __VA_ARGS__);                           \
   } while (0)
 
-template <int BN, int NS = DMA_NS, int BM = DMA_BM, bool BF = false>
+template <int BN, int NS = DMA_NS, int BM = DMA_BM, int BF = 0>
 static hipError_t launch_dma_cfg(const GemmArgs& g, bool akc, bool bkc, hipStream_t s) {
   const int n_tiles = (g.N + BN - 1) / BN, m_tiles = (g.M + BM - 1) / BM;
   const int total = n_tiles * m_tiles * g.nbatch * g.splitk;
@@ -1384,10 +1409,16 @@ static hipError_t launch_dma_cfg(const GemmArgs& g, bool akc, bool bkc, hipStrea
   const size_t shm_cap = shm_max > EPI_BYTES ? shm_max : EPI_BYTES;
   const dim3 grid(total);
 #define IGI_DMA_LAUNCH_K(KERNEL) IGI_DMA_LAUNCH_SHM(KERNEL, grid, shm_cap, shm, s, gg, n_tiles, m_tiles)
-  // BF: the bf16-input twin of the same tile (im2col products A = gather 1 / 3 with a k-contiguous weight operand only)
+  // BF: the bf16-input twin (1) or the split-bf16 twin (6) of the same tile (im2col products A = gather 1 / 3 with a
+  // k-contiguous weight operand only)
 #define IGI_DMA_LAUNCH(AK, BK_, GA)                                                                    \
   do {                                                                                                 \
-    if constexpr (BF) {                                                                                \
+    static_assert(BF == 0 || BF == 1 || BF == 6, "fp32, bf16-input or split-bf16 tiles");              \
+    if constexpr (BF == 6) {                                                                           \
+      if constexpr ((GA) != 0 && (GA) != 2 && ((GA) == 3 || (GA) == 5 || (BK_)))                      \
+        IGI_DMA_LAUNCH_K((gemm_dma_conv_x3_kernel<BN, AK, BK_, GA, NS, BM>));                          \
+      else return hipErrorInvalidValue;                                                                \
+    } else if constexpr (BF == 1) {                                                                    \
       if constexpr ((GA) != 0 && (GA) != 2 && ((GA) == 3 || (GA) == 5 || (BK_)))                      \
         IGI_DMA_LAUNCH_K((gemm_dma_conv_bf16_kernel<BN, AK, BK_, GA, NS, BM>));                        \
       else return hipErrorInvalidValue;                                                                \
@@ -1484,12 +1515,15 @@ static inline bool conv_ssa_fusable(long long M, int N, int P, int nbatch = 1, i
   return conv_tall_fwd(M, N, nbatch, splitk) && N > 32 && (P & 31) == 0 && (M & (CONV_BM_TALL - 1)) == 0;
 }
 
-// One im2col tile under its profiler class: fp32 inputs, or the bf16-input twin of the same tile (GemmArgs::conv_bf16)
+// One im2col tile under its profiler class: fp32 inputs, or the bf16-input (GemmArgs::conv_bf16 == 1) or split-bf16 (== 6)
+// twin of the same tile; the split-bf16 class of a tile sits PC_CONVX_TALL64_TT - PC_CONVB_TALL64_TT behind its bf16 class
 template <int BN, int NS, int BM>
 static hipError_t launch_conv_tile(const GemmArgs& g, bool akc, bool bkc, hipStream_t s, int pc_f32, int pc_bf16,
                                    double fl, double by) {
-  ProfScope ps(g.conv_bf16 ? pc_bf16 : pc_f32, s, fl, by);
-  return g.conv_bf16 ? launch_dma_cfg<BN, NS, BM, true>(g, akc, bkc, s) : launch_dma_cfg<BN, NS, BM>(g, akc, bkc, s);
+  const int pc_x3 = pc_bf16 + (PC_CONVX_TALL64_TT - PC_CONVB_TALL64_TT);
+  ProfScope ps(g.conv_bf16 == 6 ? pc_x3 : (g.conv_bf16 ? pc_bf16 : pc_f32), s, fl, by);
+  if (g.conv_bf16 == 6) return launch_dma_cfg<BN, NS, BM, 6>(g, akc, bkc, s);
+  return g.conv_bf16 ? launch_dma_cfg<BN, NS, BM, 1>(g, akc, bkc, s) : launch_dma_cfg<BN, NS, BM>(g, akc, bkc, s);
 }
 
 // A plain product on the 128 x 128 two-stage tile with the bf16-input inner loop (gemm_dma_bf16_kernel): same tiles,
@@ -1525,9 +1559,10 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   const bool tall_fwd = g.gather == 1 && conv_tall_fwd(g.M, g.N, g.nbatch, g.splitk);
   if (g.ssa_part && !(g.gather == 1 && conv_ssa_fusable(g.M, g.N, g.ssa_P, g.nbatch, g.splitk) && !conv_pmajor_ok(g, bkc)))
     return hipErrorInvalidValue;   // the caller plans the fused soft-argmax with conv_ssa_fusable(): only that tile emits it
-  // conv_bf16 (the tactile encoder under conv_bf16_mode()): the SAME tile choice, the bf16-input twin of each tile and a
-  // profiler class of its own (launch_conv_tile).  Only the shapes that encoder launches are built: anything else is an
-  // error, not fp32.
+  // conv_bf16 (the tactile encoder under conv_bf16_mode(): 1, under conv_x3_mode(): 6): the SAME tile choice, the
+  // bf16-input or split-bf16 twin of each tile and a profiler class of its own (launch_conv_tile).  Only the shapes that
+  // encoder launches are built: anything else is an error, not fp32.
+  if (g.conv_bf16 != 0 && g.conv_bf16 != 1 && g.conv_bf16 != 6) return hipErrorInvalidValue;
   const bool cbf = g.conv_bf16 != 0;
   if (cbf && !(g.N <= 64 && ((g.gather == 1 && akc && bkc) || (g.gather == 3 && !akc && !bkc)))) return hipErrorInvalidValue;
   // bf16_inputs (the depth backbone's big Linear under depth_bf16_mode()): this call on the 128 x 128 two-stage tile with
@@ -1568,8 +1603,10 @@ static hipError_t gemm(GemmArgs g, bool akc, bool bkc, hipStream_t s) {
   // 128-wide tile's 73 KB of epilogue staging allows two workgroups per CU; 64-wide tiles stage 37 KB: 20.6 -> 19.4 us
   if (bn == 128 && !g.gather && g.K <= DMA_BK) bn = 64;
   if (cbf) {   // the 128-row, 64-wide, three-stage tile of small batches (N <= 64: checked above)
-    ProfScope ps(g.gather == 1 ? PC_CONVB_ROW64 : (conv_pw_ok(g) ? PC_CONVB_PW64_128 : PC_CONVB_WG64), s, fl, by);
-    return launch_dma_cfg<64, DMA_NS, DMA_BM, true>(g, akc, bkc, s);
+    const int pcb = g.gather == 1 ? PC_CONVB_ROW64 : (conv_pw_ok(g) ? PC_CONVB_PW64_128 : PC_CONVB_WG64);
+    ProfScope ps(g.conv_bf16 == 6 ? pcb + (PC_CONVX_TALL64_TT - PC_CONVB_TALL64_TT) : pcb, s, fl, by);
+    if (g.conv_bf16 == 6) return launch_dma_cfg<64, DMA_NS, DMA_BM, 6>(g, akc, bkc, s);
+    return launch_dma_cfg<64, DMA_NS, DMA_BM, 1>(g, akc, bkc, s);
   }
   const int lay = akc ? (bkc ? 0 : 1) : (bkc ? 3 : 2);
   ProfScope ps((bn == 128 ? PC_DMA_128_TT : PC_DMA_64_TT) + lay, s, fl, by);

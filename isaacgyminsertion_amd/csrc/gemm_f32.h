@@ -129,7 +129,8 @@ struct GemmArgs {
                            // | 3 A = im2col (reduction-major): conv weight gradient with taps on the M side
   int bias_from_b = 0;     // Cbias = column sums of B over k (instead of A), indexed by n
   int conv_bf16 = 0;       // im2col products only (set by the tactile encoder from conv_bf16_mode() and by the depth
-                           // backbone from depth_bf16_mode()): bf16-input tiles
+                           // backbone from depth_bf16_mode()): 1 = bf16-input tiles; 6 = split-bf16 tiles (the tactile
+                           // encoder under conv_x3_mode(): three exact bf16 planes per operand, six plane products)
   int bf16_inputs = 0;     // plain (not gathered) products: THIS call runs the 128 x 128 tile's bf16-input inner loop, whatever
                            // bf16_mode() says (the depth backbone's big Linear under depth_bf16_mode()); gemm_dma.h, gemm()
   double flop_credit = 1.0;  // profiler only: algorithmic / executed flops (zero-padded operands, e.g. K 23 run as 32)

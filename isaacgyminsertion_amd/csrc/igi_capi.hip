@@ -171,6 +171,12 @@ int igi_conv_set_bf16_inputs(int on) {
   return prev;
 }
 
+int igi_conv_set_bf16x3(int on) {
+  const int prev = igi::conv_x3_mode();
+  if (on >= 0) igi::conv_x3_mode_ref() = on != 0;
+  return prev;
+}
+
 int igi_depth_set_bf16_inputs(int on) {
   const int prev = igi::depth_bf16_mode();
   if (on >= 0) igi::depth_bf16_mode_ref() = on != 0;

@@ -28,6 +28,10 @@ enum ProfClass {
   // gradient; weight gradient), which the fp32 path books under gemm_dma_kernel<64,...>
   PC_CONVB_TALL64_TT, PC_CONVB_TALL32_TT, PC_CONVB_TALL64_SSA, PC_CONVB_WG_TALL32, PC_CONVB_WG_TALL64,
   PC_CONVB_PM64, PC_CONVB_PM32, PC_CONVB_PW32, PC_CONVB_PW64, PC_CONVB_PW64_192, PC_CONVB_ROW64, PC_CONVB_WG64, PC_CONVB_PW64_128,
+  // ... and with every operand split into three exact bf16 planes, six plane products per term (conv_x3_mode():
+  // gemm_dma_conv_x3_kernel), class by class in the order of PC_CONVB_* (launch_conv_tile relies on it)
+  PC_CONVX_TALL64_TT, PC_CONVX_TALL32_TT, PC_CONVX_TALL64_SSA, PC_CONVX_WG_TALL32, PC_CONVX_WG_TALL64,
+  PC_CONVX_PM64, PC_CONVX_PM32, PC_CONVX_PW32, PC_CONVX_PW64, PC_CONVX_PW64_192, PC_CONVX_ROW64, PC_CONVX_WG64, PC_CONVX_PW64_128,
   // the 128 x 128 two-stage tile with the bf16-input inner loop asked for by ONE call (GemmArgs::bf16_inputs: the depth
   // backbone's big Linear under depth_bf16_mode()), by operand layout as PC_DMA_128_*; under the process-wide bf16_mode()
   // the same kernels stay booked as PC_DMA_128_*
@@ -66,6 +70,14 @@ static const char* const kProfNames[PC_COUNT] = {
     "gemm_dma_conv_bf16_kernel<64,false,false,5,2,192>",
     "gemm_dma_conv_bf16_kernel<64,true,true,1,3,128>", "gemm_dma_conv_bf16_kernel<64,false,false,3,3,128>",
     "gemm_dma_conv_bf16_kernel<64,false,false,5,3,128>",
+    "gemm_dma_conv_x3_kernel<64,true,true,1,2,256>", "gemm_dma_conv_x3_kernel<32,true,true,1,2,256>",
+    "gemm_dma_conv_x3_kernel<64,true,true,6,2,256>",
+    "gemm_dma_conv_x3_kernel<32,false,false,3,2,256>", "gemm_dma_conv_x3_kernel<64,false,false,3,2,256>",
+    "gemm_dma_conv_x3_kernel<64,true,true,4,2,256>", "gemm_dma_conv_x3_kernel<32,true,true,4,2,256>",
+    "gemm_dma_conv_x3_kernel<32,false,false,5,2,256>", "gemm_dma_conv_x3_kernel<64,false,false,5,2,256>",
+    "gemm_dma_conv_x3_kernel<64,false,false,5,2,192>",
+    "gemm_dma_conv_x3_kernel<64,true,true,1,3,128>", "gemm_dma_conv_x3_kernel<64,false,false,3,3,128>",
+    "gemm_dma_conv_x3_kernel<64,false,false,5,3,128>",
     "gemm_dma_bf16_kernel<true,true>", "gemm_dma_bf16_kernel<true,false>", "gemm_dma_bf16_kernel<false,false>",
     "k_pointnet_fwd", "k_pointnet_bwd", "k_softargmax_fwd", "k_softargmax_bwd",
     "gemm_dma_head_kernel<true>", "k_trunk_loss",

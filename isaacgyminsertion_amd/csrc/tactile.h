@@ -392,12 +392,22 @@ static ConvDesc conv_desc(const float* zero, int OH, int OW, int IH, int IW, int
   return d;
 }
 
+// The arithmetic of the three convolutions at this call (GemmArgs::conv_bf16): 0 fp32, 1 bf16-rounded operands
+// (conv_bf16_mode()), 6 split-bf16 (conv_x3_mode()).  Both switches on is an error: neither wins silently.
+static int tactile_conv_arith(int* cm) {
+  if (conv_bf16_mode() && conv_x3_mode()) return IGI_E_BADARG;
+  *cm = conv_x3_mode() ? 6 : (conv_bf16_mode() ? 1 : 0);
+  return 0;
+}
+
 static int tactile_forward(const igi_tactile_cfg* c, const float* x, const float* params, float* y, void* ws,
                            size_t ws_bytes, hipStream_t s) {
   TactilePlan p;
   int rc = make_tactile_plan(c, &p);
   if (rc) return rc;
   if (!x || !params || !y || !ws) return IGI_E_BADARG;
+  int cm;
+  if ((rc = tactile_conv_arith(&cm))) return rc;
   if (ws_bytes < p.w_total) return IGI_E_WORKSPACE;
   float* zero = twsp<float>(ws, p.w_zero);
   float* xin = twsp<float>(ws, p.w_xin);
@@ -419,7 +429,7 @@ static int tactile_forward(const igi_tactile_cfg* c, const float* x, const float
   }
   {  // conv1: (B,3,H,W) -> (B,H1,W1,32), straight from the caller's tensor
     GemmArgs g;
-    g.A = x; g.gather = 1; g.conv_bf16 = conv_bf16_mode(); g.conv = conv_desc(zero, p.H1, p.W1, p.H, p.W, 3, 2, 0, 8, 8, 1);
+    g.A = x; g.gather = 1; g.conv_bf16 = cm; g.conv = conv_desc(zero, p.H1, p.W1, p.H, p.W, 3, 2, 0, 8, 8, 1);
     g.B = params + p.o_w1; g.ldb = 192;   // torch's (co, c, ky, kx) IS the planar tap order
     g.M = (int)p.M1; g.N = TC_C1; g.K = 192; g.lda = 192;
     g.C = a1; g.ldc = TC_C1; g.bias = params + p.o_b1; g.epilogue = EPI_BIAS_RELU;
@@ -427,7 +437,7 @@ static int tactile_forward(const igi_tactile_cfg* c, const float* x, const float
   }
   {  // conv2
     GemmArgs g;
-    g.A = a1; g.gather = 1; g.conv_bf16 = conv_bf16_mode(); g.conv = conv_desc(zero, p.H2, p.W2, p.H1, p.W1, TC_C1, 1, 0, 4, 4);
+    g.A = a1; g.gather = 1; g.conv_bf16 = cm; g.conv = conv_desc(zero, p.H2, p.W2, p.H1, p.W1, TC_C1, 1, 0, 4, 4);
     g.B = w2r; g.ldb = 512;
     g.M = (int)p.M2; g.N = TC_C2; g.K = 512; g.lda = 512;
     g.C = a2; g.ldc = TC_C2; g.bias = params + p.o_b2; g.epilogue = EPI_BIAS_RELU;
@@ -435,7 +445,7 @@ static int tactile_forward(const igi_tactile_cfg* c, const float* x, const float
   }
   {  // conv3
     GemmArgs g;
-    g.A = a2; g.gather = 1; g.conv_bf16 = conv_bf16_mode(); g.conv = conv_desc(zero, p.H3, p.W3, p.H2, p.W2, TC_C2, 1, 0, 3, 3);
+    g.A = a2; g.gather = 1; g.conv_bf16 = cm; g.conv = conv_desc(zero, p.H3, p.W3, p.H2, p.W2, TC_C2, 1, 0, 3, 3);
     g.B = w3r; g.ldb = 576;
     g.M = (int)p.M3; g.N = TC_C3; g.K = 576; g.lda = 576;
     g.C = a3; g.ldc = TC_C3; g.bias = params + p.o_b3; g.epilogue = EPI_BIAS_RELU;
@@ -471,6 +481,8 @@ static int tactile_backward(const igi_tactile_cfg* c, const float* dy, const flo
   int rc = make_tactile_plan(c, &p);
   if (rc) return rc;
   if (!dy || !params || !grads || !ws) return IGI_E_BADARG;
+  int cm;
+  if ((rc = tactile_conv_arith(&cm))) return rc;
   if (ws_bytes < p.w_total) return IGI_E_WORKSPACE;
   float* zero = twsp<float>(ws, p.w_zero);
   float* xin = twsp<float>(ws, p.w_xin);
@@ -505,7 +517,7 @@ static int tactile_backward(const igi_tactile_cfg* c, const float* dy, const flo
   }
   {  // conv3 weight gradient
     GemmArgs g;
-    g.A = a2; g.gather = 3; g.conv_bf16 = conv_bf16_mode(); g.conv = conv_desc(zero, p.H3, p.W3, p.H2, p.W2, TC_C2, 1, 0, 3, 3); g.lda = 576;
+    g.A = a2; g.gather = 3; g.conv_bf16 = cm; g.conv = conv_desc(zero, p.H3, p.W3, p.H2, p.W2, TC_C2, 1, 0, 3, 3); g.lda = 576;
     g.B = dz3; g.ldb = TC_C3;
     g.M = 576; g.N = TC_C3; g.K = (int)p.M3;
     g.C = slab + p.s_w3; g.ldc = TC_C3; g.Cbias = slab + p.s_b3; g.bias_from_b = 1;
@@ -514,7 +526,7 @@ static int tactile_backward(const igi_tactile_cfg* c, const float* dy, const flo
   }
   {  // conv3 data gradient -> dz2 = relu'(a2) * (dz3 (*) flipped W3)
     GemmArgs g;
-    g.A = dz3; g.gather = 1; g.conv_bf16 = conv_bf16_mode(); g.conv = conv_desc(zero, p.H2, p.W2, p.H3, p.W3, TC_C3, 1, 2, 3, 3); g.lda = 576;
+    g.A = dz3; g.gather = 1; g.conv_bf16 = cm; g.conv = conv_desc(zero, p.H2, p.W2, p.H3, p.W3, TC_C3, 1, 2, 3, 3); g.lda = 576;
     g.B = w3d; g.ldb = 576;
     g.M = (int)p.M2; g.N = TC_C2; g.K = 576;
     g.C = dz2; g.ldc = TC_C2; g.aux = a2; g.ldaux = TC_C2; g.epilogue = EPI_RELUGRAD;
@@ -523,7 +535,7 @@ static int tactile_backward(const igi_tactile_cfg* c, const float* dy, const flo
   }
   {  // conv2 weight gradient
     GemmArgs g;
-    g.A = a1; g.gather = 3; g.conv_bf16 = conv_bf16_mode(); g.conv = conv_desc(zero, p.H2, p.W2, p.H1, p.W1, TC_C1, 1, 0, 4, 4); g.lda = 512;
+    g.A = a1; g.gather = 3; g.conv_bf16 = cm; g.conv = conv_desc(zero, p.H2, p.W2, p.H1, p.W1, TC_C1, 1, 0, 4, 4); g.lda = 512;
     g.B = dz2; g.ldb = TC_C2;
     g.M = 512; g.N = TC_C2; g.K = (int)p.M2;
     g.C = slab + p.s_w2; g.ldc = TC_C2; g.Cbias = slab + p.s_b2; g.bias_from_b = 1;
@@ -532,7 +544,7 @@ static int tactile_backward(const igi_tactile_cfg* c, const float* dy, const flo
   }
   {  // conv2 data gradient -> dz1
     GemmArgs g;
-    g.A = dz2; g.gather = 1; g.conv_bf16 = conv_bf16_mode(); g.conv = conv_desc(zero, p.H1, p.W1, p.H2, p.W2, TC_C2, 1, 3, 4, 4); g.lda = 1024;
+    g.A = dz2; g.gather = 1; g.conv_bf16 = cm; g.conv = conv_desc(zero, p.H1, p.W1, p.H2, p.W2, TC_C2, 1, 3, 4, 4); g.lda = 1024;
     g.B = w2d; g.ldb = 1024;
     g.M = (int)p.M1; g.N = TC_C1; g.K = 1024;
     g.C = dz1; g.ldc = TC_C1; g.aux = a1; g.ldaux = TC_C1; g.epilogue = EPI_RELUGRAD;
@@ -541,7 +553,7 @@ static int tactile_backward(const igi_tactile_cfg* c, const float* dy, const flo
   }
   {  // conv1 weight gradient (the input needs no gradient)
     GemmArgs g;
-    g.A = xin; g.gather = 3; g.conv_bf16 = conv_bf16_mode(); g.conv = conv_desc(zero, p.H1, p.W1, p.H, p.W, 4, 2, 0, 8, 8); g.lda = 256;
+    g.A = xin; g.gather = 3; g.conv_bf16 = cm; g.conv = conv_desc(zero, p.H1, p.W1, p.H, p.W, 4, 2, 0, 8, 8); g.lda = 256;
     g.B = dz1; g.ldb = TC_C1;
     g.M = 256; g.N = TC_C1; g.K = (int)p.M1;
     g.C = slab + p.s_w1; g.ldc = TC_C1; g.Cbias = slab + p.s_b1; g.bias_from_b = 1;

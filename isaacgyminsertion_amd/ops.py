@@ -1127,6 +1127,30 @@ def conv_bf16_inputs_enabled():
     return bool(_lib.lib().igi_conv_set_bf16_inputs(-1))
 
 
+class conv_bf16x3:
+    """Opt-in split-bf16 arithmetic of the tactile CNN's convolutions (igi_conv_set_bf16x3; off by default,
+    ``IGI_CONV_BF16X3=1`` starts it on): every fp32 operand split exactly into three bf16 planes, six plane products per
+    term on the bf16 matrix pipe, fp32 accumulation -- fp32-grade results, unlike ``conv_bf16_inputs``.  The twin of
+    ``conv_bf16_inputs``: ``conv_bf16x3(True)`` sets the process-wide switch at once and remembers the previous value in
+    ``.previous``; used as a context manager it restores that value on exit.  ``tactile_cnn_fwd`` records both switches
+    and its autograd formula re-establishes both around the backward op.  With both switches on the tactile ops raise."""
+
+    def __init__(self, on):
+        self.previous = bool(_lib.lib().igi_conv_set_bf16x3(1 if on else 0))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().igi_conv_set_bf16x3(1 if self.previous else 0)
+        return False
+
+
+def conv_bf16x3_enabled():
+    """the current setting of the switch (igi_conv_set_bf16x3(-1): a query)"""
+    return bool(_lib.lib().igi_conv_set_bf16x3(-1))
+
+
 @_op("tactile_cnn_fwd(Tensor x, Tensor params, int latent_dim) -> (Tensor, Tensor)")
 def tactile_cnn_fwd(x: Tensor, params: Tensor, latent_dim: int) -> Tuple[Tensor, Tensor]:
     """CNNWithSpatialSoftArgmax forward (tactile_cnn.py:62-79) on (B, 3, H, W), B a multiple of 32: implicit-GEMM
@@ -1182,6 +1206,7 @@ def _tac_setup(ctx, inputs, output):
     ctx.save_for_backward(params, output[1])
     ctx.hw = (x.shape[2], x.shape[3])
     ctx.conv_bf16 = conv_bf16_inputs_enabled()     # setup_context runs right behind the forward op: still its setting
+    ctx.conv_x3 = conv_bf16x3_enabled()
     ctx.set_materialize_grads(False)
 
 
@@ -1189,7 +1214,7 @@ def _tac_backward(ctx, dy, dws):
     params, ws = ctx.saved_tensors
     if dy is None:
         return None, None, None
-    with conv_bf16_inputs(ctx.conv_bf16):          # the arithmetic the saved activations were computed in
+    with conv_bf16_inputs(ctx.conv_bf16), conv_bf16x3(ctx.conv_x3):   # the arithmetic the saved activations were computed in
         return None, torch.ops.mi355ppo.tactile_cnn_bwd(dy.contiguous(), params, ws, ctx.hw[0], ctx.hw[1]), None
 
 

@@ -88,6 +88,7 @@ def default_config(num_envs=4096, horizon_length=32, rl_device="cuda:0", multi_g
                       "use_lin": True, "use_pcl": False, "linear": {"input_size": 15},
                       # opt-in: bf16-rounded operands, fp32 accumulation in the tactile CNN's convolutions (Runner)
                       "conv_bf16_inputs": False,
+                      "conv_bf16x3": False,
                       "transformer": {"sequence_length": 1, "num_layers": 2, "num_heads": 2, "dim_factor": 4,
                                       "output_size": 8, "lin_encoding_size": 32, "tactile_encoding_size": 32,
                                       "img_encoding_size": 32, "seg_encoding_size": 32, "load_tact": False}},

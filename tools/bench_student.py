@@ -40,7 +40,7 @@ def algorithmic_macs(config, hw):
 
 
 def student_bench(config=3, envs=2048, horizon=32, hw=(32, 64), updates=2, device="cuda:0", multi_gpu=False,
-                  profile=True, conv_bf16=False):
+                  profile=True, conv_bf16=False, conv_x3=False):
     """multi_gpu: one call per rank under torchrun (the process group is up): per-rank synthetic buffers (seed + rank),
     rank 0's initial student on every rank, ExtrinsicAdapt.update() with its gradient exchange; the time is the maximum
     over the ranks between barriers and the record says whether the parameter vectors ended bit-identical."""
@@ -62,6 +62,8 @@ def student_bench(config=3, envs=2048, horizon=32, hw=(32, 64), updates=2, devic
                          tactile_info=not img, pcl_info=pcl, img_info=img, seg_info=img, num_points=8)
     cfg.offline_train.tactile_width, cfg.offline_train.tactile_height = H, W
     cfg.offline_train.model.conv_bf16_inputs = bool(conv_bf16)
+    if conv_x3:                                       # (left unset otherwise: a checkout without the key runs the same file)
+        cfg.offline_train.model.conv_bf16x3 = True
     env = SyntheticInsertionEnv(envs, device=device, tactile_hw=None if img else (H, W),
                                 pcl_points=800 if pcl else 0, img_hw=(54, 96) if img else None)
     agent = ExtrinsicAdapt(env, None, cfg)
@@ -129,6 +131,8 @@ def student_bench(config=3, envs=2048, horizon=32, hw=(32, 64), updates=2, devic
            "finite": bool(torch.isfinite(torch.stack(losses)).all())}
     if conv_bf16:
         out["conv_bf16_inputs"] = True
+    if conv_x3:
+        out["conv_bf16x3"] = True
     if multi_gpu:
         comm = getattr(agent, "_comm", None)
         out["n_gpus"] = world
@@ -175,9 +179,12 @@ def main():
     ap.add_argument("--updates", type=int, default=2)
     ap.add_argument("--conv-bf16", action="store_true",
                     help="offline_train.model.conv_bf16_inputs=True: bf16-input, fp32-accumulate tactile convolutions")
+    ap.add_argument("--conv-x3", action="store_true",
+                    help="offline_train.model.conv_bf16x3=True: split-bf16 tactile convolutions (three exact bf16 planes per "
+                         "operand, six plane products, fp32 accumulation)")
     args = ap.parse_args()
     print(json.dumps(student_bench(args.config, args.envs, args.horizon, tuple(args.hw), args.updates,
-                                   conv_bf16=args.conv_bf16)))
+                                   conv_bf16=args.conv_bf16, conv_x3=args.conv_x3)))
 
 
 if __name__ == "__main__":
